@@ -887,8 +887,6 @@ def dry_run(args):
     n_gpus = args.gpus if in_process else world
     if world > 1 and world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
-    if args.gpus < 1 or args.steps < 1 or args.warmup < 0:
-        raise SystemExit("--gpus >= 1, --steps >= 1, --warmup >= 0")
     n_total = int(args.rows)
     nq = args.queries if args.queries > 0 else 320
     if rank != 0:
@@ -964,9 +962,15 @@ def main():
     ap.add_argument("--ann-rows-per-gpu", type=float, default=2e6, help="--gpus N > 1: rows per GPU of the sharded approximate-search legs")
     ap.add_argument("--siglip-batch", type=int, default=256)
     ap.add_argument("--siglip-steps", type=int, default=10)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the headline's answer of its last timed step (top-k scores and ids, float64) as DIR/topk_scores.npy and "
+                         "DIR/topk_ids.npy; with --queries 0 only the first 128 queries (the narrowest pass the pick may choose), so "
+                         "that the same arguments always dump the answer to the same queries")
     args = ap.parse_args()
     if args.graph_1e8 and not any(a.startswith("--time-budget") for a in sys.argv[1:]):
         args.time_budget = 1500.0
+    if args.gpus < 1 or args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--gpus >= 1, --steps >= 1, --warmup >= 0")
     if args.dry_run:
         return dry_run(args)
 
@@ -1034,6 +1038,10 @@ def main():
     qsets = mse.VectorList.generate(SEED_QUERY, 0, nq_room * n_batches, D)  # query batches, resident in HBM (root device)
     out_s = torch.empty((nq_room, k), dtype=torch.int64, device="cuda")
     out_i = torch.empty((nq_room, k), dtype=torch.int32, device="cuda")
+
+    def batch_ptr(i):
+        # batches sit nq_room queries apart, so the queries a step starts with do not depend on the measured pick below
+        return qsets.device_ptr + (i % n_batches) * nq_room * D * 2
     comm = group = None
     queries_pick = None
     host_exchange = None
@@ -1076,7 +1084,7 @@ def main():
             print(f"[bench] RCCL exchange unavailable ({e}); measuring the peer-store exchange", file=sys.stderr)
 
         def step(i):
-            qptr = qsets.device_ptr + (i % n_batches) * nq * D * 2
+            qptr = batch_ptr(i)
             group.bruteforce_topk_dev(qptr, nq, k, out_s.data_ptr(), out_i.data_ptr(), mse.MODE_MFMA)
     else:
         vecs = mse.VectorList.generate(SEED_BASE, lo, hi - lo, D)       # shard rows made on the device
@@ -1140,7 +1148,7 @@ def main():
                             "rccl_ranks": comm.size, "bytes_per_rank_per_step": int(ffi.lib().mse_topk_block_bytes(nq, k))}
 
         def step(i):
-            qptr = qsets.device_ptr + (i % n_batches) * nq * D * 2
+            qptr = batch_ptr(i)
             if host_exchange is not None:
                 host_step(qptr, nq, mse.MODE_MFMA, out_s, out_i)
             elif comm is None:
@@ -1170,6 +1178,12 @@ def main():
     elapsed = time.perf_counter() - t0
     scan_ms, scan_launches = searcher.scan_timing(0)
     stats = searcher.last_stats()
+    if args.dump_outputs and rank == 0:
+        # float64 holds both exactly (scores are dot * 2^32 in i64, ids reach 1e8); 16 B per record, capped at 64 MB
+        n_dump = min(128 if auto_nq else nq, (64 << 20) // (16 * k))
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "topk_scores.npy"), out_s[:n_dump].cpu().numpy().astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, "topk_ids.npy"), out_i[:n_dump].cpu().numpy().view(np.uint32).astype(np.float64))
     # where a step goes (last step of the timed loop): the scan kernel, the rest of the local search (pack + tournament + exact
     # re-score + certificate), the exchange leg and the merge
     breakdown = exchange_alt = None
@@ -1218,7 +1232,7 @@ def main():
         sync_all()
         ta = time.perf_counter()
         for i in range(n_alt):
-            qptr = qsets.device_ptr + (i % n_batches) * nq * D * 2
+            qptr = batch_ptr(i)
             if in_process:
                 group.bruteforce_topk_dev(qptr, 128, k, out_s.data_ptr(), out_i.data_ptr(), mse.MODE_MFMA)
             elif host_exchange is not None:
@@ -1237,8 +1251,7 @@ def main():
 
     # correctness spot check outside the timed region: the batched (MFMA) answer of the last step must equal the
     # exact-order kernel's answer for the same queries (two independent kernels), over the whole (sharded) index
-    last = (args.warmup + args.steps - 1) % n_batches
-    qptr = qsets.device_ptr + last * nq * D * 2
+    qptr = batch_ptr(args.warmup + args.steps - 1)
     m = min(8, nq)
     chk_s = torch.empty((m, k), dtype=torch.int64, device="cuda")
     chk_i = torch.empty((m, k), dtype=torch.int32, device="cuda")

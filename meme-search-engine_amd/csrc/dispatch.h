@@ -104,7 +104,7 @@ class Coalescer {
     // index of the calling worker thread within its Coalescer (0 .. n_workers-1; 0 on any other thread): run() uses it to pick
     // its own scratch when a handle has several workers
     static int worker_index();
-    int n_workers() const { return (int)workers_.size(); }
+    int n_workers() const { return n_workers_; }
     // blocks until the request was executed; returns its rc and leaves its message in the thread's mse_last_error()
     int submit(DispatchReq& r);
     // Asynchronous form (round 5): ONE host thread keeps thousands of requests in flight -- the device wants thousands of queries per
@@ -168,6 +168,7 @@ class Coalescer {
     std::atomic<int> running_{0};              // passes executing now (several workers)
     bool hold_while_busy_ = true;              // a gatherer does not start a second pass by the wait budget while one is executing
     DispatchStats st_;
+    int n_workers_ = 1;               // set before any thread starts: the threads read it, never workers_ / wakers_ while they are filled
     std::vector<std::thread> workers_;
     // Waking several hundred sleepers is a futex call that costs about a microsecond per sleeper -- on the worker's critical path that
     // was as long as the pass itself.  A pass of more than WAKE_INLINE requests is handed to the worker's companion thread, which sets

@@ -48,14 +48,18 @@ Coalescer::Coalescer(size_t max_queries, uint32_t max_wait_us, RunFn run, std::f
     : max_queries_(max_queries ? max_queries : 1), max_wait_us_(max_wait_us), run_(std::move(run)),
       on_start_(std::move(on_thread_start)) {
     if (n_workers < 1) n_workers = 1;
+    n_workers_ = n_workers;
     {
         const char* e = getenv("MSE_COALESCE_NO_HOLD");
         hold_while_busy_ = !(e && atoi(e));
     }
-    for (int w = 0; w < n_workers; w++) {
-        wakers_.emplace_back(new Waker());
-        wakers_[w]->th = std::thread([this, w] { wake_loop(w); });
-    }
+    // Every Waker exists before the first thread starts.  A companion thread reads wakers_[w] as it starts; made one by one, the next
+    // emplace_back could reallocate wakers_ between that thread's load of the buffer and its load of the element, and the thread took
+    // its Waker* from freed memory (a SIGSEGV or an abort on the first lock, right after a handle's first request made it).
+    wakers_.reserve((size_t)n_workers);
+    for (int w = 0; w < n_workers; w++) wakers_.emplace_back(new Waker());
+    for (int w = 0; w < n_workers; w++) wakers_[w]->th = std::thread([this, w] { wake_loop(w); });
+    workers_.reserve((size_t)n_workers);
     for (int w = 0; w < n_workers; w++) workers_.emplace_back([this, w] { loop(w); });
 }
 
@@ -421,7 +425,7 @@ void Coalescer::loop(int index) {
         lk.lock();
         gathering_ = false;                       // what is left (and what arrives) is the next gatherer's
         lk.unlock();
-        if (workers_.size() > 1) cv_worker_.notify_one();
+        if (n_workers_ > 1) cv_worker_.notify_one();
         const auto t_run = std::chrono::steady_clock::now();
         running_.fetch_add(1, std::memory_order_acq_rel);
         run_(batch);
@@ -463,7 +467,7 @@ void Coalescer::loop(int index) {
             wl.unlock();
             wk.cv.notify_all();
         }
-        if (workers_.size() > 1) {   // a gatherer waiting for its target re-reads expect_ / the grace period
+        if (n_workers_ > 1) {   // a gatherer waiting for its target re-reads expect_ / the grace period
             bell_.fetch_add(1, std::memory_order_release);
             futex_wake_all(&bell_);
         }

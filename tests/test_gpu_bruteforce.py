@@ -1,11 +1,12 @@
 """Parity of the HIP brute-force path with the CPU oracle, through the C ABI (mse package).
 Bit-exact bar: i64 scores and returned indices."""
+import json
 import os
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, SEED_BASE, SEED_QUERY
+from conftest import GOLDEN, ROOT, SEED_BASE, SEED_QUERY
 
 pytestmark = pytest.mark.gpu
 D = 1152
@@ -326,3 +327,25 @@ def test_only_the_queries_that_need_it_are_widened(gpu, mse, orc):
     assert st["widened_queries"] == 2, st                      # queries 3 and 77, nobody else
     sc, ids = s.bruteforce_topk(q[:8], k, mse.MODE_EXACT)
     assert np.array_equal(ids, wi[:8]) and np.array_equal(sc, ws[:8])
+
+
+def test_bench_dump_is_the_answer_of_the_last_timed_step(gpu, mse, orc, tmp_path):
+    """bench.py --dump-outputs: with the queries per step picked by measurement, the dump holds the last timed step's answer for the
+    first 128 queries of that step's batch (batches sit 320 queries apart whatever the pick), as float64, equal to a fresh search."""
+    import subprocess
+    import sys
+    n, k, steps, warmup = 2_000_000, 10, 3, 2
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rows", str(n), "--steps", str(steps), "--warmup", str(warmup),
+                        "--no-cpu-baseline", "--no-siglip", "--no-pq", "--no-shard-point", "--no-callers", "--no-graph", "--no-graph-scale",
+                        "--no-ann-scale", "--detail", "", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert json.loads(r.stdout.strip().splitlines()[-1])["steps"] == steps
+    scores, ids = np.load(out / "topk_scores.npy"), np.load(out / "topk_ids.npy")
+    assert scores.dtype == ids.dtype == np.float64 and scores.shape == ids.shape == (128, k)
+    q = orc.gen_rows_f16(SEED_QUERY, (warmup + steps - 1) % 4 * 320, 128)
+    s = mse.Searcher(mse.VectorList.generate(SEED_BASE, 0, n))
+    ws, wi = s.bruteforce_topk(q, k, mse.MODE_MFMA)
+    assert np.array_equal(scores, ws.astype(np.float64)) and np.array_equal(ids, wi.astype(np.float64))
+    se, ie = s.bruteforce_topk(q[:8], k, mse.MODE_EXACT)
+    assert np.array_equal(ie, wi[:8]) and np.array_equal(se, ws[:8])
