@@ -5,11 +5,10 @@
 // (clip_server.py:40-57, without the "visual." prefix).
 #include "../../include/mse.h"
 #include "runtime.h"
-#include "siglip.h"
+#include "siglip_encoder.h"
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <new>
 #include <string>
 #include <vector>
@@ -17,36 +16,10 @@
 using namespace mse;
 using namespace mse::siglip;
 
-namespace {
-
-size_t round_up(size_t v, size_t m) { return (v + m - 1) / m * m; }
-
-struct Block {
-    float *ln1_g, *ln1_b, *ln2_g, *ln2_b;
-    uint16_t *wqkv, *wproj, *w1, *w2;
-    float *bqkv, *bproj, *b1, *b2;
-    // LayerNorm folded into QKV / fc1 (built by mse_siglip_finalize): fp16 w * gamma, its row sums, bias + w . beta
-    uint16_t *wqkv16 = nullptr, *w116 = nullptr;
-    float *cqkv = nullptr, *c1 = nullptr, *bqkv2 = nullptr, *b12 = nullptr;
-};
-
-struct Slot {
-    enum Kind { F32, BF16_PAD } kind;
-    void* dst;
-    size_t rows, cols;          // logical shape of the source (product of leading dims, last dim)
-    size_t rows_pad, cols_pad;  // destination shape for BF16_PAD
-    bool loaded = false;
-};
-
-}  // namespace
-
-struct mse_siglip {
+// Geometry, weight store, blocks and their activations: Encoder (siglip_encoder.h); here what only the image tower has
+struct mse_siglip : Encoder {
     mse_siglip_config cfg{};
-    int tokens = 0, D = 0, H = 0, dh = 0, mlp = 0, mlp_pad = 0, kpe = 0, kpe_pad = 0;
-    int n_pad = 0, dh_pad = 96, dv_pad = 80;
-    int max_batch = 0;
-    size_t m_pad = 0;
-    hipStream_t stream = nullptr;
+    int tokens = 0, kpe = 0, kpe_pad = 0;
     // one call at a time per engine: a call enqueues its uploads and kernels on the engine's streams into shared scratch, so two
     // threads inside one engine would read each other's images (replicas are separate engines and run side by side)
     std::recursive_mutex call_mu;
@@ -55,51 +28,21 @@ struct mse_siglip {
     hipStream_t side[MAX_SIDE] = {};   // further streams of a forward pass (MSE_SIGLIP_STREAMS = 1 + how many are used; default 2)
     hipEvent_t ev_fork = nullptr, ev_join[MAX_SIDE] = {};
     int n_side = 0;
-    std::vector<void*> allocs;
-    std::map<std::string, Slot> slots;
-    bool finalized = false;
     // parameters
     uint16_t* wpe = nullptr; float* bpe = nullptr; float* pos = nullptr;
-    std::vector<Block> blocks;
     float *lnf_g = nullptr, *lnf_b = nullptr;
     float* latent = nullptr; uint16_t *wq = nullptr, *wkv = nullptr, *wpp = nullptr, *wp1 = nullptr, *wp2 = nullptr;
     float *bq = nullptr, *bkv = nullptr, *bpp = nullptr, *lnp_g = nullptr, *lnp_b = nullptr, *bp1 = nullptr, *bp2 = nullptr;
     float* qlat = nullptr;
     // activations
-    int dp = 0;              // emb_dim rounded up to whole 256-column GEMM tiles (ld of the residual-branch buffer)
     void* img_dev = nullptr;
-    uint16_t *patches = nullptr, *h = nullptr, *dlt = nullptr, *mlp_h = nullptr, *qb = nullptr, *kb = nullptr, *vtb = nullptr, *kvb = nullptr;
-    uint16_t* x = nullptr;   // residual stream [M][D], fp16
+    uint16_t *patches = nullptr, *kvb = nullptr;
     float *pool_a = nullptr, *pool_o = nullptr;
     uint16_t *pool_a16 = nullptr, *pool_ln16 = nullptr, *pool_h16 = nullptr;   // bf16 operands of the MAP head's GEMMs, rows padded to 256
     size_t pool_rows = 0;
     float* out_f32 = nullptr; uint16_t* out_f16 = nullptr;
-    float* stage = nullptr; size_t stage_elems = 0;
     int last_batch = 0;
-    // fused LayerNorm path (siglip_kernels.hip "Fused LayerNorm"); MSE_SIGLIP_NOFUSE=1 keeps LN1 / LN2 as kernels of their own
-    bool fused = false;
     bool no_small = false;       // MSE_SIGLIP_NOSMALL=1: calls of 1..4 images run the batch kernels too (bit-equal to rows of larger batches)
-    float* ln_stats = nullptr;   // [m_pad] (mean, 1/std)
-    float* ln_part = nullptr;    // [D / 64][m_pad] (sum, M2)
-    float* kparts = nullptr;     // small-batch path: fp32 partial sums of a K-split fc2 (launch_gemm GEMM_EPI_PART)
-    void* sink = nullptr;
-
-    template <typename T> T* dalloc(size_t n, bool zero = false) {
-        void* p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(n * sizeof(T), 256)) != hipSuccess) return nullptr;
-        if (zero && hipMemset(p, 0, std::max<size_t>(n * sizeof(T), 256)) != hipSuccess) return nullptr;
-        allocs.push_back(p);
-        return reinterpret_cast<T*>(p);
-    }
-    void add_f32(const std::string& name, float** dst, size_t rows, size_t cols, size_t cols_pad = 0) {
-        const size_t cp = cols_pad ? cols_pad : cols;
-        *dst = dalloc<float>(rows * cp, true);
-        slots[name] = Slot{Slot::F32, *dst, rows, cols, rows, cp};
-    }
-    void add_bf16(const std::string& name, uint16_t** dst, size_t rows, size_t cols, size_t rows_pad, size_t cols_pad) {
-        *dst = dalloc<uint16_t>(rows_pad * cols_pad, true);
-        slots[name] = Slot{Slot::BF16_PAD, *dst, rows, cols, rows_pad, cols_pad};
-    }
 };
 
 extern "C" {
@@ -115,6 +58,7 @@ mse_siglip* mse_siglip_create(const mse_siglip_config* c) {
     mse_siglip* m = new (std::nothrow) mse_siglip();
     if (!m) { fail("out of host memory"); return nullptr; }
     m->cfg = *c;
+    m->what = "siglip"; m->eps = c->eps; m->gelu_tanh = c->gelu_tanh;
     const int g = c->img_size / c->patch_size;
     m->tokens = g * g; m->D = c->emb_dim; m->H = c->num_heads; m->dh = m->D / m->H; m->mlp = c->mlp_dim;
     m->mlp_pad = (int)round_up(m->mlp, 128);
@@ -140,20 +84,10 @@ mse_siglip* mse_siglip_create(const mse_siglip_config* c) {
     m->add_bf16("trunk.patch_embed.proj.weight", &m->wpe, D, m->kpe, D, m->kpe_pad);
     m->add_f32("trunk.patch_embed.proj.bias", &m->bpe, 1, D);
     m->pos = m->dalloc<float>((size_t)m->n_pad * D, true);   // padded to the row stride (EPI_PATCH indexes it by m % n_pad)
-    m->slots["trunk.pos_embed"] = Slot{Slot::F32, m->pos, (size_t)m->tokens, D, (size_t)m->tokens, D};
-    m->blocks.resize(c->depth);
-    for (int i = 0; i < c->depth; i++) {
-        Block& b = m->blocks[i];
-        const std::string p = "trunk.blocks." + std::to_string(i) + ".";
-        m->add_f32(p + "norm1.weight", &b.ln1_g, 1, D); m->add_f32(p + "norm1.bias", &b.ln1_b, 1, D);
-        m->add_bf16(p + "attn.qkv.weight", &b.wqkv, 3 * D, D, 3 * D, D); m->add_f32(p + "attn.qkv.bias", &b.bqkv, 1, 3 * D);
-        // proj and fc2 write the residual branch: their N = D output columns are padded to whole 256-column tiles (zero weight
-        // rows, ld DP) so that the persistent 256 x 256 kernel covers them without the half-efficiency 128-column remainder launch
-        m->add_bf16(p + "attn.proj.weight", &b.wproj, D, D, DP, D); m->add_f32(p + "attn.proj.bias", &b.bproj, 1, D, DP);
-        m->add_f32(p + "norm2.weight", &b.ln2_g, 1, D); m->add_f32(p + "norm2.bias", &b.ln2_b, 1, D);
-        m->add_bf16(p + "mlp.fc1.weight", &b.w1, m->mlp, D, MP, D); m->add_f32(p + "mlp.fc1.bias", &b.b1, 1, m->mlp, MP);
-        m->add_bf16(p + "mlp.fc2.weight", &b.w2, D, m->mlp, DP, MP); m->add_f32(p + "mlp.fc2.bias", &b.b2, 1, D, DP);
-    }
+    m->slots["trunk.pos_embed"] = Slot{false, m->pos, (size_t)m->tokens, D, (size_t)m->tokens, D};
+    m->add_blocks(c->depth, BlockNames{"trunk.blocks.", "norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias",
+                                       "attn.proj.weight", "attn.proj.bias", "norm2.weight", "norm2.bias", "mlp.fc1.weight",
+                                       "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias"});
     {
         const char* e = getenv("MSE_SIGLIP_NOSMALL");
         m->no_small = e && atoi(e);
@@ -162,19 +96,7 @@ mse_siglip* mse_siglip_create(const mse_siglip_config* c) {
         const char* e = getenv("MSE_SIGLIP_NOFUSE");
         m->fused = !(e && atoi(e)) && gemm_fused_ok((int)m->m_pad, (int)D, (int)MP, m->H, m->dh, m->n_pad, m->n_pad, 8);
     }
-    bool fused_alloc_ok = true;
-    if (m->fused) {
-        for (int i = 0; i < c->depth; i++) {
-            Block& b = m->blocks[i];
-            b.wqkv16 = m->dalloc<uint16_t>(3 * D * D); b.cqkv = m->dalloc<float>(3 * D); b.bqkv2 = m->dalloc<float>(3 * D);
-            b.w116 = m->dalloc<uint16_t>(MP * D); b.c1 = m->dalloc<float>(MP); b.b12 = m->dalloc<float>(MP);
-            fused_alloc_ok = fused_alloc_ok && b.wqkv16 && b.cqkv && b.bqkv2 && b.w116 && b.c1 && b.b12;
-        }
-        m->ln_stats = m->dalloc<float>(2 * m->m_pad, true);
-        m->ln_part = m->dalloc<float>(2 * (D / 64) * m->m_pad, true);
-        m->sink = m->dalloc<char>(4096, true);
-        fused_alloc_ok = fused_alloc_ok && m->ln_stats && m->ln_part && m->sink;
-    }
+    const bool fused_alloc_ok = !m->fused || m->alloc_fused();
     m->add_f32("trunk.norm.weight", &m->lnf_g, 1, D); m->add_f32("trunk.norm.bias", &m->lnf_b, 1, D);
     const std::string ap = "trunk.attn_pool.";
     m->add_f32(ap + "latent", &m->latent, 1, D);
@@ -224,65 +146,25 @@ void mse_siglip_destroy(mse_siglip* m) {
     }
     if (m->ev_fork) (void)hipEventDestroy(m->ev_fork);
     if (m->stream) { (void)hipStreamSynchronize(m->stream); (void)hipStreamDestroy(m->stream); }
-    for (void* p : m->allocs) (void)hipFree(p);
-    if (m->stage) (void)hipFree(m->stage);
-    delete m;
+    delete m;   // frees the device memory
 }
 
-int mse_siglip_n_weights(const mse_siglip* m) { return m ? (int)m->slots.size() : 0; }
+int mse_siglip_n_weights(const mse_siglip* m) { return m ? m->n_weights() : 0; }
 
 // name of weight #idx (sorted), or NULL; lets a loader enumerate what the engine expects
-const char* mse_siglip_weight_name(const mse_siglip* m, int idx) {
-    if (!m || idx < 0 || idx >= (int)m->slots.size()) return nullptr;
-    auto it = m->slots.begin();
-    std::advance(it, idx);
-    return it->first.c_str();
-}
+const char* mse_siglip_weight_name(const mse_siglip* m, int idx) { return m ? m->weight_name(idx) : nullptr; }
 
 int mse_siglip_set_weight(mse_siglip* m, const char* name, const float* data, const size_t* shape, int ndim) {
     if (!m || !name || !data) return fail("siglip_set_weight: null argument");
-    auto it = m->slots.find(name);
-    if (it == m->slots.end()) return fail(std::string("siglip: unknown weight '") + name + "'");
-    Slot& s = it->second;
-    size_t total = 1;
-    for (int i = 0; i < ndim; i++) total *= shape[i];
-    if (total != s.rows * s.cols) return fail(std::string("siglip: wrong size for '") + name + "'");
-    if (m->stage_elems < total) {
-        if (m->stage) (void)hipFree(m->stage);
-        m->stage = nullptr;
-        MSE_HIP_TRY(hipMalloc((void**)&m->stage, total * 4));
-        m->stage_elems = total;
-    }
-    MSE_HIP_TRY(hipMemcpyAsync(m->stage, data, total * 4, hipMemcpyHostToDevice, m->stream));
-    if (s.kind == Slot::F32) {
-        if (s.cols_pad == s.cols) {
-            MSE_HIP_TRY(hipMemcpyAsync(s.dst, m->stage, total * 4, hipMemcpyDeviceToDevice, m->stream));
-        } else {
-            MSE_HIP_TRY(hipMemcpy2DAsync(s.dst, s.cols_pad * 4, m->stage, s.cols * 4, s.cols * 4, s.rows, hipMemcpyDeviceToDevice,
-                                         m->stream));
-        }
-    } else {
-        if (launch_f32_to_bf16_pad(m->stage, (int)s.rows, (int)s.cols, (int)s.cols, reinterpret_cast<uint16_t*>(s.dst),
-                                   (int)s.rows_pad, (int)s.cols_pad, m->stream)) return -1;
-    }
-    MSE_HIP_TRY(hipStreamSynchronize(m->stream));
-    s.loaded = true;
-    m->finalized = false;
-    return 0;
+    return m->set_weight(name, data, shape, ndim);
 }
 
 int mse_siglip_finalize(mse_siglip* m) {
     if (!m) return fail("null engine");
-    for (auto& kv : m->slots)
-        if (!kv.second.loaded) return fail("siglip: weight '" + kv.first + "' was never set");
+    if (m->check_loaded()) return -1;
     // the pooling query does not depend on the input: q = Linear(latent)   (model.py:94-95)
     if (launch_small_linear(m->latent, m->D, m->wq, m->D, m->bq, m->D, m->D, 1, 0, nullptr, 0, m->qlat, m->D, m->stream)) return -1;
-    if (m->fused) {
-        for (Block& b : m->blocks) {
-            if (launch_ln_fold(b.wqkv, 3 * m->D, m->D, b.ln1_g, b.ln1_b, b.bqkv, b.wqkv16, b.cqkv, b.bqkv2, m->stream)) return -1;
-            if (launch_ln_fold(b.w1, m->mlp_pad, m->D, b.ln2_g, b.ln2_b, b.b1, b.w116, b.c1, b.b12, m->stream)) return -1;
-        }
-    }
+    if (m->fold_layernorms()) return -1;
     MSE_HIP_TRY(hipStreamSynchronize(m->stream));
     m->finalized = true;
     return 0;
@@ -383,17 +265,11 @@ int mse_siglip_encode_image(mse_siglip* m, const void* images, int dtype, int on
     // within the oracle's tolerance), not bit for bit.  MSE_SIGLIP_NOSMALL=1 (read when the engine is created) keeps the batch kernels
     // for every size.
     const int sk = (!m->no_small && batch <= mse_siglip::SMALL_BATCH) ? 1 : 0;
-    auto trunk = [&](int b0, int batch, hipStream_t st) -> int {
-        const size_t r0 = (size_t)b0 * TS, bh0 = (size_t)b0 * m->H;
+    auto trunk = [&](int b0, int batch, hipStream_t st, int) -> int {
+        const size_t r0 = (size_t)b0 * TS;
         const void* v_img = reinterpret_cast<const char*>(img) + (size_t)b0 * img_stride;
         uint16_t* v_patches = m->patches + r0 * m->kpe_pad;
-        uint16_t *v_x = m->x + r0 * D, *v_h = m->h + r0 * D, *v_dlt = m->dlt + r0 * DP, *v_mlp_h = m->mlp_h + r0 * m->mlp_pad;
-        uint16_t* v_kvb = m->kvb + r0 * 2 * D;
-        float* v_ln_stats = m->ln_stats ? m->ln_stats + 2 * r0 : nullptr;
-        float* v_ln_part = m->ln_part ? m->ln_part + 2 * r0 : nullptr;
-        uint16_t* v_qb = m->qb + bh0 * m->n_pad * m->dh_pad;
-        uint16_t* v_kb = m->kb + bh0 * m->n_pad * attention_k_stride();
-        uint16_t* v_vtb = m->vtb + bh0 * m->dv_pad * m->n_pad;
+        uint16_t *v_x = m->x + r0 * D, *v_h = m->h + r0 * D, *v_kvb = m->kvb + r0 * 2 * D;
         float* v_pool_a = m->pool_a + (size_t)b0 * D;
         const int M = batch * TS;   // rows incl. the (finite, never read as keys) padding rows of every image
         const int Mp = (int)round_up(M, 256);
@@ -405,80 +281,16 @@ int mse_siglip_encode_image(mse_siglip* m, const void* images, int dtype, int on
             g.skinny = sk;
             if (launch_gemm(GEMM_EPI_PATCH, g, st)) return -1;
         }
-        const bool fused = !sk && m->fused && gemm_fused_ok(Mp, D, m->mlp_pad, m->H, m->dh, TS, m->n_pad, M);
-        if (fused && launch_row_stats(v_x, D, D, (size_t)Mp, c.eps, v_ln_stats, st)) return -1;
-        for (int i = 0; fused && i < c.depth; i++) {  // Encoder1DBlock (model.py:26-44) with LN1 / LN2 folded into the GEMMs around them
-            const Block& b = m->blocks[i];
-            {
-                GemmLaunch g; g.x = v_x; g.w = b.wqkv16; g.bias = b.bqkv2; g.csum = b.cqkv; g.ln_stats = v_ln_stats;
-                g.M = Mp; g.N = 3 * D; g.K = D; g.m_valid = M; g.tokens = TS;
-                g.q = v_qb; g.k = v_kb; g.vt = v_vtb; g.heads = m->H; g.dh = m->dh; g.dh_pad = m->dh_pad; g.n_pad = m->n_pad;
-                g.dv_pad = m->dv_pad; g.kdh_pad = attention_k_stride();
-                if (launch_gemm_fused(GEMM_EPI_QKV, g, st)) return -1;
-            }
-            if (launch_attention(v_qb, v_kb, v_vtb, batch, m->H, T, m->n_pad, m->dh, m->dh_pad, m->dv_pad, v_h, D, TS, st)) return -1;
-            {
-                GemmLaunch g; g.x = v_h; g.w = b.wproj; g.bias = b.bproj; g.M = Mp; g.N = DP; g.K = D; g.m_valid = M;
-                g.xres = v_x; g.ldr = D; g.part = v_ln_part; g.part_rows = m->m_pad; g.n_valid = D; g.sink = m->sink;
-                if (launch_gemm_fused(GEMM_EPI_RESID_LN, g, st)) return -1;   // x += attention branch, statistics for LN2
-            }
-            if (launch_ln_finalize(v_ln_part, m->m_pad, D / 64, (size_t)Mp, c.eps, v_ln_stats, st)) return -1;
-            {
-                GemmLaunch g; g.x = v_x; g.w = b.w116; g.bias = b.b12; g.csum = b.c1; g.ln_stats = v_ln_stats;
-                g.M = Mp; g.N = m->mlp_pad; g.K = D; g.m_valid = M; g.out_bf16 = v_mlp_h; g.ldo = m->mlp_pad; g.gelu_tanh = gelu_tanh;
-                if (launch_gemm_fused(GEMM_EPI_GELU, g, st)) return -1;
-            }
-            {
-                GemmLaunch g; g.x = v_mlp_h; g.w = b.w2; g.bias = b.b2; g.M = Mp; g.N = DP; g.K = m->mlp_pad; g.m_valid = M;
-                g.xres = v_x; g.ldr = D; g.part = v_ln_part; g.part_rows = m->m_pad; g.n_valid = D; g.sink = m->sink;
-                if (launch_gemm_fused(GEMM_EPI_RESID_LN, g, st)) return -1;   // x += MLP branch, statistics for the next LN1
-            }
-            if (i + 1 < c.depth && launch_ln_finalize(v_ln_part, m->m_pad, D / 64, (size_t)Mp, c.eps, v_ln_stats, st)) return -1;
-        }
+        BlockRun r; r.b0 = b0; r.nb = batch; r.tokens = T; r.skinny = sk;
+        r.fused = !sk && m->fused && gemm_fused_ok(Mp, D, m->mlp_pad, m->H, m->dh, TS, m->n_pad, M);
+        r.n_branch = sk ? D : DP; r.ld_branch = DP;   // columns >= D of the branch are padding
         // one image: fc2 (K = 4352 for 1152 columns) is split four ways along K across workgroups; its partial sums and bias are added
         // by the LayerNorm that consumes the branch (siglip_kernels.hip gemm_small_ksplit)
-        const int ksp = sk ? gemm_small_ksplit(M, D, m->mlp_pad) : 1;
-        LnDelta fc2_delta;   // what the LayerNorm after an fc2 adds to x (bias filled in per block)
-        if (ksp > 1) { fc2_delta.parts = m->kparts; fc2_delta.n_parts = ksp; fc2_delta.part_stride = (size_t)gemm_small_ksplit_rows(M) * D; fc2_delta.ldp = D; }
-        else { fc2_delta.bf16 = v_dlt; fc2_delta.ldd = DP; }
-        for (int i = 0; !fused && i < c.depth; i++) {  // Encoder1DBlock (model.py:26-44)
-            const Block& b = m->blocks[i];
-            // x += (fc2 output of the previous block), then LayerNorm
-            LnDelta d1;
-            if (i) { d1 = fc2_delta; d1.bias = m->blocks[i - 1].b2; }
-            if (launch_layernorm_d(v_x, 1, D, d1, b.ln1_g, b.ln1_b, c.eps, D, M, v_h, D, nullptr, st)) return -1;
-            {
-                GemmLaunch g; g.x = v_h; g.w = b.wqkv; g.bias = b.bqkv; g.M = Mp; g.N = 3 * D; g.K = D; g.m_valid = M; g.tokens = TS;
-                g.q = v_qb; g.k = v_kb; g.vt = v_vtb; g.heads = m->H; g.dh = m->dh; g.dh_pad = m->dh_pad; g.n_pad = m->n_pad;
-                g.dv_pad = m->dv_pad; g.kdh_pad = attention_k_stride(); g.skinny = sk;
-                if (launch_gemm(GEMM_EPI_QKV, g, st)) return -1;
-            }
-            if (launch_attention(v_qb, v_kb, v_vtb, batch, m->H, T, m->n_pad, m->dh, m->dh_pad, m->dv_pad, v_h, D, TS, st)) return -1;
-            {
-                GemmLaunch g; g.x = v_h; g.w = b.wproj; g.bias = b.bproj; g.M = Mp; g.N = sk ? D : DP; g.K = D; g.m_valid = M;
-                g.out_bf16 = v_dlt; g.ldo = DP;   // residual branch: added to x by the next LayerNorm (columns >= D are padding)
-                g.skinny = sk;
-                if (launch_gemm(GEMM_EPI_BF16, g, st)) return -1;
-            }
-            if (launch_layernorm(v_x, 1, D, v_dlt, DP, b.ln2_g, b.ln2_b, c.eps, D, M, v_h, D, nullptr, st)) return -1;   // x += attention branch
-            {
-                GemmLaunch g; g.x = v_h; g.w = b.w1; g.bias = b.b1; g.M = Mp; g.N = m->mlp_pad; g.K = D; g.m_valid = M;
-                g.out_bf16 = v_mlp_h; g.ldo = m->mlp_pad; g.gelu_tanh = gelu_tanh; g.skinny = sk;
-                if (launch_gemm(GEMM_EPI_GELU, g, st)) return -1;
-            }
-            {
-                GemmLaunch g; g.x = v_mlp_h; g.w = b.w2; g.bias = b.b2; g.M = Mp; g.N = sk ? D : DP; g.K = m->mlp_pad; g.m_valid = M;
-                g.out_bf16 = v_dlt; g.ldo = DP;   // residual branch: added to x by the next LayerNorm
-                g.skinny = sk;
-                if (ksp > 1) { g.kpart = m->kparts; g.kpart_stride = fc2_delta.part_stride; g.ksplit = ksp; g.ldr = D; }
-                if (launch_gemm(ksp > 1 ? GEMM_EPI_PART : GEMM_EPI_BF16, g, st)) return -1;
-            }
-        }
-        {
-            LnDelta df;
-            if (c.depth && !fused) { df = fc2_delta; df.bias = m->blocks[c.depth - 1].b2; }
-            if (launch_layernorm_d(v_x, 1, D, df, m->lnf_g, m->lnf_b, c.eps, D, M, v_h, D, nullptr, st)) return -1;  // model.py:50,55
-        }
+        r.ksp_fc2 = sk ? gemm_small_ksplit(M, D, m->mlp_pad) : 1;
+        r.kpart_stride = (size_t)gemm_small_ksplit_rows(M) * D;
+        LnDelta df;   // what the final LayerNorm adds to x
+        if (run_blocks(*m, r, st, &df)) return -1;
+        if (launch_layernorm_d(v_x, 1, D, df, m->lnf_g, m->lnf_b, c.eps, D, M, v_h, D, nullptr, st)) return -1;  // model.py:50,55
         // MAPHead (model.py:82-111)
         {
             GemmLaunch g; g.x = v_h; g.w = m->wkv; g.bias = m->bkv; g.M = Mp; g.N = 2 * D; g.K = D; g.m_valid = M;
@@ -492,19 +304,10 @@ int mse_siglip_encode_image(mse_siglip* m, const void* images, int dtype, int on
     // sub-batch's next kernel takes them.  MSE_SIGLIP_STREAMS=1 keeps the whole batch on one stream.
     const int parts = std::min(m->n_side + 1, batch / 16);
     const int per = parts > 1 ? (int)round_up((size_t)(batch + parts - 1) / parts, 8) : batch;
-    if (parts > 1 && per < batch) {
-        MSE_HIP_TRY(hipEventRecord(m->ev_fork, st));
-        int used = 0;
-        for (int b0 = per; b0 < batch; b0 += per, used++) {
-            MSE_HIP_TRY(hipStreamWaitEvent(m->side[used], m->ev_fork, 0));
-            if (trunk(b0, std::min(per, batch - b0), m->side[used])) return -1;
-            MSE_HIP_TRY(hipEventRecord(m->ev_join[used], m->side[used]));
-        }
-        if (trunk(0, per, st)) return -1;
-        for (int i = 0; i < used; i++) MSE_HIP_TRY(hipStreamWaitEvent(st, m->ev_join[i], 0));
-    } else if (trunk(0, batch, st)) {
-        return -1;
-    }
+    std::vector<SideRange> sides;
+    for (int b0 = per; parts > 1 && b0 < batch; b0 += per)
+        sides.push_back(SideRange{b0, std::min(per, batch - b0), m->side[sides.size()], m->ev_join[sides.size()]});
+    if (fork_join(st, m->ev_fork, sides, sides.empty() ? batch : per, trunk)) return -1;
     // proj, LayerNorm, MLP with residual on the matrix cores: the batch is one (or a few) 256-row block of the same GEMM kernels
     // (rows >= batch are zero padding; the fp32 accumulating epilogue builds pool_o = proj, then pool_o += fc2)
     {

@@ -68,7 +68,55 @@ def is_plain_bmp(data, size):
     return (w.value, h.value) == tuple(size)
 
 
-class SiglipImageEngine:
+class _SiglipEngine:
+    """Weight loading and release shared by the towers: the C functions `<_C>_n_weights`, `_weight_name`, `_set_weight`,
+    `_finalize` and `_destroy` of the engine handle `_h`."""
+    _C = None   # C prefix of the tower: "mse_siglip" / "mse_siglip_text"
+
+    def _fn(self, suffix):
+        return getattr(ffi.lib(), self._C + suffix)
+
+    def weight_names(self):
+        name, n = self._fn("_weight_name"), self._fn("_n_weights")
+        return [name(self._h, i).decode() for i in range(n(self._h))]
+
+    def set_weight(self, name, tensor):
+        a = _to_numpy_f32(tensor)
+        shape = (C.c_size_t * a.ndim)(*a.shape)
+        check(self._fn("_set_weight")(self._h, name.encode(), a.ctypes.data_as(ffi.f32p), shape, a.ndim),
+              f"{self._C[4:]}_set_weight({name})")
+
+    @staticmethod
+    def _state_key(state, name):   # the state dict's key of engine weight `name`
+        return name
+
+    @classmethod
+    def from_state_dict(cls, state, config=None, max_batch=32, eps=1e-6, gelu="erf"):
+        """state: mapping of open_clip names -> tensors; missing tensors are an error (the engine refuses to run half-loaded)."""
+        eng = cls(config, max_batch, eps, gelu)
+        for name in eng.weight_names():
+            key = cls._state_key(state, name)
+            if key not in state:
+                raise MseError(f"state dict lacks '{name}'")
+            eng.set_weight(name, state[key])
+        check(eng._fn("_finalize")(eng._h), eng._C[4:] + "_finalize")
+        return eng
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._fn("_destroy")(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SiglipImageEngine(_SiglipEngine):
+    _C = "mse_siglip"
+
     def __init__(self, config=None, max_batch=32, eps=1e-6, gelu="erf"):
         cfg = dict(SO400M_384 if config is None else config)
         self.cfg = cfg
@@ -78,28 +126,10 @@ class SiglipImageEngine:
         self._h = check_ptr(ffi.lib().mse_siglip_create(C.byref(c)), "mse_siglip_create")
         self.embedding_size = cfg["emb_dim"]
 
-    def weight_names(self):
-        L = ffi.lib()
-        return [L.mse_siglip_weight_name(self._h, i).decode() for i in range(L.mse_siglip_n_weights(self._h))]
-
-    def set_weight(self, name, tensor):
-        a = _to_numpy_f32(tensor)
-        shape = (C.c_size_t * a.ndim)(*a.shape)
-        check(ffi.lib().mse_siglip_set_weight(self._h, name.encode(), a.ctypes.data_as(ffi.f32p), shape, a.ndim),
-              f"set_weight({name})")
-
-    @classmethod
-    def from_state_dict(cls, state, config=None, max_batch=32, eps=1e-6, gelu="erf"):
-        """state: mapping of open_clip names (`visual.trunk.blocks.0.attn.qkv.weight`, ...) or the same without
-        the `visual.` prefix.  Missing tensors are an error (the engine refuses to run half-loaded)."""
-        eng = cls(config, max_batch, eps, gelu)
-        for name in eng.weight_names():
-            key = name if name in state else "visual." + name
-            if key not in state:
-                raise MseError(f"state dict lacks '{name}'")
-            eng.set_weight(name, state[key])
-        check(ffi.lib().mse_siglip_finalize(eng._h), "siglip_finalize")
-        return eng
+    @staticmethod
+    def _state_key(state, name):
+        """open_clip names (`visual.trunk.blocks.0.attn.qkv.weight`, ...) or the same without the `visual.` prefix."""
+        return name if name in state else "visual." + name
 
     def encode_image(self, images, normalize=True, out="f32"):
         """images: [b,3,H,W] float32 or float16 numpy array, already normalised (x/127.5-1).
@@ -174,17 +204,6 @@ class SiglipImageEngine:
         check(ffi.lib().mse_siglip_debug_residual(self._h, out.ctypes.data_as(ffi.f32p)), "debug_residual")
         return out.reshape(batch, n, self.embedding_size)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            ffi.lib().mse_siglip_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 # ---- text tower ------------------------------------------------------------------------------------------------
 SO400M_TEXT = dict(width=1152, layers=27, heads=16, mlp_dim=4304, context_length=64, vocab_size=32000)  # misc/clip_accursed.py:31-55
@@ -233,7 +252,9 @@ def pad_tokens(token_lists, context_length=64, pad_id=PAD_ID):
     return out
 
 
-class SiglipTextEngine:
+class SiglipTextEngine(_SiglipEngine):
+    _C = "mse_siglip_text"
+
     def __init__(self, config=None, max_batch=32, eps=1e-6, gelu="erf"):
         cfg = dict(SO400M_TEXT if config is None else config)
         self.cfg = cfg
@@ -243,27 +264,6 @@ class SiglipTextEngine:
         self._h = check_ptr(ffi.lib().mse_siglip_text_create(C.byref(c)), "mse_siglip_text_create")
         self.embedding_size = cfg["width"]
         self.context_length = cfg["context_length"]
-
-    def weight_names(self):
-        L = ffi.lib()
-        return [L.mse_siglip_text_weight_name(self._h, i).decode() for i in range(L.mse_siglip_text_n_weights(self._h))]
-
-    def set_weight(self, name, tensor):
-        a = _to_numpy_f32(tensor)
-        shape = (C.c_size_t * a.ndim)(*a.shape)
-        check(ffi.lib().mse_siglip_text_set_weight(self._h, name.encode(), a.ctypes.data_as(ffi.f32p), shape, a.ndim),
-              f"text set_weight({name})")
-
-    @classmethod
-    def from_state_dict(cls, state, config=None, max_batch=32, eps=1e-6, gelu="erf"):
-        """state: open_clip state dict (keys `text.*`); missing tensors are an error."""
-        eng = cls(config, max_batch, eps, gelu)
-        for name in eng.weight_names():
-            if name not in state:
-                raise MseError(f"state dict lacks '{name}'")
-            eng.set_weight(name, state[name])
-        check(ffi.lib().mse_siglip_text_finalize(eng._h), "siglip_text_finalize")
-        return eng
 
     def encode_text(self, tokens, normalize=True, out="f32"):
         """tokens: int [b, context_length] (already tokenised and padded).  Returns float32 [b, width] or fp16 bits."""
@@ -300,14 +300,3 @@ class SiglipTextEngine:
 
     def __call__(self, tokens):
         return self.encode_text(tokens)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            ffi.lib().mse_siglip_text_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
