@@ -11,6 +11,11 @@ A "step" = one batch of Q queries scored against the whole index (all shards), t
           shard and the records are written into the root device's buffer over peer mappings.
 Inputs (index rows and query batches) are synthetic, generated on the device, and resident in HBM
 before the timed region.  One JSON line on stdout (rank 0).
+
+A plain run does only what the headline needs: set-up (rows, queries, the measured pick of queries per pass), warm-up, the timed
+steps, the --dump-outputs files and the line.  `--full` adds everything else, after the headline: the 128-query pass, the check
+against the exact kernel, the peer-store exchange beside RCCL, the side legs (callers, shard step, SigLIP, PQ, graph, approximate
+search at 1e8 rows, graph index), the sharded approximate-search legs (N > 1) and the CPU baseline.
 """
 import argparse
 import json
@@ -901,7 +906,7 @@ def dry_run(args):
                        "exchange": {"kind": shape + ("; ONE ncclAllGather of the packed 12 B/record blocks per step" if n_gpus > 1 else ""),
                                     "rccl_ranks": 0} if n_gpus > 1 else None},
             "roofline": {"bound": "hbm", "kernel": "scan_mfma_kernel<2,20>", "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None, "traffic": None},
-            "sharded_ann": ({"skipped": "dry run"} if n_gpus > 1 and not args.no_sharded_ann else None), "dry_run": True}
+            "sharded_ann": ({"skipped": "dry run"} if args.full and n_gpus > 1 and not args.no_sharded_ann else None), "dry_run": True}
     emit(full, None)
 
 
@@ -925,6 +930,10 @@ def main():
     ap.add_argument("--queries", type=int, default=0,
                     help="queries per step (one scan pass over the rows serves up to 256); 0 = pick 128 or 256 by measured queries/s")
     ap.add_argument("--k", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run everything else the bench measures or checks: the 128-query pass, the check against "
+                         "the exact kernel, the peer-store exchange beside RCCL, the side legs, the sharded approximate-search legs and the CPU "
+                         "baseline.  The --no-* options below skip parts of a --full run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--logical-shards", action="store_true",
                     help="developer dry run of the in-process --gpus N path on fewer devices (shard g on device g mod count)")
@@ -946,7 +955,7 @@ def main():
                     help="sampled entry points of the graph-scale search (0: the medioid alone; -1: max(4096, rows / 1500))")
     ap.add_argument("--graph-kinds", default="hard,easy,ood", help="synthetic sets of the graph-index leg (bench_ann.py): easy, hard, ood")
     ap.add_argument("--graph-1e8", action="store_true",
-                    help="OPT-IN: the 1e8-row graph-index leg (a 10-13 minute build, guarded by --graph-1e8-budget); not part of the default command")
+                    help="OPT-IN: the 1e8-row graph-index leg (a 10-13 minute build, guarded by --graph-1e8-budget); with --full only, and not part of it by default")
     ap.add_argument("--no-graph-1e8", action="store_true", help="accepted for older command lines; the leg is opt-in now (--graph-1e8)")
     ap.add_argument("--graph-1e8-budget", type=float, default=1100.0,
                     help="seconds the predicted 1e8-row build may take (two passes if both fit, else one; beyond it the leg is skipped with that reason); "
@@ -971,6 +980,8 @@ def main():
         args.time_budget = 1500.0
     if args.gpus < 1 or args.steps < 1 or args.warmup < 0:
         raise SystemExit("--gpus >= 1, --steps >= 1, --warmup >= 0")
+    if args.graph_1e8 and not args.full:
+        raise SystemExit("--graph-1e8 is a leg of a --full run")
     if args.dry_run:
         return dry_run(args)
 
@@ -1193,7 +1204,7 @@ def main():
             breakdown = {"scan_ms": scan_ms / max(scan_launches, 1), "local_search_ms": t["local_search_ms"],
                          "tail_ms": t["local_search_ms"] - scan_ms / max(scan_launches, 1), "exchange_ms": t["exchange_ms"],
                          "merge_ms": t["merge_ms"], "wall_ms": t["wall_ms"], "of": "last timed step; slowest shard per leg"}
-            if group.exchange == group.EXCHANGE_RCCL:
+            if args.full and group.exchange == group.EXCHANGE_RCCL:
                 # the same index over the peer-store exchange, timed right after the headline (second variant, same line)
                 group.set_exchange(group.EXCHANGE_PEER)
                 for i in range(2):
@@ -1226,7 +1237,7 @@ def main():
     # second operating point, outside the headline's timed region: 128 queries per pass, where the scan is HBM-bound
     # (at 256 the same stream feeds twice the MFMA work and the pass is bound by the chip's power budget instead)
     alt = None
-    if nq > 128:
+    if args.full and nq > 128:
         searcher.scan_timing(2)
         n_alt = max(3, args.steps // 2)
         sync_all()
@@ -1251,20 +1262,22 @@ def main():
 
     # correctness spot check outside the timed region: the batched (MFMA) answer of the last step must equal the
     # exact-order kernel's answer for the same queries (two independent kernels), over the whole (sharded) index
-    qptr = batch_ptr(args.warmup + args.steps - 1)
-    m = min(8, nq)
-    chk_s = torch.empty((m, k), dtype=torch.int64, device="cuda")
-    chk_i = torch.empty((m, k), dtype=torch.int32, device="cuda")
-    if in_process:
-        group.bruteforce_topk_dev(qptr, m, k, chk_s.data_ptr(), chk_i.data_ptr(), mse.MODE_EXACT)
-    elif host_exchange is not None:
-        host_step(qptr, m, mse.MODE_EXACT, chk_s, chk_i)
-    elif comm is not None:
-        comm.search_dev(searcher, qptr, m, k, chk_s.data_ptr(), chk_i.data_ptr(), mse.MODE_EXACT, id_offset=lo)
-    else:
-        searcher.bruteforce_topk_dev(qptr, m, k, chk_s.data_ptr(), chk_i.data_ptr(), mse.MODE_EXACT, id_offset=lo)
-    sync_all()
-    verified = bool(torch.equal(chk_s, out_s[:m]) and torch.equal(chk_i, out_i[:m]))
+    verified = None
+    if args.full:
+        qptr = batch_ptr(args.warmup + args.steps - 1)
+        m = min(8, nq)
+        chk_s = torch.empty((m, k), dtype=torch.int64, device="cuda")
+        chk_i = torch.empty((m, k), dtype=torch.int32, device="cuda")
+        if in_process:
+            group.bruteforce_topk_dev(qptr, m, k, chk_s.data_ptr(), chk_i.data_ptr(), mse.MODE_EXACT)
+        elif host_exchange is not None:
+            host_step(qptr, m, mse.MODE_EXACT, chk_s, chk_i)
+        elif comm is not None:
+            comm.search_dev(searcher, qptr, m, k, chk_s.data_ptr(), chk_i.data_ptr(), mse.MODE_EXACT, id_offset=lo)
+        else:
+            searcher.bruteforce_topk_dev(qptr, m, k, chk_s.data_ptr(), chk_i.data_ptr(), mse.MODE_EXACT, id_offset=lo)
+        sync_all()
+        verified = bool(torch.equal(chk_s, out_s[:m]) and torch.equal(chk_i, out_i[:m]))
 
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64)
@@ -1273,7 +1286,7 @@ def main():
 
     # --gpus N > 1: the approximate-search paths over the same kind of shards (rows AND their codes / graphs partitioned), same exchange
     sharded_ann = None
-    if n_gpus > 1 and not args.no_sharded_ann:
+    if args.full and n_gpus > 1 and not args.no_sharded_ann:
         import bench_ann
         try:
             with _stdout_to_stderr():
@@ -1287,8 +1300,8 @@ def main():
             sharded_ann = {"error": repr(e)}
         ffi.check(ffi.lib().mse_set_device(local_rank), "mse_set_device")
 
-    # ---- side legs: each under the command's time budget (a leg that would not fit what is left is skipped and says so), a failure
-    # is reported in the leg's object, never fatal; seconds per leg go to the detail file ----
+    # ---- side legs (--full): each under the command's time budget (a leg that would not fit what is left is skipped and says so), a
+    # failure is reported in the leg's object, never fatal; seconds per leg go to the detail file ----
     leg_seconds = {}
     reserve = 0.0 if (args.no_cpu_baseline or n_gpus > 1) else 45.0      # the CPU baseline still comes after the legs
 
@@ -1310,31 +1323,31 @@ def main():
 
     leg_seconds["setup_and_headline"] = round(time.perf_counter() - T_START, 1)
     one = rank == 0 and n_gpus == 1 and world == 1
-    callers_line = run_leg("concurrent_callers", 15, lambda: concurrent_callers_bench(vecs, k, nq * args.steps / elapsed), one and not args.no_callers)
-    index_line = run_leg("index_callers_1e5", 10, lambda: index_callers_bench(k), one and not args.no_callers)
-    shard_line = run_leg("shard_point", 10, lambda: shard_point_bench(k, nq, elapsed / args.steps * 1e3), one and not args.no_shard_point)
+    callers_line = run_leg("concurrent_callers", 15, lambda: concurrent_callers_bench(vecs, k, nq * args.steps / elapsed), args.full and one and not args.no_callers)
+    index_line = run_leg("index_callers_1e5", 10, lambda: index_callers_bench(k), args.full and one and not args.no_callers)
+    shard_line = run_leg("shard_point", 10, lambda: shard_point_bench(k, nq, elapsed / args.steps * 1e3), args.full and one and not args.no_shard_point)
 
     # ---- second half of BASELINE.json's metric: SigLIP image embeds/s/GPU (replicas, no collective) ----
     siglip_line = None
-    if not args.no_siglip:
+    if args.full and not args.no_siglip:
         if world > 1:
             siglip_line = siglip_bench(args, world, rank, dist)       # every rank takes part (a barrier inside): no per-rank skipping
         else:
             siglip_line = run_leg("siglip", 45, lambda: siglip_bench(args, world, rank, dist))
-    pq_line = run_leg("pq_scan", 25, lambda: pq_bench(args), rank == 0 and n_gpus == 1 and not args.no_pq)
-    graph_line = run_leg("graph_search", 15, lambda: graph_bench(args), rank == 0 and n_gpus == 1 and not args.no_graph)
+    pq_line = run_leg("pq_scan", 25, lambda: pq_bench(args), args.full and rank == 0 and n_gpus == 1 and not args.no_pq)
+    graph_line = run_leg("graph_search", 15, lambda: graph_bench(args), args.full and rank == 0 and n_gpus == 1 and not args.no_graph)
 
     gscale_line = ann_line = g1e8_line = request_line = None
-    if rank == 0 and n_gpus == 1 and not (args.no_graph_scale and args.no_ann_scale):
+    if args.full and rank == 0 and n_gpus == 1 and not (args.no_graph_scale and args.no_ann_scale):
         del searcher, vecs                             # the 230 GB index makes room for the clustered sets of the next two legs
         import gc
         gc.collect()
-    if one and not args.no_ann_scale:
+    if args.full and one and not args.no_ann_scale:
         ann_line = run_leg("ann_1e8", 30, lambda: ann_scale_bench(args))
         import gc
         gc.collect()
         torch.cuda.empty_cache()
-    if rank == 0 and n_gpus == 1 and not args.no_graph_scale:
+    if args.full and rank == 0 and n_gpus == 1 and not args.no_graph_scale:
         # one row per synthetic set (bench_ann.py): easy (rounds 1-4), hard (no micro-clusters), ood (queries from another distribution,
         # graph built with a query sample + robust_stitch); the request path's call shape (T threads x 1 query) on the hard set
         import gc
@@ -1423,10 +1436,11 @@ def main():
                          "frac_of_measured_copy_ceiling": (achieved / 6290.0) if achieved else None},
             "step_breakdown": breakdown,
             "exchange_alt": exchange_alt,
-            "verified_vs_exact_kernel": verified,
             "hbm_bound_point": alt,
             "certificate": stats,
         }
+        if verified is not None:
+            line["verified_vs_exact_kernel"] = verified
         if callers_line:
             line["concurrent_callers"] = callers_line
         if index_line:
@@ -1451,7 +1465,7 @@ def main():
             line["sharded_ann"] = sharded_ann
         if note:
             line["note"] = note
-        if n_gpus == 1 and not args.no_cpu_baseline:
+        if args.full and n_gpus == 1 and not args.no_cpu_baseline:
             t_leg = time.perf_counter()
             line["cpu_baseline"] = cpu_baseline(n_total, k)
             if graph_line and "error" not in graph_line and "skipped" not in graph_line:

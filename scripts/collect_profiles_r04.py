@@ -8,7 +8,7 @@ R = os.path.join(ROOT, "gpurun_out", "r04") + "/"
 P = os.path.join(ROOT, "profiles") + "/"
 prof = json.loads(open(R + "bench_profiled.json").readline())
 open(P + "r04_bench_1e8_profiled.json", "w").write(json.dumps(prof) + "\n")
-hdr = ("# rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --steps 12 --warmup 2 --no-siglip --no-pq --no-graph --no-graph-scale --no-cpu-baseline --no-callers --no-shard-point --no-ann-scale\n"
+hdr = ("# rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --full --steps 12 --warmup 2 --no-siglip --no-pq --no-graph --no-graph-scale --no-cpu-baseline --no-callers --no-shard-point --no-ann-scale\n"
        "# (scripts/profile_r04.sh; one MI355X, 1e8 x 1152 fp16 rows).  The same command printed (profiles/r04_bench_1e8_profiled.json): %.0f queries/s, %.2f ms per step at %d queries per step,\n"
        "# roofline.avg_launch_ms %.3f (HIP events inside bench.py) -- the headline kernel below (scan_mfma_kernel<2,20> = the 320-query pass since the second half of round 4): 4 dispatches of the\n"
        "# queries-per-pass pick + 2 warm-up + 12 timed + the restore step, all at 1e8 rows.  scan_mfma2d_kernel<3,16> = the 256-query pass, scan_mfma_kernel<3,12> = 192, <3,8> = 128 (pick + hbm_bound_point).\n"

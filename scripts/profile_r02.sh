@@ -18,7 +18,7 @@ with open(sys.argv[3], "w") as f:
 PY
 }
 # 1. the bench command itself (all legs but the CPU baseline and the 1e7 graph leg, which add minutes of host work under the profiler)
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o b -- python $R/bench.py --no-cpu-baseline --no-graph-scale > $OUT/bench_profiled.json 2> $OUT/bench_profiled.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o b -- python $R/bench.py --full --no-cpu-baseline --no-graph-scale > $OUT/bench_profiled.json 2> $OUT/bench_profiled.err
 summarise $(find $OUT/bench -name "*kernel_stats.csv" | head -1) "# rocprofv3 --kernel-trace --stats -- python bench.py --no-cpu-baseline --no-graph-scale   (MI355X, round 2: 1e8 x 1152 fp16, 256 queries/step, 20 steps + 3 warm-up, then 10 steps at 128 queries)" $OUT/r02_bench_1e8_kernel_stats.txt
 python - $OUT/bench <<'PY' >> $OUT/r02_bench_1e8_kernel_stats.txt
 import csv, glob, sys
@@ -34,7 +34,7 @@ for k, v in d.items():
 PY
 # 2. HBM traffic of the scan, one counter per pass
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/pmc_$c -o p -- python $R/bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-siglip --no-pq --no-graph --no-graph-scale > $OUT/pmc_$c.log 2>&1
+  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/pmc_$c -o p -- python $R/bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-siglip --no-pq --no-graph --no-graph-scale > $OUT/pmc_$c.log 2>&1
 done
 python - $OUT <<'PY' > $OUT/r02_pmc_traffic.json
 import csv, glob, json, sys

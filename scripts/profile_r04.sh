@@ -18,7 +18,7 @@ for r in rows[:22]:
     print("%7s %11.3f %11.3f %7s  %s" % (r["Calls"], float(r["TotalDurationNs"]) / 1e6, float(r["AverageNs"]) / 1e3, r["Percentage"], r["Name"][:160]))
 PY
 }
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o b -- python $R/bench.py --steps 12 --warmup 2 --no-siglip --no-pq --no-graph --no-graph-scale --no-cpu-baseline --no-callers --no-shard-point --no-ann-scale > $OUT/bench_profiled.json 2> $OUT/bench_profiled.err
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o b -- python $R/bench.py --full --steps 12 --warmup 2 --no-siglip --no-pq --no-graph --no-graph-scale --no-cpu-baseline --no-callers --no-shard-point --no-ann-scale > $OUT/bench_profiled.json 2> $OUT/bench_profiled.err
 stats $OUT/bench $OUT/bench_kernel_stats.txt; rm -rf $OUT/bench
 timeout 600 python $R/scripts/scan_pass_probe.py 1e8 4 > $OUT/scan_variants.txt 2> $OUT/scan_variants.err
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/pq -o pq -- python $R/scripts/pq_scan_bench.py 1e8 > $OUT/pq_bench.log 2>&1
@@ -26,7 +26,7 @@ grep "^{" $OUT/pq_bench.log | tail -1 > $OUT/pq_bench_line.json
 stats $OUT/pq $OUT/pq_kernel_stats.txt; rm -rf $OUT/pq
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/pmc_$c -o pmc -- python $R/scripts/pq_scan_bench.py 1e8 > $OUT/pmc_$c.log 2>&1
-  timeout 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/pmcs_$c -o pmc -- python $R/bench.py --steps 4 --warmup 1 --no-siglip --no-pq --no-graph --no-graph-scale --no-cpu-baseline --no-callers --no-shard-point --no-ann-scale > $OUT/pmcs_$c.log 2>&1
+  timeout 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/pmcs_$c -o pmc -- python $R/bench.py --full --steps 4 --warmup 1 --no-siglip --no-pq --no-graph --no-graph-scale --no-cpu-baseline --no-callers --no-shard-point --no-ann-scale > $OUT/pmcs_$c.log 2>&1
 done
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/pmcg_$c -o pmc -- python $R/scripts/siglip_bench.py 256 2 27 > $OUT/pmcg_$c.log 2>&1

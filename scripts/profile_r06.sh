@@ -19,7 +19,7 @@ for r in rows[:24]:
 PY
 }
 SCAN="--steps 12 --warmup 2 --no-siglip --no-pq --no-graph --no-graph-scale --no-cpu-baseline --no-callers --no-shard-point --no-ann-scale"
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o b -- python $R/bench.py $SCAN --detail $OUT/bench_profiled_detail.json > $OUT/bench_profiled.json 2> $OUT/bench_profiled.err
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o b -- python $R/bench.py --full $SCAN --detail $OUT/bench_profiled_detail.json > $OUT/bench_profiled.json 2> $OUT/bench_profiled.err
 stats $OUT/bench $OUT/bench_kernel_stats.txt; rm -rf $OUT/bench
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/sg -o s -- python $R/scripts/siglip_bench.py 256 3 27 > $OUT/siglip_b256.log 2>&1
 stats $OUT/sg $OUT/siglip_b256_kernel_stats.txt; rm -rf $OUT/sg
@@ -27,7 +27,7 @@ timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/tx -o t
 stats $OUT/tx $OUT/text_b256_kernel_stats.txt; rm -rf $OUT/tx
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/pmc_$c -o pmc -- python $R/scripts/pq_trace_r05.py burst > $OUT/pmc_$c.log 2>&1
-  timeout 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/pmcs_$c -o pmc -- python $R/bench.py --steps 4 --warmup 1 ${SCAN#--steps 12 --warmup 2} --detail $OUT/pmcs_detail.json > $OUT/pmcs_$c.log 2>&1
+  timeout 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/pmcs_$c -o pmc -- python $R/bench.py --full --steps 4 --warmup 1 ${SCAN#--steps 12 --warmup 2} --detail $OUT/pmcs_detail.json > $OUT/pmcs_$c.log 2>&1
   timeout 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/pmcg_$c -o pmc -- python $R/scripts/siglip_bench.py 256 2 27 > $OUT/pmcg_$c.log 2>&1
 done
 python $R/scripts/pmc_traffic_r05.py $OUT > $OUT/pmc_traffic.json

@@ -268,6 +268,30 @@ def test_bench_dry_run_prints_the_small_line_for_every_launch_shape():
     assert r.returncode == 0
 
 
+def test_bench_side_legs_run_with_full_only():
+    """A plain `bench.py` run measures the headline alone; the side legs (here: the sharded approximate-search legs of --gpus N, which
+    a dry run reports as skipped) belong to `--full`, and the opt-in 1e8-row graph leg is refused without it."""
+    import json
+    import subprocess
+    import sys
+    bench = os.path.join(ROOT, "bench.py")
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+
+    def legs(*extra):
+        r = subprocess.run([sys.executable, bench, "--gpus", "2", "--dry-run"] + list(extra), env=env, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stderr
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line["n_gpus"] == 2 and line["value"] is None
+        return line["roofline"]["legs"]
+    assert "sharded_ann_note" not in legs()
+    assert legs("--full")["sharded_ann_note"] == "dry run"
+    assert "sharded_ann_note" not in legs("--full", "--no-sharded-ann")
+    r = subprocess.run([sys.executable, bench, "--dry-run", "--graph-1e8"], env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--full" in r.stderr
+    r = subprocess.run([sys.executable, bench, "--dry-run", "--graph-1e8", "--full"], env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+
+
 def test_bench_codec_trainer_lowers_the_query_aware_loss():
     """bench_ann.train_codec_aopq (bench data, not product: the 64 x 256 codec trained the way diskann/aopq_train.py:33-85 does -- Adam on
     the centroids against E_q[(q . residual)^2] under the codec's max-inner-product assignment, SVD rotation updates) on a small
