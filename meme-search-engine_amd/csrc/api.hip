@@ -44,6 +44,19 @@ void DevBuf::release() {
     p = nullptr;
     cap = 0;
 }
+int PinBuf::ensure(size_t bytes, size_t floor) {
+    if (bytes <= cap) return 0;
+    release();
+    const size_t want = std::max(2 * bytes, floor);
+    MSE_HIP_TRY(hipHostMalloc(&p, want, hipHostMallocDefault));
+    cap = want;
+    return 0;
+}
+void PinBuf::release() {
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    cap = 0;
+}
 
 int device_cu_count() {
     int dev = 0;
@@ -460,7 +473,6 @@ void mse_searcher_free(mse_searcher* s) {
     if (s->ev_wait) (void)hipEventDestroy(s->ev_wait);
     if (s->bev0) (void)hipEventDestroy(s->bev0);
     if (s->bev1) (void)hipEventDestroy(s->bev1);
-    if (s->pin) (void)hipHostFree(s->pin);
     delete s;
 }
 int mse_searcher_set_stream(mse_searcher* s, void* hip_stream) {

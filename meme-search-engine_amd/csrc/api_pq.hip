@@ -24,8 +24,7 @@ struct mse_index {
     mse_searcher* scratch = nullptr;
     mse::SharedExclusive rw;
     std::unique_ptr<mse::Coalescer> co;
-    void* pin = nullptr;         // pinned staging of the worker: queries up, [distances | labels] down
-    size_t pin_cap = 0;
+    mse::PinBuf pin;             // pinned staging of the worker: queries up, [distances | labels] down
     mse::DevBuf q32, out;
     std::atomic<uint64_t> retried_alone{0};
 };
@@ -194,17 +193,11 @@ int index_run_group(mse_index* idx, DispatchReq* const* reqs, size_t n_req) {
     for (size_t i = 0; i < n_req; i++) { total += reqs[i]->nq; kmax = std::max(kmax, reqs[i]->k); }
     if (total == 0 || kmax == 0 || n == 0) return 0;   // outputs were pre-filled with "nothing found"
     const size_t in_bytes = total * d * 4, out_bytes = total * kmax * 8;
-    if (idx->pin_cap < std::max(in_bytes, out_bytes)) {
-        if (idx->pin) (void)hipHostFree(idx->pin);
-        idx->pin = nullptr; idx->pin_cap = 0;
-        const size_t want = std::max<size_t>(2 * std::max(in_bytes, out_bytes), (size_t)1 << 20);
-        MSE_HIP_TRY(hipHostMalloc(&idx->pin, want, hipHostMallocDefault));
-        idx->pin_cap = want;
-    }
+    if (idx->pin.ensure(std::max(in_bytes, out_bytes), (size_t)1 << 20)) return -1;
     if (idx->q32.ensure(in_bytes) || idx->out.ensure(out_bytes)) return -1;
-    char* p = static_cast<char*>(idx->pin);
+    char* p = idx->pin.as<char>();
     for (size_t i = 0, o = 0; i < n_req; i++) { memcpy(p + o, reqs[i]->queries, reqs[i]->nq * d * 4); o += reqs[i]->nq * d * 4; }
-    MSE_HIP_TRY(hipMemcpyAsync(idx->q32.p, idx->pin, in_bytes, hipMemcpyHostToDevice, st));
+    MSE_HIP_TRY(hipMemcpyAsync(idx->q32.p, idx->pin.p, in_bytes, hipMemcpyHostToDevice, st));
     uint32_t* ids_dev = idx->out.as<uint32_t>();
     float* keys_dev = reinterpret_cast<float*>(idx->out.as<char>() + total * kmax * 4);
     s->last_widened = 0; s->last_max_groups = 0;
@@ -218,7 +211,7 @@ int index_run_group(mse_index* idx, DispatchReq* const* reqs, size_t n_req) {
                             : index_pass_exact(idx, idx->q32.as<float>() + q0 * d, m, (int)kmax, ids_dev + q0 * kmax, keys_dev + q0 * kmax, kmax);
         if (rc) return -1;
     }
-    MSE_HIP_TRY(hipMemcpyAsync(idx->pin, idx->out.p, out_bytes, hipMemcpyDeviceToHost, st));
+    MSE_HIP_TRY(hipMemcpyAsync(idx->pin.p, idx->out.p, out_bytes, hipMemcpyDeviceToHost, st));
     MSE_HIP_TRY(hipStreamSynchronize(st));
     const uint32_t* ids_h = reinterpret_cast<const uint32_t*>(p);
     const float* keys_h = reinterpret_cast<const float*>(p + total * kmax * 4);
@@ -238,16 +231,7 @@ int index_run_group(mse_index* idx, DispatchReq* const* reqs, size_t n_req) {
 }
 
 void index_run_batch(mse_index* idx, std::vector<DispatchReq*>& batch) {
-    if (index_run_group(idx, batch.data(), batch.size()) == 0) {
-        for (DispatchReq* r : batch) r->rc = 0;
-        return;
-    }
-    if (batch.size() == 1) { batch[0]->rc = -1; batch[0]->err = mse_last_error(); return; }
-    for (DispatchReq* r : batch) {   // a caller only ever sees its own failure
-        idx->retried_alone++;
-        r->rc = index_run_group(idx, &r, 1);
-        if (r->rc) r->err = mse_last_error();
-    }
+    idx->retried_alone += run_shared(batch, [idx](DispatchReq* const* reqs, size_t n) { return index_run_group(idx, reqs, n); });
 }
 
 }  // namespace
@@ -283,7 +267,6 @@ void mse_index_free(mse_index* idx) {
     if (idx->scratch) mse_searcher_free(idx->scratch);
     if (idx->codes) (void)hipFree(idx->codes);
     if (idx->view.norm_bits_dev) (void)hipFree(idx->view.norm_bits_dev);
-    if (idx->pin) (void)hipHostFree(idx->pin);
     delete idx;
 }
 size_t mse_index_ntotal(const mse_index* idx) { return idx ? idx->n : 0; }
@@ -389,7 +372,6 @@ void mse_pq_free(mse_pq* pq) {
     if (pq->centroids) (void)hipFree(pq->centroids);
     if (pq->transform) (void)hipFree(pq->transform);
     if (pq->transform_t) (void)hipFree(pq->transform_t);
-    if (pq->pin) (void)hipHostFree(pq->pin);
     if (pq->scratch) mse_searcher_free(pq->scratch);
     if (pq->lane2) mse_searcher_free(pq->lane2);
     if (pq->lane3) mse_searcher_free(pq->lane3);
@@ -757,16 +739,10 @@ static int pq_scan_topk_batch_impl(mse_pq* pq, const mse_codes* c, mse_searcher*
         const size_t n_tab = prep_all ? nq : 8;
         if (pq->a.ensure(in_bytes + 256) || pq->b.ensure(n_tab * d * 4) || pq->c.ensure(n_tab * lut_floats_b * 4)) break;
         if (s->q_stage.ensure(8 * d * 2) || s->out_scores.ensure(out_bytes)) break;
-        if (pq->pin_cap < std::max(in_bytes, out_bytes)) {
-            if (pq->pin) (void)hipHostFree(pq->pin);
-            pq->pin = nullptr; pq->pin_cap = 0;
-            const size_t want = std::max<size_t>(std::max(in_bytes, out_bytes) * 2, 1 << 16);
-            if (hipHostMalloc(&pq->pin, want, hipHostMallocDefault) != hipSuccess) { fail("pinned staging allocation failed"); break; }
-            pq->pin_cap = want;
-        }
-        memcpy(pq->pin, queries_f32, nq * d * 4);
-        if (sc_bytes) memcpy(static_cast<char*>(pq->pin) + sc_off, scales, sc_bytes);
-        if (hipMemcpyAsync(pq->a.p, pq->pin, in_bytes, hipMemcpyHostToDevice, st) != hipSuccess) { fail("H2D failed"); break; }
+        if (pq->pin.ensure(std::max(in_bytes, out_bytes), (size_t)1 << 16)) break;
+        memcpy(pq->pin.p, queries_f32, nq * d * 4);
+        if (sc_bytes) memcpy(pq->pin.as<char>() + sc_off, scales, sc_bytes);
+        if (hipMemcpyAsync(pq->a.p, pq->pin.p, in_bytes, hipMemcpyHostToDevice, st) != hipSuccess) { fail("H2D failed"); break; }
         float* scales_dev = sc_bytes ? reinterpret_cast<float*>(pq->a.as<char>() + sc_off) : nullptr;
         int64_t* const out_scores_dev = s->out_scores.as<int64_t>();
         uint32_t* const out_ids_dev = reinterpret_cast<uint32_t*>(s->out_scores.as<char>() + nq * k * 8);
@@ -858,7 +834,7 @@ static int pq_scan_topk_batch_impl(mse_pq* pq, const mse_codes* c, mse_searcher*
                                     reinterpret_cast<uint32_t*>(static_cast<char*>(block_dev) + nq * k * 8), st) || hipStreamSynchronize(st) != hipSuccess) {
                 fail("block hand-over failed"); break;
             }
-        } else if (hipMemcpyAsync(pq->pin, s->out_scores.p, nq * k * 12, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        } else if (hipMemcpyAsync(pq->pin.p, s->out_scores.p, nq * k * 12, hipMemcpyDeviceToHost, st) != hipSuccess ||
                    hipStreamSynchronize(st) != hipSuccess) { fail("D2H failed"); break; }
         {   // sustained rate: from the first scan's start to the last scan's end of this call, over its scans (they run back to back,
             // alternating between the streams: what a launch costs when the next one is already waiting behind it)
@@ -881,8 +857,8 @@ static int pq_scan_topk_batch_impl(mse_pq* pq, const mse_codes* c, mse_searcher*
                 ln->ev_used = 0;
             }
         if (!block_dev) {
-            memcpy(scores, pq->pin, nq * k * 8);
-            memcpy(ids, static_cast<char*>(pq->pin) + nq * k * 8, nq * k * 4);
+            memcpy(scores, pq->pin.p, nq * k * 8);
+            memcpy(ids, pq->pin.as<char>() + nq * k * 8, nq * k * 4);
             for (size_t i = 0; i < nq * k; i++)
                 if (ids[i] == MSE_ID_NONE) scores[i] = INT64_MIN;
         }
@@ -1035,39 +1011,26 @@ PqKey pq_key_of(const DispatchReq* q) {
     return PqKey{c, s ? s->base : nullptr, q->aux_n, q->k, static_cast<const float*>(q->aux2), c->n_desc};
 }
 void pq_run_batch(mse_pq* pq, std::vector<DispatchReq*>& batch) {
-    std::vector<char> taken(batch.size(), 0);
     std::vector<float> qs;
     std::vector<int64_t> sc;
     std::vector<uint32_t> id;
-    for (size_t i = 0; i < batch.size(); i++) {
-        if (taken[i]) continue;
-        const PqKey key = pq_key_of(batch[i]);
-        std::vector<DispatchReq*> grp;
-        for (size_t j = i; j < batch.size(); j++)
-            if (!taken[j] && key.same(pq_key_of(batch[j]))) { taken[j] = 1; grp.push_back(batch[j]); }
-        const size_t d = pq->d, k = key.k, n = grp.size();
-        qs.resize(n * d); sc.resize(n * k); id.resize(n * k);
-        for (size_t j = 0; j < n; j++) memcpy(qs.data() + j * d, grp[j]->queries, d * 4);
-        mse_searcher* s = const_cast<mse_searcher*>(static_cast<const mse_searcher*>(grp[0]->aux1));
-        int rc = mse_pq_scan_topk_batch(pq, key.c, s, qs.data(), n, key.scales, key.r, k, sc.data(), id.data());
-        if (rc == 0) {
-            for (size_t j = 0; j < n; j++) {
-                memcpy(grp[j]->out_a, sc.data() + j * k, k * 8);
-                memcpy(grp[j]->out_b, id.data() + j * k, k * 4);
-                grp[j]->rc = 0;
+    // one batch call for requests of the same key, on the searcher of the first (alone: the caller's own searcher)
+    auto run_group = [&](std::vector<DispatchReq*>& grp) {
+        const PqKey key = pq_key_of(grp[0]);
+        const size_t d = pq->d, k = key.k;
+        run_shared(grp, [&](DispatchReq* const* reqs, size_t n) {
+            qs.resize(n * d); sc.resize(n * k); id.resize(n * k);
+            for (size_t j = 0; j < n; j++) memcpy(qs.data() + j * d, reqs[j]->queries, d * 4);
+            mse_searcher* s = const_cast<mse_searcher*>(static_cast<const mse_searcher*>(reqs[0]->aux1));
+            const int rc = mse_pq_scan_topk_batch(pq, key.c, s, qs.data(), n, key.scales, key.r, k, sc.data(), id.data());
+            for (size_t j = 0; rc == 0 && j < n; j++) {
+                memcpy(reqs[j]->out_a, sc.data() + j * k, k * 8);
+                memcpy(reqs[j]->out_b, id.data() + j * k, k * 4);
             }
-            continue;
-        }
-        // the shared call failed: each caller is repeated alone with its own searcher and sees only its own outcome
-        const std::string why = mse_last_error();
-        for (size_t j = 0; j < n; j++) {
-            if (n == 1) { grp[j]->rc = rc; grp[j]->err = why; break; }
-            mse_searcher* sj = const_cast<mse_searcher*>(static_cast<const mse_searcher*>(grp[j]->aux1));
-            grp[j]->rc = mse_pq_scan_topk_batch(pq, key.c, sj, static_cast<const float*>(grp[j]->queries), 1, key.scales, key.r, k,
-                                                static_cast<int64_t*>(grp[j]->out_a), static_cast<uint32_t*>(grp[j]->out_b));
-            if (grp[j]->rc) grp[j]->err = mse_last_error();
-        }
-    }
+            return rc;
+        });
+    };
+    for_each_shared_group(batch, [](const DispatchReq& a, const DispatchReq& b) { return pq_key_of(&a).same(pq_key_of(&b)); }, run_group);
 }
 }  // namespace
 

@@ -716,11 +716,50 @@ __global__ __launch_bounds__(256) void entry_by_centroid_kernel(const float* __r
     if (tid == 0) starts[q] = entry_ids[s_idx[0] < 0 ? 0 : s_idx[0]];
 }
 
+// p + off, or null when p is null
+template <typename T> T* shifted(T* p, size_t off) { return p ? p + off : nullptr; }
+
+// A batched search's inputs, one of each per query: start node (null on the request path: the graph's entry table picks it), f16 or
+// f32 query, distance table (f16 queries with the codec) and descriptor scales
+struct SearchIn {
+    mse_searcher* s; mse_pq* pq; const mse_codes* c; const mse_graph* g; const uint32_t* starts;
+    const uint16_t* queries; const float* queries_f32; const float* luts; const float* scales; size_t nq;
+    int disable_pq; size_t beamwidth, search_list;
+    SearchIn piece(size_t q0, size_t m) const {   // queries q0 .. q0 + m - 1
+        const size_t d = s->base->d;
+        SearchIn p = *this;
+        p.starts = shifted(starts, q0); p.queries = shifted(queries, q0 * d); p.queries_f32 = shifted(queries_f32, q0 * d);
+        p.luts = shifted(luts, q0 * 16384); p.scales = scales ? scales + q0 * c->n_desc : nullptr;
+        p.nq = m;
+        return p;
+    }
+    // what calls need in common to run as one launch: the same vectors, codec, codes, graph and search parameters, the same kinds of inputs
+    bool shares_with(const SearchIn& o) const {
+        return s->base == o.s->base && pq == o.pq && c == o.c && g == o.g && disable_pq == o.disable_pq && beamwidth == o.beamwidth &&
+               search_list == o.search_list && (queries != nullptr) == (o.queries != nullptr) && (luts != nullptr) == (o.luts != nullptr) &&
+               (scales != nullptr) == (o.scales != nullptr);
+    }
+};
+
+// the list form's outputs on the host: search lists [nq][search_list] and their lengths, visited records [nq][visited_cap] (the two
+// arrays may be null) and the counters
+struct ListOut {
+    uint32_t* buf_ids; int64_t* buf_scores; uint32_t* buf_len;
+    uint32_t* visited_ids; int64_t* visited_scores; size_t visited_cap;
+    uint32_t *n_visited, *cmps, *pq_cmps;
+    ListOut piece(size_t q0, size_t search_list) const {
+        return ListOut{shifted(buf_ids, q0 * search_list), shifted(buf_scores, q0 * search_list), shifted(buf_len, q0),
+                       shifted(visited_ids, q0 * visited_cap), shifted(visited_scores, q0 * visited_cap), visited_cap,
+                       shifted(n_visited, q0), shifted(cmps, q0), shifted(pq_cmps, q0)};
+    }
+};
+
 // what the fused request path (mse_disk_query_topk) adds to a batched search: where the start nodes come from and what travels back
 struct FusedQuery {
     const mse_graph* entries = nullptr;   // start node by the graph's entry table (NULL: `starts` from the host)
     mse_searcher* entry_s = nullptr;      // searcher over the entry rows borrowed from the graph's pool for this call (row tables only)
     size_t k = 0;                         // records selected per query on the device (the largest k of the batch)
+    size_t visited_cap = 0;               // visited records kept per query on the device (fused_run grows it)
     // query q's results go to dst[q] (its first dst[q].k records) when dst is given -- the coalesced calls of many threads --
     // otherwise to row q of the contiguous arrays below ([nq][k], [nq])
     const QueryDst* dst = nullptr;
@@ -732,17 +771,370 @@ struct FusedQuery {
     int64_t* dev_sc = nullptr;
     uint32_t* dev_ids = nullptr;
     uint64_t id_offset = 0;
+    FusedQuery piece(size_t q0) const {   // the destinations of queries q0 ..
+        FusedQuery p = *this;
+        p.dst = shifted(dst, q0); p.ids = shifted(ids, q0 * k); p.scores = shifted(scores, q0 * k);
+        p.n_visited = shifted(n_visited, q0); p.cmps = shifted(cmps, q0); p.pq_cmps = shifted(pq_cmps, q0);
+        p.dev_sc = shifted(dev_sc, q0 * k); p.dev_ids = shifted(dev_ids, q0 * k);
+        return p;
+    }
 };
 
-// pinned host staging of a searcher (the fused path's ONE download per call; the coalescer's gathered inputs)
-int ensure_pin(void** pin, size_t* cap, size_t bytes) {
-    if (*cap >= bytes) return 0;
-    if (*pin) (void)hipHostFree(*pin);
-    *pin = nullptr; *cap = 0;
-    const size_t want = std::max<size_t>(2 * bytes, (size_t)1 << 16);
-    MSE_HIP_TRY(hipHostMalloc(pin, want, hipHostMallocDefault));
-    *cap = want;
+// the request path's contiguous outputs: [nq][k] ids and scores, [nq] counters (any counter pointer may be null)
+FusedQuery fused_out(size_t k, uint32_t* ids, int64_t* scores, uint32_t* n_visited, uint32_t* cmps, uint32_t* pq_cmps) {
+    FusedQuery fz;
+    fz.k = k; fz.ids = ids; fz.scores = scores; fz.n_visited = n_visited; fz.cmps = cmps; fz.pq_cmps = pq_cmps;
+    return fz;
+}
+
+// ---- argument checks: each rule set once, with the same words wherever it is checked
+// a search's own parameters (checked before a request queues and again inside the search)
+int check_params(const SearchIn& in) {
+    if (in.beamwidth == 0 || in.beamwidth > BS_BEAM_MAX) return fail("disk_search_batch: beamwidth must be 1..8");
+    if (in.search_list == 0 || in.search_list > BS_LMAX) return fail("disk_search_batch: search_list must be 1..1024");
     return 0;
+}
+// records per query of the request path
+int check_k(size_t k) { return k == 0 || k > (size_t)TOPK_KMAX - 64 ? fail("disk_query_topk: bad k / outputs") : 0; }
+// what belongs to one caller of the request path alone, found before it queues
+int check_queued(const SearchIn& in) {
+    if (check_params(in)) return -1;
+    if ((!in.disable_pq && (!in.pq || !in.c || (!in.luts && !in.queries_f32))) || (in.scales && !in.c)) return fail("disk_search_batch: null argument");
+    for (size_t q = 0; in.starts && q < in.nq; q++)
+        if (in.starts[q] >= in.g->n) return fail("disk_search_batch: start node out of range");
+    return 0;
+}
+
+// beam_search_kernel<THREADS, ADC> with one workgroup per query; ADC (scoring through the query's distance table) unless disable_pq
+template <int THREADS>
+int launch_beam(const BeamArgs& a, size_t nq, size_t lds, hipStream_t st) {
+    if constexpr (THREADS == 64) {   // one wave per query: exact scoring only, within the default LDS (no opt-in)
+        hipLaunchKernelGGL((beam_search_kernel<64, false>), dim3((unsigned)nq), dim3(64), lds, st, a);
+    } else if (a.disable_pq) {
+        MSE_DYN_LDS((beam_search_kernel<THREADS, false>), 160 * 1024 - 1024);
+        hipLaunchKernelGGL((beam_search_kernel<THREADS, false>), dim3((unsigned)nq), dim3(THREADS), lds, st, a);
+    } else {
+        MSE_DYN_LDS((beam_search_kernel<THREADS, true>), 160 * 1024 - 1024);
+        hipLaunchKernelGGL((beam_search_kernel<THREADS, true>), dim3((unsigned)nq), dim3(THREADS), lds, st, a);
+    }
+    return 0;
+}
+
+// ---- one batched search, in steps: checks, buffers, upload and entry step, launch, read-back (list form or fused form)
+const mse_codes no_codes{};   // stands in for the codes when neither codec nor codes are needed
+enum : int { REPEAT_WITH_BITMAPS = 1 };   // a read-back's answer when a search outgrew its hash table
+
+// what the steps of one search share
+struct SearchRun {
+    const SearchIn& in;
+    const ListOut* out;       // list form (host arrays) ...
+    const FusedQuery* fz;     // ... or the fused request path: the search list and the visited records stay on the device, only the k
+                              // best visited records travel back
+    const mse_base* b;
+    size_t nq, d, visited_cap;
+    bool use_hash;            // visited sets: bit maps, or hash tables of 2^table_bits entries; set_words u64 per set
+    int table_bits;
+    size_t set_words;
+    bool bias;                // descriptor scales in play
+    hipStream_t st;
+    // the searcher's scratch (kept between calls: no hipMalloc on the query path)
+    DevBuf &dq, &dl, &dsc, &dst, &bm, &oi, &os, &ol, &vi, &vs, &cnt, &qf, &qt, &fzb;
+    size_t fz_block_off = 0, fz_block_bytes = 0;
+    uint32_t* cnt_dev = nullptr;   // counters [3 nq + 1]: n_visited, cmps, pq_cmps, err
+    BeamArgs a{};
+    bool timed = false;            // mse_searcher_beam_timing: events around the launch
+    SearchRun(const SearchIn& in_, const ListOut* out_, const FusedQuery* fz_, bool use_hash_, int table_bits_, size_t set_words_)
+        : in(in_), out(out_), fz(fz_), b(in_.s->base), nq(in_.nq), d(in_.s->base->d), visited_cap(fz_ ? fz_->visited_cap : out_->visited_cap),
+          use_hash(use_hash_), table_bits(table_bits_), set_words(set_words_), bias(in_.scales && in_.c->n_desc && in_.c->desc), st(in_.s->stream),
+          dq(in_.s->pool[0]), dl(in_.s->pool[1]), dsc(in_.s->pool[2]), dst(in_.s->pool[3]), bm(in_.s->pool[4]), oi(in_.s->pool[5]),
+          os(in_.s->pool[6]), ol(in_.s->pool[7]), vi(in_.s->pool[8]), vs(in_.s->pool[9]), cnt(in_.s->pool[10]), qf(in_.s->pool[11]),
+          qt(in_.s->pool[12]), fzb(in_.s->pool[13]) {}
+};
+
+int search_check(const SearchRun& r) {
+    const SearchIn& in = r.in;
+    const mse_codes* c = in.c;
+    const FusedQuery* fz = r.fz;
+    if ((c != &no_codes && c->n != r.b->n) || in.g->n != r.b->n) return fail("disk_search_batch: vectors, codes and graph differ in length");
+    if (!in.disable_pq && (in.pq->n_chunks != 64 || in.pq->n_centroids != 256 || c->code_size != 64)) return fail("disk_search_batch: needs the 64 x 256 codec");
+    if (check_params(in)) return -1;
+    if (in.g->max_deg > BS_DEG_MAX) return fail("disk_search_batch: at most 128 neighbours per node");
+    if (c->n_desc > BS_DESC_MAX) return fail("disk_search_batch: at most 8 descriptors");
+    if (r.d % 32 || r.d > 4096) return fail("disk_search_batch: vector width must be a multiple of 32");
+    if (r.out && r.visited_cap && (!r.out->visited_ids || !r.out->visited_scores)) return fail("disk_search_batch: null visited arrays");
+    if (fz && (fz->k == 0 || fz->k > r.visited_cap || fz->k > (size_t)TOPK_KMAX - 64 || (!fz->dst && !fz->dev_sc && (!fz->ids || !fz->scores))))
+        return fail("disk_query_topk: bad k / outputs");
+    if (fz && fz->entries) {
+        const mse_graph* eg = fz->entries;
+        const bool by_rows = eg->entry_base && fz->entry_s && eg->entry_base->d == r.d, by_keys = eg->entry_keys_t && eg->entry_keys_d == r.d;
+        if (eg->n_entries == 0 || (!by_rows && !by_keys))
+            return fail("disk_query_topk: the graph has no entry table for these vectors (mse_graph_set_entries / mse_graph_set_entry_centroids)");
+    }
+    for (size_t q = 0; in.starts && q < r.nq; q++)
+        if (in.starts[q] >= r.b->n) return fail("disk_search_batch: start node out of range");
+    return 0;
+}
+
+int search_buffers(SearchRun& r) {
+    const size_t nq = r.nq, d = r.d, L = r.in.search_list, vc = r.visited_cap;
+    // fused path: entry top-1 [nq] (i64, u32) | the block that travels back in ONE copy: k best visited [nq][k] i64 scores, [nq][k] u32
+    // ids, counters [3 nq + 1] (n_visited, cmps, pq_cmps, err)
+    r.fz_block_off = (nq * 12 + 15) & ~(size_t)15;
+    r.fz_block_bytes = r.fz ? nq * r.fz->k * 12 + (3 * nq + 1) * 4 : 0;
+    if (r.fz && (r.fzb.ensure(r.fz_block_off + r.fz_block_bytes + 64) || r.in.s->pin.ensure(r.fz_block_bytes, (size_t)1 << 16))) return -1;
+    if ((r.in.queries_f32 && (r.qf.ensure(nq * d * 4) || r.qt.ensure(nq * d * 4))) || r.dq.ensure(nq * d * 2) || r.dl.ensure(r.in.disable_pq ? 16 : nq * 65536) ||
+        r.dsc.ensure(nq * BS_DESC_MAX * 4 + 16) || r.dst.ensure(nq * 4) || r.bm.ensure(nq * r.set_words * 8) || r.oi.ensure(nq * L * 4) ||
+        r.os.ensure(nq * L * 8) || r.ol.ensure(nq * 4) || r.vi.ensure(nq * vc * 4 + 16) || r.vs.ensure(nq * vc * 8 + 16) || r.cnt.ensure(nq * 12 + 16))
+        return -1;
+    // counters: their own buffer, or (fused path) the tail of the block that travels back
+    r.cnt_dev = r.fz ? reinterpret_cast<uint32_t*>(r.fzb.as<char>() + r.fz_block_off + nq * r.fz->k * 12) : r.cnt.as<uint32_t>();
+    return 0;
+}
+
+int search_upload(SearchRun& r) {
+    const SearchIn& in = r.in;
+    const size_t nq = r.nq, d = r.d;
+    hipStream_t st = r.st;
+    if (in.queries_f32) {
+        // the caller's side of query_disk_index.rs:475-477 on the device: f16 copy of the query (RNE) for the exact scores,
+        // preprocess_query (vector.rs:367-384) for the distance tables -- 64 KiB per query that never cross PCIe
+        if (in.pq && in.pq->d != d) return fail("disk_search_batch: codec and vectors differ in width");
+        MSE_HIP_TRY(hipMemcpyAsync(r.qf.p, in.queries_f32, nq * d * 4, hipMemcpyHostToDevice, st));
+        if (launch_f32_to_f16(r.qf.as<float>(), nq * d, r.dq.as<uint16_t>(), st)) return -1;
+        if (!in.disable_pq) {
+            if (launch_pq_transform(in.pq->transform, (int)d, r.qf.as<float>(), nq, r.qt.as<float>(), st)) return -1;
+            if (launch_pq_lut_batch(in.pq->centroids, (int)in.pq->n_centroids, (int)d, (int)in.pq->dpc, r.qt.as<float>(), nq, r.dl.as<float>(), st)) return -1;
+        }
+    } else {
+        // hipMemcpyDefault: the f16 queries may sit in host memory or already on the device (the text tower's output): the runtime tells by the pointer
+        MSE_HIP_TRY(hipMemcpyAsync(r.dq.p, in.queries, nq * d * 2, hipMemcpyDefault, st));
+        if (!in.disable_pq) MSE_HIP_TRY(hipMemcpyAsync(r.dl.p, in.luts, nq * 65536, hipMemcpyHostToDevice, st));
+    }
+    if (r.bias) MSE_HIP_TRY(hipMemcpyAsync(r.dsc.p, in.scales, nq * in.c->n_desc * 4, hipMemcpyHostToDevice, st));
+    if (!(r.fz && r.fz->entries)) {
+        MSE_HIP_TRY(hipMemcpyAsync(r.dst.p, in.starts, nq * 4, hipMemcpyHostToDevice, st));
+        return 0;
+    }
+    // the entry step of the request path (src/query_disk_index.rs:254-256,447-450: the medioid of the shard whose centroid is
+    // closest to the query) on the device: exact top-1 of the f16 queries over the entry rows, on this search's stream
+    const mse_graph* eg = r.fz->entries;
+    if (eg->entry_keys_t) {
+        // the reference's rule itself: centroids as keys, f32 query (an f16 query widened exactly), f64 sums, last maximum
+        hipLaunchKernelGGL(entry_by_centroid_kernel, dim3((unsigned)nq), dim3(256), d * 4, st, eg->entry_keys_t, (int)eg->n_entries, (int)d,
+                           in.queries_f32 ? r.qf.as<float>() : nullptr, r.dq.as<uint16_t>(), eg->entry_ids, r.dst.as<uint32_t>());
+        MSE_HIP_TRY(hipGetLastError());
+    } else if (nq * eg->n_entries <= ((size_t)1 << 22) && eg->n_entries <= ((size_t)1 << 20)) {
+        // a small batch: exact top-1 over the entry rows in ONE launch (entry_top1_rows_kernel) + the search kernel's prologue
+        const size_t E = eg->n_entries, n_qt = (nq + ET_Q - 1) / ET_Q;
+        size_t rows_per_wg = (E + std::max<size_t>(1, 512 / n_qt) - 1) / std::max<size_t>(1, 512 / n_qt);
+        rows_per_wg = std::max<size_t>(64, (rows_per_wg + 63) / 64 * 64);
+        const size_t n_chunks = (E + rows_per_wg - 1) / rows_per_wg;
+        DevBuf& ep = in.s->pool[14];
+        if (ep.ensure(n_chunks * nq * 12 + 64)) return -1;
+        long long* psc = ep.as<long long>();
+        uint32_t* prow = reinterpret_cast<uint32_t*>(ep.as<char>() + n_chunks * nq * 8);
+        MSE_DYN_LDS(entry_top1_rows_kernel, ET_Q * d * 2);
+        hipLaunchKernelGGL(entry_top1_rows_kernel, dim3((unsigned)n_chunks, (unsigned)n_qt), dim3(ET_THREADS), ET_Q * d * 2, st, eg->entry_rows, (int)E,
+                           (int)d, r.dq.as<uint16_t>(), (int)nq, (int)rows_per_wg, psc, prow);
+        MSE_HIP_TRY(hipGetLastError());
+        // (the best chunk per query is picked by the search kernel's first wave: no launch of its own)
+        r.a.entry_psc = psc; r.a.entry_prow = prow; r.a.entry_chunks = (int)n_chunks; r.a.entry_ids = eg->entry_ids;
+    } else {
+        int64_t* e_sc = r.fzb.as<int64_t>();
+        uint32_t* e_row = reinterpret_cast<uint32_t*>(r.fzb.as<char>() + nq * 8);
+        if (mse_searcher_set_stream(r.fz->entry_s, st)) return -1;
+        if (mse_bruteforce_topk_f16_dev(r.fz->entry_s, r.dq.p, nq, 1, MSE_MODE_AUTO, 0, e_sc, e_row)) return -1;
+        hipLaunchKernelGGL(entry_starts_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, e_row, eg->entry_ids, eg->n_entries, nq, r.dst.as<uint32_t>());
+        MSE_HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+int search_launch(SearchRun& r) {
+    const SearchIn& in = r.in;
+    mse_searcher* s = in.s;
+    const mse_codes* c = in.c;
+    const mse_graph* g = in.g;
+    const size_t nq = r.nq, d = r.d, L = in.search_list;
+    hipStream_t st = r.st;
+    MSE_HIP_TRY(hipMemsetAsync(r.bm.p, r.use_hash ? 0xff : 0, nq * r.set_words * 8, st));
+    MSE_HIP_TRY(hipMemsetAsync(r.cnt_dev, 0, (3 * nq + 1) * 4, st));
+    const size_t p_cap = in.beamwidth * ((g->max_deg + 63) / 64 * 64);
+    BeamArgs& a = r.a;   // (the entry step's fields are set)
+    a.base = r.b->dev; a.n = r.b->n; a.d = (int)d;
+    a.codes = c->codes; a.desc = r.bias ? c->desc : nullptr; a.n_desc = (int)c->n_desc;
+    a.adj = g->adj; a.deg = g->deg; a.max_deg = (int)g->max_deg; a.has_url = g->has_url;
+    a.queries = r.dq.as<uint16_t>(); a.luts = r.dl.as<float>(); a.scales = r.bias ? r.dsc.as<float>() : nullptr; a.starts = r.dst.as<uint32_t>();
+    a.beam = (int)in.beamwidth; a.L = (int)L; a.disable_pq = in.disable_pq; a.p_cap = (int)p_cap;
+    a.bm_adj = r.bm.as<uint32_t>(); a.bm_vis = r.bm.as<uint32_t>() + nq * r.set_words; a.bm_words = r.set_words; a.hash_bits = r.use_hash ? r.table_bits : 0;
+    a.out_ids = r.oi.as<uint32_t>(); a.out_scores = r.os.as<long long>(); a.out_len = r.ol.as<uint32_t>();
+    a.vis_ids = r.vi.as<uint32_t>(); a.vis_scores = r.vs.as<long long>(); a.vis_cap = r.visited_cap;
+    a.n_visited = r.cnt_dev; a.cmps = r.cnt_dev + nq; a.pq_cmps = r.cnt_dev + 2 * nq;
+    a.err = r.cnt_dev + 3 * nq;
+    a.fill_vis = r.fz ? 1 : 0;
+    a.entry_nq = (int)nq;
+    size_t hash_slots = 64;
+    while (hash_slots < 2 * p_cap) hash_slots *= 2;
+    a.hash_slots = (int)hash_slots;
+    // (beam_search_kernel's carving: table | query (exact scoring only) | list scores, pre-buffer scores, list ids, visited flags (one
+    // byte each), pre-buffer ids, ranks | first-position table)
+    const size_t lds = (in.disable_pq ? 0 : 65536) + (in.disable_pq ? ((d * 2 + 15) & ~(size_t)15) : 0) + L * 12 + ((L + 3) & ~(size_t)3) +
+                       p_cap * 16 + hash_slots * 4;
+    static const bool wide_only = MSE_DEV_KNOB("MSE_BEAM_FOUR_WAVES");   // developer library: the four-wave form for every search
+    // one wave per query once the batch fills the chip on its own (16 queries per CU); a smaller batch is latency-bound, and four waves
+    // finish a search sooner (round 5, scripts/beam_latency_probe.py, hard set: 64 queries at L = 12 0.40 ms against 0.98, at L = 200
+    // 5.7 against 8.9; from 2048 queries on the two forms are level)
+    r.timed = s->beam_timing && s->bev0 && s->beam_tot.p;
+    if (r.timed) {
+        a.totals = s->beam_tot.as<unsigned long long>();
+        MSE_HIP_TRY(hipEventRecord(s->bev0, st));
+    }
+    // A handful of queries (the request handler's one query per call): the search is a chain of dependent round trips and most of the chip
+    // idles -- sixteen waves per query gather an iteration's ~200 neighbour rows in one round instead of three (round 6; same answers,
+    // counters included: the tiling of the loops is all that changes).  MSE_BEAM_WAVES=4 / 8 / 16 forces a form (answer-preserving hook).
+    static const int force_waves = [] { const char* e = getenv("MSE_BEAM_WAVES"); return e ? atoi(e) : 0; }();
+    const int small_waves = force_waves ? force_waves : (nq <= BS_SMALL_NQ ? BS_SMALL_WAVES : 4);
+    int rc;
+    if (in.disable_pq && L <= 256 && p_cap <= 256 && !wide_only && nq > 1024 && !force_waves) rc = launch_beam<64>(a, nq, lds, st);
+    else if (small_waves == 16) rc = launch_beam<1024>(a, nq, lds, st);
+    else if (small_waves == 8) rc = launch_beam<512>(a, nq, lds, st);
+    else rc = launch_beam<BS_THREADS_MAX>(a, nq, lds, st);
+    if (rc) return -1;
+    MSE_HIP_TRY(hipGetLastError());
+    if (r.timed) MSE_HIP_TRY(hipEventRecord(s->bev1, st));
+    return 0;
+}
+
+// list form: the search lists, the counters and the visited columns any query filled come back to the host arrays
+int read_back_list(const SearchRun& r) {
+    const ListOut& o = *r.out;
+    const size_t nq = r.nq, L = r.in.search_list, vc = r.visited_cap;
+    hipStream_t st = r.st;
+    uint32_t err = 0;
+    MSE_HIP_TRY(hipMemcpyAsync(o.buf_ids, r.oi.p, nq * L * 4, hipMemcpyDeviceToHost, st));
+    MSE_HIP_TRY(hipMemcpyAsync(o.buf_scores, r.os.p, nq * L * 8, hipMemcpyDeviceToHost, st));
+    MSE_HIP_TRY(hipMemcpyAsync(o.buf_len, r.ol.p, nq * 4, hipMemcpyDeviceToHost, st));
+    MSE_HIP_TRY(hipMemcpyAsync(o.n_visited, r.a.n_visited, nq * 4, hipMemcpyDeviceToHost, st));
+    MSE_HIP_TRY(hipMemcpyAsync(o.cmps, r.a.cmps, nq * 4, hipMemcpyDeviceToHost, st));
+    MSE_HIP_TRY(hipMemcpyAsync(o.pq_cmps, r.a.pq_cmps, nq * 4, hipMemcpyDeviceToHost, st));
+    MSE_HIP_TRY(hipMemcpyAsync(&err, r.a.err, 4, hipMemcpyDeviceToHost, st));
+    MSE_HIP_TRY(hipStreamSynchronize(st));
+    if (err & 1u) return fail("disk_search_batch: a graph edge points outside the index");
+    if (err & 4u) return REPEAT_WITH_BITMAPS;
+    if (vc) {   // only the columns any query filled travel back (entries past n_visited[q] are unspecified)
+        size_t widest = 0;
+        for (size_t q = 0; q < nq; q++) widest = o.n_visited[q] > widest ? o.n_visited[q] : widest;
+        if (widest > vc) widest = vc;
+        if (widest) {
+            MSE_HIP_TRY(hipMemcpy2DAsync(o.visited_ids, vc * 4, r.vi.p, vc * 4, widest * 4, nq, hipMemcpyDeviceToHost, st));
+            MSE_HIP_TRY(hipMemcpy2DAsync(o.visited_scores, vc * 8, r.vs.p, vc * 8, widest * 8, nq, hipMemcpyDeviceToHost, st));
+            MSE_HIP_TRY(hipStreamSynchronize(st));
+        }
+    }
+    return 0;
+}
+
+// fused form: the server's last step (src/query_disk_index.rs:529-540: the visited records ordered by exact score) cut to its first k, on
+// the device: the kernel has padded every visited list to visited_cap with (ID_NONE, INT64_MIN).  Scores, ids and the counters come
+// back in ONE copy into the searcher's pinned staging (round 5: five pageable copies before).  -2: a visited list outgrew the arrays.
+int read_back_fused(const SearchRun& r) {
+    const FusedQuery& fz = *r.fz;
+    mse_searcher* s = r.in.s;
+    const size_t nq = r.nq, k = fz.k, vc = r.visited_cap;
+    hipStream_t st = r.st;
+    int64_t* top_sc = reinterpret_cast<int64_t*>(r.fzb.as<char>() + r.fz_block_off);
+    uint32_t* top_id = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(top_sc) + nq * k * 8);
+    if (r.in.g->dedup_threshold > 0.0f) {
+        // the handler's runtime de-duplication (:482-527) before its sort: a visited record that resembles an already kept one (dot of
+        // the f32-widened vectors above the threshold, visit order) leaves the list -- on the device, for every query of the batch
+        DevBuf& db = s->pool[15];
+        if (db.ensure(dedup_batch_scratch_bytes(nq, vc))) return -1;
+        if (launch_dedup_batch(r.b->dev, (int)r.d, r.vi.as<uint32_t>(), r.vs.as<long long>(), vc, r.cnt_dev, nq, r.in.g->dedup_threshold, db.p, st)) return -1;
+    }
+    SelectArgs sa{};
+    sa.kind = KEY_I64; sa.list_ids = r.vi.as<uint32_t>(); sa.list_keys = r.vs.p; sa.list_stride = vc; sa.n_list = vc;
+    sa.k = (int)k; sa.out_ids = top_id; sa.out_keys = top_sc; sa.out_stride = k; sa.nq = (int)nq;
+    if (launch_select(sa, st)) return -1;
+    const char* blk = s->pin.as<char>();
+    if (fz.dev_sc) {   // results stay on the device (global ids); the counters come back alone, at their usual place in the staging
+        if (launch_block_finish(top_sc, top_id, nq * k, fz.id_offset, fz.dev_sc, fz.dev_ids, st)) return -1;
+        MSE_HIP_TRY(hipMemcpyAsync(s->pin.p ? s->pin.as<char>() + nq * k * 12 : nullptr, r.cnt_dev, (3 * nq + 1) * 4, hipMemcpyDeviceToHost, st));
+    } else {
+        MSE_HIP_TRY(hipMemcpyAsync(s->pin.p, top_sc, r.fz_block_bytes, hipMemcpyDeviceToHost, st));
+    }
+    MSE_HIP_TRY(hipStreamSynchronize(st));
+    const int64_t* h_sc = reinterpret_cast<const int64_t*>(blk);
+    const uint32_t* h_id = reinterpret_cast<const uint32_t*>(blk + nq * k * 8);
+    const uint32_t* h_cnt = reinterpret_cast<const uint32_t*>(blk + nq * k * 12);
+    const uint32_t err = h_cnt[3 * nq];
+    if (err & 1u) return fail("disk_search_batch: a graph edge points outside the index");
+    if (err & 4u) return REPEAT_WITH_BITMAPS;
+    // the reference keeps every visited record: a list that outgrew the device arrays means the caller repeats with larger ones
+    for (size_t q = 0; q < nq; q++)
+        if (h_cnt[q] > vc) return -2;
+    for (size_t q = 0; q < nq; q++) {
+        QueryDst o = fz.dst ? fz.dst[q]
+                            : QueryDst{shifted(fz.ids, q * k), shifted(fz.scores, q * k), shifted(fz.n_visited, q), shifted(fz.cmps, q),
+                                       shifted(fz.pq_cmps, q), k};
+        // a caller's k records are the first k of the largest k's: the order (score descending, id ascending) is total
+        if (!fz.dev_sc) {
+            memcpy(o.ids, h_id + q * k, o.k * 4);
+            memcpy(o.scores, h_sc + q * k, o.k * 8);
+        }
+        if (o.n_visited) *o.n_visited = h_cnt[q];
+        if (o.cmps) *o.cmps = h_cnt[nq + q];
+        if (o.pq_cmps) *o.pq_cmps = h_cnt[2 * nq + q];
+    }
+    return 0;
+}
+
+// The batched search: list form (out) or fused form (fz), exactly one of them.  visited_mode: -1 the size rule (or MSE_VISITED_MODE),
+// 0 bit maps, 1 hash tables.
+int disk_search_batch_impl(int visited_mode, const SearchIn& in_arg, const ListOut* out, const FusedQuery* fz) {
+    SearchIn in = in_arg;
+    // with disable_pq and no descriptor bias neither the codec nor the codes are touched: both may be NULL then
+    if (!in.c && in.disable_pq && !in.scales) in.c = &no_codes;
+    if (!in.s || !in.s->base || (!in.pq && !in.disable_pq) || !in.c || !in.g || (!in.starts && !(fz && fz->entries)) || (!in.queries && !in.queries_f32) ||
+        (!in.luts && !in.queries_f32 && !in.disable_pq) ||
+        (out && (!out->buf_ids || !out->buf_scores || !out->buf_len || !out->n_visited || !out->cmps || !out->pq_cmps)))
+        return fail("disk_search_batch: null argument");
+    if (in.nq == 0) return 0;
+    const mse_base* b = in.s->base;
+    // visited sets: bit maps, or hash tables once the index is so large that the tables are the smaller ones (visited_set.h)
+    const size_t words = (b->n + 31) / 32;
+    // adjacency set: a search of list L fetches about L + a few nodes and meets <= max_deg new ids at each (measured: 2 400 inserts at
+    // L = 32, R = 64); a search that outgrows its table is caught (half-full check, err bit 4) and the batch repeated with bit maps
+    const int table_bits = visited_table_bits(std::min<size_t>(b->n, in.search_list * 128 + 2048));
+    const char* vm = getenv("MSE_VISITED_MODE");   // test hook: "hash" / "bitmap"
+    const bool use_hash = visited_mode >= 0 ? visited_mode == 1 : (vm ? !strcmp(vm, "hash") : words > ((size_t)1 << table_bits));
+    const size_t set_words = use_hash ? (size_t)1 << table_bits : words;
+    // two visited sets per query in flight: long batches go through in pieces of at most ~4 GiB of them (pool[4]: the bitmaps already held)
+    const size_t piece = std::max<size_t>(1, std::max(in.s->pool[4].cap, visited_budget_bytes()) / (set_words * 8));
+    if (in.nq > piece) {
+        for (size_t q0 = 0; q0 < in.nq; q0 += piece) {
+            const ListOut op = out ? out->piece(q0, in.search_list) : ListOut{};
+            const FusedQuery fp = fz ? fz->piece(q0) : FusedQuery{};
+            const int prc = disk_search_batch_impl(visited_mode, in.piece(q0, std::min(piece, in.nq - q0)), out ? &op : nullptr, fz ? &fp : nullptr);
+            if (prc) return prc;
+        }
+        return 0;
+    }
+    SearchRun r(in, out, fz, use_hash, table_bits, set_words);
+    if (search_check(r) || search_buffers(r) || search_upload(r) || search_launch(r)) return -1;
+    struct BeamTimed {   // read once the stream has been waited for (every read-back does before it returns)
+        mse_searcher* s; bool on; size_t nq;
+        ~BeamTimed() {
+            float ms = 0.0f;
+            if (on && hipEventQuery(s->bev1) == hipSuccess && hipEventElapsedTime(&ms, s->bev0, s->bev1) == hipSuccess) {
+                s->beam_ms_total += ms; s->beam_launches++; s->beam_queries += nq;
+            } else if (on) {
+                (void)hipGetLastError();
+            }
+        }
+    } beam_timed{in.s, r.timed, r.nq};
+    const int rc = fz ? read_back_fused(r) : read_back_list(r);
+    // a search outgrew its table: the bit maps have room for everything
+    return rc == REPEAT_WITH_BITMAPS ? disk_search_batch_impl(0, in, out, fz) : rc;
 }
 
 }  // namespace
@@ -767,10 +1159,8 @@ void mse_graph_free(mse_graph* g) {
     delete g->co;   // joins its workers; no search may be in flight
     g->co = nullptr;
     g->co_fast.store(nullptr);
-    for (mse_graph::WorkerCtx& w : g->co_ctx) {
+    for (mse_graph::WorkerCtx& w : g->co_ctx)
         if (w.s) mse_searcher_free(w.s);
-        if (w.pin) (void)hipHostFree(w.pin);
-    }
     g->co_ctx.clear();
     for (mse_searcher* es : g->entry_pool) mse_searcher_free(es);
     g->entry_pool.clear();
@@ -782,303 +1172,6 @@ void mse_graph_free(mse_graph* g) {
     if (g->deg) (void)hipFree(g->deg);
     if (g->has_url) (void)hipFree(g->has_url);
     delete g;
-}
-
-static int disk_search_batch_impl(int visited_mode, mse_searcher* s, mse_pq* pq, const mse_codes* c, const mse_graph* g, const uint32_t* starts,
-                                  const uint16_t* queries, const float* queries_f32, const float* luts, const float* scales, size_t nq,
-                                  int disable_pq, size_t beamwidth, size_t search_list, uint32_t* buf_ids, int64_t* buf_scores,
-                                  uint32_t* buf_len, uint32_t* visited_ids, int64_t* visited_scores, size_t visited_cap,
-                                  uint32_t* n_visited, uint32_t* cmps, uint32_t* pq_cmps, const FusedQuery* fz = nullptr) {
-    // with disable_pq and no descriptor bias neither the codec nor the codes are touched: both may be NULL then
-    static const mse_codes no_codes{};
-    if (!c && disable_pq && !scales) c = &no_codes;
-    const bool codec_needed = !disable_pq;
-    // fused request path (fz): the search list and the visited records stay on the device, only the k best visited records travel back
-    if (!s || !s->base || (!pq && codec_needed) || !c || !g || (!starts && !(fz && fz->entries)) || (!queries && !queries_f32) ||
-        (!luts && !queries_f32 && !disable_pq) || (!fz && (!buf_ids || !buf_scores || !buf_len || !n_visited || !cmps || !pq_cmps)))
-        return fail("disk_search_batch: null argument");
-    if (nq == 0) return 0;
-    const mse_base* b = s->base;
-    // visited sets: bit maps, or hash tables once the index is so large that the tables are the smaller ones (visited_set.h)
-    const size_t words = (b->n + 31) / 32;
-    // adjacency set: a search of list L fetches about L + a few nodes and meets <= max_deg new ids at each (measured: 2 400 inserts at
-    // L = 32, R = 64); a search that outgrows its table is caught (half-full check, err bit 4) and the batch repeated with bit maps
-    const int table_bits = visited_table_bits(std::min<size_t>(b->n, search_list * 128 + 2048));
-    const char* vm = getenv("MSE_VISITED_MODE");   // test hook: "hash" / "bitmap"
-    const bool use_hash = visited_mode >= 0 ? visited_mode == 1 : (vm ? !strcmp(vm, "hash") : words > ((size_t)1 << table_bits));
-    const size_t set_words = use_hash ? (size_t)1 << table_bits : words;
-    {   // two visited sets per query in flight: long batches go through in pieces of at most ~4 GiB of them
-        const size_t per_query = set_words * 8, piece = std::max<size_t>(1, std::max(s->pool[4].cap, visited_budget_bytes()) / per_query);   // pool[4]: the bitmaps already held
-        if (nq > piece) {
-            for (size_t q0 = 0; q0 < nq; q0 += piece) {
-                const size_t m = std::min(piece, nq - q0);
-                FusedQuery fp;
-                if (fz) {
-                    fp = *fz;
-                    if (fz->dev_sc) { fp.dev_sc = fz->dev_sc + q0 * fz->k; fp.dev_ids = fz->dev_ids + q0 * fz->k; }
-                    if (fz->dst) fp.dst = fz->dst + q0;
-                    else {
-                        fp.ids = fz->ids + q0 * fz->k; fp.scores = fz->scores + q0 * fz->k;
-                        fp.n_visited = fz->n_visited ? fz->n_visited + q0 : nullptr;
-                        fp.cmps = fz->cmps ? fz->cmps + q0 : nullptr;
-                        fp.pq_cmps = fz->pq_cmps ? fz->pq_cmps + q0 : nullptr;
-                    }
-                }
-                const int prc = disk_search_batch_impl(visited_mode, s, pq, c, g, starts ? starts + q0 : nullptr, queries ? queries + q0 * b->d : nullptr,
-                                                       queries_f32 ? queries_f32 + q0 * b->d : nullptr, luts ? luts + q0 * 16384 : nullptr,
-                                                       scales ? scales + q0 * c->n_desc : nullptr, m, disable_pq, beamwidth, search_list,
-                                                       buf_ids ? buf_ids + q0 * search_list : nullptr, buf_scores ? buf_scores + q0 * search_list : nullptr,
-                                                       buf_len ? buf_len + q0 : nullptr, visited_ids ? visited_ids + q0 * visited_cap : nullptr,
-                                                       visited_scores ? visited_scores + q0 * visited_cap : nullptr, visited_cap,
-                                                       n_visited ? n_visited + q0 : nullptr, cmps ? cmps + q0 : nullptr,
-                                                       pq_cmps ? pq_cmps + q0 : nullptr, fz ? &fp : nullptr);
-                if (prc) return prc;
-            }
-            return 0;
-        }
-    }
-    if ((c != &no_codes && c->n != b->n) || g->n != b->n) return fail("disk_search_batch: vectors, codes and graph differ in length");
-    if (codec_needed && (pq->n_chunks != 64 || pq->n_centroids != 256 || c->code_size != 64)) return fail("disk_search_batch: needs the 64 x 256 codec");
-    if (beamwidth == 0 || beamwidth > BS_BEAM_MAX) return fail("disk_search_batch: beamwidth must be 1..8");
-    if (search_list == 0 || search_list > BS_LMAX) return fail("disk_search_batch: search_list must be 1..1024");
-    if (g->max_deg > BS_DEG_MAX) return fail("disk_search_batch: at most 128 neighbours per node");
-    if (c->n_desc > BS_DESC_MAX) return fail("disk_search_batch: at most 8 descriptors");
-    if (b->d % 32 || b->d > 4096) return fail("disk_search_batch: vector width must be a multiple of 32");
-    if (!fz && visited_cap && (!visited_ids || !visited_scores)) return fail("disk_search_batch: null visited arrays");
-    if (fz && (fz->k == 0 || fz->k > visited_cap || fz->k > (size_t)TOPK_KMAX - 64 || (!fz->dst && !fz->dev_sc && (!fz->ids || !fz->scores))))
-        return fail("disk_query_topk: bad k / outputs");
-    if (fz && fz->entries) {
-        const mse_graph* eg = fz->entries;
-        const bool by_rows = eg->entry_base && fz->entry_s && eg->entry_base->d == b->d, by_keys = eg->entry_keys_t && eg->entry_keys_d == b->d;
-        if (eg->n_entries == 0 || (!by_rows && !by_keys))
-            return fail("disk_query_topk: the graph has no entry table for these vectors (mse_graph_set_entries / mse_graph_set_entry_centroids)");
-    }
-    for (size_t q = 0; starts && q < nq; q++)
-        if (starts[q] >= b->n) return fail("disk_search_batch: start node out of range");
-    hipStream_t st = s->stream;
-    const size_t d = b->d;
-    const bool bias = scales && c->n_desc && c->desc;
-    DevBuf &dq = s->pool[0], &dl = s->pool[1], &dsc = s->pool[2], &dst = s->pool[3], &bm = s->pool[4], &oi = s->pool[5], &os = s->pool[6],
-           &ol = s->pool[7], &vi = s->pool[8], &vs = s->pool[9], &cnt = s->pool[10], &qf = s->pool[11], &qt = s->pool[12], &fzb = s->pool[13];
-    // fused path: entry top-1 [nq] (i64, u32) | the block that travels back in ONE copy: k best visited [nq][k] i64 scores, [nq][k] u32
-    // ids, counters [3 nq + 1] (n_visited, cmps, pq_cmps, err)
-    const size_t fz_block_off = (nq * 12 + 15) & ~(size_t)15;
-    const size_t fz_block_bytes = fz ? nq * fz->k * 12 + (3 * nq + 1) * 4 : 0;
-    if (fz && (fzb.ensure(fz_block_off + fz_block_bytes + 64) || ensure_pin(&s->pin, &s->pin_cap, fz_block_bytes))) return -1;
-    if ((queries_f32 && (qf.ensure(nq * d * 4) || qt.ensure(nq * d * 4))) || dq.ensure(nq * d * 2) || dl.ensure(disable_pq ? 16 : nq * 65536) || dsc.ensure(nq * BS_DESC_MAX * 4 + 16) || dst.ensure(nq * 4) ||
-        bm.ensure(nq * set_words * 8) || oi.ensure(nq * search_list * 4) || os.ensure(nq * search_list * 8) || ol.ensure(nq * 4) ||
-        vi.ensure(nq * visited_cap * 4 + 16) || vs.ensure(nq * visited_cap * 8 + 16) || cnt.ensure(nq * 12 + 16))
-        return -1;
-    if (queries_f32) {
-        // the caller's side of query_disk_index.rs:475-477 on the device: f16 copy of the query (RNE) for the exact scores,
-        // preprocess_query (vector.rs:367-384) for the distance tables -- 64 KiB per query that never cross PCIe
-        if (pq && pq->d != d) return fail("disk_search_batch: codec and vectors differ in width");
-        MSE_HIP_TRY(hipMemcpyAsync(qf.p, queries_f32, nq * d * 4, hipMemcpyHostToDevice, st));
-        if (launch_f32_to_f16(qf.as<float>(), nq * d, dq.as<uint16_t>(), st)) return -1;
-        if (!disable_pq) {
-            if (launch_pq_transform(pq->transform, (int)d, qf.as<float>(), nq, qt.as<float>(), st)) return -1;
-            if (launch_pq_lut_batch(pq->centroids, (int)pq->n_centroids, (int)d, (int)pq->dpc, qt.as<float>(), nq, dl.as<float>(), st)) return -1;
-        }
-    } else {
-        // hipMemcpyDefault: the f16 queries may sit in host memory or already on the device (the text tower's output): the runtime tells by the pointer
-        MSE_HIP_TRY(hipMemcpyAsync(dq.p, queries, nq * d * 2, hipMemcpyDefault, st));
-        if (!disable_pq) MSE_HIP_TRY(hipMemcpyAsync(dl.p, luts, nq * 65536, hipMemcpyHostToDevice, st));
-    }
-    if (bias) MSE_HIP_TRY(hipMemcpyAsync(dsc.p, scales, nq * c->n_desc * 4, hipMemcpyHostToDevice, st));
-    const long long* entry_psc = nullptr;   // small-batch entry step: per-chunk bests, reduced by the search kernel itself
-    const uint32_t* entry_prow = nullptr;
-    int entry_chunks = 0;
-    if (fz && fz->entries) {
-        // the entry step of the request path (src/query_disk_index.rs:254-256,447-450: the medioid of the shard whose centroid is
-        // closest to the query) on the device: exact top-1 of the f16 queries over the entry rows, on this search's stream
-        const mse_graph* eg = fz->entries;
-        if (eg->entry_keys_t) {
-            // the reference's rule itself: centroids as keys, f32 query (an f16 query widened exactly), f64 sums, last maximum
-            hipLaunchKernelGGL(entry_by_centroid_kernel, dim3((unsigned)nq), dim3(256), d * 4, st, eg->entry_keys_t, (int)eg->n_entries, (int)d,
-                               queries_f32 ? qf.as<float>() : nullptr, dq.as<uint16_t>(), eg->entry_ids, dst.as<uint32_t>());
-            MSE_HIP_TRY(hipGetLastError());
-        } else if (nq * eg->n_entries <= ((size_t)1 << 22) && eg->n_entries <= ((size_t)1 << 20)) {
-            // a small batch: exact top-1 over the entry rows in ONE launch (entry_top1_rows_kernel) + the search kernel's prologue
-            const size_t E = eg->n_entries, n_qt = (nq + ET_Q - 1) / ET_Q;
-            size_t rows_per_wg = (E + std::max<size_t>(1, 512 / n_qt) - 1) / std::max<size_t>(1, 512 / n_qt);
-            rows_per_wg = std::max<size_t>(64, (rows_per_wg + 63) / 64 * 64);
-            const size_t n_chunks = (E + rows_per_wg - 1) / rows_per_wg;
-            DevBuf& ep = s->pool[14];
-            if (ep.ensure(n_chunks * nq * 12 + 64)) return -1;
-            long long* psc = ep.as<long long>();
-            uint32_t* prow = reinterpret_cast<uint32_t*>(ep.as<char>() + n_chunks * nq * 8);
-            MSE_DYN_LDS(entry_top1_rows_kernel, ET_Q * d * 2);
-            hipLaunchKernelGGL(entry_top1_rows_kernel, dim3((unsigned)n_chunks, (unsigned)n_qt), dim3(ET_THREADS), ET_Q * d * 2, st, eg->entry_rows, (int)E,
-                               (int)d, dq.as<uint16_t>(), (int)nq, (int)rows_per_wg, psc, prow);
-            MSE_HIP_TRY(hipGetLastError());
-            // (the best chunk per query is picked by the search kernel's first wave: no launch of its own)
-            entry_psc = psc; entry_prow = prow; entry_chunks = (int)n_chunks;
-        } else {
-            int64_t* e_sc = fzb.as<int64_t>();
-            uint32_t* e_row = reinterpret_cast<uint32_t*>(fzb.as<char>() + nq * 8);
-            if (mse_searcher_set_stream(fz->entry_s, st)) return -1;
-            if (mse_bruteforce_topk_f16_dev(fz->entry_s, dq.p, nq, 1, MSE_MODE_AUTO, 0, e_sc, e_row)) return -1;
-            hipLaunchKernelGGL(entry_starts_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, e_row, eg->entry_ids, eg->n_entries, nq, dst.as<uint32_t>());
-            MSE_HIP_TRY(hipGetLastError());
-        }
-    } else {
-        MSE_HIP_TRY(hipMemcpyAsync(dst.p, starts, nq * 4, hipMemcpyHostToDevice, st));
-    }
-    MSE_HIP_TRY(hipMemsetAsync(bm.p, use_hash ? 0xff : 0, nq * set_words * 8, st));
-    // counters: their own buffer, or (fused path) the tail of the block that travels back
-    uint32_t* cnt_dev = fz ? reinterpret_cast<uint32_t*>(fzb.as<char>() + fz_block_off + nq * fz->k * 12) : cnt.as<uint32_t>();
-    MSE_HIP_TRY(hipMemsetAsync(cnt_dev, 0, (3 * nq + 1) * 4, st));
-    const size_t p_cap = beamwidth * ((g->max_deg + 63) / 64 * 64);
-    BeamArgs a{};
-    a.base = b->dev; a.n = b->n; a.d = (int)d;
-    a.codes = c->codes; a.desc = bias ? c->desc : nullptr; a.n_desc = (int)c->n_desc;
-    a.adj = g->adj; a.deg = g->deg; a.max_deg = (int)g->max_deg; a.has_url = g->has_url;
-    a.queries = dq.as<uint16_t>(); a.luts = dl.as<float>(); a.scales = bias ? dsc.as<float>() : nullptr; a.starts = dst.as<uint32_t>();
-    a.beam = (int)beamwidth; a.L = (int)search_list; a.disable_pq = disable_pq; a.p_cap = (int)p_cap;
-    a.bm_adj = bm.as<uint32_t>(); a.bm_vis = bm.as<uint32_t>() + nq * set_words; a.bm_words = set_words; a.hash_bits = use_hash ? table_bits : 0;
-    a.out_ids = oi.as<uint32_t>(); a.out_scores = os.as<long long>(); a.out_len = ol.as<uint32_t>();
-    a.vis_ids = vi.as<uint32_t>(); a.vis_scores = vs.as<long long>(); a.vis_cap = visited_cap;
-    a.n_visited = cnt_dev; a.cmps = cnt_dev + nq; a.pq_cmps = cnt_dev + 2 * nq;
-    a.err = cnt_dev + 3 * nq;
-    a.fill_vis = fz ? 1 : 0;
-    a.entry_psc = entry_psc; a.entry_prow = entry_prow; a.entry_chunks = entry_chunks; a.entry_nq = (int)nq;
-    a.entry_ids = entry_psc ? fz->entries->entry_ids : nullptr;
-    size_t hash_slots = 64;
-    while (hash_slots < 2 * p_cap) hash_slots *= 2;
-    a.hash_slots = (int)hash_slots;
-    // (beam_search_kernel's carving: table | query (exact scoring only) | list scores, pre-buffer scores, list ids, visited flags (one
-    // byte each), pre-buffer ids, ranks | first-position table)
-    const size_t lds = (disable_pq ? 0 : 65536) + (disable_pq ? ((d * 2 + 15) & ~(size_t)15) : 0) + search_list * 12 + ((search_list + 3) & ~(size_t)3) +
-                       p_cap * 16 + hash_slots * 4;
-    static const bool wide_only = MSE_DEV_KNOB("MSE_BEAM_FOUR_WAVES");   // developer library: the four-wave form for every search
-    // one wave per query once the batch fills the chip on its own (16 queries per CU); a smaller batch is latency-bound, and four waves
-    // finish a search sooner (round 5, scripts/beam_latency_probe.py, hard set: 64 queries at L = 12 0.40 ms against 0.98, at L = 200
-    // 5.7 against 8.9; from 2048 queries on the two forms are level)
-    const bool timed = s->beam_timing && s->bev0 && s->beam_tot.p;
-    if (timed) {
-        a.totals = s->beam_tot.as<unsigned long long>();
-        MSE_HIP_TRY(hipEventRecord(s->bev0, st));
-    }
-    // A handful of queries (the request handler's one query per call): the search is a chain of dependent round trips and most of the chip
-    // idles -- sixteen waves per query gather an iteration's ~200 neighbour rows in one round instead of three (round 6; same answers,
-    // counters included: the tiling of the loops is all that changes).  MSE_BEAM_WAVES=4 / 8 / 16 forces a form (answer-preserving hook).
-    static const int force_waves = [] { const char* e = getenv("MSE_BEAM_WAVES"); return e ? atoi(e) : 0; }();
-    const int small_waves = force_waves ? force_waves : (nq <= BS_SMALL_NQ ? BS_SMALL_WAVES : 4);
-    if (disable_pq && search_list <= 256 && p_cap <= 256 && !wide_only && nq > 1024 && !force_waves) {
-        hipLaunchKernelGGL((beam_search_kernel<64, false>), dim3((unsigned)nq), dim3(64), lds, st, a);
-    } else if (small_waves == 16) {
-        if (disable_pq) {
-            MSE_DYN_LDS((beam_search_kernel<1024, false>), 160 * 1024 - 1024);
-            hipLaunchKernelGGL((beam_search_kernel<1024, false>), dim3((unsigned)nq), dim3(1024), lds, st, a);
-        } else {
-            MSE_DYN_LDS((beam_search_kernel<1024, true>), 160 * 1024 - 1024);
-            hipLaunchKernelGGL((beam_search_kernel<1024, true>), dim3((unsigned)nq), dim3(1024), lds, st, a);
-        }
-    } else if (small_waves == 8) {
-        if (disable_pq) {
-            MSE_DYN_LDS((beam_search_kernel<512, false>), 160 * 1024 - 1024);
-            hipLaunchKernelGGL((beam_search_kernel<512, false>), dim3((unsigned)nq), dim3(512), lds, st, a);
-        } else {
-            MSE_DYN_LDS((beam_search_kernel<512, true>), 160 * 1024 - 1024);
-            hipLaunchKernelGGL((beam_search_kernel<512, true>), dim3((unsigned)nq), dim3(512), lds, st, a);
-        }
-    } else {
-        if (disable_pq) {
-            MSE_DYN_LDS((beam_search_kernel<BS_THREADS_MAX, false>), 160 * 1024 - 1024);
-            hipLaunchKernelGGL((beam_search_kernel<BS_THREADS_MAX, false>), dim3((unsigned)nq), dim3(BS_THREADS_MAX), lds, st, a);
-        } else {
-            MSE_DYN_LDS((beam_search_kernel<BS_THREADS_MAX, true>), 160 * 1024 - 1024);
-            hipLaunchKernelGGL((beam_search_kernel<BS_THREADS_MAX, true>), dim3((unsigned)nq), dim3(BS_THREADS_MAX), lds, st, a);
-        }
-    }
-    MSE_HIP_TRY(hipGetLastError());
-    if (timed) MSE_HIP_TRY(hipEventRecord(s->bev1, st));
-    struct BeamTimed {   // read once the stream has been waited for (every path below does before it returns)
-        mse_searcher* s; bool on; size_t nq;
-        ~BeamTimed() {
-            float ms = 0.0f;
-            if (on && hipEventQuery(s->bev1) == hipSuccess && hipEventElapsedTime(&ms, s->bev0, s->bev1) == hipSuccess) {
-                s->beam_ms_total += ms; s->beam_launches++; s->beam_queries += nq;
-            } else if (on) {
-                (void)hipGetLastError();
-            }
-        }
-    } beam_timed{s, timed, nq};
-    uint32_t err = 0;
-    if (fz) {
-        // the server's last step (src/query_disk_index.rs:529-540: the visited records ordered by exact score) cut to its first k, on
-        // the device: the kernel has padded every visited list to visited_cap with (ID_NONE, INT64_MIN).  Scores, ids and the counters
-        // come back in ONE copy into the searcher's pinned staging (round 5: five pageable copies before).
-        int64_t* top_sc = reinterpret_cast<int64_t*>(fzb.as<char>() + fz_block_off);
-        uint32_t* top_id = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(top_sc) + nq * fz->k * 8);
-        if (g->dedup_threshold > 0.0f) {
-            // the handler's runtime de-duplication (:482-527) before its sort: a visited record that resembles an already kept one (dot of
-            // the f32-widened vectors above the threshold, visit order) leaves the list -- on the device, for every query of the batch
-            DevBuf& db = s->pool[15];
-            if (db.ensure(dedup_batch_scratch_bytes(nq, visited_cap))) return -1;
-            if (launch_dedup_batch(b->dev, (int)d, vi.as<uint32_t>(), vs.as<long long>(), visited_cap, cnt_dev, nq, g->dedup_threshold, db.p, st)) return -1;
-        }
-        SelectArgs sa{};
-        sa.kind = KEY_I64; sa.list_ids = vi.as<uint32_t>(); sa.list_keys = vs.p; sa.list_stride = visited_cap; sa.n_list = visited_cap;
-        sa.k = (int)fz->k; sa.out_ids = top_id; sa.out_keys = top_sc; sa.out_stride = fz->k; sa.nq = (int)nq;
-        if (launch_select(sa, st)) return -1;
-        const char* blk = static_cast<const char*>(s->pin);
-        if (fz->dev_sc) {   // results stay on the device (global ids); the counters come back alone, at their usual place in the staging
-            if (launch_block_finish(top_sc, top_id, nq * fz->k, fz->id_offset, fz->dev_sc, fz->dev_ids, st)) return -1;
-            MSE_HIP_TRY(hipMemcpyAsync(s->pin ? static_cast<char*>(s->pin) + nq * fz->k * 12 : nullptr, cnt_dev, (3 * nq + 1) * 4, hipMemcpyDeviceToHost, st));
-        } else {
-            MSE_HIP_TRY(hipMemcpyAsync(s->pin, top_sc, fz_block_bytes, hipMemcpyDeviceToHost, st));
-        }
-        MSE_HIP_TRY(hipStreamSynchronize(st));
-        const int64_t* h_sc = reinterpret_cast<const int64_t*>(blk);
-        const uint32_t* h_id = reinterpret_cast<const uint32_t*>(blk + nq * fz->k * 8);
-        const uint32_t* h_cnt = reinterpret_cast<const uint32_t*>(blk + nq * fz->k * 12);
-        err = h_cnt[3 * nq];
-        if (err & 1u) return fail("disk_search_batch: a graph edge points outside the index");
-        if (err & 4u)   // a search outgrew its table: the bit maps have room for everything
-            return disk_search_batch_impl(0, s, pq, c, g, starts, queries, queries_f32, luts, scales, nq, disable_pq, beamwidth, search_list, buf_ids,
-                                          buf_scores, buf_len, visited_ids, visited_scores, visited_cap, n_visited, cmps, pq_cmps, fz);
-        // the reference keeps every visited record: a list that outgrew the device arrays means the caller repeats with larger ones
-        for (size_t q = 0; q < nq; q++)
-            if (h_cnt[q] > visited_cap) return -2;
-        for (size_t q = 0; q < nq; q++) {
-            QueryDst o = fz->dst ? fz->dst[q]
-                                 : QueryDst{fz->ids + q * fz->k, fz->scores + q * fz->k, fz->n_visited ? fz->n_visited + q : nullptr,
-                                            fz->cmps ? fz->cmps + q : nullptr, fz->pq_cmps ? fz->pq_cmps + q : nullptr, fz->k};
-            // a caller's k records are the first k of the largest k's: the order (score descending, id ascending) is total
-            if (!fz->dev_sc) {
-                memcpy(o.ids, h_id + q * fz->k, o.k * 4);
-                memcpy(o.scores, h_sc + q * fz->k, o.k * 8);
-            }
-            if (o.n_visited) *o.n_visited = h_cnt[q];
-            if (o.cmps) *o.cmps = h_cnt[nq + q];
-            if (o.pq_cmps) *o.pq_cmps = h_cnt[2 * nq + q];
-        }
-        return 0;
-    }
-    MSE_HIP_TRY(hipMemcpyAsync(buf_ids, oi.p, nq * search_list * 4, hipMemcpyDeviceToHost, st));
-    MSE_HIP_TRY(hipMemcpyAsync(buf_scores, os.p, nq * search_list * 8, hipMemcpyDeviceToHost, st));
-    MSE_HIP_TRY(hipMemcpyAsync(buf_len, ol.p, nq * 4, hipMemcpyDeviceToHost, st));
-    MSE_HIP_TRY(hipMemcpyAsync(n_visited, a.n_visited, nq * 4, hipMemcpyDeviceToHost, st));
-    MSE_HIP_TRY(hipMemcpyAsync(cmps, a.cmps, nq * 4, hipMemcpyDeviceToHost, st));
-    MSE_HIP_TRY(hipMemcpyAsync(pq_cmps, a.pq_cmps, nq * 4, hipMemcpyDeviceToHost, st));
-    MSE_HIP_TRY(hipMemcpyAsync(&err, a.err, 4, hipMemcpyDeviceToHost, st));
-    MSE_HIP_TRY(hipStreamSynchronize(st));
-    if (err & 1u) return fail("disk_search_batch: a graph edge points outside the index");
-    if (err & 4u)   // a search outgrew its table: the bit maps have room for everything
-        return disk_search_batch_impl(0, s, pq, c, g, starts, queries, queries_f32, luts, scales, nq, disable_pq, beamwidth, search_list, buf_ids,
-                                      buf_scores, buf_len, visited_ids, visited_scores, visited_cap, n_visited, cmps, pq_cmps, fz);
-    if (visited_cap) {   // only the columns any query filled travel back (entries past n_visited[q] are unspecified)
-        size_t widest = 0;
-        for (size_t q = 0; q < nq; q++) widest = n_visited[q] > widest ? n_visited[q] : widest;
-        if (widest > visited_cap) widest = visited_cap;
-        if (widest) {
-            MSE_HIP_TRY(hipMemcpy2DAsync(visited_ids, visited_cap * 4, vi.p, visited_cap * 4, widest * 4, nq, hipMemcpyDeviceToHost, st));
-            MSE_HIP_TRY(hipMemcpy2DAsync(visited_scores, visited_cap * 8, vs.p, visited_cap * 8, widest * 8, nq, hipMemcpyDeviceToHost, st));
-            MSE_HIP_TRY(hipStreamSynchronize(st));
-        }
-    }
-    return 0;
 }
 
 }  // extern "C"
@@ -1100,85 +1193,68 @@ namespace {
 enum : size_t { REQ_BEAM = 0, REQ_QUERY = 1 };
 constexpr size_t FUSED_COALESCE_MAX = 16;   // calls with more queries go straight to the device on the caller's searcher
 
+// a one-query call of the list form
 struct BeamCall {
-    mse_searcher* s; mse_pq* pq; const mse_codes* c; const mse_graph* g; const uint32_t* starts;
-    const uint16_t* queries; const float* queries_f32; const float* luts; const float* scales;
-    int disable_pq; size_t beamwidth, search_list, visited_cap;
-    uint32_t* buf_ids; int64_t* buf_scores; uint32_t* buf_len; uint32_t* visited_ids; int64_t* visited_scores;
-    uint32_t *n_visited, *cmps, *pq_cmps;
+    SearchIn in;
+    ListOut out;
     bool shares_with(const BeamCall& o) const {
-        return s->base == o.s->base && pq == o.pq && c == o.c && g == o.g && disable_pq == o.disable_pq && beamwidth == o.beamwidth &&
-               search_list == o.search_list && visited_cap == o.visited_cap && (queries != nullptr) == (o.queries != nullptr) &&
-               (luts != nullptr) == (o.luts != nullptr) && (scales != nullptr) == (o.scales != nullptr) &&
-               (visited_ids != nullptr) == (o.visited_ids != nullptr) && (visited_scores != nullptr) == (o.visited_scores != nullptr);
+        return in.shares_with(o.in) && out.visited_cap == o.out.visited_cap && (out.visited_ids != nullptr) == (o.out.visited_ids != nullptr) &&
+               (out.visited_scores != nullptr) == (o.out.visited_scores != nullptr);
     }
 };
-int beam_call_alone(const BeamCall& k) {
-    return disk_search_batch_impl(-1, k.s, k.pq, k.c, k.g, k.starts, k.queries, k.queries_f32, k.luts, k.scales, 1, k.disable_pq, k.beamwidth,
-                                  k.search_list, k.buf_ids, k.buf_scores, k.buf_len, k.visited_ids, k.visited_scores, k.visited_cap, k.n_visited,
-                                  k.cmps, k.pq_cmps);
-}
-void beam_run_group(std::vector<DispatchReq*>& grp) {
-    const BeamCall& lead = *static_cast<const BeamCall*>(grp[0]->aux0);
-    (void)hipSetDevice(lead.s->base->device);
-    const size_t n = grp.size(), d = lead.s->base->d, L = lead.search_list, vc = lead.visited_cap;
-    const size_t n_desc = (lead.scales && lead.c) ? lead.c->n_desc : 0;
-    int rc = 0;
-    if (n == 1) {
-        rc = beam_call_alone(lead);
-        grp[0]->rc = rc;
-        if (rc) grp[0]->err = mse_last_error();
-        return;
-    }
-    std::vector<uint32_t> starts(n), ids(n * L), len(n), nv(n), cm(n), pc(n), vids(lead.visited_ids ? n * vc : 0);
-    std::vector<int64_t> sc(n * L), vsc(lead.visited_scores ? n * vc : 0);
-    std::vector<uint16_t> q16(lead.queries ? n * d : 0);
-    std::vector<float> q32(lead.queries_f32 ? n * d : 0), luts(lead.luts ? n * 16384 : 0), scl(n_desc ? n * n_desc : 0);
+int beam_call_alone(const BeamCall& k) { return disk_search_batch_impl(-1, k.in, &k.out, nullptr); }
+
+// `n` one-query calls that can share a launch = ONE batched search on the searcher of the first (alone: the caller's own call)
+int beam_run_requests(DispatchReq* const* reqs, size_t n) {
+    const BeamCall& lead = *static_cast<const BeamCall*>(reqs[0]->aux0);
+    if (n == 1) return beam_call_alone(lead);
+    const size_t d = lead.in.s->base->d, L = lead.in.search_list, vc = lead.out.visited_cap;
+    const size_t n_desc = (lead.in.scales && lead.in.c) ? lead.in.c->n_desc : 0;
+    std::vector<uint32_t> starts(n), ids(n * L), len(n), nv(n), cm(n), pc(n), vids(lead.out.visited_ids ? n * vc : 0);
+    std::vector<int64_t> sc(n * L), vsc(lead.out.visited_scores ? n * vc : 0);
+    std::vector<uint16_t> q16(lead.in.queries ? n * d : 0);
+    std::vector<float> q32(lead.in.queries_f32 ? n * d : 0), luts(lead.in.luts ? n * 16384 : 0), scl(n_desc ? n * n_desc : 0);
     for (size_t j = 0; j < n; j++) {
-        const BeamCall& k = *static_cast<const BeamCall*>(grp[j]->aux0);
+        const SearchIn& k = static_cast<const BeamCall*>(reqs[j]->aux0)->in;
         starts[j] = k.starts[0];
         if (k.queries) memcpy(q16.data() + j * d, k.queries, d * 2);
         if (k.queries_f32) memcpy(q32.data() + j * d, k.queries_f32, d * 4);
         if (k.luts) memcpy(luts.data() + j * 16384, k.luts, 16384 * 4);
         if (n_desc) memcpy(scl.data() + j * n_desc, k.scales, n_desc * 4);
     }
-    rc = disk_search_batch_impl(-1, lead.s, lead.pq, lead.c, lead.g, starts.data(), lead.queries ? q16.data() : nullptr,
-                                lead.queries_f32 ? q32.data() : nullptr, lead.luts ? luts.data() : nullptr, n_desc ? scl.data() : lead.scales, n,
-                                lead.disable_pq, lead.beamwidth, L, ids.data(), sc.data(), len.data(), lead.visited_ids ? vids.data() : nullptr,
-                                lead.visited_scores ? vsc.data() : nullptr, vc, nv.data(), cm.data(), pc.data());
+    SearchIn in = lead.in;
+    in.starts = starts.data(); in.queries = lead.in.queries ? q16.data() : nullptr; in.queries_f32 = lead.in.queries_f32 ? q32.data() : nullptr;
+    in.luts = lead.in.luts ? luts.data() : nullptr; in.scales = n_desc ? scl.data() : lead.in.scales; in.nq = n;
+    const ListOut out{ids.data(), sc.data(), len.data(), lead.out.visited_ids ? vids.data() : nullptr, lead.out.visited_scores ? vsc.data() : nullptr,
+                      vc, nv.data(), cm.data(), pc.data()};
+    if (const int rc = disk_search_batch_impl(-1, in, &out, nullptr)) return rc;
     for (size_t j = 0; j < n; j++) {
-        const BeamCall& k = *static_cast<const BeamCall*>(grp[j]->aux0);
-        if (rc) {     // the shared launch failed: each caller is repeated alone and sees only its own outcome
-            grp[j]->rc = beam_call_alone(k);
-            if (grp[j]->rc) grp[j]->err = mse_last_error();
-            continue;
-        }
-        memcpy(k.buf_ids, ids.data() + j * L, L * 4);
-        memcpy(k.buf_scores, sc.data() + j * L, L * 8);
-        k.buf_len[0] = len[j]; k.n_visited[0] = nv[j]; k.cmps[0] = cm[j]; k.pq_cmps[0] = pc[j];
-        if (k.visited_ids) memcpy(k.visited_ids, vids.data() + j * vc, vc * 4);
-        if (k.visited_scores) memcpy(k.visited_scores, vsc.data() + j * vc, vc * 8);
-        grp[j]->rc = 0;
+        const ListOut& o = static_cast<const BeamCall*>(reqs[j]->aux0)->out;
+        memcpy(o.buf_ids, ids.data() + j * L, L * 4);
+        memcpy(o.buf_scores, sc.data() + j * L, L * 8);
+        o.buf_len[0] = len[j]; o.n_visited[0] = nv[j]; o.cmps[0] = cm[j]; o.pq_cmps[0] = pc[j];
+        if (o.visited_ids) memcpy(o.visited_ids, vids.data() + j * vc, vc * 4);
+        if (o.visited_scores) memcpy(o.visited_scores, vsc.data() + j * vc, vc * 8);
     }
+    return 0;
+}
+
+void beam_run_group(std::vector<DispatchReq*>& grp) {
+    (void)hipSetDevice(static_cast<const BeamCall*>(grp[0]->aux0)->in.s->base->device);
+    run_shared(grp, beam_run_requests);
 }
 
 // the request path in one call: src/query_disk_index.rs:436-540
 struct QueryCall {
-    mse_searcher* s; mse_pq* pq; const mse_codes* c; const mse_graph* g; const uint32_t* starts;
-    const uint16_t* queries; const float* queries_f32; const float* luts; const float* scales; size_t nq;
-    int disable_pq; size_t beamwidth, search_list, k;
-    uint32_t* ids; int64_t* scores; uint32_t *n_visited, *cmps, *pq_cmps;
-    bool shares_with(const QueryCall& o) const {
-        return s->base == o.s->base && pq == o.pq && c == o.c && g == o.g && disable_pq == o.disable_pq && beamwidth == o.beamwidth &&
-               search_list == o.search_list && (starts != nullptr) == (o.starts != nullptr) && (queries != nullptr) == (o.queries != nullptr) &&
-               (luts != nullptr) == (o.luts != nullptr) && (scales != nullptr) == (o.scales != nullptr);
-    }
+    SearchIn in;
+    FusedQuery out;   // k and the contiguous outputs
+    bool shares_with(const QueryCall& o) const { return in.shares_with(o.in) && (in.starts != nullptr) == (o.in.starts != nullptr); }
 };
 
 // Entry searcher (row tables), the shared hold on the entry table, and the grow-and-repeat loop around the batched search.  `fz`
 // arrives with k and its destinations set.
-int fused_run(mse_searcher* s, mse_pq* pq, const mse_codes* c, const mse_graph* g, const uint32_t* starts, const uint16_t* q16, const float* q32,
-              const float* luts, const float* scales, size_t nq, int disable_pq, size_t beamwidth, size_t search_list, FusedQuery fz) {
+int fused_run(const SearchIn& in, FusedQuery fz) {
+    const mse_graph* g = in.g;
     // the table cannot be replaced under a call in flight (mse_graph_set_entries takes the lock exclusively)
     struct Shared {
         SharedExclusive* l = nullptr;
@@ -1190,7 +1266,7 @@ int fused_run(mse_searcher* s, mse_pq* pq, const mse_codes* c, const mse_graph* 
         ~Borrow() { if (es) { std::lock_guard<std::mutex> lk(g->entry_mu); g->entry_pool.push_back(es); } }
     } borrow{g};
     fz.entries = nullptr;
-    if (!starts) {
+    if (!in.starts) {
         g->entry_lock.lock_shared();
         hold.l = &g->entry_lock;
         if (g->n_entries == 0 || (!g->entry_base && !g->entry_keys_t))
@@ -1207,10 +1283,10 @@ int fused_run(mse_searcher* s, mse_pq* pq, const mse_codes* c, const mse_graph* 
     }
     // visited records per query kept on the device: a search fetches about search_list + a few nodes; a list that outgrows the arrays
     // is never cut (the reference keeps every record) -- the call is repeated with four times the room
-    size_t cap = (std::max(2 * search_list + 64, fz.k) + 63) / 64 * 64;
+    size_t& cap = fz.visited_cap;
+    cap = (std::max(2 * in.search_list + 64, fz.k) + 63) / 64 * 64;
     for (;;) {
-        const int rc = disk_search_batch_impl(-1, s, pq, c, g, starts, q16, q32, luts, scales, nq, disable_pq, beamwidth, search_list, nullptr,
-                                              nullptr, nullptr, nullptr, nullptr, cap, nullptr, nullptr, nullptr, &fz);
+        const int rc = disk_search_batch_impl(-1, in, nullptr, &fz);
         if (rc != -2) return rc;
         if (cap >= ((size_t)1 << 16)) return fail("disk_query_topk: a search visited more than 65536 records");
         // with the handler's de-duplication on, a query's similarity bits cover at most 4096 visited records: grow to exactly that
@@ -1225,53 +1301,51 @@ int fused_run(mse_searcher* s, mse_pq* pq, const mse_codes* c, const mse_graph* 
     }
 }
 
-int query_call_on(mse_searcher* s, const QueryCall& k) {
-    FusedQuery fz;
-    fz.k = k.k; fz.ids = k.ids; fz.scores = k.scores; fz.n_visited = k.n_visited; fz.cmps = k.cmps; fz.pq_cmps = k.pq_cmps;
-    return fused_run(s, k.pq, k.c, k.g, k.starts, k.queries, k.queries_f32, k.luts, k.scales, k.nq, k.disable_pq, k.beamwidth, k.search_list, fz);
-}
-
 // `n` waiting request-path calls that can share a submission = ONE entry step + ONE search launch + ONE select, on the worker's own
 // searcher.  Inputs are gathered straight into pinned memory -- also for a single request: a pageable source of more than a few KB
 // makes the runtime pin the caller's pages for the copy (a 16-query call from a numpy array: 4.8 ms against 0.5 ms).
 int query_run_requests(mse_graph::WorkerCtx& ctx, DispatchReq* const* reqs, size_t n) {
-    const QueryCall& lead = *static_cast<const QueryCall*>(reqs[0]->aux0);
-    const mse_graph* g = lead.g;
+    const SearchIn& lead = static_cast<const QueryCall*>(reqs[0]->aux0)->in;
     const size_t d = lead.s->base->d, n_desc = (lead.scales && lead.c) ? lead.c->n_desc : 0;
     size_t total = 0, kmax = 0;
     for (size_t i = 0; i < n; i++) {
         const QueryCall& k = *static_cast<const QueryCall*>(reqs[i]->aux0);
-        total += k.nq;
-        kmax = std::max(kmax, k.k);
+        total += k.in.nq;
+        kmax = std::max(kmax, k.out.k);
     }
     const size_t q_bytes = total * d * (lead.queries ? 2 : 4), sc_bytes = total * n_desc * 4, st_bytes = lead.starts ? total * 4 : 0;
     const size_t lut_bytes = lead.luts ? total * 65536 : 0;
     const size_t off_sc = (q_bytes + 63) & ~(size_t)63, off_st = (off_sc + sc_bytes + 63) & ~(size_t)63, off_lut = (off_st + st_bytes + 63) & ~(size_t)63;
-    if (ensure_pin(&ctx.pin, &ctx.pin_cap, off_lut + lut_bytes + 64)) return -1;
-    char* p = static_cast<char*>(ctx.pin);
+    if (ctx.pin.ensure(off_lut + lut_bytes + 64, (size_t)1 << 16)) return -1;
+    char* p = ctx.pin.as<char>();
     ctx.dsts.resize(total);
     size_t row = 0;
     for (size_t i = 0; i < n; i++) {
-        const QueryCall& k = *static_cast<const QueryCall*>(reqs[i]->aux0);
+        const SearchIn& k = static_cast<const QueryCall*>(reqs[i]->aux0)->in;
+        const FusedQuery& o = static_cast<const QueryCall*>(reqs[i]->aux0)->out;
         if (k.queries) memcpy(p + row * d * 2, k.queries, k.nq * d * 2);
         else memcpy(p + row * d * 4, k.queries_f32, k.nq * d * 4);
         if (n_desc) memcpy(p + off_sc + row * n_desc * 4, k.scales, k.nq * n_desc * 4);
         if (k.starts) memcpy(p + off_st + row * 4, k.starts, k.nq * 4);
         if (k.luts) memcpy(p + off_lut + row * 65536, k.luts, k.nq * 65536);
         for (size_t q = 0; q < k.nq; q++, row++)
-            ctx.dsts[row] = QueryDst{k.ids + q * k.k, k.scores + q * k.k, k.n_visited ? k.n_visited + q : nullptr, k.cmps ? k.cmps + q : nullptr,
-                                     k.pq_cmps ? k.pq_cmps + q : nullptr, k.k};
+            ctx.dsts[row] = QueryDst{o.ids + q * o.k, o.scores + q * o.k, shifted(o.n_visited, q), shifted(o.cmps, q), shifted(o.pq_cmps, q), o.k};
     }
+    SearchIn in = lead;
+    in.s = ctx.s;
+    in.starts = lead.starts ? reinterpret_cast<const uint32_t*>(p + off_st) : nullptr;
+    in.queries = lead.queries ? reinterpret_cast<const uint16_t*>(p) : nullptr;
+    in.queries_f32 = lead.queries ? nullptr : reinterpret_cast<const float*>(p);
+    in.luts = lead.luts ? reinterpret_cast<const float*>(p + off_lut) : nullptr;
+    in.scales = n_desc ? reinterpret_cast<const float*>(p + off_sc) : lead.scales;
+    in.nq = total;
     FusedQuery fz;
     fz.k = kmax; fz.dst = ctx.dsts.data();
-    return fused_run(ctx.s, lead.pq, lead.c, g, lead.starts ? reinterpret_cast<const uint32_t*>(p + off_st) : nullptr,
-                     lead.queries ? reinterpret_cast<const uint16_t*>(p) : nullptr, lead.queries ? nullptr : reinterpret_cast<const float*>(p),
-                     lead.luts ? reinterpret_cast<const float*>(p + off_lut) : nullptr, n_desc ? reinterpret_cast<const float*>(p + off_sc) : lead.scales,
-                     total, lead.disable_pq, lead.beamwidth, lead.search_list, fz);
+    return fused_run(in, fz);
 }
 
 void query_run_group(std::vector<DispatchReq*>& grp) {
-    const QueryCall& lead = *static_cast<const QueryCall*>(grp[0]->aux0);
+    const SearchIn& lead = static_cast<const QueryCall*>(grp[0]->aux0)->in;
     const mse_graph* g = lead.g;
     const mse_base* b = lead.s->base;
     (void)hipSetDevice(b->device);
@@ -1286,37 +1360,20 @@ void query_run_group(std::vector<DispatchReq*>& grp) {
             return;
         }
     }
-    if (query_run_requests(ctx, grp.data(), grp.size()) == 0) {
-        for (DispatchReq* r : grp) r->rc = 0;
-        return;
-    }
-    if (grp.size() == 1) {
-        grp[0]->rc = -1;
-        grp[0]->err = mse_last_error();
-        return;
-    }
-    // the shared submission failed: each request on its own, so that a caller only ever sees its own outcome
-    for (DispatchReq* r : grp) {
-        r->rc = query_run_requests(ctx, &r, 1);
-        if (r->rc) r->err = mse_last_error();
-    }
+    run_shared(grp, [&ctx](DispatchReq* const* reqs, size_t n) { return query_run_requests(ctx, reqs, n); });
+}
+
+bool same_call(const DispatchReq& a, const DispatchReq& b) {
+    if (a.aux_n != b.aux_n) return false;
+    return a.aux_n == REQ_BEAM ? static_cast<const BeamCall*>(a.aux0)->shares_with(*static_cast<const BeamCall*>(b.aux0))
+                               : static_cast<const QueryCall*>(a.aux0)->shares_with(*static_cast<const QueryCall*>(b.aux0));
 }
 
 void graph_run_batch(std::vector<DispatchReq*>& batch) {
-    std::vector<char> taken(batch.size(), 0);
-    std::vector<DispatchReq*> grp;
-    for (size_t i = 0; i < batch.size(); i++) {
-        if (taken[i]) continue;
-        grp.clear();
-        const size_t kind = batch[i]->aux_n;
-        for (size_t j = i; j < batch.size(); j++) {
-            if (taken[j] || batch[j]->aux_n != kind) continue;
-            const bool same = kind == REQ_BEAM ? static_cast<const BeamCall*>(batch[i]->aux0)->shares_with(*static_cast<const BeamCall*>(batch[j]->aux0))
-                                               : static_cast<const QueryCall*>(batch[i]->aux0)->shares_with(*static_cast<const QueryCall*>(batch[j]->aux0));
-            if (same) { taken[j] = 1; grp.push_back(batch[j]); }
-        }
-        if (kind == REQ_BEAM) beam_run_group(grp); else query_run_group(grp);
-    }
+    for_each_shared_group(batch, same_call, [](std::vector<DispatchReq*>& grp) {
+        if (grp[0]->aux_n == REQ_BEAM) beam_run_group(grp);
+        else query_run_group(grp);
+    });
 }
 
 Coalescer* graph_coalescer(const mse_graph* g) {
@@ -1326,11 +1383,8 @@ Coalescer* graph_coalescer(const mse_graph* g) {
         const int workers = g->co_workers > 0 ? g->co_workers : 3;
         // contexts beyond the new worker count own a searcher (device scratch, a stream) and pinned staging: freed, not dropped
         // (no worker is alive here: the previous coalescer was deleted, and with it its threads, before a new one is made)
-        for (size_t w = (size_t)workers; w < g->co_ctx.size(); w++) {
+        for (size_t w = (size_t)workers; w < g->co_ctx.size(); w++)
             if (g->co_ctx[w].s) mse_searcher_free(g->co_ctx[w].s);
-            if (g->co_ctx[w].pin) (void)hipHostFree(g->co_ctx[w].pin);
-            g->co_ctx[w] = mse_graph::WorkerCtx{};
-        }
         g->co_ctx.resize((size_t)workers);
         g->co = new (std::nothrow) Coalescer(g->co_max_queries ? g->co_max_queries : 1024, g->co_max_wait_us ? g->co_max_wait_us : 200,
                                              [](std::vector<DispatchReq*>& b) { graph_run_batch(b); }, nullptr, workers);
@@ -1341,14 +1395,15 @@ Coalescer* graph_coalescer(const mse_graph* g) {
 }
 
 // nq == 1: through the graph's coalescer.  Argument errors that belong to one caller are found before it queues.
-int beam_one_query(BeamCall& k) {
-    if (!k.s || !k.s->base || !k.g || !k.starts || (!k.queries && !k.queries_f32) || !k.buf_ids || !k.buf_scores || !k.buf_len || !k.n_visited ||
-        !k.cmps || !k.pq_cmps)
+int beam_one_query(const BeamCall& k) {
+    const SearchIn& in = k.in;
+    const ListOut& o = k.out;
+    if (!in.s || !in.s->base || !in.g || !in.starts || (!in.queries && !in.queries_f32) || !o.buf_ids || !o.buf_scores || !o.buf_len ||
+        !o.n_visited || !o.cmps || !o.pq_cmps)
         return fail("disk_search_batch: null argument");
-    if (k.beamwidth == 0 || k.beamwidth > BS_BEAM_MAX) return fail("disk_search_batch: beamwidth must be 1..8");
-    if (k.search_list == 0 || k.search_list > BS_LMAX) return fail("disk_search_batch: search_list must be 1..1024");
-    if (k.starts[0] >= k.g->n) return beam_call_alone(k);   // let the search report it in its own words
-    Coalescer* co = graph_coalescer(k.g);
+    if (check_params(in)) return -1;
+    if (in.starts[0] >= in.g->n) return beam_call_alone(k);   // let the search report it in its own words
+    Coalescer* co = graph_coalescer(in.g);
     if (!co) return -1;
     DispatchReq r;
     r.nq = 1;
@@ -1357,6 +1412,9 @@ int beam_one_query(BeamCall& k) {
     return co->submit(r);
 }
 
+// the list form: one query through the coalescer, more straight to the device
+int disk_search_batch(const BeamCall& k) { return k.in.nq == 1 ? beam_one_query(k) : disk_search_batch_impl(-1, k.in, &k.out, nullptr); }
+
 // true when p points into device (or managed) memory; plain host memory is unknown to the runtime and reported as an error
 bool is_device_pointer(const void* p) {
     hipPointerAttribute_t at{};
@@ -1364,24 +1422,21 @@ bool is_device_pointer(const void* p) {
     return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
 }
 
-int query_front(QueryCall& k) {
-    if (!k.g || !k.ids || !k.scores || (!k.queries && !k.queries_f32)) return fail("disk_query_topk: null argument");
-    if (k.nq == 0) return 0;
-    if (!k.s || !k.s->base) return fail("disk_query_topk: null searcher");
-    if (k.k == 0 || k.k > (size_t)TOPK_KMAX - 64) return fail("disk_query_topk: bad k / outputs");
+int query_front(const QueryCall& k) {
+    const SearchIn& in = k.in;
+    if (!in.g || !k.out.ids || !k.out.scores || (!in.queries && !in.queries_f32)) return fail("disk_query_topk: null argument");
+    if (in.nq == 0) return 0;
+    if (!in.s || !in.s->base) return fail("disk_query_topk: null searcher");
+    if (check_k(k.out.k)) return -1;
     // f16 queries may be device-resident (embeddings that never left the GPU): such a call cannot be gathered by the host and goes straight
     // to the device.  f32 queries are host memory by contract (the handler's input, :436-477): no runtime call on the request thread.
-    if (k.nq > FUSED_COALESCE_MAX || (k.queries && is_device_pointer(k.queries))) return query_call_on(k.s, k);
+    if (in.nq > FUSED_COALESCE_MAX || (in.queries && is_device_pointer(in.queries))) return fused_run(in, k.out);
     // what belongs to this caller alone is found before it queues
-    if (k.beamwidth == 0 || k.beamwidth > BS_BEAM_MAX) return fail("disk_search_batch: beamwidth must be 1..8");
-    if (k.search_list == 0 || k.search_list > BS_LMAX) return fail("disk_search_batch: search_list must be 1..1024");
-    if ((!k.disable_pq && (!k.pq || !k.c || (!k.luts && !k.queries_f32))) || (k.scales && !k.c)) return fail("disk_search_batch: null argument");
-    for (size_t q = 0; k.starts && q < k.nq; q++)
-        if (k.starts[q] >= k.g->n) return fail("disk_search_batch: start node out of range");
-    Coalescer* co = graph_coalescer(k.g);
+    if (check_queued(in)) return -1;
+    Coalescer* co = graph_coalescer(in.g);
     if (!co) return -1;
     DispatchReq r;
-    r.nq = k.nq;
+    r.nq = in.nq;
     r.aux0 = &k;
     r.aux_n = REQ_QUERY;
     return co->submit(r);
@@ -1396,13 +1451,8 @@ int mse_disk_search_batch(mse_searcher* s, mse_pq* pq, const mse_codes* c, const
                           uint32_t* visited_ids, int64_t* visited_scores, size_t visited_cap, uint32_t* n_visited,
                           uint32_t* cmps, uint32_t* pq_cmps) {
     if (!queries) return fail("disk_search_batch: null argument");
-    if (nq == 1) {
-        BeamCall k{s, pq, c, g, starts, queries, nullptr, luts, scales, disable_pq, beamwidth, search_list, visited_cap, buf_ids, buf_scores, buf_len,
-                   visited_ids, visited_scores, n_visited, cmps, pq_cmps};
-        return beam_one_query(k);
-    }
-    return disk_search_batch_impl(-1, s, pq, c, g, starts, queries, nullptr, luts, scales, nq, disable_pq, beamwidth, search_list, buf_ids,
-                                  buf_scores, buf_len, visited_ids, visited_scores, visited_cap, n_visited, cmps, pq_cmps);
+    return disk_search_batch(BeamCall{SearchIn{s, pq, c, g, starts, queries, nullptr, luts, scales, nq, disable_pq, beamwidth, search_list},
+                                      ListOut{buf_ids, buf_scores, buf_len, visited_ids, visited_scores, visited_cap, n_visited, cmps, pq_cmps}});
 }
 
 // ---- the request path in one call (src/query_disk_index.rs:436-540 for a batch) ---------------------------------------------
@@ -1493,16 +1543,16 @@ int mse_disk_query_topk(mse_searcher* s, mse_pq* pq, const mse_codes* c, const m
                         const float* luts, const float* scales, size_t nq, int disable_pq, size_t beamwidth, size_t search_list, size_t k,
                         uint32_t* ids, int64_t* scores, uint32_t* n_visited, uint32_t* cmps, uint32_t* pq_cmps) {
     if (!queries) return fail("disk_query_topk: null argument");
-    QueryCall q{s, pq, c, g, starts, queries, nullptr, luts, scales, nq, disable_pq, beamwidth, search_list, k, ids, scores, n_visited, cmps, pq_cmps};
-    return query_front(q);
+    return query_front(QueryCall{SearchIn{s, pq, c, g, starts, queries, nullptr, luts, scales, nq, disable_pq, beamwidth, search_list},
+                                 fused_out(k, ids, scores, n_visited, cmps, pq_cmps)});
 }
 
 int mse_disk_query_topk_f32(mse_searcher* s, mse_pq* pq, const mse_codes* c, const mse_graph* g, const uint32_t* starts, const float* queries_f32,
                             const float* scales, size_t nq, int disable_pq, size_t beamwidth, size_t search_list, size_t k, uint32_t* ids,
                             int64_t* scores, uint32_t* n_visited, uint32_t* cmps, uint32_t* pq_cmps) {
     if (!queries_f32) return fail("disk_query_topk_f32: null argument");
-    QueryCall q{s, pq, c, g, starts, nullptr, queries_f32, nullptr, scales, nq, disable_pq, beamwidth, search_list, k, ids, scores, n_visited, cmps, pq_cmps};
-    return query_front(q);
+    return query_front(QueryCall{SearchIn{s, pq, c, g, starts, nullptr, queries_f32, nullptr, scales, nq, disable_pq, beamwidth, search_list},
+                                 fused_out(k, ids, scores, n_visited, cmps, pq_cmps)});
 }
 
 // ---- the request path without a thread per request (round 5) ----------------------------------------------------------------
@@ -1551,38 +1601,31 @@ void ticket_give(mse_ticket* t) {
     }
 }
 
-int submit_f32(bool copy, mse_searcher* s, mse_pq* pq, const mse_codes* c, const mse_graph* g, const float* queries_f32, const float* scales,
-               size_t nq, int disable_pq, size_t beamwidth, size_t search_list, size_t k, uint32_t* ids, int64_t* scores,
-               uint32_t* n_visited, uint32_t* cmps, uint32_t* pq_cmps, void* user, mse_completion_queue* cq,
-               mse_ticket** ticket_out) {
-    if (!queries_f32 || !ticket_out || !g || !ids || !scores) return fail("disk_query_submit_f32: null argument");
-    if (!s || !s->base) return fail("disk_query_submit_f32: null searcher");
-    if (nq == 0 || nq > FUSED_COALESCE_MAX) return fail("disk_query_submit_f32: 1.." + std::to_string(FUSED_COALESCE_MAX) + " queries per request");
-    if (k == 0 || k > (size_t)TOPK_KMAX - 64) return fail("disk_query_topk: bad k / outputs");
-    if (beamwidth == 0 || beamwidth > BS_BEAM_MAX) return fail("disk_search_batch: beamwidth must be 1..8");
-    if (search_list == 0 || search_list > BS_LMAX) return fail("disk_search_batch: search_list must be 1..1024");
-    if ((!disable_pq && (!pq || !c)) || (scales && !c)) return fail("disk_search_batch: null argument");
-    Coalescer* co = graph_coalescer(g);
+// `call` holds f32 queries and no start nodes; copy: the ticket keeps copies of the queries and scales
+int submit_f32(bool copy, const QueryCall& call, void* user, mse_completion_queue* cq, mse_ticket** ticket_out) {
+    const SearchIn& in = call.in;
+    if (!in.queries_f32 || !ticket_out || !in.g || !call.out.ids || !call.out.scores) return fail("disk_query_submit_f32: null argument");
+    if (!in.s || !in.s->base) return fail("disk_query_submit_f32: null searcher");
+    if (in.nq == 0 || in.nq > FUSED_COALESCE_MAX) return fail("disk_query_submit_f32: 1.." + std::to_string(FUSED_COALESCE_MAX) + " queries per request");
+    if (check_k(call.out.k) || check_queued(in)) return -1;
+    Coalescer* co = graph_coalescer(in.g);
     if (!co) return -1;
     mse_ticket* t = ticket_take();
     if (!t) return fail("out of host memory");
-    const size_t d = s->base->d;
-    const float *q_use = queries_f32, *sc_use = scales;
+    t->k = call;
     if (copy) {
         try {
-            t->q32.assign(queries_f32, queries_f32 + nq * d);
-            if (scales) t->scales.assign(scales, scales + nq * c->n_desc);
+            t->q32.assign(in.queries_f32, in.queries_f32 + in.nq * in.s->base->d);
+            if (in.scales) t->scales.assign(in.scales, in.scales + in.nq * in.c->n_desc);
         } catch (const std::bad_alloc&) {
             delete t;
             return fail("out of host memory");
         }
-        q_use = t->q32.data();
-        sc_use = scales ? t->scales.data() : nullptr;
+        t->k.in.queries_f32 = t->q32.data();
+        t->k.in.scales = in.scales ? t->scales.data() : nullptr;
     }
     t->user = user;
-    t->k = QueryCall{s, pq, c, g, nullptr, nullptr, q_use, nullptr, sc_use, nq, disable_pq, beamwidth, search_list, k,
-                     ids, scores, n_visited, cmps, pq_cmps};
-    t->r.nq = nq;
+    t->r.nq = in.nq;
     t->r.aux0 = &t->k;
     t->r.aux_n = REQ_QUERY;
     t->r.owner = t;
@@ -1601,8 +1644,9 @@ int mse_disk_query_submit_f32(mse_searcher* s, mse_pq* pq, const mse_codes* c, c
                               size_t nq, int disable_pq, size_t beamwidth, size_t search_list, size_t k, uint32_t* ids, int64_t* scores,
                               uint32_t* n_visited, uint32_t* cmps, uint32_t* pq_cmps, void* user, mse_completion_queue* cq,
                               mse_ticket** ticket_out) {
-    return submit_f32(true, s, pq, c, g, queries_f32, scales, nq, disable_pq, beamwidth, search_list, k, ids, scores, n_visited, cmps, pq_cmps, user, cq,
-                      ticket_out);
+    return submit_f32(true, QueryCall{SearchIn{s, pq, c, g, nullptr, nullptr, queries_f32, nullptr, scales, nq, disable_pq, beamwidth, search_list},
+                                      fused_out(k, ids, scores, n_visited, cmps, pq_cmps)},
+                      user, cq, ticket_out);
 }
 
 // the same without the copies: queries_f32 (and scales) must stay valid and unchanged until the ticket has come back
@@ -1610,8 +1654,9 @@ int mse_disk_query_submit_f32_nocopy(mse_searcher* s, mse_pq* pq, const mse_code
                                      const float* scales, size_t nq, int disable_pq, size_t beamwidth, size_t search_list, size_t k, uint32_t* ids,
                                      int64_t* scores, uint32_t* n_visited, uint32_t* cmps, uint32_t* pq_cmps, void* user, mse_completion_queue* cq,
                                      mse_ticket** ticket_out) {
-    return submit_f32(false, s, pq, c, g, queries_f32, scales, nq, disable_pq, beamwidth, search_list, k, ids, scores, n_visited, cmps, pq_cmps, user, cq,
-                      ticket_out);
+    return submit_f32(false, QueryCall{SearchIn{s, pq, c, g, nullptr, nullptr, queries_f32, nullptr, scales, nq, disable_pq, beamwidth, search_list},
+                                       fused_out(k, ids, scores, n_visited, cmps, pq_cmps)},
+                      user, cq, ticket_out);
 }
 
 long mse_graph_completions(const mse_graph* g, mse_ticket** out, size_t max, long timeout_us) {
@@ -1664,13 +1709,12 @@ int mse_disk_query_topk_block(mse_searcher* s, mse_pq* pq, const mse_codes* c, c
     if (!g || !queries || !block_dev) return fail("disk_query_topk_block: null argument");
     if (nq == 0) return 0;
     if (!s || !s->base) return fail("disk_query_topk_block: null searcher");
-    if (k == 0 || k > (size_t)TOPK_KMAX - 64) return fail("disk_query_topk: bad k / outputs");
-    FusedQuery fz;
-    fz.k = k; fz.n_visited = n_visited; fz.cmps = cmps; fz.pq_cmps = pq_cmps;
+    if (check_k(k)) return -1;
+    FusedQuery fz = fused_out(k, nullptr, nullptr, n_visited, cmps, pq_cmps);
     fz.dev_sc = reinterpret_cast<int64_t*>(block_dev);
     fz.dev_ids = reinterpret_cast<uint32_t*>(static_cast<char*>(block_dev) + nq * k * 8);
     fz.id_offset = id_offset;
-    return fused_run(s, pq, c, g, starts, queries, nullptr, luts, scales, nq, disable_pq, beamwidth, search_list, fz);
+    return fused_run(SearchIn{s, pq, c, g, starts, queries, nullptr, luts, scales, nq, disable_pq, beamwidth, search_list}, fz);
 }
 
 int mse_graph_set_dedup(mse_graph* g, float threshold) {
@@ -1749,13 +1793,8 @@ int mse_disk_search_batch_f32(mse_searcher* s, mse_pq* pq, const mse_codes* c, c
                               size_t search_list, uint32_t* buf_ids, int64_t* buf_scores, uint32_t* buf_len, uint32_t* visited_ids,
                               int64_t* visited_scores, size_t visited_cap, uint32_t* n_visited, uint32_t* cmps, uint32_t* pq_cmps) {
     if (!queries_f32) return fail("disk_search_batch_f32: null argument");
-    if (nq == 1) {
-        BeamCall k{s, pq, c, g, starts, nullptr, queries_f32, nullptr, scales, disable_pq, beamwidth, search_list, visited_cap, buf_ids, buf_scores,
-                   buf_len, visited_ids, visited_scores, n_visited, cmps, pq_cmps};
-        return beam_one_query(k);
-    }
-    return disk_search_batch_impl(-1, s, pq, c, g, starts, nullptr, queries_f32, nullptr, scales, nq, disable_pq, beamwidth, search_list,
-                                  buf_ids, buf_scores, buf_len, visited_ids, visited_scores, visited_cap, n_visited, cmps, pq_cmps);
+    return disk_search_batch(BeamCall{SearchIn{s, pq, c, g, starts, nullptr, queries_f32, nullptr, scales, nq, disable_pq, beamwidth, search_list},
+                                      ListOut{buf_ids, buf_scores, buf_len, visited_ids, visited_scores, visited_cap, n_visited, cmps, pq_cmps}});
 }
 
 // Orders this searcher's stream after everything `producer_stream` holds now: the way to hand device-resident inputs (queries that a

@@ -21,6 +21,7 @@
 // no mutex on the way out (4096 callers, 1024 per pass: one shared condition variable woke 3072 sleepers for nothing on every
 // pass and sent all 4096 through one mutex; a variable per slot still queued 256 woken callers on the slot's mutex).
 #pragma once
+#include "../../include/mse.h"
 #include "common.h"
 #include <atomic>
 #include <chrono>
@@ -216,6 +217,41 @@ class SharedExclusive {
     size_t readers_ = 0, writers_waiting_ = 0;
     bool writer_ = false;
 };
+
+// Runs one group of requests that can share a call: call(reqs, n) returns 0, or an error with its message in mse_last_error().  When
+// the shared call fails, every request of a larger group is repeated alone, so that a caller only ever sees its own failure.  Sets
+// rc / err of every request; returns how many were repeated alone.
+template <typename Call>
+size_t run_shared(std::vector<DispatchReq*>& group, Call&& call) {
+    const int rc = call(group.data(), group.size());
+    if (rc == 0 || group.size() == 1) {
+        for (DispatchReq* r : group) {
+            r->rc = rc;
+            if (rc) r->err = mse_last_error();
+        }
+        return 0;
+    }
+    for (DispatchReq* r : group) {
+        r->rc = call(&r, 1);
+        if (r->rc) r->err = mse_last_error();
+    }
+    return group.size();
+}
+
+// Splits a pass into the groups that can share a call, in arrival order: the first request not yet taken leads a group of every later
+// one with same(lead, r); the members keep their order.  fn(group) runs each group.
+template <typename Same, typename Fn>
+void for_each_shared_group(std::vector<DispatchReq*>& batch, Same&& same, Fn&& fn) {
+    std::vector<char> taken(batch.size(), 0);
+    std::vector<DispatchReq*> group;
+    for (size_t i = 0; i < batch.size(); i++) {
+        if (taken[i]) continue;
+        group.clear();
+        for (size_t j = i; j < batch.size(); j++)
+            if (!taken[j] && same(*batch[i], *batch[j])) { taken[j] = 1; group.push_back(batch[j]); }
+        fn(group);
+    }
+}
 
 // wait budget when the caller gives none: a tenth of one pass over the rows at ~4 TB/s, between 200 us and 5 ms
 uint32_t default_wait_us(size_t n_rows, size_t row_bytes);

@@ -486,8 +486,7 @@ struct mse_dispatcher {
     const mse_base* base = nullptr;
     mse_searcher* s = nullptr;          // made on the worker thread (its stream lives on the base's device)
     std::string start_error;
-    void* pin = nullptr;                // pinned staging: queries up, [scores | ids] down
-    size_t pin_cap = 0;
+    PinBuf pin;                         // pinned staging: queries up, [scores | ids] down
     DevBuf q_dev, out_dev;
     std::unique_ptr<Coalescer> co;
     std::atomic<uint64_t> retried_alone{0};
@@ -511,28 +510,21 @@ int run_group(mse_dispatcher* D, DispatchReq* const* reqs, size_t n_req) {
     hipStream_t st = s->stream;
     const size_t in_bytes = total * d * 2, sc_bytes = total * kmax * 8, id_bytes = total * kmax * 4;
     const size_t out_bytes = sc_bytes + id_bytes;
-    if (D->pin_cap < std::max(in_bytes, out_bytes)) {
-        if (D->pin) (void)hipHostFree(D->pin);
-        D->pin = nullptr;
-        D->pin_cap = 0;
-        const size_t want = std::max<size_t>(2 * std::max(in_bytes, out_bytes), (size_t)1 << 20);
-        MSE_HIP_TRY(hipHostMalloc(&D->pin, want, hipHostMallocDefault));
-        D->pin_cap = want;
-    }
+    if (D->pin.ensure(std::max(in_bytes, out_bytes), (size_t)1 << 20)) return -1;
     if (D->q_dev.ensure(in_bytes) || D->out_dev.ensure(out_bytes)) return -1;
-    char* p = static_cast<char*>(D->pin);
+    char* p = D->pin.as<char>();
     for (size_t i = 0, o = 0; i < n_req; i++) {
         memcpy(p + o, reqs[i]->queries, reqs[i]->nq * d * 2);
         o += reqs[i]->nq * d * 2;
     }
-    MSE_HIP_TRY(hipMemcpyAsync(D->q_dev.p, D->pin, in_bytes, hipMemcpyHostToDevice, st));
+    MSE_HIP_TRY(hipMemcpyAsync(D->q_dev.p, D->pin.p, in_bytes, hipMemcpyHostToDevice, st));
     // a pass of the matrix-core scan costs less than the exact-order pass once the rows no longer fit the caches, whatever the
     // query count (40 ms against 54 ms at 1e8 rows); below that the exact pass has the shorter tail.  Same answers either way.
     const int mode = (total > 8 || b->n >= ((size_t)1 << 22)) ? MSE_MODE_MFMA : MSE_MODE_EXACT;
     int64_t* sc_dev = D->out_dev.as<int64_t>();
     uint32_t* id_dev = reinterpret_cast<uint32_t*>(D->out_dev.as<char>() + sc_bytes);
     if (mse_bruteforce_topk_f16_dev(s, D->q_dev.p, total, kmax, mode, 0, sc_dev, id_dev)) return -1;
-    MSE_HIP_TRY(hipMemcpyAsync(D->pin, D->out_dev.p, out_bytes, hipMemcpyDeviceToHost, st));
+    MSE_HIP_TRY(hipMemcpyAsync(D->pin.p, D->out_dev.p, out_bytes, hipMemcpyDeviceToHost, st));
     MSE_HIP_TRY(hipStreamSynchronize(st));
     const int64_t* sc = reinterpret_cast<const int64_t*>(p);
     const uint32_t* id = reinterpret_cast<const uint32_t*>(p + sc_bytes);
@@ -548,23 +540,10 @@ int run_group(mse_dispatcher* D, DispatchReq* const* reqs, size_t n_req) {
 }
 
 void run_batch(mse_dispatcher* D, std::vector<DispatchReq*>& batch) {
-    bool injected = false;
-    if (batch.size() > 1 && D->fail_shared.load() > 0) { D->fail_shared--; injected = true; fail("injected failure of a shared pass (test hook)"); }
-    if (!injected && run_group(D, batch.data(), batch.size()) == 0) {
-        for (DispatchReq* r : batch) r->rc = 0;
-        return;
-    }
-    if (batch.size() == 1) {
-        batch[0]->rc = -1;
-        batch[0]->err = mse_last_error();
-        return;
-    }
-    // the shared pass failed: every request is repeated on its own, so that a caller only ever sees its own failure
-    for (DispatchReq* r : batch) {
-        D->retried_alone++;
-        r->rc = run_group(D, &r, 1);
-        if (r->rc) r->err = mse_last_error();
-    }
+    D->retried_alone += run_shared(batch, [D](DispatchReq* const* reqs, size_t n) {
+        if (n > 1 && D->fail_shared.load() > 0) { D->fail_shared--; return fail("injected failure of a shared pass (test hook)"); }
+        return run_group(D, reqs, n);
+    });
 }
 
 }  // namespace
@@ -602,7 +581,6 @@ void mse_dispatcher_free(mse_dispatcher* D) {
     if (!D) return;
     D->co.reset();   // joins the worker
     if (D->s) mse_searcher_free(D->s);
-    if (D->pin) (void)hipHostFree(D->pin);
     delete D;
 }
 
@@ -635,9 +613,28 @@ int mse_dispatcher_stats(mse_dispatcher* D, uint64_t out[6]) {
 
 mse_searcher* mse_dispatcher_searcher(mse_dispatcher* D) { return D ? D->s : nullptr; }
 
-// test hook, no device needed: `threads` host threads x `rounds` one-query requests through a Coalescer whose "pass" answers
-// request payload p with 2 p + 1 and fails (for that request alone) every payload divisible by 97.  *mismatches = requests that
-// got somebody else's answer, a wrong status, or a missing error text.
+}  // extern "C"
+
+namespace {
+// the selftests' stand-in pass: answers request payload p with 2 p + 1; a group that holds a payload divisible by 97 fails as a whole
+// (as a shared device pass does), so run_shared repeats its requests alone and only those payloads fail.  Returns the repeats.
+size_t selftest_pass(std::vector<DispatchReq*>& batch) {
+    return run_shared(batch, [](DispatchReq* const* reqs, size_t n) {
+        for (size_t i = 0; i < n; i++) {
+            const uint64_t p = *static_cast<const uint64_t*>(reqs[i]->queries);
+            if (p % 97 == 0) return fail("payload " + std::to_string(p) + " refused");
+        }
+        for (size_t i = 0; i < n; i++) *static_cast<uint64_t*>(reqs[i]->out_a) = 2 * *static_cast<const uint64_t*>(reqs[i]->queries) + 1;
+        return 0;
+    });
+}
+}  // namespace
+
+extern "C" {
+
+// test hook, no device needed: `threads` host threads x `rounds` one-query requests through a Coalescer whose "pass" is
+// selftest_pass.  *mismatches = requests that got somebody else's answer, a wrong status, or a missing error text; stats_out[5] =
+// requests repeated alone after a shared pass failed.
 int mse_debug_coalescer_selftest(int threads, int rounds, uint32_t max_queries, uint32_t max_wait_us, uint64_t stats_out[6],
                                  uint64_t* mismatches) {
     return mse_debug_coalescer_selftest_workers(threads, rounds, max_queries, max_wait_us, 1, stats_out, mismatches);
@@ -646,15 +643,11 @@ int mse_debug_coalescer_selftest(int threads, int rounds, uint32_t max_queries, 
 int mse_debug_coalescer_selftest_workers(int threads, int rounds, uint32_t max_queries, uint32_t max_wait_us, int workers, uint64_t stats_out[6],
                                          uint64_t* mismatches) {
     if (threads <= 0 || rounds <= 0 || workers <= 0 || !stats_out || !mismatches) return fail("bad argument");
-    std::atomic<uint64_t> wrong_worker{0};
+    std::atomic<uint64_t> wrong_worker{0}, repeated{0};
     Coalescer co(max_queries ? max_queries : 256, max_wait_us ? max_wait_us : 200,
-                 [&wrong_worker, workers](std::vector<DispatchReq*>& batch) {
+                 [&wrong_worker, &repeated, workers](std::vector<DispatchReq*>& batch) {
                      if (Coalescer::worker_index() < 0 || Coalescer::worker_index() >= workers) wrong_worker++;
-                     for (DispatchReq* r : batch) {
-                         const uint64_t p = *static_cast<const uint64_t*>(r->queries);
-                         if (p % 97 == 0) { r->rc = -1; r->err = "payload " + std::to_string(p) + " refused"; }
-                         else { *static_cast<uint64_t*>(r->out_a) = 2 * p + 1; r->rc = 0; }
-                     }
+                     repeated += selftest_pass(batch);
                  },
                  nullptr, workers);
     std::atomic<uint64_t> bad{0};
@@ -673,14 +666,14 @@ int mse_debug_coalescer_selftest_workers(int threads, int rounds, uint32_t max_q
     for (std::thread& th : ts) th.join();
     const DispatchStats st = co.stats();
     stats_out[0] = st.queries; stats_out[1] = st.requests; stats_out[2] = st.passes; stats_out[3] = st.max_pass_queries;
-    stats_out[4] = st.deadline_fires; stats_out[5] = 0;
+    stats_out[4] = st.deadline_fires; stats_out[5] = repeated.load();
     *mismatches = bad.load() + wrong_worker.load();
     return 0;
 }
 
 // test hook, no device needed: the asynchronous side of the queue.  `async_threads` threads each keep `window` one-query records in
 // flight (n_requests each, collecting whatever completes -- their own records or another thread's) while `sync_threads` blocking
-// callers run beside them through the same Coalescer; the stand-in pass is the one above.  *mismatches = records handed back twice or
+// callers run beside them through the same Coalescer; the stand-in pass is selftest_pass.  *mismatches = records handed back twice or
 // never, wrong answers / statuses / error texts.
 int mse_debug_coalescer_selftest_async(int async_threads, int window, int n_requests, int sync_threads, uint32_t max_queries, int workers,
                                        int own_queues, uint64_t stats_out[6], uint64_t* mismatches) {
@@ -705,15 +698,7 @@ int mse_debug_coalescer_selftest_async(int async_threads, int window, int n_requ
     std::atomic<uint64_t> bad{0}, collected{0};
     std::atomic<int64_t> in_flight{0};
     {
-        Coalescer co(max_queries ? max_queries : 256, 200,
-                     [](std::vector<DispatchReq*>& batch) {
-                         for (DispatchReq* r : batch) {
-                             const uint64_t p = *static_cast<const uint64_t*>(r->queries);
-                             if (p % 97 == 0) { r->rc = -1; r->err = "payload " + std::to_string(p) + " refused"; }
-                             else { *static_cast<uint64_t*>(r->out_a) = 2 * p + 1; r->rc = 0; }
-                         }
-                     },
-                     nullptr, workers);
+        Coalescer co(max_queries ? max_queries : 256, 200, [](std::vector<DispatchReq*>& batch) { selftest_pass(batch); }, nullptr, workers);
         std::vector<std::thread> ts;
         for (int t = 0; t < async_threads; t++)
             ts.emplace_back([&, t] {

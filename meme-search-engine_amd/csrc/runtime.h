@@ -18,6 +18,25 @@ struct DevBuf {
     template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
+// growable pinned host staging: grows to max(2 x bytes, floor) by hipHostMalloc + free (contents are NOT preserved).  Move-only: it
+// lives in objects that are moved (a vector of worker contexts), never copied
+struct PinBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    PinBuf() = default;
+    PinBuf(PinBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    PinBuf& operator=(PinBuf&& o) noexcept {
+        if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
+    PinBuf(const PinBuf&) = delete;
+    PinBuf& operator=(const PinBuf&) = delete;
+    int ensure(size_t bytes, size_t floor);
+    void release();
+    ~PinBuf() { release(); }
+    template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
+};
+
 int device_cu_count();
 
 // one level of the selection tournament (topk.hip)
@@ -94,8 +113,7 @@ struct mse_searcher {
     size_t ev_used = 0;
     // pinned host staging of the fused request path (ONE download per call: scores, ids and counters) and the event of
     // mse_searcher_wait_stream
-    void* pin = nullptr;
-    size_t pin_cap = 0;
+    mse::PinBuf pin;
     hipEvent_t ev_wait = nullptr;
 };
 
@@ -120,8 +138,8 @@ struct mse_pq {
     uint64_t scan_launches = 0;
     double span_ms_total = 0.0;       // first scan start .. last scan end of the batch calls with >= 4 scans (mse_pq_scan_sustained)
     uint64_t span_scans = 0;
-    void* pin = nullptr;              // pinned host staging of the scan entry points (one upload + one download per call, both
-    size_t pin_cap = 0;               // truly asynchronous: a pageable source makes the runtime stage and block per copy)
+    mse::PinBuf pin;                  // pinned host staging of the scan entry points (one upload + one download per call, both
+                                      // truly asynchronous: a pageable source makes the runtime stage and block per copy)
 };
 
 struct mse_codes {
@@ -158,8 +176,7 @@ struct mse_graph {
     mutable std::atomic<mse::Coalescer*> co_fast{nullptr};   // == co once made: the request threads' lock-free way to it
     struct WorkerCtx {
         mse_searcher* s = nullptr;   // made on first use over the callers' base
-        void* pin = nullptr;         // gathered inputs (queries, scales, starts, tables)
-        size_t pin_cap = 0;
+        mse::PinBuf pin;             // gathered inputs (queries, scales, starts, tables)
         std::vector<mse::QueryDst> dsts;   // where each gathered query's results go
     };
     mutable std::vector<WorkerCtx> co_ctx;
