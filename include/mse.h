@@ -130,6 +130,33 @@ int mse_searcher_scan_timing(mse_searcher* s, int enable, double* total_ms, uint
  * candidate set, and the widest group count used. */
 int mse_searcher_last_stats(const mse_searcher* s, uint32_t* n_widened, uint32_t* max_groups);
 
+/* ---- filtered brute-force search: top-k over an allowed-row set (FAISS SearchParameters.sel / IDSelector) -----------------
+ * A filter is one bit per row, kept on the device that was current on the calling thread when it was made, padded with zero bits
+ * to whole 256-row scan tiles.  It is immutable: to change one, make another.  It may be shorter than the base it is used on
+ * (rows at or past mse_filter_len are excluded -- the flat index grows under add), not longer.  Using it with a base on another
+ * device is an error, not a copy.
+ * bits: LSB-first bitmap, row r = bit (r % 8) of byte r / 8 (numpy.packbits(..., bitorder="little")); bits past n_rows are ignored.
+ * from_ids: duplicates allowed; an id >= n_rows is an error (nothing is made).  Both return NULL on error (mse_last_error). */
+typedef struct mse_filter mse_filter;
+mse_filter* mse_filter_from_bits(const uint8_t* bits, size_t n_rows);
+mse_filter* mse_filter_from_ids(const uint32_t* ids, size_t n_ids, size_t n_rows);
+void mse_filter_free(mse_filter* f);
+size_t mse_filter_len(const mse_filter* f);      /* n_rows */
+size_t mse_filter_count(const mse_filter* f);    /* allowed rows, counted on the device at creation */
+/* Brute-force top-k over the allowed rows only.  The result is exactly what mse_bruteforce_topk_f16 returns on a base made of the
+ * allowed rows alone, with ids mapped back to the original rows: the same i64 scores, (score desc, id asc) order, unfilled slots
+ * INT64_MIN / MSE_ID_NONE.  Arguments and limits are those of the unfiltered calls (k <= 1984); a null filter is an error.
+ * MSE_MODE_EXACT scores the filter's allowed rows in the reference order; MSE_MODE_MFMA runs the matrix-core scan with the filter
+ * applied in its group maxima (+ exact re-score + certificate); MSE_MODE_AUTO takes the exact path when the allowed rows are few
+ * next to the rows (the sparse path), otherwise the unfiltered rule.  MSE_MODE_AUTO host calls of at most one pass go
+ * to the base's coalescer, as unfiltered ones do: they share a pass with the requests of the same filter object only. */
+int mse_bruteforce_topk_filtered_f16(mse_searcher* s, const mse_filter* f, const uint16_t* queries, size_t nq, size_t k,
+                                     int mode, int64_t* scores, uint32_t* ids);
+/* The _dev form is asynchronous on the searcher's stream, like mse_bruteforce_topk_f16_dev: the filter (and the buffers) must
+ * outlive the work it queued -- synchronise the stream before mse_filter_free. */
+int mse_bruteforce_topk_filtered_f16_dev(mse_searcher* s, const mse_filter* f, const void* queries_dev, size_t nq, size_t k,
+                                         int mode, uint64_t id_offset, void* scores_dev, void* ids_dev);
+
 /* ---- cross-thread query coalescer ----------------------------------------------------------
  * The reference serves ONE query per request from many threads at once: `index.search(&query, k)` under a shared read
  * guard per HTTP request (src/main.rs:896-934,1043-1049), and a thread per core with its own Scratch, one search per
@@ -148,6 +175,9 @@ typedef struct mse_dispatcher mse_dispatcher;
 mse_dispatcher* mse_dispatcher_new(const mse_base* b, size_t max_queries_per_pass, uint32_t max_wait_us);
 void mse_dispatcher_free(mse_dispatcher* d);               /* no call may be in flight */
 int mse_dispatcher_topk_f16(mse_dispatcher* d, const uint16_t* queries, size_t nq, size_t k, int64_t* scores, uint32_t* ids);
+/* the same over the rows filter f allows (f null: all rows); requests share a pass only with requests of the same filter object */
+int mse_dispatcher_topk_filtered_f16(mse_dispatcher* d, const mse_filter* f, const uint16_t* queries, size_t nq, size_t k,
+                                     int64_t* scores, uint32_t* ids);
 /* out: [0] queries answered, [1] requests, [2] passes, [3] most queries in one pass, [4] passes started by the wait budget,
  * [5] requests repeated alone after a failed shared pass */
 int mse_dispatcher_stats(mse_dispatcher* d, uint64_t out[6]);
@@ -275,6 +305,11 @@ size_t mse_index_ntotal(const mse_index* idx);
  * :1016) and is not starved by them.  Concurrent searches meet in the index's coalescer (above) and share passes: <= 8 waiting
  * queries over a cache-sized index take the exact pass, anything more ONE matrix-core pass + f32 re-score + certificate. */
 int mse_index_search(mse_index* idx, const float* queries, size_t nq, size_t k, float* distances, int64_t* labels);
+/* mse_index_search over the rows filter f allows: exactly what mse_index_search returns on an index of the allowed rows alone,
+ * labels mapped back (same f32 distances; -FLT_MAX / -1 padding).  f may be shorter than the index (made before an add: the new
+ * rows are excluded), not longer; a null filter is an error.  Coalesced with the searches of the same filter object. */
+int mse_index_search_filtered(mse_index* idx, const mse_filter* f, const float* queries, size_t nq, size_t k,
+                              float* distances, int64_t* labels);
 int mse_index_stats(mse_index* idx, uint64_t out[6]);     /* as mse_dispatcher_stats */
 
 /* ---- product quantiser: diskann::vector::ProductQuantizer (vector.rs:308-406) ------------ */

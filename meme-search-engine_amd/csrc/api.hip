@@ -158,17 +158,22 @@ int ensure_base_norm(const mse_base* b, hipStream_t st) {
     return 0;
 }
 
-// exact mode, one pass of <= 8 queries already staged (padded) in s->q_stage
+// exact mode, one pass of <= 8 queries already staged (padded) in s->q_stage.  With a filter (non-empty, no longer than the base):
+// the filter's allowed rows only, scanned through its ascending id list; level 0 then holds list positions, so an excluded row is
+// absent -- not merely low: an allowed row whose score saturates to INT64_MIN still ranks -- and (score desc, position asc) is
+// (score desc, id asc).  The selected positions are mapped back to row ids before the finish.
 static int exact_pass(mse_searcher* s, int nq_pass, int k, uint64_t id_offset, int64_t* out_scores, uint32_t* out_ids,
-                      size_t out_stride) {
+                      size_t out_stride, const mse_filter* f = nullptr) {
     const mse_base* b = s->base;
-    if (s->scores.ensure((size_t)nq_pass * b->n * 8)) return -1;
-    if (launch_scan_exact(b->dev, b->n, (int)b->d, s->q_stage.p, nq_pass, false, s->scores.as<int64_t>(), b->n, nullptr,
-                          s->n_cu, s->stream)) return -1;
+    const size_t n = f ? f->count : b->n;
+    if (s->scores.ensure((size_t)nq_pass * n * 8)) return -1;
+    if (launch_scan_exact(b->dev, n, (int)b->d, s->q_stage.p, nq_pass, false, s->scores.as<int64_t>(), n, nullptr,
+                          s->n_cu, s->stream, f ? f->ids : nullptr)) return -1;
     if (s->sel_keys.ensure((size_t)nq_pass * k * 8)) return -1;
     uint32_t* sel = nullptr;
-    LevelRef l0{KEY_I64, s->scores.p, b->n, 1, b->n, false, 0};
+    LevelRef l0{KEY_I64, s->scores.p, n, 1, n, false, 0};
     if (descend(s, l0, nq_pass, k, &sel, s->sel_keys.p)) return -1;
+    if (f && launch_map_positions(sel, (size_t)nq_pass * k, f->ids, s->stream)) return -1;
     return launch_finalize(sel, s->sel_keys.as<int64_t>(), k, k, nq_pass, id_offset, out_scores, out_ids, out_stride,
                            nullptr, 0, 0, 0, nullptr, nullptr, s->stream);
 }
@@ -189,9 +194,12 @@ static size_t mfma_call_tile(const mse_base* b, size_t k) {
     return std::max(fit, tile);
 }
 
-// MFMA mode for up to mfma_call_tile(base) queries (device pointer to [nq][d] f16, contiguous)
+// MFMA mode for up to mfma_call_tile(base) queries (device pointer to [nq][d] f16, contiguous).  With a filter: the scan's group
+// maxima are over allowed rows only (-FLT_MAX for a group without one), candidate expansion drops excluded rows, and the exact
+// fallback is the filtered exact pass; the certificate is unchanged (every allowed row outside the chosen groups is at most its
+// group's masked maximum, and the largest row norm still bounds eps).
 static int mfma_pass(mse_searcher* s, const uint16_t* q_dev, int nq_pass, int k, uint64_t id_offset,
-                     int64_t* out_scores, uint32_t* out_ids, size_t out_stride) {
+                     int64_t* out_scores, uint32_t* out_ids, size_t out_stride, const mse_filter* f = nullptr) {
     const mse_base* b = s->base;
     hipStream_t st = s->stream;
     const int d = (int)b->d;
@@ -210,13 +218,15 @@ static int mfma_pass(mse_searcher* s, const uint16_t* q_dev, int nq_pass, int k,
     // the full passes go out as ONE launch (a small base has few row tiles: its passes fill the chip side by side), then the remainder
     const size_t one_tile_packed = (size_t)(d / 64) * tile * 128;
     if (s->qpacked.ensure(std::max(mfma_packed_bytes(d), (size_t)std::max(n_full, 1) * one_tile_packed))) return -1;
+    const uint32_t* mask = f ? f->words : nullptr;
+    const size_t mask_words = f ? f->n_words : 0;
     if (n_full &&
         launch_scan_mfma(b->dev, b->n, d, s->q_stage.as<uint16_t>(), tile, s->qpacked.p, s->gmax.as<float>(), s->n_cu, st,
-                         s->timing ? s->ev0 : nullptr, s->timing && !rem ? s->ev1 : nullptr, nq_pad, n_full)) return -1;
+                         s->timing ? s->ev0 : nullptr, s->timing && !rem ? s->ev1 : nullptr, nq_pad, n_full, mask, mask_words)) return -1;
     if (rem &&
         launch_scan_mfma(b->dev, b->n, d, s->q_stage.as<uint16_t>() + (size_t)n_full * tile * d, nq_pad - n_full * tile, s->qpacked.p,
                          s->gmax.as<float>() + n_full * tile, s->n_cu, st, s->timing && !n_full ? s->ev0 : nullptr,
-                         s->timing ? s->ev1 : nullptr, nq_pad, 1)) return -1;
+                         s->timing ? s->ev1 : nullptr, nq_pad, 1, mask, mask_words)) return -1;
     bool timing_pending = s->timing;
     if (s->eps.ensure((size_t)nq_pass * 8) || s->margin.ensure((size_t)nq_pass * 8)) return -1;   // second halves: the widening's compact set
     // |mfma score - exact-order score| <= 2 * gamma_1151 * sum|x_i q_i| <= 1.4e-4 * |x||q|; doubled again
@@ -238,7 +248,9 @@ static int mfma_pass(mse_searcher* s, const uint16_t* q_dev, int nq_pass, int k,
         if (descend(s, l0, nq, kg_eff, &gsel, s->gkeys.p)) return -1;
         const size_t n_cand = (size_t)kg_eff * GROUP_ROWS;
         if (s->cand_ids.ensure((size_t)nq * n_cand * 4) || s->cand_scores.ensure((size_t)nq * n_cand * 8)) return -1;
-        if (launch_expand_groups(gsel, kg_eff, kg_eff, GROUP_ROWS, b->n, s->cand_ids.as<uint32_t>(), n_cand, nq, st)) return -1;
+        if (f ? launch_expand_groups_masked(gsel, kg_eff, kg_eff, GROUP_ROWS, b->n, f->words, f->n_words, s->cand_ids.as<uint32_t>(), n_cand,
+                                            nq, st)
+              : launch_expand_groups(gsel, kg_eff, kg_eff, GROUP_ROWS, b->n, s->cand_ids.as<uint32_t>(), n_cand, nq, st)) return -1;
         if (launch_score_rows(b->dev, b->n, d, qs, false, s->cand_ids.as<uint32_t>(), (size_t)nq * n_cand, n_cand,
                               s->cand_scores.as<int64_t>(), nullptr, st)) return -1;
         // final exact selection among the re-scored candidates
@@ -313,13 +325,30 @@ static int mfma_pass(mse_searcher* s, const uint16_t* q_dev, int nq_pass, int k,
         for (int j = 0; j < nqp; j++)
             MSE_HIP_TRY(hipMemcpyAsync(s->q_stage.as<char>() + (size_t)j * d * 2, s->wq.as<char>() + (size_t)rest[r0 + j] * d * 2, (size_t)d * 2,
                                        hipMemcpyDeviceToDevice, st));
-        if (exact_pass(s, nqp, k, id_offset, w_s, w_i, (size_t)k)) return -1;
+        if (exact_pass(s, nqp, k, id_offset, w_s, w_i, (size_t)k, f)) return -1;
         std::vector<uint32_t> dst(nqp);
         for (int j = 0; j < nqp; j++) dst[j] = bad[rest[r0 + j]];
         MSE_HIP_TRY(hipMemcpyAsync(idx_dev, dst.data(), (size_t)nqp * 4, hipMemcpyHostToDevice, st));
         if (launch_scatter_topk(idx_dev, nullptr, nqp, k, w_s, w_i, out_scores, out_ids, out_stride, st)) return -1;
         MSE_HIP_TRY(hipStreamSynchronize(st));
     }
+    return 0;
+}
+
+// The sparse path: scoring the filter's id list directly (exact_pass: the list is read once per 8 queries) beats the masked scan (every
+// row streamed once per pass) when count x ceil(nq / 8) x 3 <= n_rows x ceil(nq / pass width) x 2.  Measured on one MI355X, 1e8 x 1152
+// (scripts/filtered_scan_probe.py, profiles/filtered_scan_probe.json): the list pass costs 0.56 ns per listed row per 8 queries, the
+// masked scan 0.40 ns per row per pass of <= 128 queries and 0.74 ns at 320 -- e.g. 1.6e6 allowed rows x 320 queries: list 35 ms,
+// scan 74 ms; 6.3e6 x 64: 28 against 40 ms; 1.25e7 x 64: 57 against 40 ms.  The factor 3 / 2 sits between those costs.
+bool filter_sparse(const mse_base* b, const mse_filter* f, size_t nq) {
+    const size_t tile = (size_t)mfma_query_tile((int)b->d);
+    return f->count * ((nq + 7) / 8) * 3 <= b->n * ((nq + tile - 1) / tile) * 2;
+}
+
+int check_filter(const mse_base* b, const mse_filter* f) {
+    if (!f) return fail("null filter");
+    if (f->n_rows > b->n) return fail("filter is longer than the base (" + std::to_string(f->n_rows) + " > " + std::to_string(b->n) + " rows)");
+    if (f->device != b->device) return fail("filter was made on another device than the base's");   // no silent copy
     return 0;
 }
 
@@ -504,6 +533,16 @@ int mse_searcher_last_stats(const mse_searcher* s, uint32_t* n_widened, uint32_t
 
 size_t mse_queries_per_pass_max(size_t d) { return d && d % 64 == 0 ? (size_t)mfma_query_tile((int)d) : 0; }
 
+// every one of the [nq][k] output slots empty (INT64_MIN / MSE_ID_NONE)
+static int fill_empty(mse_searcher* s, size_t nq, size_t k, int64_t* out_scores, uint32_t* out_ids) {
+    std::vector<int64_t> hs(nq * k, INT64_MIN);
+    std::vector<uint32_t> hi(nq * k, MSE_ID_NONE);
+    MSE_HIP_TRY(hipMemcpyAsync(out_scores, hs.data(), hs.size() * 8, hipMemcpyHostToDevice, s->stream));
+    MSE_HIP_TRY(hipMemcpyAsync(out_ids, hi.data(), hi.size() * 4, hipMemcpyHostToDevice, s->stream));
+    MSE_HIP_TRY(hipStreamSynchronize(s->stream));
+    return 0;
+}
+
 int mse_bruteforce_topk_f16_dev(mse_searcher* s, const void* queries_dev, size_t nq, size_t k, int mode,
                                 uint64_t id_offset, void* scores_dev, void* ids_dev) {
     if (!s) return fail("null searcher");
@@ -517,15 +556,7 @@ int mse_bruteforce_topk_f16_dev(mse_searcher* s, const void* queries_dev, size_t
     if (mode == MSE_MODE_AUTO) mode = nq <= 8 ? MSE_MODE_EXACT : MSE_MODE_MFMA;
     s->last_widened = 0;
     s->last_max_groups = 0;
-    if (b->n == 0) {
-        // nothing to score: every slot is empty
-        std::vector<int64_t> hs(nq * k, INT64_MIN);
-        std::vector<uint32_t> hi(nq * k, MSE_ID_NONE);
-        MSE_HIP_TRY(hipMemcpyAsync(out_scores, hs.data(), hs.size() * 8, hipMemcpyHostToDevice, s->stream));
-        MSE_HIP_TRY(hipMemcpyAsync(out_ids, hi.data(), hi.size() * 4, hipMemcpyHostToDevice, s->stream));
-        MSE_HIP_TRY(hipStreamSynchronize(s->stream));
-        return 0;
-    }
+    if (b->n == 0) return fill_empty(s, nq, k, out_scores, out_ids);   // nothing to score
     if (mode == MSE_MODE_EXACT) {
         for (size_t q0 = 0; q0 < nq; q0 += 8) {
             const int nqp = (int)std::min<size_t>(8, nq - q0);
@@ -567,6 +598,16 @@ int mse_debug_mfma_group_max(mse_searcher* s, const uint16_t* queries, size_t nq
     return 0;
 }
 
+// the base's coalescer, made on first use (null if it cannot be made: callers then answer directly)
+static mse_dispatcher* base_dispatcher(const mse_base* b) {
+    std::lock_guard<std::mutex> g(b->disp_mu);
+    if (!b->disp && !b->disp_failed) {
+        b->disp = mse_dispatcher_new(b, 0, 0);
+        if (!b->disp) b->disp_failed = true;
+    }
+    return b->disp;
+}
+
 int mse_bruteforce_topk_f16(mse_searcher* s, const uint16_t* queries, size_t nq, size_t k, int mode, int64_t* scores,
                             uint32_t* ids) {
     if (!s) return fail("null searcher");
@@ -577,16 +618,7 @@ int mse_bruteforce_topk_f16(mse_searcher* s, const uint16_t* queries, size_t nq,
         // Answers are those of every other mode; a lone caller fires its pass at once (dispatch.h).  Only requests that fit one pass
         // go there: a larger batch fills passes on its own and stays on the caller's searcher (its stream, its timing, its
         // last_stats).  If the coalescer cannot be made (no memory for its worker's scratch) the call is answered directly as well.
-        const mse_base* b = s->base;
-        mse_dispatcher* disp = nullptr;
-        {
-            std::lock_guard<std::mutex> g(b->disp_mu);
-            if (!b->disp && !b->disp_failed) {
-                b->disp = mse_dispatcher_new(b, 0, 0);
-                if (!b->disp) b->disp_failed = true;
-            }
-            disp = b->disp;
-        }
+        mse_dispatcher* disp = base_dispatcher(s->base);
         if (disp) return mse_dispatcher_topk_f16(disp, queries, nq, k, scores, ids);
     }
     const size_t d = s->base->d;
@@ -648,6 +680,147 @@ int mse_score_rows_f16(mse_searcher* s, const uint32_t* ids, size_t n_ids, const
     if (launch_score_rows(b->dev, b->n, (int)d, s->q_stage.p, false, s->cand_ids.as<uint32_t>(), n_ids, n_ids,
                           s->cand_scores.as<int64_t>(), nullptr, s->stream)) return -1;
     MSE_HIP_TRY(hipMemcpyAsync(out, s->cand_scores.p, n_ids * 8, hipMemcpyDeviceToHost, s->stream));
+    MSE_HIP_TRY(hipStreamSynchronize(s->stream));
+    return 0;
+}
+
+// ---- row filters (filter.hip) and the filtered brute-force search -----------------------------------------------------------
+
+static mse_filter* filter_alloc(size_t n_rows) {
+    if (n_rows > 0xFFFFFFFEull) { fail("row ids are u32: too many rows"); return nullptr; }
+    mse_filter* f = new (std::nothrow) mse_filter();
+    if (!f) { fail("out of host memory"); return nullptr; }
+    f->n_rows = n_rows;
+    f->n_words = (n_rows + 255) / 256 * 8;   // whole 256-row scan tiles: one word per 32-row group
+    if (hipGetDevice(&f->device) != hipSuccess) f->device = 0;
+    if (hipMalloc((void**)&f->words, std::max<size_t>(f->n_words, 1) * 4) != hipSuccess) {
+        delete f; fail("hipMalloc failed for the filter"); return nullptr;
+    }
+    return f;
+}
+
+// the filter's id list and count, from its bitmap (on the device); frees f on failure
+static mse_filter* filter_finish(mse_filter* f) {
+    DevBuf scratch;
+    unsigned long long count = 0;
+    hipError_t e = hipSuccess;
+    if (scratch.ensure(filter_compact_scratch_bytes(f->n_words) + 8)) goto bad;
+    if (hipMalloc((void**)&f->ids, std::max<size_t>(f->n_rows, 1) * 4) != hipSuccess) { fail("hipMalloc failed for the filter"); goto bad; }
+    {
+        unsigned long long* count_dev = scratch.as<unsigned long long>();
+        if (launch_filter_compact(f->words, f->n_words, f->ids, count_dev, scratch.as<char>() + 8, nullptr)) goto bad;
+        e = hipMemcpy(&count, count_dev, 8, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) { fail(std::string("filter: ") + hipGetErrorString(e)); goto bad; }
+    }
+    f->count = (size_t)count;
+    return f;
+bad:
+    mse_filter_free(f);
+    return nullptr;
+}
+
+mse_filter* mse_filter_from_bits(const uint8_t* bits, size_t n_rows) {
+    if (!bits && n_rows) { fail("null bitmap"); return nullptr; }
+    mse_filter* f = filter_alloc(n_rows);
+    if (!f) return nullptr;
+    std::vector<uint32_t> w(std::max<size_t>(f->n_words, 1), 0u);
+    if (n_rows) {
+        std::memcpy(w.data(), bits, (n_rows + 7) / 8);   // LSB-first bytes = little-endian words
+        if (n_rows % 32) w[n_rows / 32] &= (1u << (n_rows % 32)) - 1u;   // no bit past the last row
+    }
+    if (hipMemcpy(f->words, w.data(), w.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        mse_filter_free(f); fail("hipMemcpy failed for the filter"); return nullptr;
+    }
+    return filter_finish(f);
+}
+
+mse_filter* mse_filter_from_ids(const uint32_t* ids, size_t n_ids, size_t n_rows) {
+    if (!ids && n_ids) { fail("null id array"); return nullptr; }
+    for (size_t i = 0; i < n_ids; i++)
+        if (ids[i] >= n_rows) { fail("filter: id " + std::to_string(ids[i]) + " is not below n_rows " + std::to_string(n_rows)); return nullptr; }
+    mse_filter* f = filter_alloc(n_rows);
+    if (!f) return nullptr;
+    // all on the null stream: the blocking read-back of the count in filter_finish orders the OR kernel and the compaction
+    DevBuf idb;
+    if (idb.ensure(std::max<size_t>(n_ids, 1) * 4)) { mse_filter_free(f); return nullptr; }
+    if (hipMemset(f->words, 0, std::max<size_t>(f->n_words, 1) * 4) != hipSuccess ||
+        (n_ids && hipMemcpy(idb.p, ids, n_ids * 4, hipMemcpyHostToDevice) != hipSuccess)) {
+        mse_filter_free(f);
+        fail("filter: device upload failed");
+        return nullptr;
+    }
+    if (launch_filter_or_ids(f->words, f->n_words, idb.as<uint32_t>(), n_ids, nullptr)) { mse_filter_free(f); return nullptr; }
+    return filter_finish(f);
+}
+
+void mse_filter_free(mse_filter* f) {
+    if (!f) return;
+    if (f->words) (void)hipFree(f->words);
+    if (f->ids) (void)hipFree(f->ids);
+    delete f;
+}
+size_t mse_filter_len(const mse_filter* f) { return f ? f->n_rows : 0; }
+size_t mse_filter_count(const mse_filter* f) { return f ? f->count : 0; }
+
+
+
+int mse_bruteforce_topk_filtered_f16_dev(mse_searcher* s, const mse_filter* f, const void* queries_dev, size_t nq, size_t k, int mode,
+                                         uint64_t id_offset, void* scores_dev, void* ids_dev) {
+    if (!s) return fail("null searcher");
+    if (check_filter(s->base, f)) return -1;
+    if (nq == 0 || k == 0) return 0;
+    if (k > (size_t)TOPK_KMAX - 64) return fail("k too large (max 1984)");
+    if (mode != MSE_MODE_AUTO && mode != MSE_MODE_EXACT && mode != MSE_MODE_MFMA) return fail("unknown mode");
+    const mse_base* b = s->base;
+    const int d = (int)b->d;
+    int64_t* out_scores = reinterpret_cast<int64_t*>(scores_dev);
+    uint32_t* out_ids = reinterpret_cast<uint32_t*>(ids_dev);
+    const uint16_t* q = reinterpret_cast<const uint16_t*>(queries_dev);
+    s->last_widened = 0;
+    s->last_max_groups = 0;
+    if (f->count == 0) return fill_empty(s, nq, k, out_scores, out_ids);   // nothing allowed
+    // MODE_EXACT: the filtered exact pass.  MODE_MFMA: the masked matrix-core scan.  MODE_AUTO: the exact pass on the sparse side of the
+    // crossover; otherwise the unfiltered rule (the coalescer's, dispatch.hip): the masked scan for more than 8 queries, and for any
+    // count once the rows have outgrown the caches.  Answers are identical on every path.
+    if (mode == MSE_MODE_AUTO)
+        mode = filter_sparse(b, f, nq) ? MSE_MODE_EXACT : (nq > 8 || b->n >= ((size_t)1 << 22)) ? MSE_MODE_MFMA : MSE_MODE_EXACT;
+    if (mode == MSE_MODE_EXACT) {
+        for (size_t q0 = 0; q0 < nq; q0 += 8) {
+            const int nqp = (int)std::min<size_t>(8, nq - q0);
+            if (s->q_stage.ensure((size_t)8 * d * 2)) return -1;
+            MSE_HIP_TRY(hipMemsetAsync(s->q_stage.p, 0, (size_t)8 * d * 2, s->stream));
+            MSE_HIP_TRY(hipMemcpyAsync(s->q_stage.p, q + q0 * d, (size_t)nqp * d * 2, hipMemcpyDeviceToDevice, s->stream));
+            if (exact_pass(s, nqp, (int)k, id_offset, out_scores + q0 * k, out_ids + q0 * k, k, f)) return -1;
+        }
+        return 0;
+    }
+    const size_t tile = mfma_call_tile(b, k);
+    for (size_t q0 = 0; q0 < nq; q0 += tile) {
+        const int nqp = (int)std::min<size_t>(tile, nq - q0);
+        if (mfma_pass(s, q + q0 * d, nqp, (int)k, id_offset, out_scores + q0 * k, out_ids + q0 * k, k, f)) return -1;
+    }
+    return 0;
+}
+
+int mse_bruteforce_topk_filtered_f16(mse_searcher* s, const mse_filter* f, const uint16_t* queries, size_t nq, size_t k, int mode,
+                                     int64_t* scores, uint32_t* ids) {
+    if (!s) return fail("null searcher");
+    if (check_filter(s->base, f)) return -1;
+    if (nq == 0 || k == 0) return 0;
+    if (k > (size_t)TOPK_KMAX - 64) return fail("k too large (max 1984)");
+    if (mode == MSE_MODE_AUTO && nq <= (size_t)mfma_query_tile((int)s->base->d)) {
+        // as mse_bruteforce_topk_f16: the base's coalescer, where the request shares a pass with the requests of the same filter
+        mse_dispatcher* disp = base_dispatcher(s->base);
+        if (disp) return mse_dispatcher_topk_filtered_f16(disp, f, queries, nq, k, scores, ids);
+    }
+    const size_t d = s->base->d;
+    DevBuf qd;
+    if (qd.ensure(nq * d * 2)) return -1;
+    if (s->out_scores.ensure(nq * k * 8) || s->out_ids.ensure(nq * k * 4)) return -1;
+    MSE_HIP_TRY(hipMemcpyAsync(qd.p, queries, nq * d * 2, hipMemcpyHostToDevice, s->stream));
+    if (mse_bruteforce_topk_filtered_f16_dev(s, f, qd.p, nq, k, mode, 0, s->out_scores.p, s->out_ids.p)) return -1;
+    MSE_HIP_TRY(hipMemcpyAsync(scores, s->out_scores.p, nq * k * 8, hipMemcpyDeviceToHost, s->stream));
+    MSE_HIP_TRY(hipMemcpyAsync(ids, s->out_ids.p, nq * k * 4, hipMemcpyDeviceToHost, s->stream));
     MSE_HIP_TRY(hipStreamSynchronize(s->stream));
     return 0;
 }

@@ -67,18 +67,22 @@ namespace {
 
 // <= 8 f32 queries against every row in the stated FAISS order (scan_exact.hip, QF32), tournament, ids + f32 keys into
 // out_ids / out_keys ([nq][out_stride], ID_NONE-padded)
-int index_pass_exact(mse_index* idx, const float* q32_dev, int nqp, int k, uint32_t* out_ids, float* out_keys, size_t out_stride) {
+// With a filter (non-empty, no longer than the index): its allowed rows only, through its ascending id list (api.hip exact_pass).
+int index_pass_exact(mse_index* idx, const float* q32_dev, int nqp, int k, uint32_t* out_ids, float* out_keys, size_t out_stride,
+                     const mse_filter* f = nullptr) {
     mse_searcher* s = idx->scratch;
     hipStream_t st = s->stream;
-    const size_t d = idx->d, n = idx->n;
+    const size_t d = idx->d, n = f ? f->count : idx->n;
     if (s->q_stage.ensure(8 * d * 4) || s->scores.ensure((size_t)nqp * n * 4)) return -1;
     MSE_HIP_TRY(hipMemsetAsync(s->q_stage.p, 0, 8 * d * 4, st));
     MSE_HIP_TRY(hipMemcpyAsync(s->q_stage.p, q32_dev, (size_t)nqp * d * 4, hipMemcpyDeviceToDevice, st));
-    if (launch_scan_exact(idx->codes, n, (int)d, s->q_stage.p, nqp, true, nullptr, n, s->scores.as<float>(), s->n_cu, st)) return -1;
+    if (launch_scan_exact(idx->codes, n, (int)d, s->q_stage.p, nqp, true, nullptr, n, s->scores.as<float>(), s->n_cu, st,
+                          f ? f->ids : nullptr)) return -1;
     if (s->sel_keys.ensure((size_t)nqp * k * 4)) return -1;
     uint32_t* sel = nullptr;
     LevelRef l0{KEY_F32, s->scores.p, n, 1, n, false, 0};
     if (descend(s, l0, nqp, k, &sel, s->sel_keys.p)) return -1;
+    if (f && launch_map_positions(sel, (size_t)nqp * k, f->ids, st)) return -1;
     MSE_HIP_TRY(hipMemcpy2DAsync(out_ids, out_stride * 4, sel, (size_t)k * 4, (size_t)k * 4, nqp, hipMemcpyDeviceToDevice, st));
     MSE_HIP_TRY(hipMemcpy2DAsync(out_keys, out_stride * 4, s->sel_keys.p, (size_t)k * 4, (size_t)k * 4, nqp, hipMemcpyDeviceToDevice, st));
     return 0;
@@ -89,7 +93,9 @@ int index_pass_exact(mse_index* idx, const float* q32_dev, int nqp, int k, uint3
 // certificate.  The bound on what the nomination can have missed is the f16 scan's (api.hip mfma_pass) plus the query
 // rounding, |x . (q - f16(q))| <= |x| |q - f16(q)| (measured per query, not assumed).  A query whose certificate fails widens
 // its candidate set and finally repeats through the exact pass: answers equal index_pass_exact's.
-int index_pass_mfma(mse_index* idx, const float* q32_dev, int nqp, int k, uint32_t* out_ids, float* out_keys, size_t out_stride) {
+// With a filter: the masked scan, excluded rows dropped at candidate expansion, the filtered exact pass as the fallback (api.hip mfma_pass).
+int index_pass_mfma(mse_index* idx, const float* q32_dev, int nqp, int k, uint32_t* out_ids, float* out_keys, size_t out_stride,
+                    const mse_filter* f = nullptr) {
     mse_searcher* s = idx->scratch;
     hipStream_t st = s->stream;
     const int d = idx->d;
@@ -101,7 +107,8 @@ int index_pass_mfma(mse_index* idx, const float* q32_dev, int nqp, int k, uint32
     const size_t n_groups = (n + GROUP_ROWS - 1) / GROUP_ROWS;
     if (s->gmax.ensure(n_groups * (size_t)nq_pad * 4) || s->qpacked.ensure(mfma_packed_bytes(d))) return -1;
     if (launch_scan_mfma(idx->codes, n, d, s->q_stage.as<uint16_t>(), nq_pad, s->qpacked.p, s->gmax.as<float>(), s->n_cu, st,
-                         s->timing ? s->ev0 : nullptr, s->timing ? s->ev1 : nullptr)) return -1;
+                         s->timing ? s->ev0 : nullptr, s->timing ? s->ev1 : nullptr, 0, 1, f ? f->words : nullptr, f ? f->n_words : 0))
+        return -1;
     bool timing_pending = s->timing;
     if (s->eps.ensure((size_t)nqp * 8) || s->margin.ensure((size_t)nqp * 8)) return -1;   // second halves: the widening's compact set
     if (launch_query_eps_f32(q32_dev, s->q_stage.as<uint16_t>(), nqp, d, idx->view.norm_bits_dev, 2.8e-4f, s->eps.as<float>(), st)) return -1;
@@ -116,7 +123,8 @@ int index_pass_mfma(mse_index* idx, const float* q32_dev, int nqp, int k, uint32
         if (descend(s, l0, nq, kg_eff, &gsel, s->gkeys.p)) return -1;
         const size_t n_cand = (size_t)kg_eff * GROUP_ROWS;
         if (s->cand_ids.ensure((size_t)nq * n_cand * 4) || s->cand_scores.ensure((size_t)nq * n_cand * 4)) return -1;
-        if (launch_expand_groups(gsel, kg_eff, kg_eff, GROUP_ROWS, n, s->cand_ids.as<uint32_t>(), n_cand, nq, st)) return -1;
+        if (f ? launch_expand_groups_masked(gsel, kg_eff, kg_eff, GROUP_ROWS, n, f->words, f->n_words, s->cand_ids.as<uint32_t>(), n_cand, nq, st)
+              : launch_expand_groups(gsel, kg_eff, kg_eff, GROUP_ROWS, n, s->cand_ids.as<uint32_t>(), n_cand, nq, st)) return -1;
         if (launch_score_rows(idx->codes, n, d, q32, true, s->cand_ids.as<uint32_t>(), (size_t)nq * n_cand, n_cand, nullptr,
                               s->cand_scores.as<float>(), st)) return -1;
         SelectArgs a{};
@@ -179,7 +187,7 @@ int index_pass_mfma(mse_index* idx, const float* q32_dev, int nqp, int k, uint32
     for (int j = 0; j < nb; j++) {   // cannot widen further: the exact pass, straight into the query's own output rows
         if (!open_q[j]) continue;
         if (index_pass_exact(idx, wq32 + (size_t)j * d, 1, k, out_ids + (size_t)bad[j] * out_stride, out_keys + (size_t)bad[j] * out_stride,
-                             out_stride)) return -1;
+                             out_stride, f)) return -1;
     }
     return 0;
 }
@@ -191,7 +199,8 @@ int index_run_group(mse_index* idx, DispatchReq* const* reqs, size_t n_req) {
     const size_t d = idx->d, n = idx->n;
     size_t total = 0, kmax = 0;
     for (size_t i = 0; i < n_req; i++) { total += reqs[i]->nq; kmax = std::max(kmax, reqs[i]->k); }
-    if (total == 0 || kmax == 0 || n == 0) return 0;   // outputs were pre-filled with "nothing found"
+    const mse_filter* f = static_cast<const mse_filter*>(reqs[0]->aux0);   // the group's filter (its key, index_run_batch), or null
+    if (total == 0 || kmax == 0 || n == 0 || (f && f->count == 0)) return 0;   // outputs were pre-filled with "nothing found"
     const size_t in_bytes = total * d * 4, out_bytes = total * kmax * 8;
     if (idx->pin.ensure(std::max(in_bytes, out_bytes), (size_t)1 << 20)) return -1;
     if (idx->q32.ensure(in_bytes) || idx->out.ensure(out_bytes)) return -1;
@@ -203,12 +212,13 @@ int index_run_group(mse_index* idx, DispatchReq* const* reqs, size_t n_req) {
     s->last_widened = 0; s->last_max_groups = 0;
     // same rule as the f16 dispatcher (dispatch.hip): the matrix-core pass for more than 8 queries, and for any count once the
     // rows have outgrown the caches
-    const bool mfma = total > 8 || n >= ((size_t)1 << 22);
+    // (filtered: the id-list pass on the sparse side of the crossover, api.hip filter_sparse)
+    const bool mfma = (total > 8 || n >= ((size_t)1 << 22)) && !(f && filter_sparse(&idx->view, f, total));
     const size_t tile = mfma ? (size_t)mfma_query_tile((int)d) : 8;
     for (size_t q0 = 0; q0 < total; q0 += tile) {
         const int m = (int)std::min(tile, total - q0);
-        const int rc = mfma ? index_pass_mfma(idx, idx->q32.as<float>() + q0 * d, m, (int)kmax, ids_dev + q0 * kmax, keys_dev + q0 * kmax, kmax)
-                            : index_pass_exact(idx, idx->q32.as<float>() + q0 * d, m, (int)kmax, ids_dev + q0 * kmax, keys_dev + q0 * kmax, kmax);
+        const int rc = mfma ? index_pass_mfma(idx, idx->q32.as<float>() + q0 * d, m, (int)kmax, ids_dev + q0 * kmax, keys_dev + q0 * kmax, kmax, f)
+                            : index_pass_exact(idx, idx->q32.as<float>() + q0 * d, m, (int)kmax, ids_dev + q0 * kmax, keys_dev + q0 * kmax, kmax, f);
         if (rc) return -1;
     }
     MSE_HIP_TRY(hipMemcpyAsync(idx->pin.p, idx->out.p, out_bytes, hipMemcpyDeviceToHost, st));
@@ -231,10 +241,34 @@ int index_run_group(mse_index* idx, DispatchReq* const* reqs, size_t n_req) {
 }
 
 void index_run_batch(mse_index* idx, std::vector<DispatchReq*>& batch) {
-    idx->retried_alone += run_shared(batch, [idx](DispatchReq* const* reqs, size_t n) { return index_run_group(idx, reqs, n); });
+    auto run = [idx](std::vector<DispatchReq*>& group) {
+        idx->retried_alone += run_shared(group, [idx](DispatchReq* const* reqs, size_t n) { return index_run_group(idx, reqs, n); });
+    };
+    bool filtered = false;
+    for (const DispatchReq* r : batch) filtered = filtered || r->aux0;
+    if (!filtered) { run(batch); return; }   // unfiltered requests only: one group, as always
+    // requests share a pass only with requests of the same filter object (null = unfiltered)
+    for_each_shared_group(batch, [](const DispatchReq& a, const DispatchReq& b) { return a.aux0 == b.aux0; }, run);
 }
 
 }  // namespace
+
+static int index_search(mse_index* idx, const mse_filter* f, const float* queries, size_t nq, size_t k, float* distances, int64_t* labels) {
+    if (!idx) return fail("null index");
+    if (nq == 0 || k == 0) return 0;
+    if (!queries || !distances || !labels) return fail("null argument");
+    if (k > (size_t)TOPK_KMAX - 64) return fail("k too large (max 1984)");
+    // index.read() of src/main.rs:1046: any number of searches at once; they meet in the coalescer and share passes (a filtered one
+    // with the searches of the same filter object: DispatchReq::aux0 is the group key)
+    idx->rw.lock_shared();
+    if (f && check_filter(&idx->view, f)) { idx->rw.unlock_shared(); return -1; }   // rows past the filter are excluded; add only grows
+    for (size_t i = 0; i < nq * k; i++) { distances[i] = -FLT_MAX; labels[i] = -1; }
+    DispatchReq r;
+    r.queries = queries; r.nq = nq; r.k = k; r.out_a = distances; r.out_b = labels; r.aux0 = f;
+    const int rc = idx->co->submit(r);
+    idx->rw.unlock_shared();
+    return rc;
+}
 
 mse_index* mse_index_new(int d) {
     if (d <= 0 || d % 64 != 0 || d > D_MAX) {
@@ -309,18 +343,14 @@ int mse_index_add(mse_index* idx, const float* x, size_t n) {
 }
 
 int mse_index_search(mse_index* idx, const float* queries, size_t nq, size_t k, float* distances, int64_t* labels) {
+    return index_search(idx, nullptr, queries, nq, k, distances, labels);
+}
+
+int mse_index_search_filtered(mse_index* idx, const mse_filter* f, const float* queries, size_t nq, size_t k, float* distances,
+                              int64_t* labels) {
     if (!idx) return fail("null index");
-    if (nq == 0 || k == 0) return 0;
-    if (!queries || !distances || !labels) return fail("null argument");
-    if (k > (size_t)TOPK_KMAX - 64) return fail("k too large (max 1984)");
-    for (size_t i = 0; i < nq * k; i++) { distances[i] = -FLT_MAX; labels[i] = -1; }
-    // index.read() of src/main.rs:1046: any number of searches at once; they meet in the coalescer and share passes
-    idx->rw.lock_shared();
-    DispatchReq r;
-    r.queries = queries; r.nq = nq; r.k = k; r.out_a = distances; r.out_b = labels;
-    const int rc = idx->co->submit(r);
-    idx->rw.unlock_shared();
-    return rc;
+    if (!f) return fail("null filter");
+    return index_search(idx, f, queries, nq, k, distances, labels);
 }
 
 int mse_index_stats(mse_index* idx, uint64_t out[6]) {

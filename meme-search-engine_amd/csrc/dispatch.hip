@@ -523,7 +523,10 @@ int run_group(mse_dispatcher* D, DispatchReq* const* reqs, size_t n_req) {
     const int mode = (total > 8 || b->n >= ((size_t)1 << 22)) ? MSE_MODE_MFMA : MSE_MODE_EXACT;
     int64_t* sc_dev = D->out_dev.as<int64_t>();
     uint32_t* id_dev = reinterpret_cast<uint32_t*>(D->out_dev.as<char>() + sc_bytes);
-    if (mse_bruteforce_topk_f16_dev(s, D->q_dev.p, total, kmax, mode, 0, sc_dev, id_dev)) return -1;
+    // a group shares one filter (its key, aux0; run_batch): the filtered search picks its own path by the same rule and the crossover
+    const mse_filter* f = static_cast<const mse_filter*>(reqs[0]->aux0);
+    if (f ? mse_bruteforce_topk_filtered_f16_dev(s, f, D->q_dev.p, total, kmax, MSE_MODE_AUTO, 0, sc_dev, id_dev)
+          : mse_bruteforce_topk_f16_dev(s, D->q_dev.p, total, kmax, mode, 0, sc_dev, id_dev)) return -1;
     MSE_HIP_TRY(hipMemcpyAsync(D->pin.p, D->out_dev.p, out_bytes, hipMemcpyDeviceToHost, st));
     MSE_HIP_TRY(hipStreamSynchronize(st));
     const int64_t* sc = reinterpret_cast<const int64_t*>(p);
@@ -540,10 +543,17 @@ int run_group(mse_dispatcher* D, DispatchReq* const* reqs, size_t n_req) {
 }
 
 void run_batch(mse_dispatcher* D, std::vector<DispatchReq*>& batch) {
-    D->retried_alone += run_shared(batch, [D](DispatchReq* const* reqs, size_t n) {
-        if (n > 1 && D->fail_shared.load() > 0) { D->fail_shared--; return fail("injected failure of a shared pass (test hook)"); }
-        return run_group(D, reqs, n);
-    });
+    auto run = [D](std::vector<DispatchReq*>& group) {
+        D->retried_alone += run_shared(group, [D](DispatchReq* const* reqs, size_t n) {
+            if (n > 1 && D->fail_shared.load() > 0) { D->fail_shared--; return fail("injected failure of a shared pass (test hook)"); }
+            return run_group(D, reqs, n);
+        });
+    };
+    bool filtered = false;
+    for (const DispatchReq* r : batch) filtered = filtered || r->aux0;
+    if (!filtered) { run(batch); return; }   // unfiltered requests only: one group, as always
+    // requests share a pass only with requests of the same filter object (null = unfiltered)
+    for_each_shared_group(batch, [](const DispatchReq& a, const DispatchReq& b) { return a.aux0 == b.aux0; }, run);
 }
 
 }  // namespace
@@ -585,7 +595,13 @@ void mse_dispatcher_free(mse_dispatcher* D) {
 }
 
 int mse_dispatcher_topk_f16(mse_dispatcher* D, const uint16_t* queries, size_t nq, size_t k, int64_t* scores, uint32_t* ids) {
+    return mse_dispatcher_topk_filtered_f16(D, nullptr, queries, nq, k, scores, ids);
+}
+
+int mse_dispatcher_topk_filtered_f16(mse_dispatcher* D, const mse_filter* f, const uint16_t* queries, size_t nq, size_t k, int64_t* scores,
+                                     uint32_t* ids) {
     if (!D) return fail("null dispatcher");
+    if (f && check_filter(D->base, f)) return -1;
     if (nq == 0 || k == 0) return 0;
     // argument errors never enter the queue: they belong to this caller alone
     if (!queries || !scores || !ids) return fail("null argument");
@@ -596,6 +612,7 @@ int mse_dispatcher_topk_f16(mse_dispatcher* D, const uint16_t* queries, size_t n
     r.k = k;
     r.out_a = scores;
     r.out_b = ids;
+    r.aux0 = f;   // the group key: a pass is shared by requests of one filter only
     return D->co->submit(r);
 }
 

@@ -1,0 +1,151 @@
+// Row filters of the filtered brute-force search (include/mse.h mse_filter): the device bitmap, its compacted id list, and the two
+// small kernels the filtered passes add around the existing ones (api.hip exact_pass / mfma_pass).
+//
+// Bitmap: one bit per row, LSB first, one u32 word per 32-row group (the group of the MFMA scan's epilogue), padded with zero words
+// to a whole number of 256-row scan tiles.  Id list: the allowed rows in ascending order, built once per filter -- the exact pass and
+// the sparse path score it instead of all rows, and a position in it orders as its id does, so (score desc, position asc) selection
+// is (score desc, id asc) selection.
+#include "common.h"
+#include "kernels.h"
+
+namespace mse {
+namespace {
+
+constexpr int CB = 256;   // words per compaction block (8192 rows)
+
+__global__ void or_ids_kernel(uint32_t* __restrict__ words, const uint32_t* __restrict__ ids, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const uint32_t id = ids[i];
+        atomicOr(&words[id >> 5], 1u << (id & 31));
+    }
+}
+
+// inclusive scan of v over the CB threads of the block (Hillis-Steele in LDS); returns this thread's inclusive prefix
+__device__ uint32_t block_scan(uint32_t v, uint32_t* tmp) {
+    const int t = threadIdx.x;
+    tmp[t] = v;
+    __syncthreads();
+    for (int off = 1; off < CB; off <<= 1) {
+        const uint32_t add = t >= off ? tmp[t - off] : 0u;
+        __syncthreads();
+        tmp[t] += add;
+        __syncthreads();
+    }
+    const uint32_t r = tmp[t];
+    __syncthreads();
+    return r;
+}
+
+// set bits per block of CB words
+__global__ __launch_bounds__(CB) void count_blocks_kernel(const uint32_t* __restrict__ words, size_t n_words, uint32_t* __restrict__ counts) {
+    __shared__ uint32_t tmp[CB];
+    const size_t w = (size_t)blockIdx.x * CB + threadIdx.x;
+    const uint32_t c = w < n_words ? (uint32_t)__popc(words[w]) : 0u;
+    const uint32_t s = block_scan(c, tmp);
+    if (threadIdx.x == CB - 1) counts[blockIdx.x] = s;
+}
+
+// exclusive prefix of the block counts (one workgroup; each thread walks a contiguous chunk) and the total
+__global__ __launch_bounds__(CB) void scan_blocks_kernel(const uint32_t* __restrict__ counts, size_t n_blocks,
+                                                        unsigned long long* __restrict__ offsets, unsigned long long* __restrict__ total) {
+    __shared__ unsigned long long part[CB];
+    const size_t per = (n_blocks + CB - 1) / CB;
+    const size_t lo = (size_t)threadIdx.x * per, hi = lo + per < n_blocks ? lo + per : n_blocks;
+    unsigned long long s = 0;
+    for (size_t b = lo; b < hi; b++) s += counts[b];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long run = 0;
+        for (int t = 0; t < CB; t++) { const unsigned long long v = part[t]; part[t] = run; run += v; }
+        *total = run;
+    }
+    __syncthreads();
+    unsigned long long run = part[threadIdx.x];
+    for (size_t b = lo; b < hi; b++) { offsets[b] = run; run += counts[b]; }
+}
+
+__global__ __launch_bounds__(CB) void compact_kernel(const uint32_t* __restrict__ words, size_t n_words,
+                                                    const unsigned long long* __restrict__ offsets, uint32_t* __restrict__ ids) {
+    __shared__ uint32_t tmp[CB];
+    const size_t w = (size_t)blockIdx.x * CB + threadIdx.x;
+    uint32_t bits = w < n_words ? words[w] : 0u;
+    const uint32_t c = (uint32_t)__popc(bits);
+    size_t at = offsets[blockIdx.x] + block_scan(c, tmp) - c;
+    while (bits) {
+        const int b = __ffs(bits) - 1;
+        ids[at++] = (uint32_t)(w * 32 + b);
+        bits &= bits - 1;
+    }
+}
+
+__global__ void expand_groups_masked_kernel(const uint32_t* __restrict__ parents, size_t par_stride, size_t n_par, int group,
+                                            size_t n_rows, const uint32_t* __restrict__ words, size_t n_words,
+                                            uint32_t* __restrict__ ids, size_t ids_stride, int nq) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t per_q = n_par * (size_t)group;
+    if (i >= per_q * (size_t)nq) return;
+    const size_t q = i / per_q, r = i % per_q;
+    const uint32_t p = parents[q * par_stride + r / group];
+    uint32_t id = ID_NONE;
+    if (p != ID_NONE) {
+        const size_t row = (size_t)p * group + (r % group);
+        if (row < n_rows && (row >> 5) < n_words && ((words[row >> 5] >> (row & 31)) & 1u)) id = (uint32_t)row;
+    }
+    ids[q * ids_stride + r] = id;
+}
+
+__global__ void map_positions_kernel(uint32_t* __restrict__ sel, size_t n, const uint32_t* __restrict__ list) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t p = sel[i];
+    if (p != ID_NONE) sel[i] = list[p];
+}
+
+}  // namespace
+
+int launch_filter_or_ids(uint32_t* words, size_t n_words, const uint32_t* ids, size_t n, hipStream_t stream) {
+    (void)n_words;   // the caller has checked every id against the filter's length
+    if (n == 0) return 0;
+    const size_t blocks = std::min<size_t>((n + 255) / 256, 65535);
+    hipLaunchKernelGGL(or_ids_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, words, ids, n);
+    MSE_HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+size_t filter_compact_scratch_bytes(size_t n_words) {
+    const size_t nb = std::max<size_t>((n_words + CB - 1) / CB, 1);
+    return nb * 4 + nb * 8 + 8 + 16;
+}
+
+int launch_filter_compact(const uint32_t* words, size_t n_words, uint32_t* ids_out, unsigned long long* count_dev, void* scratch,
+                          hipStream_t stream) {
+    const size_t nb = std::max<size_t>((n_words + CB - 1) / CB, 1);
+    if (nb > 0x7fffffffull) return fail("filter: too many rows");
+    unsigned long long* offsets = reinterpret_cast<unsigned long long*>(scratch);
+    uint32_t* counts = reinterpret_cast<uint32_t*>(offsets + nb);
+    hipLaunchKernelGGL(count_blocks_kernel, dim3((unsigned)nb), dim3(CB), 0, stream, words, n_words, counts);
+    hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(CB), 0, stream, counts, nb, offsets, count_dev);
+    hipLaunchKernelGGL(compact_kernel, dim3((unsigned)nb), dim3(CB), 0, stream, words, n_words, offsets, ids_out);
+    MSE_HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_expand_groups_masked(const uint32_t* parents, size_t par_stride, size_t n_par, int group, size_t n_rows, const uint32_t* words,
+                                size_t n_words, uint32_t* ids, size_t ids_stride, int nq, hipStream_t stream) {
+    const size_t total = n_par * (size_t)group * (size_t)nq;
+    if (total == 0) return 0;
+    hipLaunchKernelGGL(expand_groups_masked_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, parents, par_stride, n_par,
+                       group, n_rows, words, n_words, ids, ids_stride, nq);
+    MSE_HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_map_positions(uint32_t* sel, size_t n, const uint32_t* list, hipStream_t stream) {
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(map_positions_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, sel, n, list);
+    MSE_HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+}  // namespace mse

@@ -12,8 +12,9 @@ constexpr int TOPK_FANOUT = 256;   // children per tournament group
 constexpr int GROUP_ROWS = 32;     // base rows per group maximum written by the MFMA scan
 
 // ---- scan_exact.hip ------------------------------------------------------------------------
+// ids != nullptr (filtered search): score rows ids[0 .. n_rows) instead of rows 0 .. n_rows; scores stay at the list positions
 int launch_scan_exact(const uint16_t* base, size_t n_rows, int d, const void* queries_dev, int nq, bool q_is_f32,
-                      int64_t* scores, size_t score_stride, float* fscores, int n_cu, hipStream_t stream);
+                      int64_t* scores, size_t score_stride, float* fscores, int n_cu, hipStream_t stream, const uint32_t* ids = nullptr);
 int launch_score_rows(const uint16_t* base, size_t n_rows, int d, const void* queries_dev, bool q_is_f32,
                       const uint32_t* ids_dev, size_t n_pairs, size_t pairs_per_query, int64_t* out, float* fout,
                       hipStream_t stream);
@@ -131,12 +132,27 @@ int launch_rank(const int64_t* scores, size_t n, const uint32_t* targets, int m,
 size_t dedup_batch_scratch_bytes(size_t nq, size_t cap);
 int launch_dedup_batch(const uint16_t* base, int d, uint32_t* vis_ids, long long* vis_scores, size_t cap, const uint32_t* n_visited, size_t nq,
                        float threshold, void* bits, hipStream_t st);
+// ---- filter.hip: row filters of the filtered brute-force search -------------------------------------------------------------
+// words: n_words zeroed bitmap words; sets the bit of each of the n ids (all < 32 * n_words)
+int launch_filter_or_ids(uint32_t* words, size_t n_words, const uint32_t* ids, size_t n, hipStream_t stream);
+// the ids of the set bits, ascending, into ids_out (room for every set bit); *count_dev = how many.  scratch: filter_compact_scratch_bytes
+size_t filter_compact_scratch_bytes(size_t n_words);
+int launch_filter_compact(const uint32_t* words, size_t n_words, uint32_t* ids_out, unsigned long long* count_dev, void* scratch,
+                          hipStream_t stream);
+// launch_expand_groups, with ID_NONE for rows whose bit is clear (or at / past 32 * n_words)
+int launch_expand_groups_masked(const uint32_t* parents, size_t par_stride, size_t n_par, int group, size_t n_rows, const uint32_t* words,
+                                size_t n_words, uint32_t* ids, size_t ids_stride, int nq, hipStream_t stream);
+// sel[i] = list[sel[i]] (ID_NONE stays): positions in the filter's id list -> row ids
+int launch_map_positions(uint32_t* sel, size_t n, const uint32_t* list, hipStream_t stream);
+
 // ---- scan_mfma.hip ---------------------------------------------------------------------------
 // group_max[q_pad_index][g] layout: [n_groups][nq_pad] floats (group-major), nq_pad multiple of 32
 int launch_scan_mfma(const uint16_t* base, size_t n_rows, int d, const uint16_t* queries_dev, int nq_pad,
                      void* packed_scratch, float* group_max, int n_cu, hipStream_t stream,
                      hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr, int gm_stride = 0 /* row stride of group_max; 0 = nq_pad */,
-                     int n_pass = 1 /* passes in this launch: consecutive nq_pad-row query tiles, consecutive column ranges of group_max */);  // events bracket the scan kernel only
+                     int n_pass = 1 /* passes in this launch: consecutive nq_pad-row query tiles, consecutive column ranges of group_max */,
+                     const uint32_t* mask = nullptr, size_t mask_words = 0 /* filtered search: one bitmap word per 32-row group */);
+                     // events bracket the scan kernel only
 size_t mfma_packed_bytes(int d);
 int mfma_query_tile(int d);  // most queries one pass handles at width d (320 or 256)
 int mfma_pad(int nq, int d);   // padded query count of a pass of nq <= 256 queries: 128, 192 or 256

@@ -75,6 +75,16 @@ struct mse_base {
     mutable bool norm_ready = false;
 };
 
+// row filter of the filtered brute-force search (filter.hip; immutable once made)
+struct mse_filter {
+    int device = 0;              // HIP ordinal the bitmap lives on
+    size_t n_rows = 0;           // rows it speaks for; rows at or past it are excluded
+    size_t n_words = 0;          // bitmap words: one per 32-row group, padded to whole 256-row scan tiles
+    size_t count = 0;            // allowed rows
+    uint32_t* words = nullptr;   // device bitmap
+    uint32_t* ids = nullptr;     // device: the allowed rows, ascending (count of them)
+};
+
 struct mse_searcher {
     const mse_base* base = nullptr;
     hipStream_t stream = nullptr;
@@ -149,6 +159,10 @@ struct mse_codes {
 };
 
 namespace mse {
+// a filter may be used on base b: same device, no longer than the rows (api.hip); 0, or -1 with the error set
+int check_filter(const mse_base* b, const mse_filter* f);
+// the sparse side of the crossover: nq queries through the filter's id list cost less than the masked scan over all rows (api.hip)
+bool filter_sparse(const mse_base* b, const mse_filter* f, size_t nq);
 // largest row norm of the base (x 1.0001), computed once and kept on the device as float bits (b->norm_bits_dev)
 int ensure_base_norm(const mse_base* b, hipStream_t st);
 // device memory the batched graph searches may spend on visited sets per launch: half of the free HBM, 256 MiB .. 64 GiB

@@ -73,11 +73,16 @@ constexpr int ROWS_PER_BLOCK = ROWS_PER_WAVE * WAVES;
 
 // scores[j * score_stride + row] for j < nq_valid.  queries: [QB][d] (f16 bits or f32), rows
 // beyond nq_valid must be readable (the host pads the staging buffer).
-template <int QB, bool QF32>
+// row read for list position `row`: the row itself, or (filtered search: one trailing argument, the filter's ascending id list)
+// ids[row].  The unfiltered kernels take an empty pack: their arguments and code are those of the kernels before the list form.
+__device__ __forceinline__ size_t source_row(size_t row) { return row; }
+__device__ __forceinline__ size_t source_row(size_t row, const uint32_t* ids) { return ids[row]; }
+
+template <int QB, bool QF32, typename... Ids>
 __global__ __launch_bounds__(256) void scan_exact_kernel(const uint16_t* __restrict__ base, size_t n_rows, int d,
                                                          const void* __restrict__ queries, int nq_valid,
                                                          int64_t* __restrict__ scores, size_t score_stride,
-                                                         float* __restrict__ fscores) {
+                                                         float* __restrict__ fscores, Ids... ids) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int QEL = QF32 ? 4 : 2;
     const int qbytes = d * QEL;
@@ -102,7 +107,7 @@ __global__ __launch_bounds__(256) void scan_exact_kernel(const uint16_t* __restr
         size_t row = rb + rw;
         const bool valid = row < n_rows;
         if (!valid) row = n_rows - 1;
-        const uint4* xp = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(base) + row * row_bytes) + part;
+        const uint4* xp = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(base) + source_row(row, ids...) * row_bytes) + part;
 
         float acc[QB][8];
 #pragma unroll
@@ -177,10 +182,14 @@ __global__ __launch_bounds__(256) void score_rows_kernel(const uint16_t* __restr
 
 template <int QB, bool QF32>
 int launch_scan(const uint16_t* base, size_t n_rows, int d, const void* q, int nq_valid, int64_t* scores,
-                size_t stride, float* fscores, int grid, hipStream_t stream) {
+                size_t stride, float* fscores, int grid, hipStream_t stream, const uint32_t* ids) {
     const size_t lds = (size_t)QB * d * (QF32 ? 4 : 2);
-    hipLaunchKernelGGL((scan_exact_kernel<QB, QF32>), dim3(grid), dim3(256), lds, stream, base, n_rows, d, q, nq_valid,
-                       scores, stride, fscores);
+    if (ids)
+        hipLaunchKernelGGL((scan_exact_kernel<QB, QF32, const uint32_t*>), dim3(grid), dim3(256), lds, stream, base, n_rows, d, q,
+                           nq_valid, scores, stride, fscores, ids);
+    else
+        hipLaunchKernelGGL((scan_exact_kernel<QB, QF32>), dim3(grid), dim3(256), lds, stream, base, n_rows, d, q, nq_valid,
+                           scores, stride, fscores);
     MSE_HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -191,7 +200,7 @@ int exact_scan_block() { return 8; }
 
 // queries_dev: [qb_padded][d] where qb_padded = next of {1,2,4,8} >= nq (caller pads with zeros).
 int launch_scan_exact(const uint16_t* base, size_t n_rows, int d, const void* queries_dev, int nq, bool q_is_f32,
-                      int64_t* scores, size_t score_stride, float* fscores, int n_cu, hipStream_t stream) {
+                      int64_t* scores, size_t score_stride, float* fscores, int n_cu, hipStream_t stream, const uint32_t* ids) {
     if (n_rows == 0 || nq == 0) return 0;
     if (d % 64 != 0 || d <= 0 || d > D_MAX) return fail("vector width must be a positive multiple of 64");
     if (nq > 8) return fail("launch_scan_exact handles at most 8 queries per pass");
@@ -202,9 +211,9 @@ int launch_scan_exact(const uint16_t* base, size_t n_rows, int d, const void* qu
 #define MSE_CASE(QB)                                                                                             \
     case QB:                                                                                                     \
         return q_is_f32 ? launch_scan<QB, true>(base, n_rows, d, queries_dev, nq, scores, score_stride, fscores, \
-                                                grid, stream)                                                    \
+                                                grid, stream, ids)                                               \
                         : launch_scan<QB, false>(base, n_rows, d, queries_dev, nq, scores, score_stride, fscores, \
-                                                 grid, stream);
+                                                 grid, stream, ids);
     switch (qb) {
         MSE_CASE(1)
         MSE_CASE(2)

@@ -105,15 +105,26 @@ __device__ __forceinline__ void dma16(const void* gptr, void* lds_wave_base) {
                                      (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
 
+// Filtered search (include/mse.h mse_filter): the MASKED form of the scan kernels takes two trailing arguments, the filter's
+// bitmap (one u32 word per 32-row group, bit r = row 32 g + r) and its word count (groups at or past it have no allowed row).  An
+// accumulator of an excluded row enters its group's maximum as -FLT_MAX, so a group without allowed rows writes -FLT_MAX and every
+// allowed row stays below its group's (masked) maximum: the certificate holds as it is.  The unmasked kernels take an empty pack,
+// so their argument lists and code are those of the kernels before the masked form existed.
+constexpr float MASKED_OUT = -3.402823466e+38f;
+__device__ __forceinline__ uint32_t group_word(size_t group, const uint32_t* words, size_t n_words) {
+    return group < n_words ? words[group] : 0u;
+}
+
 // S = stages in each wave's ring of X K-blocks (S-1 blocks in flight beyond the one being consumed);
 // nkb must be a multiple of S so that stage indices are compile-time constants.
 // NCT = 16-query column tiles per pass (8: 128 queries, 16: 256 queries)
 // ABL (developer ablations, MSE_SCAN_ABL; results are then meaningless, only the timing is of interest):
 // bit 0 no MFMAs, bit 1 no query-tile DMA, bit 2 no X DMA, bit 3 no B-fragment LDS reads
-template <int S, int NCT, int ABL = 0>
+template <int S, int NCT, int ABL = 0, typename... Mask>
 __global__ __launch_bounds__(W * 64) void scan_mfma_kernel(const uint16_t* __restrict__ base, size_t n_rows, int d,
                                                            const uint4* __restrict__ packed_ro,
-                                                           float* __restrict__ gmax, int nq_pad, size_t n_tiles, uint32_t y_packed, uint32_t y_cols) {
+                                                           float* __restrict__ gmax, int nq_pad, size_t n_tiles, uint32_t y_packed, uint32_t y_cols,
+                                                           Mask... mask) {
     constexpr int BN = NCT * 16;
     constexpr int QT_BYTES = BN * 128;       // one query tile: BN x 64 f16
     constexpr int QI = BN / 64;              // DMA instructions per wave per query tile
@@ -271,6 +282,18 @@ __global__ __launch_bounds__(W * 64) void scan_mfma_kernel(const uint16_t* __res
 
         // epilogue: per query column, max over this wave's 32 rows (2 row tiles x 4 accumulator rows x 4 lane groups)
         const size_t group = tile * W + wave;
+        if constexpr (sizeof...(Mask) != 0) {
+            // acc[rt][ct][r] of lane (i, g) holds row 16 rt + 4 g + r of the group (16x16x32 C layout; LDS row = wave row, dma_x)
+            const uint32_t w = group_word(group, mask...) >> (4 * g);
+#pragma unroll
+            for (int rt = 0; rt < 2; rt++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    if ((w >> (16 * rt + r)) & 1u) continue;
+#pragma unroll
+                    for (int ct = 0; ct < NCT; ct++) acc[rt][ct][r] = MASKED_OUT;
+                }
+        }
 #pragma unroll
         for (int ct = 0; ct < NCT; ct++) {
             float m = fmaxf(fmaxf(acc[0][ct][0], acc[0][ct][1]), fmaxf(acc[0][ct][2], acc[0][ct][3]));
@@ -306,10 +329,12 @@ __device__ unsigned long long g_scan_prof[4];
 __device__ __forceinline__ uint32_t memtime() { return (uint32_t)__builtin_amdgcn_s_memtime(); }   // deltas fit 32 bits
 #endif
 
-template <int S, int MF, int PROF = 0>
+template <int S, int MF, int PROF = 0, typename... Mask>
 __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __restrict__ base, size_t n_rows, int d,
                                                              const uint4* __restrict__ packed_ro,
-                                                             float* __restrict__ gmax, int nq_pad, size_t n_tiles, uint32_t y_packed, uint32_t y_cols) {
+                                                             float* __restrict__ gmax, int nq_pad, size_t n_tiles, uint32_t y_packed, uint32_t y_cols,
+                                                             Mask... mask) {
+    static_assert(sizeof...(Mask) == 0 || (MF == 16 && PROF == 0), "the masked form is the product kernel's");
     constexpr int BN = 256;
     constexpr int QT_BYTES = BN * 128;
     constexpr int QI = BN / 64;
@@ -456,6 +481,21 @@ __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __r
         }
 
         // epilogue: per query column, max over each 32-row group of this wave (two groups)
+        if constexpr (sizeof...(Mask) != 0) {
+            // acc[2 p + h][ct][r] of lane (i, g) holds row 16 h + 4 g + r of group p (LDS row = row of the row group, src_ptr)
+#pragma unroll
+            for (int p = 0; p < 2; p++) {
+                const uint32_t w = group_word(tile * W + rg * 2 + p, mask...) >> (4 * g);
+#pragma unroll
+                for (int h = 0; h < 2; h++)
+#pragma unroll
+                    for (int r = 0; r < 4; r++) {
+                        if ((w >> (16 * h + r)) & 1u) continue;
+#pragma unroll
+                        for (int ct = 0; ct < NCTW; ct++) acc[2 * p + h][ct][r] = MASKED_OUT;
+                    }
+            }
+        }
 #pragma unroll
         for (int p = 0; p < 2; p++) {
             const size_t group = tile * W + rg * 2 + p;
@@ -653,29 +693,26 @@ __global__ __launch_bounds__(W * 64) void scan_mfma2s_kernel(const uint16_t* __r
 thread_local unsigned g_pass_count = 1;
 thread_local uint32_t g_pass_packed = 0, g_pass_cols = 0;
 
-template <typename K>
+template <typename K, typename... Mask>
 int launch_kernel(K kernel, size_t lds, size_t grid, hipStream_t stream, const uint16_t* base, size_t n_rows, int d,
-                  const uint4* packed, float* group_max, int nq_pad) {
+                  const uint4* packed, float* group_max, int nq_pad, Mask... mask) {
     const size_t n_tiles = (n_rows + TILE_ROWS - 1) / TILE_ROWS;
     if (grid > n_tiles) grid = n_tiles;
     MSE_DYN_LDS(kernel, lds);
     hipLaunchKernelGGL(kernel, dim3((unsigned)grid, g_pass_count), dim3(W * 64), lds, stream, base, n_rows, d, packed, group_max, nq_pad, n_tiles,
-                       g_pass_packed, g_pass_cols);
+                       g_pass_packed, g_pass_cols, mask...);
     MSE_HIP_TRY(hipGetLastError());
     return 0;
 }
 
-template <int S, int NCT, int ABL>
+template <int S, int NCT, int ABL, typename... Mask>
 int launch_variant(size_t grid, hipStream_t stream, const uint16_t* base, size_t n_rows, int d, const uint4* packed,
-                   float* group_max, int nq_pad) {
+                   float* group_max, int nq_pad, Mask... mask) {
     const size_t lds = 2 * (size_t)(NCT * 16 * 128) + (size_t)W * S * 4096;  // S = 3: 128 KiB at 128 queries, 160 KiB at 256
-    return launch_kernel(scan_mfma_kernel<S, NCT, ABL>, lds, grid, stream, base, n_rows, d, packed, group_max, nq_pad);
+    return launch_kernel(scan_mfma_kernel<S, NCT, ABL, Mask...>, lds, grid, stream, base, n_rows, d, packed, group_max, nq_pad, mask...);
 }
 
 #ifdef MSE_DEV_KERNELS
-template <int S, int NCT, int ABL>
-int launch_variant(size_t grid, hipStream_t stream, const uint16_t* base, size_t n_rows, int d, const uint4* packed,
-                   float* group_max, int nq_pad);
 
 template <int S>
 int launch_2s(size_t grid, hipStream_t stream, const uint16_t* base, size_t n_rows, int d, const uint4* packed,
@@ -690,11 +727,11 @@ int launch_2s(size_t grid, hipStream_t stream, const uint16_t* base, size_t n_ro
 }
 #endif
 
-template <int S, int MF, int PROF = 0>
+template <int S, int MF, int PROF = 0, typename... Mask>
 int launch_2d(size_t grid, hipStream_t stream, const uint16_t* base, size_t n_rows, int d, const uint4* packed,
-              float* group_max, int nq_pad) {
+              float* group_max, int nq_pad, Mask... mask) {
     const size_t lds = 2 * (size_t)(256 * 128) + (size_t)4 * S * 8192;
-    return launch_kernel(scan_mfma2d_kernel<S, MF, PROF>, lds, grid, stream, base, n_rows, d, packed, group_max, nq_pad);
+    return launch_kernel(scan_mfma2d_kernel<S, MF, PROF, Mask...>, lds, grid, stream, base, n_rows, d, packed, group_max, nq_pad, mask...);
 }
 
 }  // namespace
@@ -714,7 +751,7 @@ size_t mfma_packed_bytes(int d) { return (size_t)(d / KB) * 320 * 128; }
 // packed_scratch: mfma_packed_bytes(d) bytes of device scratch owned by the caller (per searcher)
 int launch_scan_mfma(const uint16_t* base, size_t n_rows, int d, const uint16_t* queries_dev, int nq_pad,
                      void* packed_scratch, float* group_max, int n_cu, hipStream_t stream, hipEvent_t ev_begin,
-                     hipEvent_t ev_end, int gm_stride, int n_pass) {
+                     hipEvent_t ev_end, int gm_stride, int n_pass, const uint32_t* mask, size_t mask_words) {
     if (n_rows == 0) return 0;
     if (n_pass < 1 || n_pass > 65535) return fail("scan_mfma: 1..65535 passes per launch");
     if (n_pass > 1 && !gm_stride) return fail("scan_mfma: batched passes need a common group-maximum stride");
@@ -740,6 +777,7 @@ int launch_scan_mfma(const uint16_t* base, size_t n_rows, int d, const uint16_t*
     const size_t grid = (size_t)n_cu;  // one workgroup per CU
     int rc = -2;
 #ifdef MSE_DEV_KERNELS
+    if (!mask) {
     // Developer build only (make dev -> libmse_hip_dev.so, scripts/scan_ablate.py): timing ablations whose RESULTS ARE WRONG
     // and alternative tilings.  None of this is compiled into the product library.
     const int abl = getenv("MSE_SCAN_ABL") ? atoi(getenv("MSE_SCAN_ABL")) : 0;
@@ -764,28 +802,31 @@ int launch_scan_mfma(const uint16_t* base, size_t n_rows, int d, const uint16_t*
     else if (nq_pad == 256 && S == 3 && v2d == 163) rc = launch_2d<3, 16, 3>(grid, stream, base, n_rows, d, packed, group_max, gs);
     else if (nq_pad == 256 && S == 3 && v2d == 17) rc = launch_2s<3>(grid, stream, base, n_rows, d, packed, group_max, gs);
     else if (nq_pad == 256 && S == 3 && v2d == 32) rc = launch_2d<3, 32>(grid, stream, base, n_rows, d, packed, group_max, gs);
+    }
     if (rc != -2) {
         if (rc) return rc;
         if (ev_end) MSE_HIP_TRY(hipEventRecord(ev_end, stream));
         return 0;
     }
 #endif
+    // the product configurations below, each unmasked or masked (filtered search: the bitmap as two trailing kernel arguments)
+    auto run = [&](auto launch) { return mask ? launch(mask, mask_words) : launch(); };
     if (nq_pad == 320) {
         // 20 column tiles per wave (32 rows x 320 queries, 160 accumulator registers of 252 used: 24 tiles spill and run 2.6x
         // slower), two-stage row ring: 2 x 40 KiB of query tiles + 8 x 2 x 4 KiB = 144 KiB of LDS.
-        rc = launch_variant<2, 20, 0>(grid, stream, base, n_rows, d, packed, group_max, gs);
+        rc = run([&](auto... m) { return launch_variant<2, 20, 0>(grid, stream, base, n_rows, d, packed, group_max, gs, m...); });
     } else if (nq_pad == 192) {
         // 12 column tiles on the one-dimensional wave split (32 rows x 192 queries per wave, 96 accumulators): the point between
         // the HBM-bound 128-query pass and the power-bound 256-query pass (profiles/r04_scan_variants.txt)
-        rc = launch_variant<3, 12, 0>(grid, stream, base, n_rows, d, packed, group_max, gs);
+        rc = run([&](auto... m) { return launch_variant<3, 12, 0>(grid, stream, base, n_rows, d, packed, group_max, gs, m...); });
     } else if (nq_pad == 128) {
-        if (S == 3) rc = launch_variant<3, 8, 0>(grid, stream, base, n_rows, d, packed, group_max, gs);
-        else if (S == 2) rc = launch_variant<2, 8, 0>(grid, stream, base, n_rows, d, packed, group_max, gs);
-        else rc = launch_variant<1, 8, 0>(grid, stream, base, n_rows, d, packed, group_max, gs);
+        if (S == 3) rc = run([&](auto... m) { return launch_variant<3, 8, 0>(grid, stream, base, n_rows, d, packed, group_max, gs, m...); });
+        else if (S == 2) rc = run([&](auto... m) { return launch_variant<2, 8, 0>(grid, stream, base, n_rows, d, packed, group_max, gs, m...); });
+        else rc = run([&](auto... m) { return launch_variant<1, 8, 0>(grid, stream, base, n_rows, d, packed, group_max, gs, m...); });
     } else {
-        if (S == 3) rc = launch_2d<3, 16>(grid, stream, base, n_rows, d, packed, group_max, gs);
-        else if (S == 2) rc = launch_variant<2, 16, 0>(grid, stream, base, n_rows, d, packed, group_max, gs);
-        else rc = launch_variant<1, 16, 0>(grid, stream, base, n_rows, d, packed, group_max, gs);
+        if (S == 3) rc = run([&](auto... m) { return launch_2d<3, 16>(grid, stream, base, n_rows, d, packed, group_max, gs, m...); });
+        else if (S == 2) rc = run([&](auto... m) { return launch_variant<2, 16, 0>(grid, stream, base, n_rows, d, packed, group_max, gs, m...); });
+        else rc = run([&](auto... m) { return launch_variant<1, 16, 0>(grid, stream, base, n_rows, d, packed, group_max, gs, m...); });
     }
     if (rc) return rc;
     if (ev_end) MSE_HIP_TRY(hipEventRecord(ev_end, stream));

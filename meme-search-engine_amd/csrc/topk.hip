@@ -433,7 +433,9 @@ __global__ void finalize_kernel(const uint32_t* __restrict__ sel_ids, const int6
         } else {
             const float g = group_keys[(size_t)q * gk_stride + (kg - 1)];
             const uint32_t idk = sel_ids[(size_t)q * sel_stride + (k - 1)];
-            if (idk == ID_NONE) {
+            // a k-th score of INT64_MIN (saturated fixed point) proves nothing: a row outside the groups that also saturates ties with
+            // it and may have the lower id -- only examining every group decides
+            if (idk == ID_NONE || sel_scores[(size_t)q * sel_stride + (k - 1)] == INT64_MIN) {
                 m = -__builtin_inff();
             } else {
                 const float sk = (float)((double)sel_scores[(size_t)q * sel_stride + (k - 1)] / 4294967296.0);

@@ -56,6 +56,13 @@ SIGNATURES = {
     "mse_bruteforce_topk_f16": (C.c_int, [vp, u16p, sz, sz, C.c_int, i64p, u32p]),
     "mse_bruteforce_topk_f16_dev": (C.c_int, [vp, vp, sz, sz, C.c_int, C.c_uint64, vp, vp]),
     "mse_bruteforce_scores_f16": (C.c_int, [vp, u16p, i64p]),
+    "mse_filter_from_bits": (vp, [u8p, sz]),
+    "mse_filter_from_ids": (vp, [u32p, sz, sz]),
+    "mse_filter_free": (None, [vp]),
+    "mse_filter_len": (sz, [vp]),
+    "mse_filter_count": (sz, [vp]),
+    "mse_bruteforce_topk_filtered_f16": (C.c_int, [vp, vp, u16p, sz, sz, C.c_int, i64p, u32p]),
+    "mse_bruteforce_topk_filtered_f16_dev": (C.c_int, [vp, vp, vp, sz, sz, C.c_int, C.c_uint64, vp, vp]),
     "mse_bruteforce_ranks_f16": (C.c_int, [vp, u16p, u32p, sz, u32p]),
     "mse_score_rows_f16": (C.c_int, [vp, u32p, sz, u16p, i64p]),
     "mse_merge_topk_dev": (C.c_int, [vp, vp, vp, sz, sz, sz, vp, vp]),
@@ -93,10 +100,12 @@ SIGNATURES = {
     "mse_index_add": (C.c_int, [vp, f32p, sz]),
     "mse_index_ntotal": (sz, [vp]),
     "mse_index_search": (C.c_int, [vp, f32p, sz, sz, f32p, i64p]),
+    "mse_index_search_filtered": (C.c_int, [vp, vp, f32p, sz, sz, f32p, i64p]),
     "mse_index_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
     "mse_dispatcher_new": (vp, [vp, sz, C.c_uint32]),
     "mse_dispatcher_free": (None, [vp]),
     "mse_dispatcher_topk_f16": (C.c_int, [vp, u16p, sz, sz, i64p, u32p]),
+    "mse_dispatcher_topk_filtered_f16": (C.c_int, [vp, vp, u16p, sz, sz, i64p, u32p]),
     "mse_dispatcher_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
     "mse_dispatcher_searcher": (vp, [vp]),
     "mse_debug_dispatcher_fail_shared": (C.c_int, [vp, C.c_uint32]),

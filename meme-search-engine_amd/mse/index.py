@@ -7,7 +7,7 @@ import numpy as np
 
 from . import ffi
 from .ffi import check, check_ptr
-from .vector import _p
+from .vector import RowFilter, _p
 
 
 class SearchResult:
@@ -27,14 +27,24 @@ class ScalarQuantizerIndex:
     def ntotal(self):
         return int(ffi.lib().mse_index_ntotal(self._h))
 
-    def search(self, query, k):
-        """labels == -1 marks an empty slot (main.rs:908: `id.get()?`)."""
+    def search(self, query, k, allow=None):
+        """labels == -1 marks an empty slot (main.rs:908: `id.get()?`).  allow: a RowFilter or a boolean row mask -- the search
+        over those rows only (rows added after the filter was made are excluded)."""
         q = np.ascontiguousarray(query, np.float32).reshape(-1, self.d)
         nq = q.shape[0]
         dist = np.empty((nq, k), np.float32)
         lab = np.empty((nq, k), np.int64)
-        check(ffi.lib().mse_index_search(self._h, _p(q, C.c_float), nq, k, _p(dist, C.c_float), _p(lab, C.c_int64)),
-              "index.search")
+        if allow is None:
+            check(ffi.lib().mse_index_search(self._h, _p(q, C.c_float), nq, k, _p(dist, C.c_float), _p(lab, C.c_int64)),
+                  "index.search")
+            return SearchResult(dist, lab)
+        f, owned = RowFilter.wrap(allow)
+        try:
+            check(ffi.lib().mse_index_search_filtered(self._h, f._h, _p(q, C.c_float), nq, k, _p(dist, C.c_float), _p(lab, C.c_int64)),
+                  "index.search")
+        finally:
+            if owned:
+                f.close()
         return SearchResult(dist, lab)
 
     def stats(self):

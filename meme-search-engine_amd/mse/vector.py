@@ -110,6 +110,56 @@ class VectorList:
             pass
 
 
+class RowFilter:
+    """Allowed-row set of the filtered search (mse_filter): `allowed` is a boolean array of n_rows entries, or an integer array of
+    row ids (duplicates allowed; then n_rows is required).  The bitmap lives on the current device and is immutable.  len() is
+    n_rows; .count the allowed rows."""
+
+    def __init__(self, allowed, n_rows=None):
+        a = np.asarray(allowed)
+        if a.dtype == np.bool_:
+            a = a.reshape(-1)
+            if n_rows is not None and n_rows != a.size:
+                raise ValueError("a boolean filter has one entry per row: n_rows must be its length")
+            bits = np.packbits(a, bitorder="little")
+            self._h = check_ptr(ffi.lib().mse_filter_from_bits(_p(bits, C.c_uint8), a.size), "mse_filter_from_bits")
+        elif np.issubdtype(a.dtype, np.integer):
+            if n_rows is None:
+                raise ValueError("a filter made from row ids needs n_rows")
+            a = a.reshape(-1)
+            if a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF):
+                raise ValueError("row ids must be in 0 .. 2**32 - 1")
+            ids = np.ascontiguousarray(a, np.uint32)
+            self._h = check_ptr(ffi.lib().mse_filter_from_ids(_p(ids, C.c_uint32), ids.size, int(n_rows)), "mse_filter_from_ids")
+        else:
+            raise TypeError("allowed must be a boolean mask or an integer id array")
+
+    @classmethod
+    def wrap(cls, allow):
+        """(filter, owned): a RowFilter as it is, anything else made into one (and owned by the caller, to close)."""
+        if isinstance(allow, RowFilter):
+            return allow, False
+        return cls(allow), True
+
+    def __len__(self):
+        return int(ffi.lib().mse_filter_len(self._h))
+
+    @property
+    def count(self):
+        return int(ffi.lib().mse_filter_count(self._h))
+
+    def close(self):
+        if self._h:
+            ffi.lib().mse_filter_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Searcher:
     """Per-thread scratch + stream (reference `Scratch`: lib.rs:157-175, query_disk_index.rs:116-123)."""
 
@@ -134,21 +184,41 @@ class Searcher:
         return {"kernel_ms": out[0] / 1e3, "launches": int(out[1]), "queries": int(out[2]), "rows_scored": int(out[3]),
                 "nodes_fetched": int(out[4]), "adc_scored": int(out[5]), "iterations": int(out[6]), "iterations_replayed": int(out[7])}
 
-    def bruteforce_topk(self, queries, k, mode=MODE_AUTO):
+    def bruteforce_topk(self, queries, k, mode=MODE_AUTO, allow=None):
         """Brute-force scan + ranking of `evaluate` (query_disk_index.rs:262-273) for a query batch.
-        Returns (scores int64 [nq,k], ids uint32 [nq,k])."""
+        Returns (scores int64 [nq,k], ids uint32 [nq,k]).  allow: a RowFilter or a boolean row mask -- top-k over those rows only."""
         d = self.vecs.d_emb
         q = _bits(queries).reshape(-1, d)
         nq = q.shape[0]
         scores = np.empty((nq, k), np.int64)
         ids = np.empty((nq, k), np.uint32)
-        check(ffi.lib().mse_bruteforce_topk_f16(self._h, _p(q, C.c_uint16), nq, k, mode, _p(scores, C.c_int64),
-                                                _p(ids, C.c_uint32)), "bruteforce_topk")
+        if allow is None:
+            check(ffi.lib().mse_bruteforce_topk_f16(self._h, _p(q, C.c_uint16), nq, k, mode, _p(scores, C.c_int64),
+                                                    _p(ids, C.c_uint32)), "bruteforce_topk")
+            return scores, ids
+        f, owned = RowFilter.wrap(allow)
+        try:
+            check(ffi.lib().mse_bruteforce_topk_filtered_f16(self._h, f._h, _p(q, C.c_uint16), nq, k, mode, _p(scores, C.c_int64),
+                                                             _p(ids, C.c_uint32)), "bruteforce_topk")
+        finally:
+            if owned:
+                f.close()
         return scores, ids
 
-    def bruteforce_topk_dev(self, queries_dev, nq, k, scores_dev, ids_dev, mode=MODE_AUTO, id_offset=0):
-        check(ffi.lib().mse_bruteforce_topk_f16_dev(self._h, queries_dev, nq, k, mode, id_offset, scores_dev, ids_dev),
-              "bruteforce_topk_dev")
+    def bruteforce_topk_dev(self, queries_dev, nq, k, scores_dev, ids_dev, mode=MODE_AUTO, id_offset=0, allow=None):
+        if allow is None:
+            check(ffi.lib().mse_bruteforce_topk_f16_dev(self._h, queries_dev, nq, k, mode, id_offset, scores_dev, ids_dev),
+                  "bruteforce_topk_dev")
+            return
+        f, owned = RowFilter.wrap(allow)
+        try:
+            check(ffi.lib().mse_bruteforce_topk_filtered_f16_dev(self._h, f._h, queries_dev, nq, k, mode, id_offset, scores_dev,
+                                                                 ids_dev), "bruteforce_topk_dev")
+            if owned:   # the call is asynchronous on the searcher's stream: the filter must outlive it
+                check(ffi.lib().mse_device_synchronize(), "bruteforce_topk_dev")
+        finally:
+            if owned:
+                f.close()
 
     def merge_topk_dev(self, gathered_scores_dev, gathered_ids_dev, n_shards, nq, k, out_scores_dev, out_ids_dev):
         """k-way merge of all-gathered [n_shards][nq][k] shard results (device pointers)."""
@@ -211,14 +281,24 @@ class Dispatcher:
         self.vecs = vecs
         self._h = check_ptr(ffi.lib().mse_dispatcher_new(vecs._h, max_queries_per_pass, max_wait_us), "mse_dispatcher_new")
 
-    def search(self, queries, k):
+    def search(self, queries, k, allow=None):
+        """allow: a RowFilter -- requests share a pass only with requests of the same filter object."""
         d = self.vecs.d_emb
         q = _bits(queries).reshape(-1, d)
         nq = q.shape[0]
         scores = np.empty((nq, k), np.int64)
         ids = np.empty((nq, k), np.uint32)
-        check(ffi.lib().mse_dispatcher_topk_f16(self._h, _p(q, C.c_uint16), nq, k, _p(scores, C.c_int64), _p(ids, C.c_uint32)),
-              "dispatcher.search")
+        if allow is None:
+            check(ffi.lib().mse_dispatcher_topk_f16(self._h, _p(q, C.c_uint16), nq, k, _p(scores, C.c_int64), _p(ids, C.c_uint32)),
+                  "dispatcher.search")
+            return scores, ids
+        f, owned = RowFilter.wrap(allow)
+        try:
+            check(ffi.lib().mse_dispatcher_topk_filtered_f16(self._h, f._h, _p(q, C.c_uint16), nq, k, _p(scores, C.c_int64),
+                                                             _p(ids, C.c_uint32)), "dispatcher.search")
+        finally:
+            if owned:
+                f.close()
         return scores, ids
 
     def stats(self):
