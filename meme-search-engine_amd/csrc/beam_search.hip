@@ -48,12 +48,34 @@ struct BeamArgs {
     uint32_t* vis_ids; long long* vis_scores; size_t vis_cap; uint32_t* n_visited;
     uint32_t* cmps; uint32_t* pq_cmps; uint32_t* err;
     unsigned long long* totals;   // optional (mse_searcher_beam_timing): [0] rows scored exactly, [1] nodes fetched, [2] ADC-scored neighbours
-    int hash_slots;   // LDS table of a beam iteration's neighbour ids: power of two >= 2 x p_cap
+    int hash_slots;   // LDS table of a beam iteration's neighbour ids: power of two >= 2 x p_cap (also holds p_cap i64 scores)
     int fill_vis;   // fused request path: slots of the visited arrays past n_visited are set to (ID_NONE, INT64_MIN) for the device top-k
     // small-batch entry step (entry_top1_rows_kernel): the per-chunk bests [chunk][query] are reduced HERE, by the search's first wave,
     // instead of by a launch of their own (a dependent launch costs ~35 us in a pass of ~280); null = start nodes in `starts`
     const long long* entry_psc; const uint32_t* entry_prow; const uint32_t* entry_ids; int entry_chunks, entry_nq;
 };
+
+// beam_search_kernel's dynamic LDS, byte offsets in carving order: distance table (ADC scoring) | query (exact scoring) | list scores |
+// pre-buffer scores | list ids | visited flags (one byte each) | pre-buffer ids | ranks | first-position table.  The kernel carves by
+// it and the host sizes the launch by it, so the two cannot drift apart.  Every region starts on 8 bytes: the first-position table is
+// also read as i64 scores (s_lsc), and an L whose flags end at 4 mod 8 used to leave it misaligned (L = 12, 100, 300, ...).
+struct BeamLds {
+    uint32_t q, nb_sc, pre_sc, nb_id, nb_vis, pre_id, rank, hash, bytes;   // (LDS offsets: 32 bits are plenty)
+};
+__host__ __device__ inline BeamLds beam_lds(bool adc, uint32_t d, uint32_t L, uint32_t p_cap, uint32_t hash_slots) {
+    auto up8 = [](uint32_t x) { return (x + 7u) & ~7u; };
+    BeamLds o;
+    o.q = adc ? 65536u : 0u;
+    o.nb_sc = o.q + (adc ? 0u : (d * 2 + 15u) & ~15u);
+    o.pre_sc = up8(o.nb_sc + L * 8);
+    o.nb_id = up8(o.pre_sc + p_cap * 8);
+    o.nb_vis = up8(o.nb_id + L * 4);
+    o.pre_id = up8(o.nb_vis + L);
+    o.rank = up8(o.pre_id + p_cap * 4);
+    o.hash = up8(o.rank + p_cap * 4);
+    o.bytes = o.hash + hash_slots * 4;
+    return o;
+}
 
 // THREADS = 256: four waves per query (wave 0 walks the list, all four score and merge) -- needed when the 64 KiB distance table of
 // a query sits in LDS (two queries per CU either way) and for the longest lists (4 x THREADS list entries / pre-buffer entries).
@@ -68,27 +90,29 @@ template <int THREADS, bool ADC>
 __global__ __launch_bounds__(THREADS, THREADS == 64 ? 4 : 1) void beam_search_kernel(BeamArgs a) {
     constexpr bool EXACT = !ADC;   // the call's disable_pq
     constexpr int BS_THREADS = THREADS;
+    // the merge places up to 4 newcomers and moves up to 4 list entries per thread; the one-wave form is launched only for search
+    // lists and pre-buffers of at most 256 (search_launch)
+    static_assert(THREADS == 64 || (4 * THREADS >= BS_BEAM_MAX * BS_DEG_MAX && 4 * THREADS >= BS_LMAX), "merge must cover the pre-buffer and the list");
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lut_bytes = EXACT ? 0 : 65536;   // the distance table is only needed when neighbours are scored by ADC
+    // the distance table is only needed when neighbours are scored by ADC; the list is sized by this call's search_list and the
+    // pre-buffer by its beam width, so that the usual settings (L = 200, beam 4) leave room for two workgroups per CU next to their
+    // 64 KiB tables, eight without tables
+    const size_t p_cap = (size_t)a.p_cap;
+    const BeamLds ly = beam_lds(ADC, (uint32_t)a.d, (uint32_t)a.L, (uint32_t)a.p_cap, (uint32_t)a.hash_slots);
     float* s_lut = reinterpret_cast<float*>(smem);
     // ADC-scored searches (64 KiB of table per query) score only the few FETCHED nodes exactly: their query stays in global memory
     // (L2-resident, four rows per iteration read it), so that two workgroups fit a CU up to search lists of ~760 (round 6; with the
     // query in LDS and 4-byte visited flags the second workgroup was lost above L = 480: 143 k queries/s at L = 400 against 55 k at 600)
-    const int q_bytes = EXACT ? ((a.d * 2 + 15) & ~15) : 0;
-    const uint16_t* const s_q = reinterpret_cast<const uint16_t*>(smem + lut_bytes);   // exact scoring: the query in LDS
-    const uint16_t* const g_q = a.queries + (size_t)blockIdx.x * a.d;                   // ADC scoring: the query where it lies
+    const uint16_t* const s_q = reinterpret_cast<const uint16_t*>(smem + ly.q);   // exact scoring: the query in LDS
+    const uint16_t* const g_q = a.queries + (size_t)blockIdx.x * a.d;             // ADC scoring: the query where it lies
     // (two call sites per use, so that each inlined copy of the dot product knows its address space: LDS reads stay ds_read)
-    char* p = smem + lut_bytes + q_bytes;
-    // the list is sized by this call's search_list and the pre-buffer by its beam width, so that the usual settings
-    // (L = 200, beam 4) leave room for two workgroups per CU next to their 64 KiB tables, eight without tables
-    const size_t l_cap = (size_t)a.L, p_cap = (size_t)a.p_cap;
-    long long* nb_sc = reinterpret_cast<long long*>(p); p += l_cap * 8;
-    long long* pre_sc = reinterpret_cast<long long*>(p); p += p_cap * 8;
-    uint32_t* nb_id = reinterpret_cast<uint32_t*>(p); p += l_cap * 4;
-    uint8_t* nb_vis = reinterpret_cast<uint8_t*>(p); p += (l_cap + 3) & ~(size_t)3;   // one byte per entry
-    uint32_t* pre_id = reinterpret_cast<uint32_t*>(p); p += p_cap * 4;
-    int* s_rank = reinterpret_cast<int*>(p); p += p_cap * 4;
-    uint32_t* s_hash = reinterpret_cast<uint32_t*>(p);   // [hash_slots]: first positions of the ids of one beam iteration's lists
+    long long* nb_sc = reinterpret_cast<long long*>(smem + ly.nb_sc);
+    long long* pre_sc = reinterpret_cast<long long*>(smem + ly.pre_sc);
+    uint32_t* nb_id = reinterpret_cast<uint32_t*>(smem + ly.nb_id);
+    uint8_t* nb_vis = reinterpret_cast<uint8_t*>(smem + ly.nb_vis);   // one byte per entry
+    uint32_t* pre_id = reinterpret_cast<uint32_t*>(smem + ly.pre_id);
+    int* s_rank = reinterpret_cast<int*>(smem + ly.rank);
+    uint32_t* s_hash = reinterpret_cast<uint32_t*>(smem + ly.hash);   // [hash_slots]: first positions of the ids of one beam iteration's lists
     __shared__ int s_len, s_next, s_npts, s_npre, s_abort, s_nlive;
     __shared__ uint32_t s_pts[BS_BEAM_MAX];
     __shared__ int s_seg[BS_BEAM_MAX];
@@ -108,7 +132,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 64 ? 4 : 1) void beam_search_ke
             reinterpret_cast<float4*>(s_lut)[e] = reinterpret_cast<const float4*>(a.luts + qi * 16384)[e];
     if (EXACT)
         for (int e = tid; e < a.d / 8; e += BS_THREADS)
-            reinterpret_cast<uint4*>(smem + lut_bytes)[e] = reinterpret_cast<const uint4*>(a.queries + qi * a.d)[e];
+            reinterpret_cast<uint4*>(smem + ly.q)[e] = reinterpret_cast<const uint4*>(a.queries + qi * a.d)[e];
     if (tid < BS_DESC_MAX) s_scales[tid] = (use_bias && tid < a.n_desc) ? a.scales[qi * a.n_desc + tid] : 0.0f;
     uint32_t start_by_entry = 0;
     if (a.entry_psc && wave == 0) {   // the best chunk of the entry step: larger score, lower row on ties
@@ -198,12 +222,18 @@ __global__ __launch_bounds__(THREADS, THREADS == 64 ? 4 : 1) void beam_search_ke
         uint32_t* const s_fresh = s_cat + p_cap;                        // [p_cap] 1 = goes into the pre-buffer
         for (int e = tid; e < a.hash_slots; e += BS_THREADS) s_hash[e] = 0xffffffffu;
         // ADC-scored searches: the adjacency entries wait in registers while wave 0 gathers the fetched rows, so that both round trips
-        // are in flight together (the latency-bound form: 6.5 us of a 17 us iteration were these two, one after the other)
-        constexpr int ADJ_PER = ADC ? (BS_BEAM_MAX * 64 + BS_THREADS - 1) / BS_THREADS : 1;
-        [[maybe_unused]] uint32_t nb_r[ADJ_PER], dg_r[ADJ_PER];
+        // are in flight together (the latency-bound form: 6.5 us of a 17 us iteration were these two, one after the other).  Registers
+        // hold the slots of a beam of 8 nodes of degree 64 (ADJ_REG per thread); the slots past them -- merged indexes: up to 8 x 128 --
+        // are loaded and written once the registers are drained (ADJ_PER per thread in all).  Every slot must be written: s_cat is read
+        // below as node ids.  (All 1024 slots in registers took the four-wave kernel past 256 registers, one workgroup per CU instead of
+        // two; holding it to two by its launch bounds cost 7-10 % of the ADC-scored searches at beam 4.)
+        constexpr int ADJ_REG = ADC ? (BS_BEAM_MAX * 64 + BS_THREADS - 1) / BS_THREADS : 1;
+        constexpr int ADJ_PER = ADC ? (BS_BEAM_MAX * BS_DEG_MAX + BS_THREADS - 1) / BS_THREADS : 1;
+        static_assert(!ADC || ADJ_PER * BS_THREADS >= BS_BEAM_MAX * BS_DEG_MAX, "ADC adjacency staging must cover beam x max_deg slots");
+        [[maybe_unused]] uint32_t nb_r[ADJ_REG], dg_r[ADJ_REG];
         if constexpr (ADC) {
 #pragma unroll
-            for (int i = 0; i < ADJ_PER; i++) {
+            for (int i = 0; i < ADJ_REG; i++) {
                 const int e = tid + i * BS_THREADS;
                 nb_r[i] = 0xffffffffu; dg_r[i] = 0u;
                 if (e < ncat) {
@@ -239,12 +269,27 @@ __global__ __launch_bounds__(THREADS, THREADS == 64 ? 4 : 1) void beam_search_ke
         }
         if constexpr (ADC) {
 #pragma unroll
-            for (int i = 0; i < ADJ_PER; i++) {
+            for (int i = 0; i < ADJ_REG; i++) {
                 const int e = tid + i * BS_THREADS;
                 if (e < ncat) {
                     const int pos = e - (e / md) * md;
                     uint32_t nb = nb_r[i];
                     if ((uint32_t)pos >= dg_r[i]) nb = 0xffffffffu;
+                    else if (nb >= a.n) { nb = 0xffffffffu; atomicOr(a.err, 1u); }
+                    s_cat[e] = nb;
+                }
+            }
+            // the slots past the registers' (an iteration of more than 8 x 64 slots), once the registers are free again
+            if (ncat > ADJ_REG * BS_THREADS) {
+#pragma unroll 1
+                for (int i = ADJ_REG; i < ADJ_PER; i++) {
+                    const int e = tid + i * BS_THREADS;
+                    if (e >= ncat) break;
+                    const int j = e / md, pos = e - j * md;
+                    const uint32_t pt = s_pts[j];
+                    const uint32_t dg = a.deg[pt];
+                    uint32_t nb = a.adj[(size_t)pt * md + pos];
+                    if ((uint32_t)pos >= dg) nb = 0xffffffffu;
                     else if (nb >= a.n) { nb = 0xffffffffu; atomicOr(a.err, 1u); }
                     s_cat[e] = nb;
                 }
@@ -976,10 +1021,7 @@ int search_launch(SearchRun& r) {
     size_t hash_slots = 64;
     while (hash_slots < 2 * p_cap) hash_slots *= 2;
     a.hash_slots = (int)hash_slots;
-    // (beam_search_kernel's carving: table | query (exact scoring only) | list scores, pre-buffer scores, list ids, visited flags (one
-    // byte each), pre-buffer ids, ranks | first-position table)
-    const size_t lds = (in.disable_pq ? 0 : 65536) + (in.disable_pq ? ((d * 2 + 15) & ~(size_t)15) : 0) + L * 12 + ((L + 3) & ~(size_t)3) +
-                       p_cap * 16 + hash_slots * 4;
+    const size_t lds = beam_lds(!in.disable_pq, (uint32_t)d, (uint32_t)L, (uint32_t)p_cap, (uint32_t)hash_slots).bytes;   // beam_search_kernel's carving
     static const bool wide_only = MSE_DEV_KNOB("MSE_BEAM_FOUR_WAVES");   // developer library: the four-wave form for every search
     // one wave per query once the batch fills the chip on its own (16 queries per CU); a smaller batch is latency-bound, and four waves
     // finish a search sooner (round 5, scripts/beam_latency_probe.py, hard set: 64 queries at L = 12 0.40 ms against 0.98, at L = 200

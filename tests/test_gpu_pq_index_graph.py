@@ -830,7 +830,9 @@ def test_long_batches_go_through_in_pieces(gpu, mse, orc, monkeypatch):
 @pytest.mark.parametrize("beamwidth,disable_pq", [(4, False), (8, True)])
 def test_device_resident_beam_search_wide_lists(gpu, mse, orc, beamwidth, disable_pq):
     """Merged indexes carry the union of a point's lists from its shards -- up to 2 R = 128 neighbours (dump_processor.rs:282-291).
-    Lists of up to 100 ids, with an id repeated across the two 64-neighbour rounds, beam 8 x 100 newcomers per iteration."""
+    Lists of up to 100 ids, with an id repeated across the two 64-neighbour rounds: beam 4 x 100 slots per iteration with ADC scoring,
+    beam 8 x 100 exactly scored.  ADC-scored iterations of more than 512 slots (beyond the kernel's register staging) up to 8 x 128,
+    and the rest of the parameter range, are in test_gpu_beam_envelope.py."""
     rng = np.random.default_rng(23)
     n, deg, L, nq = 2500, 100, 80, 7
     x = clustered_rows(orc, n, n_centres=10)
