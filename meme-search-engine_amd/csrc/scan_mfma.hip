@@ -320,6 +320,23 @@ __global__ __launch_bounds__(W * 64) void scan_mfma_kernel(const uint16_t* __res
 // in-order vmcnt queue than the query pieces the wait is counted for).
 // MF = 16: v_mfma_f32_16x16x32_f16; MF = 32: v_mfma_f32_32x32x16_f16 (2 x 4 tiles of 32 x 32, 16 accumulators each) over the
 // same LDS images.
+//
+// BN = queries per pass: 256, or 320 (MF = 16, S = 2 only): a wave owns 64 rows x 160 queries (4 x 10 tiles, 160 accumulators) and
+// reads 8 A + 20 B fragments per K block where the 1-D <2,20> kernel reads 4 + 40 for the same 80 MFMAs (224 against 352 KiB of LDS
+// reads per K block per CU).  LDS: 2 x 40 KiB of query tiles + 4 row groups x 2 stages x 8 KiB = 144 KiB, as the 1-D kernel.
+// The two-stage ring differs from the 1-D kernel's in one thing.  There a wave consumes only rows it fetched itself, so its own
+// vmcnt(0) at the top of an iteration is enough.  Here half of the block a wave consumes next was fetched by its partner wave, and
+// only a barrier AFTER the partner's wait publishes it: the closing wait of an iteration is vmcnt(0), not vmcnt(4), and nothing is
+// waited for at the top.  Block kb + 1 and query tile kb + 1 are therefore both issued and landed inside iteration kb (their
+// buffers are free from its first instruction: both were last read in iteration kb - 1, which ended in a barrier), and the row
+// pieces, which come from HBM, go FIRST and close together (in front of MFMA groups 1, 2, 3, 4), the query pieces, L2 hits, after them
+// (6, 8, .. 14), so that the last piece has six MFMA groups of flight before the closing wait.
+// MEASURED (1e8 x 1152 rows, one process, arms alternated, six rounds of 3 s, profiles/scan_320_2d_ab.txt), scan kernel / queries/s:
+// 1-D <2,20> 70.35 ms / 4 483 | this schedule 68.05 ms / 4 632 (+3.3 %, in every round) | rows first, a piece in front of every other
+// group (1 .. 17; PROF = 5) 69.80 ms / 4 518 | queries first (PROF = 4) 73.08 ms / 4 317 against 70.73 / 4 459 for <2,20> on that box:
+// with everything due inside one iteration, what is issued late is waited for.
+// Code object: register and scratch figures at launch_scan_mfma's 320-query branch.  The masked form (filtered search) spills two
+// registers with this order and keeps the every-other-group one.
 typedef float float16v __attribute__((ext_vector_type(16)));
 
 #ifdef MSE_DEV_KERNELS
@@ -329,15 +346,19 @@ __device__ unsigned long long g_scan_prof[4];
 __device__ __forceinline__ uint32_t memtime() { return (uint32_t)__builtin_amdgcn_s_memtime(); }   // deltas fit 32 bits
 #endif
 
-template <int S, int MF, int PROF = 0, typename... Mask>
+template <int S, int MF, int PROF = 0, int BN = 256, typename... Mask>
 __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __restrict__ base, size_t n_rows, int d,
                                                              const uint4* __restrict__ packed_ro,
                                                              float* __restrict__ gmax, int nq_pad, size_t n_tiles, uint32_t y_packed, uint32_t y_cols,
                                                              Mask... mask) {
     static_assert(sizeof...(Mask) == 0 || (MF == 16 && PROF == 0), "the masked form is the product kernel's");
-    constexpr int BN = 256;
+    static_assert(BN == 256 || (BN == 320 && MF == 16 && S == 2), "320 queries: 16x16x32 tiles on the two-stage ring only");
+    constexpr int HALF = BN / 2;             // queries of one query half
     constexpr int QT_BYTES = BN * 128;
-    constexpr int QI = BN / 64;
+    constexpr int QI = BN / 64;              // DMA pieces per wave per query tile: 8 waves x QI x 64 lanes = the tile's BN x 8 slots
+    constexpr bool XF = S == 2 && PROF != 4; // two-stage ring: row pieces FIRST (see the closing wait); PROF = 4: query pieces first;
+                                             // PROF = 5: rows first, one piece in front of every other MFMA group as in the S = 3 form
+    constexpr int CLOSE = S == 2 ? 0 : 4;    // DMAs that may still fly at the closing barrier
     constexpr int RG_BYTES = 64 * 128;       // one K block of a row group
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
@@ -384,7 +405,7 @@ __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __r
     const int g = MF == 16 ? (lane >> 4) : (lane >> 5);
     const int swz = (i >> 1) & 7;
     constexpr int NKS = MF == 16 ? 2 : 4;          // k steps per K block
-    constexpr int NRT = 64 / MF, NCTW = 128 / MF;  // row / column tiles of the wave
+    constexpr int NRT = 64 / MF, NCTW = HALF / MF; // row / column tiles of the wave
     constexpr int NACC = MF == 16 ? 4 : 16;
     typedef typename std::conditional<MF == 16, float4v, float16v>::type accv;
 
@@ -419,18 +440,18 @@ __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __r
                 const char* const qsrc = packed + (size_t)kq * QT_BYTES;
                 char* const qdst = qbase + (buf ^ 1) * QT_BYTES + wave * (QI * 1024);
                 auto issue_piece = [&](int p) {
-                    if (p < QI) dma16(qsrc + p * 1024, qdst + p * 1024);
-                    else dma16((x_next ? rn[p - QI] : rp[p - QI]) + xoff, xdst + (p - QI) * 1024);
+                    const int pq = XF ? p - 4 : p, px = XF ? p : p - QI;
+                    if (XF ? p >= 4 : p < QI) dma16(qsrc + pq * 1024, qdst + pq * 1024);
+                    else dma16((x_next ? rn[px] : rp[px]) + xoff, xdst + px * 1024);
                 };
-                if (S == 2) vm_wait<0>();
 
                 const u32x4* xs = reinterpret_cast<const u32x4*>(xbase + j * RG_BYTES) + i * 8;
-                const u32x4* qt = reinterpret_cast<const u32x4*>(qbase + buf * QT_BYTES) + (qh * 128 + i) * 8;
+                const u32x4* qt = reinterpret_cast<const u32x4*>(qbase + buf * QT_BYTES) + (qh * HALF + i) * 8;
                 auto slot = [&](int ks) { return (MF == 16 ? (4 * ks + g) : (2 * ks + g)) ^ swz; };
                 half8 a[2][NRT];   // A fragments of k step ks live in a[ks & 1]; the next k step's are read while this one multiplies
 #pragma unroll
                 for (int rt = 0; rt < NRT; rt++) a[0][rt] = as_half8(xs[rt * (MF * 8) + slot(0)]);
-                constexpr int NT = NKS * NCTW;   // B fragments per K block: 16 in both forms
+                constexpr int NT = NKS * NCTW;   // B fragments per K block: 16 at 256 queries in both forms, 20 at 320
                 u32x4 bq[3];
                 bq[0] = qt[0 * (MF * 8) + slot(0)];
                 bq[1] = qt[1 * (MF * 8) + slot(0)];
@@ -445,8 +466,15 @@ __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __r
                     __builtin_amdgcn_sched_barrier(0);
                     {
                         constexpr int STEP = NT / (QI + 4);
-                        if (t >= 1 && (t - 1) % STEP == 0 && (t - 1) / STEP < QI + 4) {
-                            issue_piece((t - 1) / STEP);
+                        int pc = -1;   // the DMA piece issued in front of MFMA group t (t is a constant of the unrolled loop)
+                        // row pieces before groups 1-4, query pieces before 6, 8, ...; the masked form keeps the every-other-group
+                        // order of PROF = 5: with the early order it spills two registers (12 B of scratch)
+                        if constexpr (S == 2 && PROF != 4 && PROF != 5 && sizeof...(Mask) == 0) {
+                            if (t >= 1 && t <= 4) pc = t - 1;
+                            else if (t >= 6 && (t - 6) % 2 == 0 && (t - 6) / 2 < QI) pc = 4 + (t - 6) / 2;
+                        } else if (t >= 1 && (t - 1) % STEP == 0 && (t - 1) / STEP < QI + 4) pc = (t - 1) / STEP;
+                        if (pc >= 0) {
+                            issue_piece(pc);
                             __builtin_amdgcn_sched_barrier(0);
                         }
                     }
@@ -462,7 +490,7 @@ __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __r
 #ifdef MSE_DEV_KERNELS
                 if constexpr (PROF == 1) {
                     const uint32_t t0 = memtime();
-                    vm_wait<4>();
+                    vm_wait<CLOSE>();
                     const uint32_t t1 = memtime();
                     __builtin_amdgcn_s_barrier();
                     const uint32_t t2 = memtime();
@@ -470,7 +498,7 @@ __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __r
                 } else
 #endif
                 {
-                    vm_wait<4>();
+                    vm_wait<CLOSE>();
 #ifdef MSE_DEV_KERNELS
                     if constexpr (PROF != 2)   // PROF = 2: timing ablation WITHOUT the barrier (racy, results meaningless)
 #endif
@@ -513,7 +541,7 @@ __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __r
                     for (int r = 1; r < 16; r++) m = fmaxf(m, acc[p][ct][r]);
                     m = fmaxf(m, __shfl_xor(m, 32));
                 }
-                if (g == 0 && group < n_groups) gmax[group * (size_t)nq_pad + qh * 128 + ct * MF + i] = m;
+                if (g == 0 && group < n_groups) gmax[group * (size_t)nq_pad + qh * HALF + ct * MF + i] = m;
             }
         }
 
@@ -727,11 +755,11 @@ int launch_2s(size_t grid, hipStream_t stream, const uint16_t* base, size_t n_ro
 }
 #endif
 
-template <int S, int MF, int PROF = 0, typename... Mask>
+template <int S, int MF, int PROF = 0, int BN = 256, typename... Mask>
 int launch_2d(size_t grid, hipStream_t stream, const uint16_t* base, size_t n_rows, int d, const uint4* packed,
               float* group_max, int nq_pad, Mask... mask) {
-    const size_t lds = 2 * (size_t)(256 * 128) + (size_t)4 * S * 8192;
-    return launch_kernel(scan_mfma2d_kernel<S, MF, PROF, Mask...>, lds, grid, stream, base, n_rows, d, packed, group_max, nq_pad, mask...);
+    const size_t lds = 2 * (size_t)(BN * 128) + (size_t)4 * S * 8192;   // 160 KiB at 256 queries (S = 3), 144 KiB at 320 (S = 2)
+    return launch_kernel(scan_mfma2d_kernel<S, MF, PROF, BN, Mask...>, lds, grid, stream, base, n_rows, d, packed, group_max, nq_pad, mask...);
 }
 
 }  // namespace
@@ -796,6 +824,10 @@ int launch_scan_mfma(const uint16_t* base, size_t n_rows, int d, const uint16_t*
             default: break;
         }
     }
+    // the 320-query pass on the one-dimensional wave split (the product kernel of rounds 4-6) and the 2-D form's other piece orders
+    else if (nq_pad == 320 && v2d == 0) rc = launch_variant<2, 20, 0>(grid, stream, base, n_rows, d, packed, group_max, gs);
+    else if (nq_pad == 320 && v2d == 165) rc = launch_2d<2, 16, 5, 320>(grid, stream, base, n_rows, d, packed, group_max, gs);
+    else if (nq_pad == 320 && v2d == 164) rc = launch_2d<2, 16, 4, 320>(grid, stream, base, n_rows, d, packed, group_max, gs);
     else if (nq_pad == 256 && S == 3 && v2d == 0) rc = launch_variant<3, 16, 0>(grid, stream, base, n_rows, d, packed, group_max, gs);
     else if (nq_pad == 256 && S == 3 && v2d == 161) rc = launch_2d<3, 16, 1>(grid, stream, base, n_rows, d, packed, group_max, gs);
     else if (nq_pad == 256 && S == 3 && v2d == 162) rc = launch_2d<3, 16, 2>(grid, stream, base, n_rows, d, packed, group_max, gs);
@@ -812,9 +844,11 @@ int launch_scan_mfma(const uint16_t* base, size_t n_rows, int d, const uint16_t*
     // the product configurations below, each unmasked or masked (filtered search: the bitmap as two trailing kernel arguments)
     auto run = [&](auto launch) { return mask ? launch(mask, mask_words) : launch(); };
     if (nq_pad == 320) {
-        // 20 column tiles per wave (32 rows x 320 queries, 160 accumulator registers of 252 used: 24 tiles spill and run 2.6x
-        // slower), two-stage row ring: 2 x 40 KiB of query tiles + 8 x 2 x 4 KiB = 144 KiB of LDS.
-        rc = run([&](auto... m) { return launch_variant<2, 20, 0>(grid, stream, base, n_rows, d, packed, group_max, gs, m...); });
+        // 2-D wave split, 64 rows x 160 queries per wave (4 x 10 tiles = 160 accumulator registers; 384 queries per pass spill and
+        // run 2.6x slower), two-stage row ring: 2 x 40 KiB of query tiles + 4 x 2 x 8 KiB = 144 KiB (147 456 B) of LDS.
+        // Code object (hipcc --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage): unmasked 255 VGPRs, masked 256; both 0
+        // spilled, 0 scratch, 2 waves per SIMD.  The 1-D <2,20> kernel this replaced is kept in the developer library (MSE_SCAN_2D=0).
+        rc = run([&](auto... m) { return launch_2d<2, 16, 0, 320>(grid, stream, base, n_rows, d, packed, group_max, gs, m...); });
     } else if (nq_pad == 192) {
         // 12 column tiles on the one-dimensional wave split (32 rows x 192 queries per wave, 96 accumulators): the point between
         // the HBM-bound 128-query pass and the power-bound 256-query pass (profiles/r04_scan_variants.txt)

@@ -17,7 +17,7 @@ for k, name in (("x8", "pq_scan64x4"), ("x4", "pq_scan64x4_four_per_pass"), ("x1
         f = pq[k]["FETCH_SIZE"]; w = pq[k]["WRITE_SIZE"] or [0.0]
         out[name] = {"vectors": 100000000, "algorithmic_bytes_per_launch": 6800000000, "dispatches": len(f),
                      "hbm_read_bytes_per_launch": sum(f) / len(f) * 2048, "hbm_write_bytes_per_launch": sum(w) / len(w) * 1024}
-sc = collect("pmcs_", lambda k: "320" if "scan_mfma_kernel<2, 20" in k else "256" if "scan_mfma2d_kernel" in k else "128" if "scan_mfma_kernel<3, 8" in k else "192" if "scan_mfma_kernel<3, 12" in k else None)
+sc = collect("pmcs_", lambda k: "320" if "scan_mfma_kernel<2, 20" in k or ("scan_mfma2d_kernel" in k and ", 320" in k) else "256" if "scan_mfma2d_kernel" in k else "128" if "scan_mfma_kernel<3, 8" in k else "192" if "scan_mfma_kernel<3, 12" in k else None)
 out["rows"] = 100000000
 out["algorithmic_bytes_per_launch"] = 230400000000
 out["per_pass"] = {}
