@@ -187,8 +187,8 @@ static size_t mfma_call_tile(const mse_base* b, size_t k) {
     const size_t tile = (size_t)mfma_query_tile((int)b->d);
     const size_t n_groups = (b->n + GROUP_ROWS - 1) / GROUP_ROWS;
     size_t fit = ((size_t)256 << 20) / (std::max<size_t>(n_groups, 1) * 4) / tile * tile;
-    // the first round re-scores (k + 8) groups of 32 rows per query: ids + scores of all queries within 1 GiB
-    const size_t per_query = std::min<size_t>(std::max<size_t>(k + 8, 16), TOPK_KMAX) * GROUP_ROWS * 12;
+    // the first round re-scores (k + 8) groups of 32 or 64 rows (mfma_pass) per query: ids + scores of all queries within 1 GiB
+    const size_t per_query = std::min<size_t>(std::max<size_t>(k + 8, 16), TOPK_KMAX) * 64 * 12;
     fit = std::min(fit, ((size_t)1 << 30) / per_query / tile * tile);
     if (fit > 8192 / tile * tile) fit = 8192 / tile * tile;
     return std::max(fit, tile);
@@ -198,6 +198,11 @@ static size_t mfma_call_tile(const mse_base* b, size_t k) {
 // maxima are over allowed rows only (-FLT_MAX for a group without one), candidate expansion drops excluded rows, and the exact
 // fallback is the filtered exact pass; the certificate is unchanged (every allowed row outside the chosen groups is at most its
 // group's masked maximum, and the largest row norm still bounds eps).
+// Rows per group maximum (gr): 64 when every pass of the call is a 320-query pass, whose waves own 64 rows each (mfma_group_rows),
+// else 32.  The certificate does not care -- every row outside the chosen groups is at most its group's maximum, whatever a group is --
+// and the kg0 groups re-scored per query are then twice as many rows.
+// The queries are read where the caller has them: the scan's pack kernel writes the padding of the last pass as zeros, and the norms,
+// the re-score and the widening only ever touch the nq_pass real rows.
 static int mfma_pass(mse_searcher* s, const uint16_t* q_dev, int nq_pass, int k, uint64_t id_offset,
                      int64_t* out_scores, uint32_t* out_ids, size_t out_stride, const mse_filter* f = nullptr) {
     const mse_base* b = s->base;
@@ -209,11 +214,13 @@ static int mfma_pass(mse_searcher* s, const uint16_t* q_dev, int nq_pass, int k,
     const int n_full = nq_pass / tile, rem = nq_pass - n_full * tile;
     const int nq_pad = n_full * tile + (rem ? mfma_pad(rem, d) : 0);
     if (ensure_base_norm(b, st)) return -1;
-    // padded query tile
-    if (s->q_stage.ensure((size_t)nq_pad * d * 2)) return -1;
-    MSE_HIP_TRY(hipMemsetAsync(s->q_stage.p, 0, (size_t)nq_pad * d * 2, st));
-    MSE_HIP_TRY(hipMemcpyAsync(s->q_stage.p, q_dev, (size_t)nq_pass * d * 2, hipMemcpyDeviceToDevice, st));
-    const size_t n_groups = (b->n + GROUP_ROWS - 1) / GROUP_ROWS;
+    if (reinterpret_cast<uintptr_t>(q_dev) & 15) {   // the kernels read query rows in 16-byte pieces: a misaligned array is copied once
+        if (s->q_stage.ensure((size_t)nq_pass * d * 2)) return -1;
+        MSE_HIP_TRY(hipMemcpyAsync(s->q_stage.p, q_dev, (size_t)nq_pass * d * 2, hipMemcpyDeviceToDevice, st));
+        q_dev = s->q_stage.as<uint16_t>();
+    }
+    const int gr = tile == 320 && (!rem || nq_pad - n_full * tile == 320) ? mfma_group_rows(320) : GROUP_ROWS;
+    const size_t n_groups = (b->n + gr - 1) / gr;
     if (s->gmax.ensure(n_groups * (size_t)nq_pad * 4)) return -1;
     // the full passes go out as ONE launch (a small base has few row tiles: its passes fill the chip side by side), then the remainder
     const size_t one_tile_packed = (size_t)(d / 64) * tile * 128;
@@ -221,20 +228,22 @@ static int mfma_pass(mse_searcher* s, const uint16_t* q_dev, int nq_pass, int k,
     const uint32_t* mask = f ? f->words : nullptr;
     const size_t mask_words = f ? f->n_words : 0;
     if (n_full &&
-        launch_scan_mfma(b->dev, b->n, d, s->q_stage.as<uint16_t>(), tile, s->qpacked.p, s->gmax.as<float>(), s->n_cu, st,
-                         s->timing ? s->ev0 : nullptr, s->timing && !rem ? s->ev1 : nullptr, nq_pad, n_full, mask, mask_words)) return -1;
+        launch_scan_mfma(b->dev, b->n, d, q_dev, tile, s->qpacked.p, s->gmax.as<float>(), s->n_cu, st,
+                         s->timing ? s->ev0 : nullptr, s->timing && !rem ? s->ev1 : nullptr, nq_pad, n_full, mask, mask_words, n_full * tile, gr)) return -1;
     if (rem &&
-        launch_scan_mfma(b->dev, b->n, d, s->q_stage.as<uint16_t>() + (size_t)n_full * tile * d, nq_pad - n_full * tile, s->qpacked.p,
+        launch_scan_mfma(b->dev, b->n, d, q_dev + (size_t)n_full * tile * d, nq_pad - n_full * tile, s->qpacked.p,
                          s->gmax.as<float>() + n_full * tile, s->n_cu, st, s->timing && !n_full ? s->ev0 : nullptr,
-                         s->timing ? s->ev1 : nullptr, nq_pad, 1, mask, mask_words)) return -1;
+                         s->timing ? s->ev1 : nullptr, nq_pad, 1, mask, mask_words, rem, gr)) return -1;
     bool timing_pending = s->timing;
     if (s->eps.ensure((size_t)nq_pass * 8) || s->margin.ensure((size_t)nq_pass * 8)) return -1;   // second halves: the widening's compact set
     // |mfma score - exact-order score| <= 2 * gamma_1151 * sum|x_i q_i| <= 1.4e-4 * |x||q|; doubled again
     // because the matrix core's internal rounding is not documented.
-    if (launch_query_eps(s->q_stage.as<uint16_t>(), nq_pass, d, b->norm_bits_dev, 2.8e-4f, s->eps.as<float>(), st))
+    if (launch_query_eps(q_dev, nq_pass, d, b->norm_bits_dev, 2.8e-4f, s->eps.as<float>(), st))
         return -1;
 
-    std::vector<float> margin_h(nq_pass);
+    // the margins come back into pinned memory: a true asynchronous copy, then the one synchronisation that ends the round
+    if (s->margin_pin.ensure((size_t)nq_pass * 4, 4096)) return -1;
+    float* const margin_h = s->margin_pin.as<float>();
     const int kg0 = (int)std::min<size_t>(std::max(k + 8, 16), TOPK_KMAX);
     s->last_widened = 0;
     // One round of: tournament over the group maxima -> the kg best groups' rows re-scored exactly -> exact top-k -> certificate.
@@ -246,11 +255,11 @@ static int mfma_pass(mse_searcher* s, const uint16_t* q_dev, int nq_pass, int k,
         uint32_t* gsel = nullptr;
         LevelRef l0{KEY_F32, gm, 1, (size_t)gm_pad, n_groups, true, gm_pad};
         if (descend(s, l0, nq, kg_eff, &gsel, s->gkeys.p)) return -1;
-        const size_t n_cand = (size_t)kg_eff * GROUP_ROWS;
+        const size_t n_cand = (size_t)kg_eff * gr;
         if (s->cand_ids.ensure((size_t)nq * n_cand * 4) || s->cand_scores.ensure((size_t)nq * n_cand * 8)) return -1;
-        if (f ? launch_expand_groups_masked(gsel, kg_eff, kg_eff, GROUP_ROWS, b->n, f->words, f->n_words, s->cand_ids.as<uint32_t>(), n_cand,
+        if (f ? launch_expand_groups_masked(gsel, kg_eff, kg_eff, gr, b->n, f->words, f->n_words, s->cand_ids.as<uint32_t>(), n_cand,
                                             nq, st)
-              : launch_expand_groups(gsel, kg_eff, kg_eff, GROUP_ROWS, b->n, s->cand_ids.as<uint32_t>(), n_cand, nq, st)) return -1;
+              : launch_expand_groups(gsel, kg_eff, kg_eff, gr, b->n, s->cand_ids.as<uint32_t>(), n_cand, nq, st)) return -1;
         if (launch_score_rows(b->dev, b->n, d, qs, false, s->cand_ids.as<uint32_t>(), (size_t)nq * n_cand, n_cand,
                               s->cand_scores.as<int64_t>(), nullptr, st)) return -1;
         // final exact selection among the re-scored candidates
@@ -262,12 +271,12 @@ static int mfma_pass(mse_searcher* s, const uint16_t* q_dev, int nq_pass, int k,
         if (launch_select(a, st)) return -1;
         if (launch_finalize(s->misc.as<uint32_t>(), s->sel_keys.as<int64_t>(), k, k, nq, id_off, dst_s, dst_i, dst_stride,
                             s->gkeys.as<float>(), kg_eff, kg_eff, n_groups, eps_dev, margin_dev, st)) return -1;
-        MSE_HIP_TRY(hipMemcpyAsync(margin_h.data(), margin_dev, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+        MSE_HIP_TRY(hipMemcpyAsync(margin_h, margin_dev, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
         MSE_HIP_TRY(hipStreamSynchronize(st));
         s->last_max_groups = std::max<uint32_t>(s->last_max_groups, (uint32_t)kg_eff);
         return 0;
     };
-    if (round(s->gmax.as<float>(), nq_pad, s->q_stage.as<uint16_t>(), nq_pass, kg0, s->eps.as<float>(), s->margin.as<float>(), out_scores,
+    if (round(s->gmax.as<float>(), nq_pad, q_dev, nq_pass, kg0, s->eps.as<float>(), s->margin.as<float>(), out_scores,
               out_ids, out_stride, id_offset)) return -1;
     if (timing_pending) {
         float ms = 0.0f;
@@ -288,7 +297,7 @@ static int mfma_pass(mse_searcher* s, const uint16_t* q_dev, int nq_pass, int k,
     uint32_t* idx_dev = s->widx.as<uint32_t>();
     uint8_t* take_dev = reinterpret_cast<uint8_t*>(idx_dev + nb);
     MSE_HIP_TRY(hipMemcpyAsync(idx_dev, bad.data(), (size_t)nb * 4, hipMemcpyHostToDevice, st));
-    if (launch_gather_rows16(s->q_stage.p, (size_t)d * 2, idx_dev, nb, s->wq.p, st)) return -1;
+    if (launch_gather_rows16(q_dev, (size_t)d * 2, idx_dev, nb, s->wq.p, st)) return -1;
     if (launch_gather_columns(s->gmax.as<float>(), nq_pad, n_groups, idx_dev, nb, s->wg.as<float>(), nbp, st)) return -1;
     float* eps2 = s->eps.as<float>() + nq_pass;
     float* margin2 = s->margin.as<float>() + nq_pass;

@@ -9,7 +9,7 @@ namespace mse {
 constexpr uint32_t ID_NONE = 0xFFFFFFFFu;
 constexpr int TOPK_KMAX = 2048;    // largest k (incl. margin) one selection can return
 constexpr int TOPK_FANOUT = 256;   // children per tournament group
-constexpr int GROUP_ROWS = 32;     // base rows per group maximum written by the MFMA scan
+constexpr int GROUP_ROWS = 32;     // base rows per group maximum written by the MFMA scan (64 on the 320-query pass: mfma_group_rows)
 
 // ---- scan_exact.hip ------------------------------------------------------------------------
 // ids != nullptr (filtered search): score rows ids[0 .. n_rows) instead of rows 0 .. n_rows; scores stay at the list positions
@@ -151,10 +151,14 @@ int launch_scan_mfma(const uint16_t* base, size_t n_rows, int d, const uint16_t*
                      void* packed_scratch, float* group_max, int n_cu, hipStream_t stream,
                      hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr, int gm_stride = 0 /* row stride of group_max; 0 = nq_pad */,
                      int n_pass = 1 /* passes in this launch: consecutive nq_pad-row query tiles, consecutive column ranges of group_max */,
-                     const uint32_t* mask = nullptr, size_t mask_words = 0 /* filtered search: one bitmap word per 32-row group */);
+                     const uint32_t* mask = nullptr, size_t mask_words = 0 /* filtered search: one bitmap word per 32-row group */,
+                     int nq_rows = -1 /* query rows that exist at queries_dev, over all passes; the rest of the last pass is packed as
+                                         zeros.  -1 = all n_pass x nq_pad */,
+                     int group_rows = GROUP_ROWS /* base rows per written maximum: 32, or 64 (nq_pad 320 only) */);
                      // events bracket the scan kernel only
 size_t mfma_packed_bytes(int d);
 int mfma_query_tile(int d);  // most queries one pass handles at width d (320 or 256)
 int mfma_pad(int nq, int d);   // padded query count of a pass of nq <= 256 queries: 128, 192 or 256
+int mfma_group_rows(int nq_pad);   // rows per group maximum a search pass of that width asks for: 64 at 320 queries, else 32
 
 }  // namespace mse

@@ -26,7 +26,8 @@
 //     barrier per 64-element K block.  The tile is shared by 256 rows, so L2->LDS query traffic is BN/256 of the
 //     HBM traffic (it competes with the HBM stream for the CU's outstanding-miss slots).
 //   - epilogue per 32-row group: max over the rows of each query column -> group_max[group][q]
-//     (the level-0 array of the selection tournament).  4 bytes written per 32*2304 bytes read.
+//     (the level-0 array of the selection tournament).  4 bytes written per 32*2304 bytes read.  (The 320-query kernel's search
+//     passes write one maximum per 64 rows, the rows of one wave: scan_mfma2d_kernel GR = 64.)
 // Roofline: HBM.  Algorithmic bytes = 2*d per base row per pass of <= 128 queries; PMC FETCH_SIZE (x2 on
 // gfx950, KiB) = 1.007 x that.
 //
@@ -76,18 +77,21 @@ constexpr int W = 8;              // waves per workgroup
 constexpr int TILE_ROWS = 32 * W;
 
 // packed[kb][q][slot ^ ((q>>1)&7)] = 16-byte slot `slot` of K block kb of query q   (bn queries per tile)
-__global__ void pack_queries_kernel(const uint16_t* __restrict__ queries, int d, int bn, uint4* __restrict__ packed) {
+// Query rows at or past n_rows (counted over all passes of the launch) are the padding of the last pass: they are packed as zeros, so
+// the caller's [n_rows][d] array is read where it lies and needs no padded copy.
+__global__ void pack_queries_kernel(const uint16_t* __restrict__ queries, int d, int bn, int n_rows, uint4* __restrict__ packed) {
     const int nkb = d / KB;
     const int QT_SLOTS = bn * 8;
     const int total = nkb * QT_SLOTS;
     queries += (size_t)blockIdx.y * bn * d;   // batched passes: pass y = the next bn query rows, the next `total` slots
+    n_rows -= blockIdx.y * bn;
     packed += (size_t)blockIdx.y * total;
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
         const int kb = idx / QT_SLOTS;
         const int r = idx % QT_SLOTS;
         const int q = r >> 3, slot_sw = r & 7;
         const int slot = slot_sw ^ ((q >> 1) & 7);
-        packed[idx] = *reinterpret_cast<const uint4*>(queries + (size_t)q * d + kb * KB + slot * 8);
+        packed[idx] = q < n_rows ? *reinterpret_cast<const uint4*>(queries + (size_t)q * d + kb * KB + slot * 8) : uint4{0u, 0u, 0u, 0u};
     }
 }
 
@@ -346,13 +350,14 @@ __device__ unsigned long long g_scan_prof[4];
 __device__ __forceinline__ uint32_t memtime() { return (uint32_t)__builtin_amdgcn_s_memtime(); }   // deltas fit 32 bits
 #endif
 
-template <int S, int MF, int PROF = 0, int BN = 256, typename... Mask>
+template <int S, int MF, int PROF = 0, int BN = 256, int GR = 32, typename... Mask>
 __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __restrict__ base, size_t n_rows, int d,
                                                              const uint4* __restrict__ packed_ro,
                                                              float* __restrict__ gmax, int nq_pad, size_t n_tiles, uint32_t y_packed, uint32_t y_cols,
                                                              Mask... mask) {
     static_assert(sizeof...(Mask) == 0 || (MF == 16 && PROF == 0), "the masked form is the product kernel's");
     static_assert(BN == 256 || (BN == 320 && MF == 16 && S == 2), "320 queries: 16x16x32 tiles on the two-stage ring only");
+    static_assert(GR == 32 || (GR == 64 && MF == 16), "rows per written maximum: 32, or the wave's 64");
     constexpr int HALF = BN / 2;             // queries of one query half
     constexpr int QT_BYTES = BN * 128;
     constexpr int QI = BN / 64;              // DMA pieces per wave per query tile: 8 waves x QI x 64 lanes = the tile's BN x 8 slots
@@ -366,7 +371,7 @@ __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __r
     const int rg = wave >> 1, qh = wave & 1;
     const int nkb = d / KB;
     const size_t row_bytes = (size_t)d * 2;
-    const size_t n_groups = (n_rows + 31) / 32;
+    const size_t n_groups = (n_rows + GR - 1) / GR;
     char* const qbase = smem;
     char* const xbase = smem + 2 * QT_BYTES + rg * (S * RG_BYTES);
     gmax += (size_t)blockIdx.y * y_cols;   // batched passes (launch_scan_mfma n_pass > 1): pass y has its own query tiles and columns
@@ -508,8 +513,8 @@ __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __r
             }
         }
 
-        // epilogue: per query column, max over each 32-row group of this wave (two groups)
-        if constexpr (sizeof...(Mask) != 0) {
+        // epilogue: per query column, max over each 32-row group of this wave (two groups), or over all 64 rows (GR = 64)
+        if constexpr (sizeof...(Mask) != 0 && GR == 32) {
             // acc[2 p + h][ct][r] of lane (i, g) holds row 16 h + 4 g + r of group p (LDS row = row of the row group, src_ptr)
 #pragma unroll
             for (int p = 0; p < 2; p++) {
@@ -524,24 +529,51 @@ __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __r
                     }
             }
         }
-#pragma unroll
-        for (int p = 0; p < 2; p++) {
-            const size_t group = tile * W + rg * 2 + p;
+        if constexpr (GR == 64) {
+            // one maximum per wave and column: the wave's 64 rows are rows 64 (4 tile + rg) .. + 63 of the base.  Rows past the end were
+            // clamped to the last row, which lies in the same 64-row group whenever that group has a row at all.
+            const size_t group = tile * 4 + rg;
+            // masked form: bit 4 rt + r of `allowed` = this lane's row 16 rt + 4 g + r of the wave (acc[rt][.][r]) is an allowed row; an
+            // excluded row enters the maximum as MASKED_OUT (selected here, not written into the accumulators: that form spills)
+            uint32_t allowed = 0xFFFFu;
+            if constexpr (sizeof...(Mask) != 0) {
+                const uint32_t w0 = group_word(group * 2, mask...) >> (4 * g), w1 = group_word(group * 2 + 1, mask...) >> (4 * g);
+                allowed = (w0 & 15u) | ((w0 >> 16 & 15u) << 4) | ((w1 & 15u) << 8) | ((w1 >> 16 & 15u) << 12);
+            }
+            auto av = [&](int rt, int ct, int r) {
+                if constexpr (sizeof...(Mask) != 0) return (allowed >> (4 * rt + r)) & 1u ? acc[rt][ct][r] : MASKED_OUT;
+                else return acc[rt][ct][r];
+            };
 #pragma unroll
             for (int ct = 0; ct < NCTW; ct++) {
-                float m;
-                if constexpr (MF == 16) {
-                    m = fmaxf(fmaxf(acc[2 * p][ct][0], acc[2 * p][ct][1]), fmaxf(acc[2 * p][ct][2], acc[2 * p][ct][3]));
-                    m = fmaxf(m, fmaxf(fmaxf(acc[2 * p + 1][ct][0], acc[2 * p + 1][ct][1]), fmaxf(acc[2 * p + 1][ct][2], acc[2 * p + 1][ct][3])));
-                    m = fmaxf(m, __shfl_xor(m, 16));
-                    m = fmaxf(m, __shfl_xor(m, 32));
-                } else {
-                    m = acc[p][ct][0];
+                float m = fmaxf(fmaxf(av(0, ct, 0), av(0, ct, 1)), fmaxf(av(0, ct, 2), av(0, ct, 3)));
 #pragma unroll
-                    for (int r = 1; r < 16; r++) m = fmaxf(m, acc[p][ct][r]);
-                    m = fmaxf(m, __shfl_xor(m, 32));
-                }
+                for (int rt = 1; rt < 4; rt++)
+                    m = fmaxf(m, fmaxf(fmaxf(av(rt, ct, 0), av(rt, ct, 1)), fmaxf(av(rt, ct, 2), av(rt, ct, 3))));
+                m = fmaxf(m, __shfl_xor(m, 16));
+                m = fmaxf(m, __shfl_xor(m, 32));
                 if (g == 0 && group < n_groups) gmax[group * (size_t)nq_pad + qh * HALF + ct * MF + i] = m;
+            }
+        } else {
+#pragma unroll
+            for (int p = 0; p < 2; p++) {
+                const size_t group = tile * W + rg * 2 + p;
+#pragma unroll
+                for (int ct = 0; ct < NCTW; ct++) {
+                    float m;
+                    if constexpr (MF == 16) {
+                        m = fmaxf(fmaxf(acc[2 * p][ct][0], acc[2 * p][ct][1]), fmaxf(acc[2 * p][ct][2], acc[2 * p][ct][3]));
+                        m = fmaxf(m, fmaxf(fmaxf(acc[2 * p + 1][ct][0], acc[2 * p + 1][ct][1]), fmaxf(acc[2 * p + 1][ct][2], acc[2 * p + 1][ct][3])));
+                        m = fmaxf(m, __shfl_xor(m, 16));
+                        m = fmaxf(m, __shfl_xor(m, 32));
+                    } else {
+                        m = acc[p][ct][0];
+#pragma unroll
+                        for (int r = 1; r < 16; r++) m = fmaxf(m, acc[p][ct][r]);
+                        m = fmaxf(m, __shfl_xor(m, 32));
+                    }
+                    if (g == 0 && group < n_groups) gmax[group * (size_t)nq_pad + qh * HALF + ct * MF + i] = m;
+                }
             }
         }
 
@@ -755,11 +787,11 @@ int launch_2s(size_t grid, hipStream_t stream, const uint16_t* base, size_t n_ro
 }
 #endif
 
-template <int S, int MF, int PROF = 0, int BN = 256, typename... Mask>
+template <int S, int MF, int PROF = 0, int BN = 256, int GR = 32, typename... Mask>
 int launch_2d(size_t grid, hipStream_t stream, const uint16_t* base, size_t n_rows, int d, const uint4* packed,
               float* group_max, int nq_pad, Mask... mask) {
     const size_t lds = 2 * (size_t)(BN * 128) + (size_t)4 * S * 8192;   // 160 KiB at 256 queries (S = 3), 144 KiB at 320 (S = 2)
-    return launch_kernel(scan_mfma2d_kernel<S, MF, PROF, BN, Mask...>, lds, grid, stream, base, n_rows, d, packed, group_max, nq_pad, mask...);
+    return launch_kernel(scan_mfma2d_kernel<S, MF, PROF, BN, GR, Mask...>, lds, grid, stream, base, n_rows, d, packed, group_max, nq_pad, mask...);
 }
 
 }  // namespace
@@ -776,11 +808,27 @@ int mfma_pad(int nq, int d) {
 
 size_t mfma_packed_bytes(int d) { return (size_t)(d / KB) * 320 * 128; }
 
+// rows per group maximum of a pass padded to nq_pad queries: the 320-query kernel's waves own 64 rows each and write one maximum for
+// them; every other kernel writes 32-row groups.  (The developer library keeps 32 while one of its kernel knobs is set: the kernels
+// they select write 32-row groups.)  -DMSE_GROUP_ROWS_320=32 builds the library with 32-row groups everywhere, for an A/B of the group
+// size alone (scripts/step_tail_ab.py compares builds).
+#ifndef MSE_GROUP_ROWS_320
+#define MSE_GROUP_ROWS_320 64
+#endif
+int mfma_group_rows(int nq_pad) {
+#ifdef MSE_DEV_KERNELS
+    if (getenv("MSE_SCAN_2D") || getenv("MSE_SCAN_ABL")) return 32;
+#endif
+    return nq_pad == 320 ? MSE_GROUP_ROWS_320 : 32;
+}
+
 // packed_scratch: mfma_packed_bytes(d) bytes of device scratch owned by the caller (per searcher)
 int launch_scan_mfma(const uint16_t* base, size_t n_rows, int d, const uint16_t* queries_dev, int nq_pad,
                      void* packed_scratch, float* group_max, int n_cu, hipStream_t stream, hipEvent_t ev_begin,
-                     hipEvent_t ev_end, int gm_stride, int n_pass, const uint32_t* mask, size_t mask_words) {
+                     hipEvent_t ev_end, int gm_stride, int n_pass, const uint32_t* mask, size_t mask_words, int nq_rows, int group_rows) {
     if (n_rows == 0) return 0;
+    if (group_rows != 32 && !(group_rows == 64 && nq_pad == 320)) return fail("scan_mfma: 32 rows per group maximum, or 64 on the 320-query pass");
+    if (nq_rows < 0) nq_rows = n_pass * nq_pad;
     if (n_pass < 1 || n_pass > 65535) return fail("scan_mfma: 1..65535 passes per launch");
     if (n_pass > 1 && !gm_stride) return fail("scan_mfma: batched passes need a common group-maximum stride");
     // the kernels use their last integer argument only as the row stride of group_max: a pass may write its nq_pad columns into a
@@ -794,7 +842,7 @@ int launch_scan_mfma(const uint16_t* base, size_t n_rows, int d, const uint16_t*
     // n_pass > 1: queries_dev holds n_pass x nq_pad rows, packed_scratch n_pass x mfma_packed_bytes(d), and pass y writes columns
     // [y * nq_pad, (y + 1) * nq_pad) of group_max -- ONE launch; a small base (a few row tiles) then fills the chip with its passes
     // side by side instead of running them one after the other on a few CUs
-    hipLaunchKernelGGL(pack_queries_kernel, dim3(64, (unsigned)n_pass), dim3(256), 0, stream, queries_dev, d, nq_pad, packed);
+    hipLaunchKernelGGL(pack_queries_kernel, dim3(64, (unsigned)n_pass), dim3(256), 0, stream, queries_dev, d, nq_pad, nq_rows, packed);
     struct PassScope {
         PassScope(unsigned n, uint32_t pk, uint32_t cols) { g_pass_count = n; g_pass_packed = pk; g_pass_cols = cols; }
         ~PassScope() { g_pass_count = 1; g_pass_packed = 0; g_pass_cols = 0; }
@@ -805,7 +853,7 @@ int launch_scan_mfma(const uint16_t* base, size_t n_rows, int d, const uint16_t*
     const size_t grid = (size_t)n_cu;  // one workgroup per CU
     int rc = -2;
 #ifdef MSE_DEV_KERNELS
-    if (!mask) {
+    if (!mask && group_rows == 32) {
     // Developer build only (make dev -> libmse_hip_dev.so, scripts/scan_ablate.py): timing ablations whose RESULTS ARE WRONG
     // and alternative tilings.  None of this is compiled into the product library.
     const int abl = getenv("MSE_SCAN_ABL") ? atoi(getenv("MSE_SCAN_ABL")) : 0;
@@ -848,7 +896,11 @@ int launch_scan_mfma(const uint16_t* base, size_t n_rows, int d, const uint16_t*
         // run 2.6x slower), two-stage row ring: 2 x 40 KiB of query tiles + 4 x 2 x 8 KiB = 144 KiB (147 456 B) of LDS.
         // Code object (hipcc --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage): unmasked 255 VGPRs, masked 256; both 0
         // spilled, 0 scratch, 2 waves per SIMD.  The 1-D <2,20> kernel this replaced is kept in the developer library (MSE_SCAN_2D=0).
-        rc = run([&](auto... m) { return launch_2d<2, 16, 0, 320>(grid, stream, base, n_rows, d, packed, group_max, gs, m...); });
+        // group_rows = 64 (the search passes): one maximum per wave's 64 rows instead of two per 32 -- half the array of group maxima,
+        // half the 64-byte partial stores, half of what the tournament's first level reads back.  Code object of that form: 255 VGPRs
+        // unmasked and masked (the mask is applied by selection in the epilogue), 0 spilled, 0 scratch.
+        if (group_rows == 64) rc = run([&](auto... m) { return launch_2d<2, 16, 0, 320, 64>(grid, stream, base, n_rows, d, packed, group_max, gs, m...); });
+        else rc = run([&](auto... m) { return launch_2d<2, 16, 0, 320>(grid, stream, base, n_rows, d, packed, group_max, gs, m...); });
     } else if (nq_pad == 192) {
         // 12 column tiles on the one-dimensional wave split (32 rows x 192 queries per wave, 96 accumulators): the point between
         // the HBM-bound 128-query pass and the power-bound 256-query pass (profiles/r04_scan_variants.txt)
