@@ -509,6 +509,52 @@ int mse_disk_query_topk(mse_searcher* s, mse_pq* pq, const mse_codes* c, const m
 int mse_disk_query_topk_f32(mse_searcher* s, mse_pq* pq, const mse_codes* c, const mse_graph* g, const uint32_t* starts, const float* queries_f32,
                             const float* scales, size_t nq, int disable_pq, size_t beamwidth, size_t search_list, size_t k, uint32_t* ids,
                             int64_t* scores, uint32_t* n_visited, uint32_t* cmps, uint32_t* pq_cmps);
+/* ---- filtered graph search: the request path over an allowed-row set (the post-filter of the reference's query_index,
+ * src/main.rs:904-927, moved into the search) ----
+ * The reference has a static form of this: a record whose url is empty is walked through but never returned
+ * (src/query_disk_index.rs:172; has_url of mse_graph_from_host).  A filtered search is the reference's greedy_search over an index
+ * whose has_url is (has_url AND allowed): three regimes.
+ *   MSE_FILTERED_GRAPH  the traversal of src/query_disk_index.rs:144-212 unchanged -- disallowed nodes are fetched, expanded and sit in
+ *                       the NeighbourBuffer like any other; a fetched node enters the visited list only if has_url (when the graph has the
+ *                       array) AND the filter allows it.  Runs at the caller's search_list.  The entry step is not filtered.
+ *   MSE_FILTERED_LIST   no traversal: the exact k best of the rows {allowed AND has_url} by fast_dot(f16 query, row) + descriptor product
+ *                       (the bias only with scales and codes that carry descriptors), (score desc, id asc), padding INT64_MIN /
+ *                       MSE_ID_NONE; an excluded row is absent, not merely low.  n_visited = cmps = eligible rows, pq_cmps = 0.  f32
+ *                       queries are scored through their RNE f16 copies (:477).  pq / luts / starts / beamwidth are not used (beamwidth
+ *                       and search_list must still be in range); d must be a multiple of 64.  An error while mse_graph_set_dedup is on
+ *                       (the reference de-duplicates in visit order, :482-527; a scan has none) unless the filter allows nothing.
+ *   MSE_FILTERED_AUTO   mse_filtered_plan(mse_graph_len, mse_filter_count(f), search_list, dedup on?) picks: no allowed row -> LIST
+ *                       (all padding, nothing launched); L' = ceil(search_list * n_rows / allowed) <= 1024 -> GRAPH at
+ *                       max(search_list, L') (the search then visits about as many ALLOWED nodes as an unfiltered search at search_list
+ *                       visits nodes); else LIST -- or GRAPH at 1024 when de-duplication is on.  A pure host function, so a caller can ask
+ *                       what AUTO will do; AUTO then equals the explicit call at its answer.
+ * Rows at or past mse_filter_len(f) are excluded; a filter longer than the graph, or on another device than the vectors, is an error, as
+ * is a null filter or an unknown regime; argument errors write nothing.  The filter must outlive the call / the ticket.  Everything else
+ * -- arguments, limits, outputs, coalescing of small calls -- is that of the unfiltered call each one extends; coalesced calls and
+ * tickets share a submission only with requests of the same filter object, regime and effective search_list, and never with unfiltered ones.
+ *   mse_disk_search_batch_filtered       extends mse_disk_search_batch (:144-212 with :172 filtered): GRAPH, list form
+ *   mse_disk_query_topk_filtered / _f32  extend mse_disk_query_topk / _f32 (:436-540)
+ *   mse_disk_query_submit_filtered_f32   extends mse_disk_query_submit_f32 (:640-655,716-732: tickets) */
+#define MSE_FILTERED_AUTO 0
+#define MSE_FILTERED_GRAPH 1
+#define MSE_FILTERED_LIST 2
+int mse_filtered_plan(size_t n_rows, size_t allowed, size_t search_list, int dedup_on, int* regime, size_t* search_list_eff);
+int mse_disk_search_batch_filtered(mse_searcher* s, mse_pq* pq, const mse_codes* c, const mse_graph* g, const mse_filter* f, const uint32_t* starts,
+                                   const uint16_t* queries, const float* luts, const float* scales, size_t nq, int disable_pq, size_t beamwidth,
+                                   size_t search_list, uint32_t* buf_ids, int64_t* buf_scores, uint32_t* buf_len, uint32_t* visited_ids,
+                                   int64_t* visited_scores, size_t visited_cap, uint32_t* n_visited, uint32_t* cmps, uint32_t* pq_cmps);
+int mse_disk_query_topk_filtered(mse_searcher* s, mse_pq* pq, const mse_codes* c, const mse_graph* g, const mse_filter* f, int regime,
+                                 const uint32_t* starts, const uint16_t* queries, const float* luts, const float* scales, size_t nq, int disable_pq,
+                                 size_t beamwidth, size_t search_list, size_t k, uint32_t* ids, int64_t* scores, uint32_t* n_visited, uint32_t* cmps,
+                                 uint32_t* pq_cmps);
+int mse_disk_query_topk_filtered_f32(mse_searcher* s, mse_pq* pq, const mse_codes* c, const mse_graph* g, const mse_filter* f, int regime,
+                                     const uint32_t* starts, const float* queries_f32, const float* scales, size_t nq, int disable_pq, size_t beamwidth,
+                                     size_t search_list, size_t k, uint32_t* ids, int64_t* scores, uint32_t* n_visited, uint32_t* cmps,
+                                     uint32_t* pq_cmps);
+int mse_disk_query_submit_filtered_f32(mse_searcher* s, mse_pq* pq, const mse_codes* c, const mse_graph* g, const mse_filter* f, int regime,
+                                       const float* queries_f32, const float* scales, size_t nq, int disable_pq, size_t beamwidth, size_t search_list,
+                                       size_t k, uint32_t* ids, int64_t* scores, uint32_t* n_visited, uint32_t* cmps, uint32_t* pq_cmps, void* user,
+                                       mse_completion_queue* cq, mse_ticket** ticket_out);
 /* A shard's form of the call (multi-GPU, below): the [nq][k] results stay on the device as a packed block -- [nq*k] i64 scores, then
  * [nq*k] u32 ids + id_offset (mse_topk_block_bytes(nq, k) bytes at block_dev) -- ready for the exchange; never coalesced. */
 int mse_disk_query_topk_block(mse_searcher* s, mse_pq* pq, const mse_codes* c, const mse_graph* g, const uint32_t* starts, const uint16_t* queries,

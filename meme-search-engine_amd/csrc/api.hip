@@ -164,16 +164,23 @@ int ensure_base_norm(const mse_base* b, hipStream_t st) {
 // (score desc, id asc).  The selected positions are mapped back to row ids before the finish.
 static int exact_pass(mse_searcher* s, int nq_pass, int k, uint64_t id_offset, int64_t* out_scores, uint32_t* out_ids,
                       size_t out_stride, const mse_filter* f = nullptr) {
+    return exact_pass_list(s, nq_pass, k, id_offset, out_scores, out_ids, out_stride, f ? f->ids : nullptr, f ? f->count : s->base->n, nullptr);
+}
+
+// The pass itself: rows ids[0 .. n) (ascending; null = rows 0 .. n), and -- the filtered graph search's LIST regime -- the descriptor
+// bias of every listed row added to its score BEFORE the selection (bias: descriptors, their count, the pass's scales on the device).
+int exact_pass_list(mse_searcher* s, int nq_pass, int k, uint64_t id_offset, int64_t* out_scores, uint32_t* out_ids, size_t out_stride,
+                    const uint32_t* ids, size_t n, const ListBias* bias) {
     const mse_base* b = s->base;
-    const size_t n = f ? f->count : b->n;
     if (s->scores.ensure((size_t)nq_pass * n * 8)) return -1;
     if (launch_scan_exact(b->dev, n, (int)b->d, s->q_stage.p, nq_pass, false, s->scores.as<int64_t>(), n, nullptr,
-                          s->n_cu, s->stream, f ? f->ids : nullptr)) return -1;
+                          s->n_cu, s->stream, ids)) return -1;
+    if (bias && launch_list_bias(ids, n, bias->desc, bias->n_desc, bias->scales_dev, nq_pass, s->scores.as<int64_t>(), n, s->stream)) return -1;
     if (s->sel_keys.ensure((size_t)nq_pass * k * 8)) return -1;
     uint32_t* sel = nullptr;
     LevelRef l0{KEY_I64, s->scores.p, n, 1, n, false, 0};
     if (descend(s, l0, nq_pass, k, &sel, s->sel_keys.p)) return -1;
-    if (f && launch_map_positions(sel, (size_t)nq_pass * k, f->ids, s->stream)) return -1;
+    if (ids && launch_map_positions(sel, (size_t)nq_pass * k, ids, s->stream)) return -1;
     return launch_finalize(sel, s->sel_keys.as<int64_t>(), k, k, nq_pass, id_offset, out_scores, out_ids, out_stride,
                            nullptr, 0, 0, 0, nullptr, nullptr, s->stream);
 }

@@ -53,6 +53,9 @@ struct BeamArgs {
     // small-batch entry step (entry_top1_rows_kernel): the per-chunk bests [chunk][query] are reduced HERE, by the search's first wave,
     // instead of by a launch of their own (a dependent launch costs ~35 us in a pass of ~280); null = start nodes in `starts`
     const long long* entry_psc; const uint32_t* entry_prow; const uint32_t* entry_ids; int entry_chunks, entry_nq;
+    // filtered search (mse_filter): one bit per row, rows at or past flt_rows excluded; null = every row allowed.  A fetched node is
+    // expanded whatever its bit says; the bit only decides, with has_url, whether it enters the visited list
+    const uint32_t* flt_words; size_t flt_rows;
 };
 
 // beam_search_kernel's dynamic LDS, byte offsets in carving order: distance table (ADC scoring) | query (exact scoring) | list scores |
@@ -258,7 +261,8 @@ __global__ __launch_bounds__(THREADS, THREADS == 64 ? 4 : 1) void beam_search_ke
             const uint32_t pt = s_pts[tid];
             bool first = true;
             for (int i = 0; i < tid; i++) first &= s_pts[i] != pt;
-            const bool url = !a.has_url || a.has_url[pt];
+            bool url = !a.has_url || a.has_url[pt];
+            if (a.flt_words) url = url && pt < a.flt_rows && ((a.flt_words[pt >> 5] >> (pt & 31)) & 1u);
             s_visok[tid] = (first && visited_insert(bm_vis, a.hash_bits, pt) && url) ? 1 : 0;
         }
         if (wave == 0 && (!EXACT || n_iter == 0)) {   // (exactly scored searches: s_ptsc was taken from the list above)
@@ -770,6 +774,9 @@ struct SearchIn {
     mse_searcher* s; mse_pq* pq; const mse_codes* c; const mse_graph* g; const uint32_t* starts;
     const uint16_t* queries; const float* queries_f32; const float* luts; const float* scales; size_t nq;
     int disable_pq; size_t beamwidth, search_list;
+    // filtered search: the allowed-row set (null: none) and the regime the call runs in -- MSE_FILTERED_GRAPH or _LIST; AUTO has been
+    // resolved by then (filtered_resolve), and search_list is the effective one
+    const mse_filter* filter = nullptr; int regime = MSE_FILTERED_GRAPH;
     SearchIn piece(size_t q0, size_t m) const {   // queries q0 .. q0 + m - 1
         const size_t d = s->base->d;
         SearchIn p = *this;
@@ -778,9 +785,10 @@ struct SearchIn {
         p.nq = m;
         return p;
     }
-    // what calls need in common to run as one launch: the same vectors, codec, codes, graph and search parameters, the same kinds of inputs
+    // what calls need in common to run as one launch: the same vectors, codec, codes, graph and search parameters, the same kinds of inputs,
+    // the same filter object (or none) and regime
     bool shares_with(const SearchIn& o) const {
-        return s->base == o.s->base && pq == o.pq && c == o.c && g == o.g && disable_pq == o.disable_pq && beamwidth == o.beamwidth &&
+        return filter == o.filter && regime == o.regime && s->base == o.s->base && pq == o.pq && c == o.c && g == o.g && disable_pq == o.disable_pq && beamwidth == o.beamwidth &&
                search_list == o.search_list && (queries != nullptr) == (o.queries != nullptr) && (luts != nullptr) == (o.luts != nullptr) &&
                (scales != nullptr) == (o.scales != nullptr);
     }
@@ -844,6 +852,7 @@ int check_k(size_t k) { return k == 0 || k > (size_t)TOPK_KMAX - 64 ? fail("disk
 // what belongs to one caller of the request path alone, found before it queues
 int check_queued(const SearchIn& in) {
     if (check_params(in)) return -1;
+    if (in.regime == MSE_FILTERED_LIST) return 0;   // a list pass reads neither codec nor tables nor start nodes
     if ((!in.disable_pq && (!in.pq || !in.c || (!in.luts && !in.queries_f32))) || (in.scales && !in.c)) return fail("disk_search_batch: null argument");
     for (size_t q = 0; in.starts && q < in.nq; q++)
         if (in.starts[q] >= in.g->n) return fail("disk_search_batch: start node out of range");
@@ -903,6 +912,7 @@ int search_check(const SearchRun& r) {
     if ((c != &no_codes && c->n != r.b->n) || in.g->n != r.b->n) return fail("disk_search_batch: vectors, codes and graph differ in length");
     if (!in.disable_pq && (in.pq->n_chunks != 64 || in.pq->n_centroids != 256 || c->code_size != 64)) return fail("disk_search_batch: needs the 64 x 256 codec");
     if (check_params(in)) return -1;
+    if (in.filter && check_filter(r.b, in.filter)) return -1;
     if (in.g->max_deg > BS_DEG_MAX) return fail("disk_search_batch: at most 128 neighbours per node");
     if (c->n_desc > BS_DESC_MAX) return fail("disk_search_batch: at most 8 descriptors");
     if (r.d % 32 || r.d > 4096) return fail("disk_search_batch: vector width must be a multiple of 32");
@@ -1017,6 +1027,7 @@ int search_launch(SearchRun& r) {
     a.n_visited = r.cnt_dev; a.cmps = r.cnt_dev + nq; a.pq_cmps = r.cnt_dev + 2 * nq;
     a.err = r.cnt_dev + 3 * nq;
     a.fill_vis = r.fz ? 1 : 0;
+    a.flt_words = in.filter ? in.filter->words : nullptr; a.flt_rows = in.filter ? in.filter->n_rows : 0;
     a.entry_nq = (int)nq;
     size_t hash_slots = 64;
     while (hash_slots < 2 * p_cap) hash_slots *= 2;
@@ -1293,9 +1304,115 @@ struct QueryCall {
     bool shares_with(const QueryCall& o) const { return in.shares_with(o.in) && (in.starts != nullptr) == (o.in.starts != nullptr); }
 };
 
+// ---- filtered search (include/mse.h "filtered graph search") ----------------------------------------------------------------------
+// what the LIST regime asks of a call beyond the filter's own checks (found before a request queues, and again when it runs)
+int check_list_regime(const SearchIn& in) {
+    const mse_base* b = in.s->base;
+    if (in.filter->count && in.g->dedup_threshold > 0.0f)
+        return fail("disk_query_topk_filtered: the LIST regime has no visit order to de-duplicate in (mse_graph_set_dedup is on)");
+    if (b->d % 64) return fail("disk_query_topk_filtered: the LIST regime needs a vector width that is a multiple of 64");
+    if (in.g->n != b->n) return fail("disk_search_batch: vectors, codes and graph differ in length");
+    if (in.scales && !in.c) return fail("disk_search_batch: null argument");
+    if (in.scales && in.c->n_desc && in.c->desc && (in.c->n != b->n || in.c->n_desc > BS_DESC_MAX))
+        return fail(in.c->n != b->n ? "disk_search_batch: vectors, codes and graph differ in length" : "disk_search_batch: at most 8 descriptors");
+    return 0;
+}
+
+// A filtered call's front: the filter's own checks, then the plan -- AUTO becomes the regime and the effective search_list the call
+// runs (and shares a submission) at.  Explicit GRAPH never widens.
+int filtered_resolve(SearchIn& in, int regime) {
+    if (!in.filter) return fail("disk_query_topk_filtered: null filter");
+    if (!in.g) return fail("disk_query_topk_filtered: null argument");
+    if (!in.s || !in.s->base) return fail("disk_query_topk_filtered: null searcher");
+    if (regime != MSE_FILTERED_AUTO && regime != MSE_FILTERED_GRAPH && regime != MSE_FILTERED_LIST) return fail("disk_query_topk_filtered: unknown regime");
+    if (check_filter(in.s->base, in.filter)) return -1;
+    if (in.filter->n_rows > in.g->n) return fail("disk_query_topk_filtered: filter is longer than the graph");
+    if (check_params(in)) return -1;
+    if (regime == MSE_FILTERED_AUTO) {
+        size_t eff = 0;
+        if (mse_filtered_plan(in.g->n, in.filter->count, in.search_list, in.g->dedup_threshold > 0.0f, &regime, &eff)) return -1;
+        in.search_list = eff;
+    }
+    in.regime = regime;
+    return regime == MSE_FILTERED_LIST ? check_list_regime(in) : 0;
+}
+
+// The LIST regime: no traversal.  The eligible rows -- allowed by the filter AND carrying a url -- are scored exactly through their
+// ascending id list, 8 queries per pass (the sparse path of the filtered brute-force search, api.hip), the descriptor bias is added
+// before the selection, and the tournament picks the k best by (score desc, id asc).  An ineligible row is absent, not merely low.
+// Counters: n_visited = cmps = eligible rows, pq_cmps = 0.  Results go where the fused request path's go (fz.dst or the contiguous arrays).
+int list_run(const SearchIn& in, const FusedQuery& fz) {
+    mse_searcher* s = in.s;
+    const mse_base* b = s->base;
+    const mse_graph* g = in.g;
+    const mse_filter* f = in.filter;
+    const size_t nq = in.nq, d = b->d, k = fz.k;
+    if (!f) return fail("disk_query_topk_filtered: null filter");
+    if (check_filter(b, f) || check_list_regime(in) || check_k(k)) return -1;
+    if (fz.dev_sc || (!fz.dst && (!fz.ids || !fz.scores))) return fail("disk_query_topk: bad k / outputs");
+    if (nq == 0) return 0;
+    hipStream_t st = s->stream;
+    const bool bias = in.scales && in.c->n_desc && in.c->desc;
+    const size_t n_desc = bias ? in.c->n_desc : 0;
+    // the eligible rows: the filter's own list, or -- a graph with a has_url array -- the compaction of (bitmap AND has_url)
+    const uint32_t* ids = f->ids;
+    size_t n_el = f->count;
+    if (n_el && g->has_url) {
+        DevBuf &wb = s->pool[15], &ib = s->pool[8];
+        const size_t w_bytes = (f->n_words * 4 + 15) & ~(size_t)15;
+        if (wb.ensure(16 + w_bytes + filter_compact_scratch_bytes(f->n_words)) || ib.ensure(n_el * 4)) return -1;
+        unsigned long long* count_dev = wb.as<unsigned long long>();
+        uint32_t* words = reinterpret_cast<uint32_t*>(wb.as<char>() + 16);
+        if (launch_filter_and_flags(f->words, f->n_words, g->has_url, g->n, words, st)) return -1;
+        if (launch_filter_compact(words, f->n_words, ib.as<uint32_t>(), count_dev, wb.as<char>() + 16 + w_bytes, st)) return -1;
+        unsigned long long count = 0;
+        MSE_HIP_TRY(hipMemcpyAsync(&count, count_dev, 8, hipMemcpyDeviceToHost, st));
+        MSE_HIP_TRY(hipStreamSynchronize(st));
+        ids = ib.as<uint32_t>();
+        n_el = (size_t)count;
+    }
+    std::vector<int64_t> h_sc(nq * k, INT64_MIN);
+    std::vector<uint32_t> h_id(nq * k, MSE_ID_NONE);
+    if (n_el) {
+        DevBuf &dq = s->pool[0], &dsc = s->pool[2], &oi = s->pool[5], &os = s->pool[6], &qf = s->pool[11];
+        if (dq.ensure(nq * d * 2) || oi.ensure(nq * k * 4) || os.ensure(nq * k * 8) || s->q_stage.ensure((size_t)8 * d * 2) ||
+            (bias && dsc.ensure(nq * n_desc * 4)))
+            return -1;
+        if (in.queries_f32) {   // the RNE f16 copy scores, as in the unfiltered f32 call (src/query_disk_index.rs:477)
+            if (qf.ensure(nq * d * 4)) return -1;
+            MSE_HIP_TRY(hipMemcpyAsync(qf.p, in.queries_f32, nq * d * 4, hipMemcpyHostToDevice, st));
+            if (launch_f32_to_f16(qf.as<float>(), nq * d, dq.as<uint16_t>(), st)) return -1;
+        } else {
+            MSE_HIP_TRY(hipMemcpyAsync(dq.p, in.queries, nq * d * 2, hipMemcpyDefault, st));
+        }
+        if (bias) MSE_HIP_TRY(hipMemcpyAsync(dsc.p, in.scales, nq * n_desc * 4, hipMemcpyHostToDevice, st));
+        for (size_t q0 = 0; q0 < nq; q0 += 8) {
+            const int nqp = (int)std::min<size_t>(8, nq - q0);
+            MSE_HIP_TRY(hipMemsetAsync(s->q_stage.p, 0, (size_t)8 * d * 2, st));
+            MSE_HIP_TRY(hipMemcpyAsync(s->q_stage.p, dq.as<uint16_t>() + q0 * d, (size_t)nqp * d * 2, hipMemcpyDeviceToDevice, st));
+            const ListBias lb{in.c ? in.c->desc : nullptr, (int)n_desc, dsc.as<float>() + q0 * n_desc};
+            if (exact_pass_list(s, nqp, (int)k, 0, os.as<int64_t>() + q0 * k, oi.as<uint32_t>() + q0 * k, k, ids, n_el, bias ? &lb : nullptr)) return -1;
+        }
+        MSE_HIP_TRY(hipMemcpyAsync(h_sc.data(), os.p, nq * k * 8, hipMemcpyDeviceToHost, st));
+        MSE_HIP_TRY(hipMemcpyAsync(h_id.data(), oi.p, nq * k * 4, hipMemcpyDeviceToHost, st));
+        MSE_HIP_TRY(hipStreamSynchronize(st));
+    }
+    for (size_t q = 0; q < nq; q++) {
+        const QueryDst o = fz.dst ? fz.dst[q]
+                                  : QueryDst{fz.ids + q * k, fz.scores + q * k, shifted(fz.n_visited, q), shifted(fz.cmps, q), shifted(fz.pq_cmps, q), k};
+        memcpy(o.ids, h_id.data() + q * k, o.k * 4);
+        memcpy(o.scores, h_sc.data() + q * k, o.k * 8);
+        if (o.n_visited) *o.n_visited = (uint32_t)n_el;
+        if (o.cmps) *o.cmps = (uint32_t)n_el;
+        if (o.pq_cmps) *o.pq_cmps = 0;
+    }
+    return 0;
+}
+
 // Entry searcher (row tables), the shared hold on the entry table, and the grow-and-repeat loop around the batched search.  `fz`
 // arrives with k and its destinations set.
 int fused_run(const SearchIn& in, FusedQuery fz) {
+    if (in.regime == MSE_FILTERED_LIST) return list_run(in, fz);
     const mse_graph* g = in.g;
     // the table cannot be replaced under a call in flight (mse_graph_set_entries takes the lock exclusively)
     struct Shared {
@@ -1497,6 +1614,39 @@ int mse_disk_search_batch(mse_searcher* s, mse_pq* pq, const mse_codes* c, const
                                       ListOut{buf_ids, buf_scores, buf_len, visited_ids, visited_scores, visited_cap, n_visited, cmps, pq_cmps}});
 }
 
+// GRAPH regime, list form: the search of mse_disk_search_batch with has_url AND allowed in has_url's place (src/query_disk_index.rs:172)
+int mse_disk_search_batch_filtered(mse_searcher* s, mse_pq* pq, const mse_codes* c, const mse_graph* g, const mse_filter* f, const uint32_t* starts,
+                                   const uint16_t* queries, const float* luts, const float* scales, size_t nq, int disable_pq, size_t beamwidth,
+                                   size_t search_list, uint32_t* buf_ids, int64_t* buf_scores, uint32_t* buf_len, uint32_t* visited_ids,
+                                   int64_t* visited_scores, size_t visited_cap, uint32_t* n_visited, uint32_t* cmps, uint32_t* pq_cmps) {
+    if (!queries) return fail("disk_search_batch: null argument");
+    SearchIn in{s, pq, c, g, starts, queries, nullptr, luts, scales, nq, disable_pq, beamwidth, search_list, f};
+    if (filtered_resolve(in, MSE_FILTERED_GRAPH)) return -1;
+    return disk_search_batch(BeamCall{in, ListOut{buf_ids, buf_scores, buf_len, visited_ids, visited_scores, visited_cap, n_visited, cmps, pq_cmps}});
+}
+
+// The plan of MSE_FILTERED_AUTO: a search that must visit about as many ALLOWED nodes as an unfiltered search at
+// search_list visits nodes needs a list of search_list x n_rows / allowed; past the longest list the kernel holds, the scan.
+int mse_filtered_plan(size_t n_rows, size_t allowed, size_t search_list, int dedup_on, int* regime, size_t* search_list_eff) {
+    if (!regime || !search_list_eff) return fail("filtered_plan: null argument");
+    if (search_list == 0 || search_list > BS_LMAX) return fail("filtered_plan: search_list must be 1..1024");
+    if (allowed > n_rows) return fail("filtered_plan: more allowed rows than rows");
+    if (n_rows > 0xFFFFFFFFull) return fail("filtered_plan: row ids are u32: too many rows");
+    if (allowed == 0) {   // nothing to return: the list pass over no rows launches nothing
+        *regime = MSE_FILTERED_LIST; *search_list_eff = search_list;
+        return 0;
+    }
+    const size_t widened = (search_list * n_rows + allowed - 1) / allowed;   // <= 2^42: no overflow
+    if (widened <= (size_t)BS_LMAX) {
+        *regime = MSE_FILTERED_GRAPH; *search_list_eff = std::max(search_list, widened);
+    } else if (dedup_on) {   // the scan has no visit order to de-duplicate in: the longest search instead
+        *regime = MSE_FILTERED_GRAPH; *search_list_eff = BS_LMAX;
+    } else {
+        *regime = MSE_FILTERED_LIST; *search_list_eff = search_list;
+    }
+    return 0;
+}
+
 // ---- the request path in one call (src/query_disk_index.rs:436-540 for a batch) ---------------------------------------------
 static void clear_entries_locked(mse_graph* g) {   // entry_lock held exclusively
     {
@@ -1597,6 +1747,26 @@ int mse_disk_query_topk_f32(mse_searcher* s, mse_pq* pq, const mse_codes* c, con
                                  fused_out(k, ids, scores, n_visited, cmps, pq_cmps)});
 }
 
+int mse_disk_query_topk_filtered(mse_searcher* s, mse_pq* pq, const mse_codes* c, const mse_graph* g, const mse_filter* f, int regime,
+                                 const uint32_t* starts, const uint16_t* queries, const float* luts, const float* scales, size_t nq, int disable_pq,
+                                 size_t beamwidth, size_t search_list, size_t k, uint32_t* ids, int64_t* scores, uint32_t* n_visited, uint32_t* cmps,
+                                 uint32_t* pq_cmps) {
+    if (!queries) return fail("disk_query_topk: null argument");
+    SearchIn in{s, pq, c, g, starts, queries, nullptr, luts, scales, nq, disable_pq, beamwidth, search_list, f};
+    if (filtered_resolve(in, regime)) return -1;
+    return query_front(QueryCall{in, fused_out(k, ids, scores, n_visited, cmps, pq_cmps)});
+}
+
+int mse_disk_query_topk_filtered_f32(mse_searcher* s, mse_pq* pq, const mse_codes* c, const mse_graph* g, const mse_filter* f, int regime,
+                                     const uint32_t* starts, const float* queries_f32, const float* scales, size_t nq, int disable_pq, size_t beamwidth,
+                                     size_t search_list, size_t k, uint32_t* ids, int64_t* scores, uint32_t* n_visited, uint32_t* cmps,
+                                     uint32_t* pq_cmps) {
+    if (!queries_f32) return fail("disk_query_topk_f32: null argument");
+    SearchIn in{s, pq, c, g, starts, nullptr, queries_f32, nullptr, scales, nq, disable_pq, beamwidth, search_list, f};
+    if (filtered_resolve(in, regime)) return -1;
+    return query_front(QueryCall{in, fused_out(k, ids, scores, n_visited, cmps, pq_cmps)});
+}
+
 // ---- the request path without a thread per request (round 5) ----------------------------------------------------------------
 // A ticket owns everything a queued request needs after the submitting call returned: the request record, the call's arguments and
 // a copy of the query (the caller's buffer is free again at once; the OUTPUT arrays stay the caller's and must outlive the ticket's
@@ -1689,6 +1859,15 @@ int mse_disk_query_submit_f32(mse_searcher* s, mse_pq* pq, const mse_codes* c, c
     return submit_f32(true, QueryCall{SearchIn{s, pq, c, g, nullptr, nullptr, queries_f32, nullptr, scales, nq, disable_pq, beamwidth, search_list},
                                       fused_out(k, ids, scores, n_visited, cmps, pq_cmps)},
                       user, cq, ticket_out);
+}
+
+int mse_disk_query_submit_filtered_f32(mse_searcher* s, mse_pq* pq, const mse_codes* c, const mse_graph* g, const mse_filter* f, int regime,
+                                       const float* queries_f32, const float* scales, size_t nq, int disable_pq, size_t beamwidth, size_t search_list,
+                                       size_t k, uint32_t* ids, int64_t* scores, uint32_t* n_visited, uint32_t* cmps, uint32_t* pq_cmps, void* user,
+                                       mse_completion_queue* cq, mse_ticket** ticket_out) {
+    SearchIn in{s, pq, c, g, nullptr, nullptr, queries_f32, nullptr, scales, nq, disable_pq, beamwidth, search_list, f};
+    if (filtered_resolve(in, regime)) return -1;
+    return submit_f32(true, QueryCall{in, fused_out(k, ids, scores, n_visited, cmps, pq_cmps)}, user, cq, ticket_out);
 }
 
 // the same without the copies: queries_f32 (and scales) must stay valid and unchanged until the ticket has come back

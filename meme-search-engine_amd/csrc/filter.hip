@@ -1,5 +1,7 @@
 // Row filters of the filtered brute-force search (include/mse.h mse_filter): the device bitmap, its compacted id list, and the two
-// small kernels the filtered passes add around the existing ones (api.hip exact_pass / mfma_pass).
+// small kernels the filtered passes add around the existing ones (api.hip exact_pass / mfma_pass).  The filtered graph search's LIST
+// regime (beam_search.hip list_run) adds two more: the bitmap of the rows that are allowed AND carry a url, and the descriptor bias of
+// a list pass.
 //
 // Bitmap: one bit per row, LSB first, one u32 word per 32-row group (the group of the MFMA scan's epilogue), padded with zero words
 // to a whole number of 256-row scan tiles.  Id list: the allowed rows in ascending order, built once per filter -- the exact pass and
@@ -102,7 +104,65 @@ __global__ void map_positions_kernel(uint32_t* __restrict__ sel, size_t n, const
     if (p != ID_NONE) sel[i] = list[p];
 }
 
+// out[w] = words[w] with the bits of rows whose byte in has_url is zero cleared (rows at or past n_rows: cleared).  One thread per word;
+// its 32 flag bytes are two 16-byte loads (has_url comes from hipMalloc: 256-byte aligned, and 32 w is a multiple of 32).
+__global__ void and_flags_kernel(const uint32_t* __restrict__ words, size_t n_words, const uint8_t* __restrict__ has_url, size_t n_rows,
+                                 uint32_t* __restrict__ out) {
+    const size_t w = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= n_words) return;
+    const uint32_t in = words[w];
+    uint32_t keep = 0u;
+    const size_t r0 = w * 32;
+    if (in && r0 + 32 <= n_rows) {
+        const uint4 lo = *reinterpret_cast<const uint4*>(has_url + r0), hi = *reinterpret_cast<const uint4*>(has_url + r0 + 16);
+        const uint32_t v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+#pragma unroll
+            for (int b = 0; b < 4; b++) keep |= ((v[i] >> (8 * b)) & 0xffu) ? 1u << (4 * i + b) : 0u;
+    } else if (in) {
+        for (int b = 0; b < 32 && r0 + b < n_rows; b++) keep |= has_url[r0 + b] ? 1u << b : 0u;
+    }
+    out[w] = in & keep;
+}
+
+// scores[j][p] += descriptor_product(scales[j], row ids[p]) for the nq (<= 8) queries of a list pass: per term the f32 product is
+// truncated to fixed point, the terms are summed as integers (the beam kernel's bias(pt); src/query_disk_index.rs:135-142).  A row's
+// descriptor bytes are read once for all queries.  The sum wraps like the reference's release build (unsigned add: no overflow trap).
+__global__ void list_bias_kernel(const uint32_t* __restrict__ ids, size_t n, const uint8_t* __restrict__ desc, int n_desc,
+                                 const float* __restrict__ scales, int nq, int64_t* __restrict__ scores, size_t stride) {
+    __shared__ float s_sc[8 * 8];
+    if (threadIdx.x < 64) s_sc[threadIdx.x] = (int)threadIdx.x < nq * n_desc ? scales[threadIdx.x] : 0.0f;
+    __syncthreads();
+    const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const uint8_t* dp = desc + (size_t)ids[p] * n_desc;
+    float dv[8];
+    for (int t = 0; t < n_desc; t++) dv[t] = (float)dp[t];
+    for (int j = 0; j < nq; j++) {
+        int64_t r = 0;
+        for (int t = 0; t < n_desc; t++) r += scale_dot_result(s_sc[j * n_desc + t] * dv[t]);
+        scores[(size_t)j * stride + p] = (int64_t)((uint64_t)scores[(size_t)j * stride + p] + (uint64_t)r);
+    }
+}
+
 }  // namespace
+
+int launch_filter_and_flags(const uint32_t* words, size_t n_words, const uint8_t* has_url, size_t n_rows, uint32_t* out, hipStream_t stream) {
+    if (n_words == 0) return 0;
+    hipLaunchKernelGGL(and_flags_kernel, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, stream, words, n_words, has_url, n_rows, out);
+    MSE_HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_list_bias(const uint32_t* ids, size_t n, const uint8_t* desc, int n_desc, const float* scales, int nq, int64_t* scores, size_t stride,
+                     hipStream_t stream) {
+    if (n == 0 || nq == 0) return 0;
+    if (nq > 8 || n_desc < 1 || n_desc > 8) return fail("list bias: at most 8 queries and 8 descriptors");
+    hipLaunchKernelGGL(list_bias_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, ids, n, desc, n_desc, scales, nq, scores, stride);
+    MSE_HIP_TRY(hipGetLastError());
+    return 0;
+}
 
 int launch_filter_or_ids(uint32_t* words, size_t n_words, const uint32_t* ids, size_t n, hipStream_t stream) {
     (void)n_words;   // the caller has checked every id against the filter's length

@@ -144,6 +144,11 @@ int launch_expand_groups_masked(const uint32_t* parents, size_t par_stride, size
                                 size_t n_words, uint32_t* ids, size_t ids_stride, int nq, hipStream_t stream);
 // sel[i] = list[sel[i]] (ID_NONE stays): positions in the filter's id list -> row ids
 int launch_map_positions(uint32_t* sel, size_t n, const uint32_t* list, hipStream_t stream);
+// out[w] = words[w] AND (has_url != 0 for the word's 32 rows; rows at or past n_rows excluded): the rows a filtered LIST search may return
+int launch_filter_and_flags(const uint32_t* words, size_t n_words, const uint8_t* has_url, size_t n_rows, uint32_t* out, hipStream_t stream);
+// scores[j * stride + p] += descriptor_product(scales + j * n_desc, row ids[p]) for j < nq <= 8, p < n (i64, per-term truncation)
+int launch_list_bias(const uint32_t* ids, size_t n, const uint8_t* desc, int n_desc, const float* scales, int nq, int64_t* scores, size_t stride,
+                     hipStream_t stream);
 
 // ---- scan_mfma.hip ---------------------------------------------------------------------------
 // group_max[q_pad_index][g] layout: [n_groups][nq_pad] floats (group-major), nq_pad multiple of 32

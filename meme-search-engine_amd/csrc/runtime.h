@@ -164,6 +164,12 @@ namespace mse {
 int check_filter(const mse_base* b, const mse_filter* f);
 // the sparse side of the crossover: nq queries through the filter's id list cost less than the masked scan over all rows (api.hip)
 bool filter_sparse(const mse_base* b, const mse_filter* f, size_t nq);
+// One exact pass of <= 8 queries (staged, padded, in s->q_stage) over the rows ids[0 .. n) -- ascending; null: rows 0 .. n -- and the
+// exact top-k of each: i64 scores in the reference order, (score desc, id asc), padding INT64_MIN / ID_NONE; a row that is not listed is
+// absent.  bias (optional, needs ids): the descriptor product of every listed row is added to its score before the selection.
+struct ListBias { const uint8_t* desc; int n_desc; const float* scales_dev; };   // scales_dev: [nq_pass][n_desc] on the device
+int exact_pass_list(mse_searcher* s, int nq_pass, int k, uint64_t id_offset, int64_t* out_scores, uint32_t* out_ids, size_t out_stride,
+                    const uint32_t* ids, size_t n, const ListBias* bias);
 // largest row norm of the base (x 1.0001), computed once and kept on the device as float bits (b->norm_bits_dev)
 int ensure_base_norm(const mse_base* b, hipStream_t st);
 // device memory the batched graph searches may spend on visited sets per launch: half of the free HBM, 256 MiB .. 64 GiB

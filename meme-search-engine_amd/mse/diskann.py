@@ -151,9 +151,32 @@ class DeviceGraph:
             pass
 
 
+REGIMES = {"auto": 0, "graph": 1, "list": 2}   # MSE_FILTERED_*
+_REGIME_NAMES = {v: k for k, v in REGIMES.items()}
+
+
+def _regime(regime):
+    try:
+        return REGIMES[regime] if isinstance(regime, str) else int(regime)
+    except KeyError:
+        raise ValueError(f"regime must be one of {sorted(REGIMES)}") from None
+
+
+def filtered_plan(n_rows, allowed, search_list, dedup_on=False):
+    """What regime="auto" does for a filter of `allowed` rows on a graph of `n_rows` (mse_filtered_plan): (regime name, effective
+    search_list).  No allowed row: "list" (all padding).  L' = ceil(search_list * n_rows / allowed) <= 1024: "graph" at max(search_list,
+    L'); otherwise "list" -- or "graph" at 1024 with the de-duplication on."""
+    rg, eff = C.c_int(), C.c_size_t()
+    check(ffi.lib().mse_filtered_plan(int(n_rows), int(allowed), int(search_list), int(bool(dedup_on)), C.byref(rg), C.byref(eff)),
+          "filtered_plan")
+    return _REGIME_NAMES[rg.value], int(eff.value)
+
+
 def disk_search_batch(searcher: Searcher, quantizer, codes, dgraph: DeviceGraph, starts, queries, luts=None, descriptor_scales=None,
-                      disable_pq=False, beamwidth=1, search_list=1000, visited_cap=4096, as_arrays=False):
+                      disable_pq=False, beamwidth=1, search_list=1000, visited_cap=4096, as_arrays=False, filter=None):
     """query_disk_index::greedy_search for a batch of queries, entirely on the device (one workgroup per query).
+    filter (a RowFilter, f16 queries only): the same traversal, but a fetched node enters the visited list only if the filter allows
+    it (and it has a url) -- the search over an index whose has_url is has_url AND allowed.
     as_arrays=True returns the padded output arrays themselves (dict: buf_ids, buf_scores, buf_len, visited_ids,
     visited_scores, n_visited, cmps, pq_cmps) instead of one tuple per query.
     queries: f16 rows with `luts` (QueryLUTs / [nq][64*256] f32; not needed with disable_pq), or f32 rows with luts=None --
@@ -183,7 +206,14 @@ def disk_search_batch(searcher: Searcher, quantizer, codes, dgraph: DeviceGraph,
     tail = (nq, int(bool(disable_pq)), int(beamwidth), int(search_list), _p(bi, C.c_uint32), _p(bs, C.c_int64), _p(bl, C.c_uint32),
             _p(vi, C.c_uint32), _p(vs, C.c_int64), visited_cap, _p(nv, C.c_uint32), _p(cm, C.c_uint32), _p(pc, C.c_uint32))
     scp = _p(sc, C.c_float) if sc is not None else None
-    if from_f32:
+    if filter is not None:
+        if from_f32:
+            raise MseError("disk_search_batch: a filtered search takes f16 queries (with luts, or disable_pq)")
+        check(ffi.lib().mse_disk_search_batch_filtered(searcher._h, quantizer._h if quantizer is not None else None,
+                                                       codes._h if codes is not None else None, dgraph._h, filter._h, _p(st, C.c_uint32),
+                                                       _p(q, C.c_uint16), _p(tables, C.c_float) if tables is not None else None, scp, *tail),
+              "disk_search_batch_filtered")
+    elif from_f32:
         check(ffi.lib().mse_disk_search_batch_f32(searcher._h, quantizer._h if quantizer is not None else None,
                                                   codes._h if codes is not None else None, dgraph._h, _p(st, C.c_uint32), _p(q, C.c_float),
                                                   scp, *tail), "disk_search_batch_f32")
@@ -243,12 +273,15 @@ def coalescer_stats(dgraph):
 
 
 def disk_query_topk(searcher: Searcher, quantizer, codes, dgraph, queries, k, starts=None, luts=None, descriptor_scales=None,
-                    disable_pq=False, beamwidth=1, search_list=1000):
+                    disable_pq=False, beamwidth=1, search_list=1000, filter=None, regime="auto"):
     """The request path of query_disk_index (:436-540) for a batch in one device submission: entry node (by the graph's entry table
     when `starts` is None), greedy_search, the visited records ordered by exact score and cut to the first k.  f16 query rows in
     (a host array, or `(device_pointer, nq)` for rows already on the device),
     (ids [nq, k] uint32, scores [nq, k] int64, stats dict) out; ids / scores equal topk_of_visited(disk_search_batch(...)) for the
-    same start nodes.  Rows with fewer than k visited records are padded with ID_NONE / INT64_MIN."""
+    same start nodes.  Rows with fewer than k visited records are padded with ID_NONE / INT64_MIN.
+    filter (a RowFilter): only rows it allows (and that have a url) are returned.  regime "graph": the same traversal at search_list,
+    disallowed nodes walked through but not returned; "list": the exact k best of the eligible rows, no traversal (n_visited = cmps =
+    eligible rows); "auto": whichever filtered_plan(len(graph), filter.count, search_list, dedup on) names, at its search_list."""
     from_f32 = False
     if isinstance(queries, tuple):      # (device pointer, nq): f16 rows already resident on the searcher's device, contiguous
         q_ptr, nq = C.cast(C.c_void_p(int(queries[0])), C.POINTER(C.c_uint16)), int(queries[1])
@@ -280,7 +313,14 @@ def disk_query_topk(searcher: Searcher, quantizer, codes, dgraph, queries, k, st
     head = (searcher._h, quantizer._h if quantizer is not None else None, codes._h if codes is not None else None, dgraph._h,
             _p(st, C.c_uint32) if st is not None else None, q_ptr)
     scp = _p(sc, C.c_float) if sc is not None else None
-    if from_f32:
+    if filter is not None:
+        fhead = head[:4] + (filter._h, _regime(regime)) + head[4:]
+        if from_f32:
+            check(ffi.lib().mse_disk_query_topk_filtered_f32(*fhead, scp, *tail), "disk_query_topk_filtered_f32")
+        else:
+            check(ffi.lib().mse_disk_query_topk_filtered(*fhead, _p(tables, C.c_float) if tables is not None else None, scp, *tail),
+                  "disk_query_topk_filtered")
+    elif from_f32:
         check(ffi.lib().mse_disk_query_topk_f32(*head, scp, *tail), "disk_query_topk_f32")
     else:
         check(ffi.lib().mse_disk_query_topk(*head, _p(tables, C.c_float) if tables is not None else None, scp, *tail), "disk_query_topk")
@@ -296,10 +336,13 @@ class QueryTickets:
     submitted it (the output arrays of requests in flight are kept alive on the graph object); with own_queue=True the object has a
     completion queue of its own."""
 
-    def __init__(self, searcher: Searcher, quantizer, codes, dgraph, k, disable_pq=False, beamwidth=1, search_list=1000, own_queue=False):
+    def __init__(self, searcher: Searcher, quantizer, codes, dgraph, k, disable_pq=False, beamwidth=1, search_list=1000, own_queue=False,
+                 filter=None, regime="auto"):
         """own_queue=True: a completion queue of this object's own (mse_completion_queue_*): its requests come back through its
-        collect() / fileno() and nowhere else -- one per event loop of a host that runs several."""
+        collect() / fileno() and nowhere else -- one per event loop of a host that runs several.
+        filter / regime: as disk_query_topk; the filter is kept alive by this object (copy=False is for unfiltered requests)."""
         import threading
+        self._filter, self._regime = filter, _regime(regime)
         self._s, self._pq, self._codes, self._g = searcher, quantizer, codes, dgraph
         self.k, self.disable_pq, self.beamwidth, self.search_list = int(k), bool(disable_pq), int(beamwidth), int(search_list)
         self._q = None
@@ -348,9 +391,14 @@ class QueryTickets:
             self._reg["out"][tag] = (key if key is not None else tag, ids, scores) + (() if copy else (q, sc))   # before the request can complete
         t = C.c_void_p()
         try:
+            if self._filter is not None and not copy:
+                raise MseError("QueryTickets: copy=False is not available with a filter")
             fn = ffi.lib().mse_disk_query_submit_f32 if copy else ffi.lib().mse_disk_query_submit_f32_nocopy
+            flt = ()
+            if self._filter is not None:
+                fn, flt = ffi.lib().mse_disk_query_submit_filtered_f32, (self._filter._h, self._regime)
             check(fn(self._s._h, self._pq._h if self._pq is not None else None,
-                                                      self._codes._h if self._codes is not None else None, self._g._h, _p(q, C.c_float),
+                                                      self._codes._h if self._codes is not None else None, self._g._h, *flt, _p(q, C.c_float),
                                                       _p(sc, C.c_float) if sc is not None else None, nq, int(self.disable_pq), self.beamwidth,
                                                       self.search_list, self.k, _p(ids, C.c_uint32), _p(scores, C.c_int64), None, None, None,
                                                       C.c_void_p(tag), self._q, C.byref(t)), "disk_query_submit_f32")

@@ -181,6 +181,15 @@ SIGNATURES = {
     "mse_debug_coalescer_selftest_workers": (C.c_int, [C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "mse_debug_coalescer_selftest_async": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "mse_disk_query_topk": (C.c_int, [vp, vp, vp, vp, u32p, u16p, f32p, f32p, sz, C.c_int, sz, sz, sz, u32p, i64p, u32p, u32p, u32p]),
+    "mse_filtered_plan": (C.c_int, [sz, sz, sz, C.c_int, C.POINTER(C.c_int), C.POINTER(sz)]),
+    "mse_disk_search_batch_filtered": (C.c_int, [vp, vp, vp, vp, vp, u32p, u16p, f32p, f32p, sz, C.c_int, sz, sz, u32p, i64p, u32p, u32p, i64p,
+                                                 sz, u32p, u32p, u32p]),
+    "mse_disk_query_topk_filtered": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, u32p, u16p, f32p, f32p, sz, C.c_int, sz, sz, sz, u32p, i64p, u32p,
+                                               u32p, u32p]),
+    "mse_disk_query_topk_filtered_f32": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, u32p, f32p, f32p, sz, C.c_int, sz, sz, sz, u32p, i64p, u32p,
+                                                   u32p, u32p]),
+    "mse_disk_query_submit_filtered_f32": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, f32p, f32p, sz, C.c_int, sz, sz, sz, u32p, i64p, u32p, u32p,
+                                                     u32p, vp, vp, C.POINTER(vp)]),
     "mse_graph_new": (vp, [sz, sz]),
     "mse_graph_to_host": (C.c_int, [vp, u32p, u32p]),
     "mse_graph_len": (sz, [vp]),
