@@ -685,10 +685,13 @@ int mse_siglip_set_weight(mse_siglip* m, const char* name, const float* data, co
 int mse_siglip_finalize(mse_siglip* m);                              /* fails if a weight is missing */
 /* images: [batch,3,H,W], dtype 0 = f32 / 1 = f16, already normalised (x/127.5 - 1); batch > max_batch is an
  * error (the reference asserts, clip_server.py:139).  Outputs (either may be NULL) are host [batch, emb_dim].
- * Batch invariance: rows of calls of >= 5 images are bit-equal whatever the batch.  Calls of 1-4 images run small-batch
- * kernels with another summation order: an image embedded alone (query time) and the same image inside a larger batch (index
- * time) agree to bf16 rounding (cosine within 1e-4; both within 1e-3 of the fp32 model), not bit for bit.  A pipeline that needs
- * index/query bit-equality sets MSE_SIGLIP_NOSMALL=1 in the environment before mse_siglip_create (read once, there). */
+ * Batch invariance: rows of calls of >= 5 images are bit-equal whatever the batch and however many streams
+ * (MSE_SIGLIP_STREAMS) the call is split over -- every kernel is chosen from the call, never from the size of one of its
+ * sub-batches.  Calls of 1-4 images run small-batch kernels with another summation order: an image embedded alone (query
+ * time) and the same image inside a larger batch (index time) agree to bf16 rounding (cosine within 1e-4; both within 1e-3 of
+ * the fp32 model), not bit for bit.  A pipeline that needs index/query bit-equality sets MSE_SIGLIP_NOSMALL=1 in the
+ * environment before mse_siglip_create (read once, there): calls of every size, one image included, then return the rows of
+ * a larger batch bit for bit. */
 int mse_siglip_encode_image(mse_siglip* m, const void* images, int dtype, int on_device, int batch, int normalize,
                             float* out_f32, uint16_t* out_f16);
 /* Same from decoded RGB bytes [batch][H][W][3] (host): the ToTensor / Normalize(0.5, 0.5) / .half() / stack steps of the
@@ -717,6 +720,8 @@ int mse_debug_gemm_small(int rows, int N, int K, int epi, int variant, int iters
  * the reference; geometry from misc/clip_accursed.py:31-55 and clip_server.py:107,182: width 1152, 27 layers,
  * 16 heads, mlp 4304, context 64, vocabulary 32000, no causal mask, last position pooled, Linear projection with
  * bias.  Weight names are open_clip's (`text.token_embedding.weight`, `text.transformer.resblocks.N. ...`).
+ * Every row is within 1e-3 cosine of the fp32 model and a call is deterministic; NO bit-equality of a text across call sizes
+ * (or MSE_SIGLIP_TEXT_PARTS) is promised, and no tolerance between call sizes has been measured.
  * Tokenisation (sentencepiece, pad id 1, clip_server.py:129) stays on the host. */
 typedef struct mse_siglip_text mse_siglip_text;
 typedef struct mse_siglip_text_config {

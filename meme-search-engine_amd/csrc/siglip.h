@@ -70,11 +70,15 @@ int launch_row_stats(const uint16_t* x_f16, int ldx, int width, size_t rows, flo
 int launch_ln_finalize(const float* part, size_t part_rows, int groups, size_t rows, float eps, float* stats, hipStream_t st);
 // delta (optional, bf16 [rows][ldd]): x += delta is applied and written back before normalising
 // x: fp32 rows, or fp16 rows (x_is_f16: the towers' residual stream)
+// wg: 1 = a workgroup per row (layernorm_wg_kernel: few rows), 0 = a wave per row (layernorm_kernel).  The two differ in the last
+// bits, so the caller chooses from what the CALL is -- never from `rows` of one launch: a call of at most LN_WG_MAX_ROWS token rows
+// on the small-batch path takes 1 for every LayerNorm of its blocks, every other call 0 whatever its sub-batches hold.
+constexpr size_t LN_WG_MAX_ROWS = 1024;
 int launch_layernorm(void* x, int x_is_f16, int ldx, const uint16_t* delta, int ldd, const float* gamma, const float* beta, float eps,
-                     int width, size_t rows, uint16_t* out, int ldo, float* out_f32, hipStream_t st);
+                     int width, size_t rows, uint16_t* out, int ldo, float* out_f32, int wg, hipStream_t st);
 // token rows of image b are rows b * tstride + t (t < tokens; the rest of the stride is padding)
 int launch_layernorm_d(void* x, int x_is_f16, int ldx, const LnDelta& delta, const float* gamma, const float* beta, float eps,
-                       int width, size_t rows, uint16_t* out, int ldo, float* out_f32, hipStream_t st);
+                       int width, size_t rows, uint16_t* out, int ldo, float* out_f32, int wg, hipStream_t st);
 int launch_patchify(const void* img, int is_f16, int B, int C, int H, int W, int P, int k_pad, int tstride, uint16_t* out,
                     hipStream_t st);
 int launch_attention(const uint16_t* q, const uint16_t* k, const uint16_t* vt, int B, int heads, int tokens, int n_pad, int dh,

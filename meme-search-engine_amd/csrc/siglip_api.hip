@@ -265,6 +265,10 @@ int mse_siglip_encode_image(mse_siglip* m, const void* images, int dtype, int on
     // within the oracle's tolerance), not bit for bit.  MSE_SIGLIP_NOSMALL=1 (read when the engine is created) keeps the batch kernels
     // for every size.
     const int sk = (!m->no_small && batch <= mse_siglip::SMALL_BATCH) ? 1 : 0;
+    // The LayerNorm kernel of the trunk, also by the CALL: the workgroup-per-row kernel for a small call of at most LN_WG_MAX_ROWS
+    // token rows (ONE image), layernorm_kernel for everything else -- a trailing sub-batch of one image and a one-image call under
+    // MSE_SIGLIP_NOSMALL=1 included, whose rows must equal those of any larger batch bit for bit.
+    const int ln_wg = sk && (size_t)batch * TS <= LN_WG_MAX_ROWS;
     auto trunk = [&](int b0, int batch, hipStream_t st, int) -> int {
         const size_t r0 = (size_t)b0 * TS;
         const void* v_img = reinterpret_cast<const char*>(img) + (size_t)b0 * img_stride;
@@ -281,7 +285,7 @@ int mse_siglip_encode_image(mse_siglip* m, const void* images, int dtype, int on
             g.skinny = sk;
             if (launch_gemm(GEMM_EPI_PATCH, g, st)) return -1;
         }
-        BlockRun r; r.b0 = b0; r.nb = batch; r.tokens = T; r.skinny = sk;
+        BlockRun r; r.b0 = b0; r.nb = batch; r.tokens = T; r.skinny = sk; r.ln_wg = ln_wg;
         r.fused = !sk && m->fused && gemm_fused_ok(Mp, D, m->mlp_pad, m->H, m->dh, TS, m->n_pad, M);
         r.n_branch = sk ? D : DP; r.ld_branch = DP;   // columns >= D of the branch are padding
         // one image: fc2 (K = 4352 for 1152 columns) is split four ways along K across workgroups; its partial sums and bias are added
@@ -290,7 +294,7 @@ int mse_siglip_encode_image(mse_siglip* m, const void* images, int dtype, int on
         r.kpart_stride = (size_t)gemm_small_ksplit_rows(M) * D;
         LnDelta df;   // what the final LayerNorm adds to x
         if (run_blocks(*m, r, st, &df)) return -1;
-        if (launch_layernorm_d(v_x, 1, D, df, m->lnf_g, m->lnf_b, c.eps, D, M, v_h, D, nullptr, st)) return -1;  // model.py:50,55
+        if (launch_layernorm_d(v_x, 1, D, df, m->lnf_g, m->lnf_b, c.eps, D, M, v_h, D, nullptr, ln_wg, st)) return -1;  // model.py:50,55
         // MAPHead (model.py:82-111)
         {
             GemmLaunch g; g.x = v_h; g.w = m->wkv; g.bias = m->bkv; g.M = Mp; g.N = 2 * D; g.K = D; g.m_valid = M;
@@ -317,7 +321,8 @@ int mse_siglip_encode_image(mse_siglip* m, const void* images, int dtype, int on
         GemmLaunch g; g.x = m->pool_a16; g.w = m->wpp; g.bias = m->bpp; g.M = Bp; g.N = D; g.K = D; g.m_valid = batch;
         g.resid = m->pool_o; g.ldr = D; g.skinny = sk;
         if (launch_gemm(GEMM_EPI_RESID, g, st)) return -1;
-        if (launch_layernorm(m->pool_o, 0, D, nullptr, 0, m->lnp_g, m->lnp_b, c.eps, D, batch, m->pool_ln16, D, nullptr, st)) return -1;
+        // (one pooled row per image: the workgroup-per-row kernel at EVERY batch, so a row never changes with the batch around it)
+        if (launch_layernorm(m->pool_o, 0, D, nullptr, 0, m->lnp_g, m->lnp_b, c.eps, D, batch, m->pool_ln16, D, nullptr, 1, st)) return -1;
         GemmLaunch g1; g1.x = m->pool_ln16; g1.w = m->wp1; g1.bias = m->bp1; g1.M = Bp; g1.N = m->mlp_pad; g1.K = D; g1.m_valid = batch;
         g1.out_bf16 = m->pool_h16; g1.ldo = m->mlp_pad; g1.gelu_tanh = gelu_tanh; g1.skinny = sk;
         if (launch_gemm(GEMM_EPI_GELU, g1, st)) return -1;

@@ -99,6 +99,7 @@ struct BlockRun {
     int tokens = 0;              // attention length (the token stride is n_pad)
     bool fused = false;          // LN1 / LN2 folded into the GEMMs around them
     int skinny = 0;              // unfused: GemmLaunch::skinny of QKV, proj, fc1, fc2
+    int ln_wg = 0;               // unfused: launch_layernorm_d's `wg` of LN1 / LN2, decided by the caller for the whole CALL
     int n_branch = 0, ld_branch = 0;   // unfused: output columns of proj / fc2 and the row stride of the branch they write (dlt)
     hipStream_t side = nullptr;        // unfused: GemmLaunch::side (and its events) of QKV, proj, fc2
     hipEvent_t side_fork = nullptr, side_join = nullptr;

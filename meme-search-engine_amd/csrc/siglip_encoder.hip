@@ -162,7 +162,7 @@ int run_blocks(const Encoder& e, const BlockRun& r, hipStream_t st, LnDelta* las
         const Block& b = e.blocks[i];
         LnDelta d1;   // x += (fc2 output of the previous block), then LayerNorm
         if (i) { d1 = fc2_delta; d1.bias = e.blocks[i - 1].b2; }
-        if (launch_layernorm_d(x, 1, D, d1, b.ln1_g, b.ln1_b, e.eps, D, M, h, D, nullptr, st)) return -1;
+        if (launch_layernorm_d(x, 1, D, d1, b.ln1_g, b.ln1_b, e.eps, D, M, h, D, nullptr, r.ln_wg, st)) return -1;
         {
             GemmLaunch g; g.x = h; g.w = b.wqkv; g.bias = b.bqkv; g.skinny = r.skinny;
             g.side = r.side; g.ev_fork = r.side_fork; g.ev_join = r.side_join;
@@ -176,7 +176,7 @@ int run_blocks(const Encoder& e, const BlockRun& r, hipStream_t st, LnDelta* las
         }
         LnDelta d2 = k_split(r.ksp_proj);   // x += attention branch, then LayerNorm
         if (r.ksp_proj > 1) d2.bias = b.bproj;
-        if (launch_layernorm_d(x, 1, D, d2, b.ln2_g, b.ln2_b, e.eps, D, M, h, D, nullptr, st)) return -1;
+        if (launch_layernorm_d(x, 1, D, d2, b.ln2_g, b.ln2_b, e.eps, D, M, h, D, nullptr, r.ln_wg, st)) return -1;
         {
             GemmLaunch g; g.x = h; g.w = b.w1; g.bias = b.b1; g.M = Mp; g.N = MP; g.K = D; g.m_valid = M;
             g.out_bf16 = mlp_h; g.ldo = MP; g.gelu_tanh = e.gelu_tanh; g.skinny = r.skinny;

@@ -1341,9 +1341,11 @@ __global__ __launch_bounds__(256) void layernorm_kernel(XT* __restrict__ x, int 
 // The same LayerNorm for FEW rows (one text = 64 rows, one image = 736: the query path; round 6): a whole workgroup per row instead of a
 // wave -- every lane holds at most two 4-element pieces, all of a row's loads (x, the branch or its K-split slabs, gamma, beta) are in
 // flight together, and 64 rows spread over 64 CUs instead of 16.  Same arithmetic per element; the two sums meet across the four waves
-// in LDS in a fixed order, so a row's result differs from layernorm_kernel's in the last bits (rows <= LN_WG_MAX_ROWS only: one image,
-// up to 16 texts, the pooled rows of any batch -- a given call size always takes the same kernel).
-constexpr size_t LN_WG_MAX_ROWS = 1024;
+// in LDS in a fixed order, so a row's result differs from layernorm_kernel's in the last bits.  Which of the two runs is therefore the
+// CALLER's choice (launch_layernorm_d's `wg`), made from what the call is and never from a launch's row count: the towers take this
+// kernel when the whole CALL is at most LN_WG_MAX_ROWS token rows on the small-batch path (one image, up to 16 texts), and always for
+// the pooled rows (one per image or text).  A sub-batch or a part of a larger call, however few rows it has, runs layernorm_kernel
+// like the rest of its call (tests/test_gpu_siglip_boundaries.py).
 template <typename XT>
 __global__ __launch_bounds__(256) void layernorm_wg_kernel(XT* __restrict__ x, int ldx, const LnDelta dl, const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, float eps, int width, uint16_t* __restrict__ out,
@@ -2720,11 +2722,11 @@ int launch_ln_finalize(const float* part, size_t part_rows, int groups, size_t r
 }
 
 int launch_layernorm_d(void* x, int x_is_f16, int ldx, const LnDelta& delta, const float* gamma, const float* beta, float eps,
-                       int width, size_t rows, uint16_t* out, int ldo, float* out_f32, hipStream_t st) {
+                       int width, size_t rows, uint16_t* out, int ldo, float* out_f32, int wg, hipStream_t st) {
     if (rows == 0) return 0;
     if (width % 4 || width > 2048) return fail("layernorm: width must be a multiple of 4, at most 2048");
     if (delta.parts && (delta.bf16 || delta.n_parts < 1 || !delta.bias || delta.ldp % 4)) return fail("layernorm: bad partial-sum delta");
-    if (rows <= LN_WG_MAX_ROWS) {   // few rows: a workgroup per row (the query path's one text / one image)
+    if (wg) {   // few rows in the CALL: a workgroup per row (the query path's one text / one image; the pooled rows)
         if (x_is_f16)
             hipLaunchKernelGGL(layernorm_wg_kernel<_Float16>, dim3((unsigned)rows), dim3(256), 0, st, reinterpret_cast<_Float16*>(x), ldx, delta, gamma,
                                beta, eps, width, out, ldo, out_f32);
@@ -2745,10 +2747,10 @@ int launch_layernorm_d(void* x, int x_is_f16, int ldx, const LnDelta& delta, con
 }
 
 int launch_layernorm(void* x, int x_is_f16, int ldx, const uint16_t* delta, int ldd, const float* gamma, const float* beta, float eps,
-                     int width, size_t rows, uint16_t* out, int ldo, float* out_f32, hipStream_t st) {
+                     int width, size_t rows, uint16_t* out, int ldo, float* out_f32, int wg, hipStream_t st) {
     LnDelta d;
     d.bf16 = delta; d.ldd = ldd;
-    return launch_layernorm_d(x, x_is_f16, ldx, d, gamma, beta, eps, width, rows, out, ldo, out_f32, st);
+    return launch_layernorm_d(x, x_is_f16, ldx, d, gamma, beta, eps, width, rows, out, ldo, out_f32, wg, st);
 }
 
 int launch_patchify(const void* img, int is_f16, int B, int C, int H, int W, int P, int k_pad, int tstride, uint16_t* out,

@@ -163,6 +163,7 @@ static int text_forward(mse_siglip_text* m, const int64_t* tokens, int batch, in
     run.ksp_fc2 = gemm_small_ksplit(M, D, m->mlp_pad);
     run.ksp_proj = gemm_small_ksplit_short(M, D, D);   // the output projection of ONE text (the slabs share fc2's buffer: consumed in turn)
     run.kpart_stride = (size_t)gemm_small_ksplit_rows(M) * D;
+    run.ln_wg = (size_t)M <= LN_WG_MAX_ROWS;   // by the CALL's rows (up to 16 texts): every part of a larger call runs layernorm_kernel
     // parts of a large batch (decided here because the fused path is chosen by the size of a part, the same for every part of a call)
     const int parts = batch >= 32 ? std::min(m->n_parts, batch / 16) : 1;
     const int per = parts > 1 ? std::max(4, (batch / parts) / 4 * 4) : batch;
@@ -187,12 +188,13 @@ static int text_forward(mse_siglip_text* m, const int64_t* tokens, int batch, in
     std::vector<SideRange> sides;
     for (int pt = 1; pt < parts; pt++) sides.push_back(SideRange{pt * per, pt + 1 == parts ? batch - pt * per : per, m->part_s[pt], m->part_join[pt]});
     if (fork_join(st, m->ev_fork, sides, parts > 1 ? per : batch, blocks)) return -1;
-    // final LayerNorm of the LAST position only (pool_type "last"), then the projection with bias
+    // final LayerNorm of the LAST position only (pool_type "last": one row per text, the workgroup-per-row kernel at every batch), then
+    // the projection with bias
     {
         LnDelta df;   // rows b * T + (T - 1): row stride T * D of x, of the bf16 branch and of the partial sums alike
         if (last.parts) { df = last; df.parts += (size_t)(T - 1) * D; df.ldp = T * D; }
         else if (last.bf16) { df.bf16 = last.bf16 + (size_t)(T - 1) * D; df.ldd = T * D; }
-        if (launch_layernorm_d(m->x + (size_t)(T - 1) * D, 1, T * D, df, m->lnf_g, m->lnf_b, c.eps, D, batch, nullptr, D, m->pooled, st)) return -1;
+        if (launch_layernorm_d(m->x + (size_t)(T - 1) * D, 1, T * D, df, m->lnf_g, m->lnf_b, c.eps, D, batch, nullptr, D, m->pooled, 1, st)) return -1;
     }
     if (launch_small_linear(m->pooled, D, m->wproj, D, m->bproj, D, D, batch, 0, nullptr, 0, m->feat, D, st)) return -1;
     if (launch_l2norm(m->feat, D, D, batch, normalize, m->out_f32, m->out_f16, st)) return -1;
