@@ -619,6 +619,45 @@ int mse_robust_stitch(mse_searcher* s, mse_graph* g, const uint32_t* queries_ord
  * cfg->r ids, *n_neigh receives the count.  n_cand is unbounded (the best maxc are kept, :233-234). */
 int mse_robust_prune(mse_searcher* s, const uint32_t* cand_ids, const int64_t* cand_scores, size_t n_cand, uint32_t p,
                      const mse_build_config* cfg, uint32_t* neigh, size_t* n_neigh);
+/* ---- delete rows and repair the graph on the device (FreshDiskANN's delete consolidation, stated so that it is deterministic) ----
+ * D is the delete set, N(x) the list of x AS IT WAS WHEN THE CALL STARTED.
+ *  1. A node p not in D is affected if N(p) contains a member of D.  Lists of unaffected live nodes are not touched.
+ *  2. The candidate list C of an affected p comes from walking N(p) in list order: an entry v not in D contributes v; an entry v
+ *     in D contributes the members of N(v), in list order.  From everything contributed, members of D and p itself are dropped and
+ *     only the FIRST occurrence of an id is kept.  Every candidate c is scored fast_dot(row p, row c), the reference's value bit
+ *     for bit, as merge_existing_neighbours scores (lib.rs:215-221).
+ *  3. The new list of p is robust_prune(p, C, cfg) (lib.rs:227-285) exactly as mse_robust_prune and the build compute it: stable
+ *     sort by score, cut to cfg->maxc, the alpha walk, saturate_graph honoured.  An empty C gives an empty list.
+ *  4. Every v in D ends with an empty list, has_url = 0 and a set bit in the graph's deleted map; a graph that had no has_url
+ *     array gets one, all ones elsewhere.
+ *  5. Rows, ids and codes do not move: ids stay stable, nothing is compacted.
+ * What follows from the rule:
+ *  - every candidate list reads only start-of-call lists, and a live node's list is written only by that node's own work, so the
+ *    result does not depend on how the affected nodes are batched;
+ *  - deleting D1 and then D2 is NOT the same as deleting the union of D1 and D2;
+ *  - a second call with the same D changes nothing;
+ *  - after the call the graph is, for every search entry point, indistinguishable from
+ *    mse_graph_from_host(repaired adj, deg, has_url AND NOT D).
+ * The searcher's base supplies the rows; its length must equal the graph's.  Limits: cfg->r <= mse_graph_max_degree(g) <= 128,
+ * cfg->r <= 64, cfg->maxc <= 1024, d as the build requires (cfg->l is not used).  Errors (mse_last_error) that leave the graph
+ * untouched: a null filter or config; a filter of another length; a node of the graph's entry table (mse_graph_set_entries /
+ * _set_entry_centroids) in D -- the caller moves the entry first; an edge outside the graph.  Like the entry setters, the call waits
+ * for the request-path calls in flight on the graph (direct, coalesced, tickets) and keeps new ones out while it runs.  Rows already
+ * deleted that appear in D again are ignored and not counted in stats[0].
+ * Only the request path is kept out.  The other calls that read or write the graph's lists -- mse_graph_search_batch,
+ * mse_build_graph, mse_robust_stitch, mse_graph_to_host, mse_graph_random_fill, the shard group's searches over an attached
+ * graph -- do not take part in the lock: the caller must not run them while a delete or a restore runs on the same graph.
+ * The call's scratch (the candidate slab of one batch, about 256 MiB at the default batch) stays with the searcher until
+ * mse_searcher_free, so that repeated small deletes allocate nothing while they hold the graph. */
+/* the set bits of `deleted` (an mse_filter over mse_graph_len(g) rows) name the rows to remove; batch = affected nodes per
+ * group of launches (0 = default; the result does not depend on it); stats: [0] rows newly deleted, [1] lists rewritten,
+ * [2] largest candidate list, [3] candidate lists longer than cfg->maxc */
+int mse_graph_delete_rows(mse_searcher* s, mse_graph* g, const mse_filter* deleted, const mse_build_config* cfg, size_t batch,
+                          uint64_t stats[4]);
+int mse_graph_deleted(const mse_graph* g, uint8_t* out_or_null /* [n] 0/1 */, size_t* count);
+/* give freed slots back: clears the deleted mark and sets has_url = 1 for ids that are deleted (others are an error); their lists
+ * stay empty until mse_build_graph is run over them */
+int mse_graph_restore_rows(mse_graph* g, const uint32_t* ids, size_t n_ids);
 /* diskann::greedy_search (lib.rs:183-211) GPU-resident and batched over queries (the in-RAM scorer, A21): one
  * workgroup per query, outputs as mse_greedy_search leaves them in `buf`: buf_ids/buf_scores [nq][search_list]
  * (first buf_len[q] valid, best first), n_distances [nq] = GreedySearchCounters.distances. */

@@ -1224,6 +1224,7 @@ void mse_graph_free(mse_graph* g) {
     if (g->adj) (void)hipFree(g->adj);
     if (g->deg) (void)hipFree(g->deg);
     if (g->has_url) (void)hipFree(g->has_url);
+    if (g->deleted) (void)hipFree(g->deleted);
     delete g;
 }
 
@@ -1255,7 +1256,21 @@ struct BeamCall {
                (out.visited_scores != nullptr) == (o.out.visited_scores != nullptr);
     }
 };
-int beam_call_alone(const BeamCall& k) { return disk_search_batch_impl(-1, k.in, &k.out, nullptr); }
+// Every request-path call holds the graph's entry_lock shared while it runs on the device: replacing the entry table and
+// mse_graph_delete_rows (graph_delete.hip), which rewrites lists and flags, take it exclusively.  Not re-entrant (writers are preferred):
+// taken once, at the outermost call that reaches the device.
+struct GraphShared {
+    SharedExclusive* l = nullptr;
+    explicit GraphShared(const mse_graph* g) : l(g ? &g->entry_lock : nullptr) { if (l) l->lock_shared(); }
+    ~GraphShared() { if (l) l->unlock_shared(); }
+    GraphShared(const GraphShared&) = delete;
+    GraphShared& operator=(const GraphShared&) = delete;
+};
+int beam_impl_shared(const SearchIn& in, const ListOut& out) {
+    GraphShared hold(in.g);
+    return disk_search_batch_impl(-1, in, &out, nullptr);
+}
+int beam_call_alone(const BeamCall& k) { return beam_impl_shared(k.in, k.out); }
 
 // `n` one-query calls that can share a launch = ONE batched search on the searcher of the first (alone: the caller's own call)
 int beam_run_requests(DispatchReq* const* reqs, size_t n) {
@@ -1280,7 +1295,7 @@ int beam_run_requests(DispatchReq* const* reqs, size_t n) {
     in.luts = lead.in.luts ? luts.data() : nullptr; in.scales = n_desc ? scl.data() : lead.in.scales; in.nq = n;
     const ListOut out{ids.data(), sc.data(), len.data(), lead.out.visited_ids ? vids.data() : nullptr, lead.out.visited_scores ? vsc.data() : nullptr,
                       vc, nv.data(), cm.data(), pc.data()};
-    if (const int rc = disk_search_batch_impl(-1, in, &out, nullptr)) return rc;
+    if (const int rc = beam_impl_shared(in, out)) return rc;
     for (size_t j = 0; j < n; j++) {
         const ListOut& o = static_cast<const BeamCall*>(reqs[j]->aux0)->out;
         memcpy(o.buf_ids, ids.data() + j * L, L * 4);
@@ -1412,13 +1427,11 @@ int list_run(const SearchIn& in, const FusedQuery& fz) {
 // Entry searcher (row tables), the shared hold on the entry table, and the grow-and-repeat loop around the batched search.  `fz`
 // arrives with k and its destinations set.
 int fused_run(const SearchIn& in, FusedQuery fz) {
-    if (in.regime == MSE_FILTERED_LIST) return list_run(in, fz);
     const mse_graph* g = in.g;
-    // the table cannot be replaced under a call in flight (mse_graph_set_entries takes the lock exclusively)
-    struct Shared {
-        SharedExclusive* l = nullptr;
-        ~Shared() { if (l) l->unlock_shared(); }
-    } hold;
+    // neither the entry table nor the lists and flags can be replaced under a call in flight (mse_graph_set_entries and
+    // mse_graph_delete_rows take the lock exclusively)
+    GraphShared hold(g);
+    if (in.regime == MSE_FILTERED_LIST) return list_run(in, fz);
     // a searcher over the entry rows for the duration of this call (made on first use, returned to the graph's pool afterwards)
     struct Borrow {
         const mse_graph* g; mse_searcher* es = nullptr;
@@ -1426,8 +1439,6 @@ int fused_run(const SearchIn& in, FusedQuery fz) {
     } borrow{g};
     fz.entries = nullptr;
     if (!in.starts) {
-        g->entry_lock.lock_shared();
-        hold.l = &g->entry_lock;
         if (g->n_entries == 0 || (!g->entry_base && !g->entry_keys_t))
             return fail("disk_query_topk: the graph has no entry table (mse_graph_set_entries / mse_graph_set_entry_centroids)");
         fz.entries = g;
@@ -1572,7 +1583,7 @@ int beam_one_query(const BeamCall& k) {
 }
 
 // the list form: one query through the coalescer, more straight to the device
-int disk_search_batch(const BeamCall& k) { return k.in.nq == 1 ? beam_one_query(k) : disk_search_batch_impl(-1, k.in, &k.out, nullptr); }
+int disk_search_batch(const BeamCall& k) { return k.in.nq == 1 ? beam_one_query(k) : beam_impl_shared(k.in, k.out); }
 
 // true when p points into device (or managed) memory; plain host memory is unknown to the runtime and reported as an error
 bool is_device_pointer(const void* p) {

@@ -695,12 +695,14 @@ __global__ __launch_bounds__(GB_THREADS, 2) void prune_kernel(PruneParams pp, co
     if (threadIdx.x == 0) out_len[b] = (uint32_t)nn;
 }
 
-__global__ void apply_lists_kernel(uint32_t* adj, uint32_t* deg, int r, const uint32_t* points, const uint32_t* staged, const uint32_t* staged_len,
-                                   int nb) {
+// staged list k (at most 64 ids, stride r) becomes the list of points[k] (stride `stride` >= r: the build's graphs have stride r, a
+// graph repaired by graph_delete.hip may be wider than the lists it receives)
+__global__ void apply_lists_kernel(uint32_t* adj, uint32_t* deg, int stride, int r, const uint32_t* points, const uint32_t* staged,
+                                   const uint32_t* staged_len, int nb) {
     const int k = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6), e = threadIdx.x & 63;
     if (k >= nb) return;
     const uint32_t p = points[k], len = staged_len[k];
-    if ((uint32_t)e < len) adj[(size_t)p * r + e] = staged[(size_t)k * r + e];
+    if ((uint32_t)e < len) adj[(size_t)p * stride + e] = staged[(size_t)k * r + e];
     if (e == 0) deg[p] = len;
 }
 
@@ -1232,6 +1234,40 @@ template <typename K> int set_lds(K kernel) {
 
 }  // namespace
 
+// ---- robust_prune over candidate lists in HBM and the write-back of the new lists, for graph_delete.hip (kernels.h) ----------------
+namespace mse {
+
+int prune_mfma_eps(const mse_base* b, const mse_build_config* cfg, hipStream_t st, long long* eps_fix) {
+    *eps_fix = 0;
+    if (b->d != 1152 || getenv("MSE_BUILD_EXACT_PRUNE")) return 0;   // the candidate-major MFMA walk is built for d = 1152
+    return mfma_bound(b, cfg, st, eps_fix);
+}
+
+int launch_prune_lists(const PruneLaunch& p, const uint32_t* ci, const long long* cs, size_t stride, const uint32_t* counts, const uint32_t* points,
+                       uint32_t* out_ids, uint32_t* out_len, size_t nb, hipStream_t st) {
+    if (nb == 0) return 0;
+    if (set_lds(prune_kernel<false>) || set_lds(prune_kernel<true>)) return -1;
+    PruneParams pp{p.base, p.d, p.qb, p.alpha, p.qalpha, p.r, p.saturate, p.n, p.err, p.eps_fix};
+    if (pp.eps_fix > 0)
+        hipLaunchKernelGGL(prune_kernel<true>, dim3((unsigned)nb), dim3(GB_THREADS), prune_lds_bytes(p.d), st, pp, ci, cs, stride, counts, points, p.maxc,
+                           out_ids, out_len);
+    else
+        hipLaunchKernelGGL(prune_kernel<false>, dim3((unsigned)nb), dim3(GB_THREADS), prune_lds_bytes(p.d), st, pp, ci, cs, stride, counts, points, p.maxc,
+                           out_ids, out_len);
+    MSE_HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_apply_lists(uint32_t* adj, uint32_t* deg, size_t stride, int r, const uint32_t* points, const uint32_t* staged, const uint32_t* staged_len,
+                       size_t nb, hipStream_t st) {
+    if (nb == 0) return 0;
+    hipLaunchKernelGGL(apply_lists_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, st, adj, deg, (int)stride, r, points, staged, staged_len, (int)nb);
+    MSE_HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+}  // namespace mse
+
 extern "C" {
 
 mse_graph* mse_graph_new(size_t n, size_t max_deg) {
@@ -1379,7 +1415,7 @@ int mse_build_graph(mse_searcher* s, mse_graph* g, const uint32_t* order, size_t
                 if (bm.ensure(batch * set_words * 4)) return -1;
             }
         }
-        hipLaunchKernelGGL(apply_lists_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, st, g->adj, g->deg, r, a.points, stg.as<uint32_t>(),
+        hipLaunchKernelGGL(apply_lists_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, st, g->adj, g->deg, r, r, a.points, stg.as<uint32_t>(),
                            stg_len.as<uint32_t>(), (int)nb);
         MSE_HIP_TRY(hipGetLastError());
         // back edges grouped by the list they touch, each group in (position in batch, position in list) order, lists with many

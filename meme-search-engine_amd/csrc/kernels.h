@@ -150,6 +150,40 @@ int launch_filter_and_flags(const uint32_t* words, size_t n_words, const uint8_t
 int launch_list_bias(const uint32_t* ids, size_t n, const uint8_t* desc, int n_desc, const float* scales, int nq, int64_t* scores, size_t stride,
                      hipStream_t stream);
 
+// ---- graph_build.hip: what graph_delete.hip shares with the build ---------------------------------------------------------------
+// robust_prune (lib.rs:227-285), one workgroup per candidate list: list k is (ci, cs)[k * stride ..][0 .. counts[k]) in HBM, its point
+// points[k]; the new list (at most r ids) goes to out_ids[k * r ..], its length to out_len[k].  eps_fix: prune_mfma_eps (runtime.h)
+struct PruneLaunch {
+    const uint16_t* base; uint32_t n; int d;
+    uint32_t qb; long long alpha, qalpha; int r, maxc, saturate;
+    long long eps_fix; uint32_t* err;   // err: one zeroed device word (bits 16 / 32: a candidate id outside the index)
+};
+int launch_prune_lists(const PruneLaunch& p, const uint32_t* ci, const long long* cs, size_t stride, const uint32_t* counts, const uint32_t* points,
+                       uint32_t* out_ids, uint32_t* out_len, size_t nb, hipStream_t stream);
+// list of points[k] = staged[k * r ..][0 .. staged_len[k]) (staged_len <= 64); the graph's lists have stride `stride` >= r
+int launch_apply_lists(uint32_t* adj, uint32_t* deg, size_t stride, int r, const uint32_t* points, const uint32_t* staged, const uint32_t* staged_len,
+                       size_t nb, hipStream_t stream);
+
+// ---- graph_delete.hip: delete consolidation (include/mse.h mse_graph_delete_rows) -----------------------------------------------
+// dbits: the delete set D, one bit per node (words as mse_filter keeps them).  All counters / error words are zeroed by the caller.
+// affected[w] = the nodes of word w that are not in D and list a member of D; *err |= 1 for an edge outside the graph or a list longer
+// than the stride; *n_new += members of D whose bit in `deleted` (may be null) is clear
+int launch_delete_mark(const uint32_t* adj, const uint32_t* deg, size_t n, int stride, const uint32_t* dbits, const uint32_t* deleted,
+                       uint32_t* affected, uint32_t* err, uint32_t* n_new, hipStream_t stream);
+// *hit |= 1 if one of the ids is in D
+int launch_delete_check_ids(const uint32_t* ids, size_t n_ids, const uint32_t* dbits, uint32_t* hit, hipStream_t stream);
+// candidate list of each of points[0 .. nb): the walk of include/mse.h, scored against the point; list k to (cand_ids, cand_sc)[k * cap ..],
+// its length to counts[k].  cap >= stride + stride^2.  table: scratch_bytes = delete_gather_table_bytes(stride, nb) (0: the walk's table
+// fits the LDS).  stats[0] = longest list (max), stats[1] += lists longer than maxc
+size_t delete_gather_table_bytes(int stride, size_t nb);
+int launch_delete_gather(const uint16_t* base, size_t n, int d, const uint32_t* adj, const uint32_t* deg, int stride, const uint32_t* dbits,
+                         const uint32_t* points, size_t nb, uint32_t* cand_ids, long long* cand_sc, size_t cap, uint32_t* counts, void* table,
+                         int maxc, uint32_t* stats, uint32_t* err, hipStream_t stream);
+// every member of D: empty list, has_url = 0, bit set in `deleted`
+int launch_delete_finish(uint32_t* deg, uint8_t* has_url, uint32_t* deleted, const uint32_t* dbits, size_t n, hipStream_t stream);
+// restore: bit cleared in `deleted`, has_url = 1
+int launch_delete_restore(uint8_t* has_url, uint32_t* deleted, const uint32_t* ids, size_t n_ids, hipStream_t stream);
+
 // ---- scan_mfma.hip ---------------------------------------------------------------------------
 // group_max[q_pad_index][g] layout: [n_groups][nq_pad] floats (group-major), nq_pad multiple of 32
 int launch_scan_mfma(const uint16_t* base, size_t n_rows, int d, const uint16_t* queries_dev, int nq_pad,

@@ -51,6 +51,7 @@ struct LevelRef {
 }  // namespace mse
 
 struct mse_searcher;
+struct mse_build_config;
 namespace mse {
 // Tournament descent: ids of the k best level-0 entries per query in *sel_out ([nq][k], best first);
 // their raw keys in keys_out when it is not null.  Uses the searcher's scratch and stream.
@@ -105,6 +106,7 @@ struct mse_searcher {
     mse::DevBuf thr;          // [2][nq] u64: k-th best score key of each tournament level, the floor of the level below
     const unsigned long long* last_kth = nullptr;   // after descend(): k-th best level-0 key per query (sortable), or null
     mse::DevBuf pool[16];     // scratch of the batched graph searches (kept between calls: no hipMalloc on the query path)
+    mse::DevBuf del_scratch[10];   // scratch of mse_graph_delete_rows (graph_delete.hip), kept between calls for the same reason
     uint32_t last_widened = 0, last_max_groups = 0;
     // optional HIP-event timing of the dominant (scan) kernel, for bench.py's roofline line
     bool timing = false;
@@ -172,6 +174,8 @@ int exact_pass_list(mse_searcher* s, int nq_pass, int k, uint64_t id_offset, int
                     const uint32_t* ids, size_t n, const ListBias* bias);
 // largest row norm of the base (x 1.0001), computed once and kept on the device as float bits (b->norm_bits_dev)
 int ensure_base_norm(const mse_base* b, hipStream_t st);
+// error bound of the matrix-core products robust_prune may decide by (graph_build.hip): *eps_fix = 0 means exact dots only
+int prune_mfma_eps(const mse_base* b, const ::mse_build_config* cfg, hipStream_t st, long long* eps_fix);
 // device memory the batched graph searches may spend on visited sets per launch: half of the free HBM, 256 MiB .. 64 GiB
 // (MSE_VISITED_BUDGET_KB overrides, for tests)
 size_t visited_budget_bytes();
@@ -189,6 +193,9 @@ struct mse_graph {
     uint32_t* deg = nullptr;   // device [n]
     uint8_t* has_url = nullptr;  // device [n] or null (= all)
     size_t n = 0, max_deg = 0;
+    // rows removed by mse_graph_delete_rows (graph_delete.hip): one bit per node on the device (null until the first delete) and how many
+    uint32_t* deleted = nullptr;
+    size_t n_deleted = 0;
     // meeting point of the ONE-query calls of mse_disk_search_batch(_f32) from many threads (beam_search.hip), made on first use
     // and of the small calls of mse_disk_query_topk(_f32) (round 5): the whole request path of every waiting caller in one
     // submission, on a searcher and pinned staging that belong to the WORKER (one set per worker thread)
@@ -207,7 +214,8 @@ struct mse_graph {
     // entry table of the fused request path (beam_search.hip), one of two kinds:
     //   mse_graph_set_entries          copies of the entry records' vectors + their node ids; entry = exact top-1 over the copies
     //   mse_graph_set_entry_centroids  the reference's rule: f32 shard centroids as keys (transposed [d][n_entries]) + medioid ids
-    // Request-path calls hold entry_lock shared for their duration; replacing the table takes it exclusively.
+    // Request-path calls hold entry_lock shared for their duration; replacing the table takes it exclusively, and so does
+    // mse_graph_delete_rows / _restore_rows while it rewrites lists and flags.
     uint16_t* entry_rows = nullptr;
     uint32_t* entry_ids = nullptr;
     size_t n_entries = 0;

@@ -5,7 +5,7 @@ import numpy as np
 
 from . import ffi
 from .ffi import MseError, check, check_ptr
-from .vector import Searcher, _bits, _p
+from .vector import RowFilter, Searcher, _bits, _p
 
 
 class NeighbourBuffer:
@@ -130,7 +130,91 @@ def disk_greedy_search(searcher: Searcher, quantizer, codes, graph: IndexGraph, 
     return DiskSearchResult(buf, vids[:k].copy(), vsc[:k].copy(), int(cm.value), int(pc.value))
 
 
-class DeviceGraph:
+DELETE_STATS = ("deleted", "lists_rewritten", "max_candidates", "lists_over_maxc")   # stats[0..4) of mse_graph_delete_rows
+
+
+class _RowDeletes:
+    """delete_rows / deleted / restore_rows of the two classes that wrap an mse_graph (include/mse.h "delete rows and repair the
+    graph")."""
+
+    def _graph_handle(self):
+        h = getattr(self, "_h", None)
+        if not h:
+            raise MseError("the graph is closed")
+        return h
+
+    def _n_rows(self):
+        return int(ffi.lib().mse_graph_len(self._graph_handle()))
+
+    def to_host(self) -> IndexGraph:
+        """The adjacency as it is in HBM now: adj [n, max_degree], deg [n]."""
+        h = self._graph_handle()
+        n, r = self._n_rows(), int(ffi.lib().mse_graph_max_degree(h))
+        adj, deg = np.empty((n, r), np.uint32), np.empty(n, np.uint32)
+        check(ffi.lib().mse_graph_to_host(h, _p(adj, C.c_uint32), _p(deg, C.c_uint32)), "graph_to_host")
+        return IndexGraph(adj, deg)
+
+    def delete_rows(self, searcher: Searcher, ids_or_filter, config, batch=0):
+        """Remove rows from the live graph and repair the lists that pointed at them, on the device (mse_graph_delete_rows).
+        ids_or_filter: a RowFilter over the graph's rows whose SET bits name the rows to remove, a boolean mask with one entry per row, or
+        an integer array of row ids.  config: an IndexBuildConfig (r, maxc, alpha, saturate_graph are used).  batch: affected nodes per
+        group of launches (0 = default; the result does not depend on it).  Returns {"deleted", "lists_rewritten", "max_candidates",
+        "lists_over_maxc"}."""
+        if not isinstance(config, ffi.BuildConfig):
+            raise TypeError("config must be an IndexBuildConfig")
+        if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or batch < 0:
+            raise ValueError("batch must be a non-negative integer (0 = default)")
+        if searcher is None or getattr(searcher, "_h", None) is None:
+            raise MseError("delete_rows needs the searcher over the graph's rows")
+        h = self._graph_handle()
+        owned = False
+        if isinstance(ids_or_filter, RowFilter):
+            flt = ids_or_filter
+        else:
+            a = np.asarray(ids_or_filter)
+            if a.dtype != np.bool_ and not (np.issubdtype(a.dtype, np.integer) or a.size == 0):
+                raise TypeError("ids_or_filter must be a RowFilter, a boolean mask or an integer id array")
+            n = self._n_rows()
+            if a.dtype == np.bool_:
+                if a.size != n:
+                    raise ValueError(f"a boolean mask has one entry per row: {a.size} entries for a graph of {n} rows")
+                flt = RowFilter(a)
+            else:
+                a = a.reshape(-1).astype(np.int64)
+                if a.size and (a.min() < 0 or a.max() >= n):
+                    raise ValueError(f"row ids must be in 0 .. {n - 1}")
+                flt = RowFilter(a, n)
+            owned = True
+        try:
+            out = (C.c_uint64 * 4)()
+            check(ffi.lib().mse_graph_delete_rows(searcher._h, h, flt._h, C.byref(config), int(batch), out), "graph_delete_rows")
+        finally:
+            if owned:
+                flt.close()
+        return {name: int(out[i]) for i, name in enumerate(DELETE_STATS)}
+
+    def deleted(self):
+        """Boolean array over the graph's rows: True where the row has been deleted (and not restored)."""
+        h = self._graph_handle()
+        out = np.zeros(self._n_rows(), np.uint8)
+        cnt = C.c_size_t()
+        check(ffi.lib().mse_graph_deleted(h, _p(out, C.c_uint8), C.byref(cnt)), "graph_deleted")
+        return out.astype(bool)
+
+    def restore_rows(self, ids):
+        """Give freed slots back (mse_graph_restore_rows): every id must be a deleted row, named once.  The rows count as live again
+        (has_url = 1) with EMPTY lists: write their new vectors, tell the base (rows_changed) and run build() over them."""
+        a = np.asarray(ids)
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise TypeError("ids must be an integer array")
+        a = a.reshape(-1)
+        if a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF):
+            raise ValueError("row ids must be in 0 .. 2**32 - 1")
+        i = np.ascontiguousarray(a, np.uint32)
+        check(ffi.lib().mse_graph_restore_rows(self._graph_handle(), _p(i, C.c_uint32), i.size), "graph_restore_rows")
+
+
+class DeviceGraph(_RowDeletes):
     """Adjacency (and the has-url flags of the records) resident in HBM for disk_search_batch."""
 
     def __init__(self, graph: IndexGraph, has_url=None):
@@ -500,7 +584,7 @@ def IndexBuildConfig(r=64, l=192, maxc=750, alpha=65536, query_alpha=65536, satu
     return ffi.BuildConfig(r, l, maxc, alpha, query_alpha, int(bool(saturate_graph)), query_breakpoint, max_add_per_stitch_iter)
 
 
-class BuildGraph:
+class BuildGraph(_RowDeletes):
     """The graph under construction, resident in HBM (IndexGraph::empty + the build passes)."""
 
     def __init__(self, n, r, graph: IndexGraph = None):

@@ -198,6 +198,9 @@ SIGNATURES = {
     "mse_build_graph": (C.c_int, [vp, vp, u32p, sz, sz, C.c_uint32, vp]),
     "mse_robust_stitch": (C.c_int, [vp, vp, u32p, vp]),
     "mse_robust_prune": (C.c_int, [vp, u32p, i64p, sz, C.c_uint32, vp, u32p, C.POINTER(sz)]),
+    "mse_graph_delete_rows": (C.c_int, [vp, vp, vp, vp, sz, C.POINTER(C.c_uint64)]),
+    "mse_graph_deleted": (C.c_int, [vp, u8p, C.POINTER(sz)]),
+    "mse_graph_restore_rows": (C.c_int, [vp, u32p, sz]),
     "mse_graph_search_batch": (C.c_int, [vp, vp, u32p, u16p, sz, sz, C.c_int, C.c_uint32, u32p, i64p, u32p, u32p]),
     "mse_dedup_visited": (C.c_int, [vp, u32p, sz, C.c_float, u8p]),
     "mse_select_shard": (C.c_int, [f32p, sz, sz, f32p, C.POINTER(sz)]),
