@@ -656,8 +656,51 @@ int mse_graph_delete_rows(mse_searcher* s, mse_graph* g, const mse_filter* delet
                           uint64_t stats[4]);
 int mse_graph_deleted(const mse_graph* g, uint8_t* out_or_null /* [n] 0/1 */, size_t* count);
 /* give freed slots back: clears the deleted mark and sets has_url = 1 for ids that are deleted (others are an error); their lists
- * stay empty until mse_build_graph is run over them */
+ * stay empty until mse_build_graph is run over them (mse_graph_insert_rows below does all of it -- rows, codes, flags and links -- in
+ * one call under the lock) */
 int mse_graph_restore_rows(mse_graph* g, const uint32_t* ids, size_t n_ids);
+/* ---- insert rows into freed slots of a live graph index (the other direction of the delete above) ----------------------------------
+ * One call puts n_rows new vectors into n_rows FREE SLOTS: rows that are marked in the graph's deleted map.  The index does not grow;
+ * capacity comes from spare slots (upload the graph, the vectors and the codes with more rows than are live, the spare ones with empty
+ * lists; mse_graph_delete_rows over the spare ids marks them -- no list is rewritten -- and they are inserted into later).
+ *  1. Validate, before anything changes: no null argument; graph and base of one length; codes_or_null, if given, of the graph's
+ *     length, and then pq_or_null given with the base's d and the codes' chunk count (a quantiser without codes is refused too);
+ *     descriptors given exactly when the codes carry descriptors; cfg within the limits of mse_build_graph (r equal to the graph's
+ *     stride and at most 64, l and maxc at most 1024, d a multiple of 32); every slot in range, marked deleted and named once
+ *     (checked on the device against the deleted map); start in range, live and not a slot.  On any of these errors mse_last_error
+ *     names the check, and rows, codes, descriptors, flags, lists and the deleted map are bit for bit what they were.
+ *  2. Stage: row i goes to base row slots[i]; codes[slots[i]] = the code mse_pq_quantize_batch returns for the f32 widening of row i
+ *     (the same launches, over a contiguous staging slab); desc[slots[i]] = descriptors[i].  The base's cached norm bound (the MFMA
+ *     certificate's three words) is RAISED to cover the new rows, each contributing exactly what a fresh measurement computes for it,
+ *     and never lowered: a bound that is too large is still a bound, and mse_base_rows_changed remains the way to re-measure.  A
+ *     bound that was never measured stays unmeasured.  Owned bases (mse_base_from_host, mse_base_generate) and wrapped ones
+ *     (mse_base_wrap_device) are both written: memory given to mse_base_wrap_device must be writable by the device.
+ *  3. Restore: the deleted mark of each slot is cleared, has_url[slots[i]] = has_url_or_null ? has_url_or_null[i] : 1.
+ *  4. Link: exactly mse_build_graph(s, g, order = slots, n_rows, batch, medioid = start, cfg) on the graph as it stands after step 3:
+ *     the searches and prunes of a batch see the graph as it was before that batch, then the batch's lists are replaced, then the back
+ *     edges are applied in (position in batch, position in list) order.  batch = 0 selects a default (64); the result depends on the
+ *     batch exactly as the build's does.
+ *  5. Lock: the whole call holds the graph's entry lock exclusively, as mse_graph_delete_rows does: a request-path call (direct,
+ *     coalesced or tickets) sees the index wholly before or wholly after the insert.  As with the delete, the calls outside that lock
+ *     -- mse_graph_search_batch, mse_build_graph, mse_robust_stitch, mse_graph_to_host, brute-force scans and dispatchers over the same
+ *     base, the shard group -- are the caller's to keep out while an insert runs.
+ *  6. Afterwards the index is, for every search entry point, indistinguishable from a fresh upload of the new rows, the new codes and
+ *     descriptors, the linked adj / deg and the new has_url.
+ * stats: [0] rows inserted, [1] batches run.  The call's scratch (a staging slab of at most 16384 rows and the link step's buffers)
+ * stays with the searcher until mse_searcher_free, so that repeated small inserts allocate nothing while they hold the graph.
+ * Not covered: growing n, compacting ids, the shard group, the on-disk writers, the flat index (mse_index). */
+int mse_graph_insert_rows(mse_searcher* s, mse_graph* g, mse_pq* pq_or_null, mse_codes* codes_or_null, const uint32_t* slots, size_t n_rows,
+                          const uint16_t* rows_f16 /* host [n_rows][d] */, const uint8_t* descriptors_or_null /* host [n_rows][n_desc] */,
+                          const uint8_t* has_url_or_null /* host [n_rows] */, uint32_t start, const mse_build_config* cfg, size_t batch,
+                          uint64_t stats[2]);
+/* the same with the rows already resident on the searcher's device (e.g. an encoder's f16 output), 16-byte aligned; slots, descriptors
+ * and flags stay host arrays */
+int mse_graph_insert_rows_dev(mse_searcher* s, mse_graph* g, mse_pq* pq_or_null, mse_codes* codes_or_null, const uint32_t* slots, size_t n_rows,
+                              const void* rows_f16_dev, const uint8_t* descriptors_or_null, const uint8_t* has_url_or_null, uint32_t start,
+                              const mse_build_config* cfg, size_t batch, uint64_t stats[2]);
+/* test hook: the base's cached norm bound as float bits -- [0] largest row norm x 1.0001, [1] largest subnormal mass of a row
+ * x 1.0001, [2] largest |component| -- measured first if it is not ready */
+int mse_debug_base_norm_bits(const mse_base* b, uint32_t out[3]);
 /* diskann::greedy_search (lib.rs:183-211) GPU-resident and batched over queries (the in-RAM scorer, A21): one
  * workgroup per query, outputs as mse_greedy_search leaves them in `buf`: buf_ids/buf_scores [nq][search_list]
  * (first buf_len[q] valid, best first), n_distances [nq] = GreedySearchCounters.distances. */

@@ -1312,20 +1312,41 @@ int mse_build_graph(mse_searcher* s, mse_graph* g, const uint32_t* order, size_t
         if (order[i] >= b->n) return fail("build_graph: point out of range");
     if (n_order == 0) return 0;
     if (batch == 0) batch = 1;
+    if (check_graph(g, s->stream, "build_graph")) return -1;
+    DevBuf d_order;
+    BuildScratch sc;   // per call, as ever: a build is one long call
+    if (d_order.ensure(n_order * 4)) return -1;
+    MSE_HIP_TRY(hipMemcpyAsync(d_order.p, order, n_order * 4, hipMemcpyHostToDevice, s->stream));
+    return build_graph_on_device(s, g, d_order.as<uint32_t>(), n_order, batch, medioid, cfg, sc, "build_graph", nullptr);
+}
+
+}  // extern "C"
+
+namespace mse {
+
+int check_build_config(const mse_searcher* s, const mse_graph* g, const mse_build_config* cfg, const char* who) { return check_config(s, g, cfg, who); }
+
+// The body of mse_build_graph over a device-resident order (validated by the caller, as are the config and the graph's edges): what
+// mse_graph_insert_rows (graph_insert.hip) links new nodes with.  Ends with the stream drained.
+int build_graph_on_device(mse_searcher* s, mse_graph* g, const uint32_t* order_dev, size_t n_order, size_t batch, uint32_t medioid,
+                          const mse_build_config* cfg, BuildScratch& sc, const char* who, size_t* n_batches) {
+    const mse_base* b = s->base;
+    const std::string pre = std::string(who) + ": ";
+    if (n_batches) *n_batches = 0;
+    if (n_order == 0) return 0;
     if (batch > n_order) batch = n_order;
     if (batch > 65536) batch = 65536;
     hipStream_t st = s->stream;
-    if (check_graph(g, st, "build_graph")) return -1;
+    DevBuf &bm = sc.bm, &vli = sc.vli, &vls = sc.vls, &stg = sc.stg, &stg_len = sc.stg_len, &err = sc.err, &cnts = sc.cnts, &grp = sc.grp;
     const int r = (int)cfg->r, d = (int)b->d;
     const size_t words = (b->n + 31) / 32;
     const char* vm = getenv("MSE_VISITED_MODE");   // test hook: "hash" / "bitmap"
     size_t vl_cap = std::max<size_t>(4096, 2 * cfg->l * cfg->r) + cfg->r;
-    DevBuf d_order, bm, vli, vls, stg, stg_len, err, cnts, grp;
     // visited sets: bit maps, or hash tables once the index is so large that the tables are the smaller ones (visited_set.h)
     int table_bits = visited_table_bits(std::min<size_t>(b->n, vl_cap));
     bool use_hash = vm ? !strcmp(vm, "hash") : words > ((size_t)1 << table_bits);
     size_t set_words = use_hash ? (size_t)1 << table_bits : words;
-    if (cnts.ensure(batch * 4) || d_order.ensure(n_order * 4) || bm.ensure(batch * set_words * 4) || vli.ensure(batch * vl_cap * 4) || vls.ensure(batch * vl_cap * 8) ||
+    if (cnts.ensure(batch * 4) || bm.ensure(batch * set_words * 4) || vli.ensure(batch * vl_cap * 4) || vls.ensure(batch * vl_cap * 8) ||
         stg.ensure(batch * r * 4) || stg_len.ensure(batch * 4) || err.ensure(8))
         return -1;
     // back-edge grouping on the device (group_*_kernel): a table of >= 2 slots per entry of a batch + per-entry / per-target arrays
@@ -1355,7 +1376,6 @@ int mse_build_graph(mse_searcher* s, mse_graph* g, const uint32_t* order, size_t
     MSE_HIP_TRY(hipMemsetAsync(ga.cnt, 0, TS * 4, st));
     MSE_HIP_TRY(hipMemsetAsync(ga.t_fill, 0, n_ent * 4, st));
     MSE_HIP_TRY(hipMemsetAsync(err.p, 0, 8, st));                           // [0] search / prune (reset per try), [1] back edges (sticky)
-    MSE_HIP_TRY(hipMemcpyAsync(d_order.p, order, n_order * 4, hipMemcpyHostToDevice, st));
     if (set_lds(graph_search_kernel<true>) || set_lds(prune_kernel<false>) || set_lds(prune_kernel<true>)) return -1;
     const size_t lds = search_lds_bytes(d, (int)cfg->l);
     PruneParams pp{b->dev, d, cfg->query_breakpoint, cfg->alpha, cfg->query_alpha, r, (int)cfg->saturate_graph, (uint32_t)b->n, err.as<uint32_t>(), 0};
@@ -1380,7 +1400,7 @@ int mse_build_graph(mse_searcher* s, mse_graph* g, const uint32_t* order, size_t
     if (eps_fix > 0 && d == 1152 && !getenv("MSE_BUILD_EXACT_PRUNE")) pp.eps_fix = eps_fix;
     for (size_t b0 = 0; b0 < n_order; b0 += batch) {
         const size_t nb = std::min(batch, n_order - b0);
-        a.points = d_order.as<uint32_t>() + b0;
+        a.points = order_dev + b0;
         for (;;) {
             a.vl_ids = vli.as<uint32_t>(); a.vl_sc = vls.as<long long>(); a.vl_cap = (uint32_t)vl_cap;
             a.bitmap = bm.as<uint32_t>(); a.bm_words = set_words; a.hash_bits = use_hash ? table_bits : 0;
@@ -1399,8 +1419,8 @@ int mse_build_graph(mse_searcher* s, mse_graph* g, const uint32_t* order, size_t
             MSE_HIP_TRY(hipMemcpyAsync(e2, err.p, 8, hipMemcpyDeviceToHost, st));
             MSE_HIP_TRY(hipStreamSynchronize(st));
             const uint32_t e = e2[0];
-            if (e2[1]) return fail("build_graph: internal error " + std::to_string(e2[1]) + " (a candidate id outside the index)");   // the previous batch's back edges
-            if (e & 1u) return fail("build_graph: a graph edge points outside the index");
+            if (e2[1]) return fail(pre + "internal error " + std::to_string(e2[1]) + " (a candidate id outside the index)");   // the previous batch's back edges
+            if (e & 1u) return fail(pre + "a graph edge points outside the index");
             if (!(e & 6u)) break;
             // a search visited more nodes than there was room for (list or table): repeat the batch with more (the graph is untouched so far)
             if (e & 2u) {
@@ -1446,12 +1466,17 @@ int mse_build_graph(mse_searcher* s, mse_graph* g, const uint32_t* order, size_t
         MSE_HIP_TRY(hipGetLastError());
         // (no wait here: the back edges' error word is sticky and is read with the next batch's, or below)
     }
+    if (n_batches) *n_batches = (n_order + batch - 1) / batch;
     uint32_t e_last[2] = {0, 0};
     MSE_HIP_TRY(hipMemcpyAsync(e_last, err.p, 8, hipMemcpyDeviceToHost, st));
     MSE_HIP_TRY(hipStreamSynchronize(st));
-    if (e_last[1]) return fail("build_graph: internal error " + std::to_string(e_last[1]) + " (a candidate id outside the index)");
+    if (e_last[1]) return fail(pre + "internal error " + std::to_string(e_last[1]) + " (a candidate id outside the index)");
     return 0;
 }
+
+}  // namespace mse
+
+extern "C" {
 
 int mse_robust_stitch(mse_searcher* s, mse_graph* g, const uint32_t* queries_order, const mse_build_config* cfg) {
     if (check_config(s, g, cfg, "robust_stitch")) return -1;

@@ -37,6 +37,12 @@ struct PinBuf {
     template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
+// device scratch of one run of build_graph_on_device (graph_build.hip): visited sets and lists, staged lists, error words, the
+// back-edge grouping.  mse_build_graph makes one per call; mse_graph_insert_rows keeps one on the searcher
+struct BuildScratch {
+    DevBuf cnts, bm, vli, vls, stg, stg_len, err, grp;
+};
+
 int device_cu_count();
 
 // one level of the selection tournament (topk.hip)
@@ -52,6 +58,7 @@ struct LevelRef {
 
 struct mse_searcher;
 struct mse_build_config;
+struct mse_graph;
 namespace mse {
 // Tournament descent: ids of the k best level-0 entries per query in *sel_out ([nq][k], best first);
 // their raw keys in keys_out when it is not null.  Uses the searcher's scratch and stream.
@@ -107,6 +114,8 @@ struct mse_searcher {
     const unsigned long long* last_kth = nullptr;   // after descend(): k-th best level-0 key per query (sortable), or null
     mse::DevBuf pool[16];     // scratch of the batched graph searches (kept between calls: no hipMalloc on the query path)
     mse::DevBuf del_scratch[10];   // scratch of mse_graph_delete_rows (graph_delete.hip), kept between calls for the same reason
+    mse::DevBuf ins_scratch[8];    // scratch of mse_graph_insert_rows (graph_insert.hip): slots, staging slabs, codes, flags
+    mse::BuildScratch ins_build;   // ... and of its link step
     uint32_t last_widened = 0, last_max_groups = 0;
     // optional HIP-event timing of the dominant (scan) kernel, for bench.py's roofline line
     bool timing = false;
@@ -176,6 +185,13 @@ int exact_pass_list(mse_searcher* s, int nq_pass, int k, uint64_t id_offset, int
 int ensure_base_norm(const mse_base* b, hipStream_t st);
 // error bound of the matrix-core products robust_prune may decide by (graph_build.hip): *eps_fix = 0 means exact dots only
 int prune_mfma_eps(const mse_base* b, const ::mse_build_config* cfg, hipStream_t st, long long* eps_fix);
+// the limits mse_build_graph sets on the searcher, the graph and the config (graph_build.hip); 0, or -1 with the error set
+int check_build_config(const mse_searcher* s, const ::mse_graph* g, const ::mse_build_config* cfg, const char* who);
+// mse_build_graph after its validation, over an order that is already on the device: order_dev[0 .. n_order) in batches of `batch`
+// (>= 1) from `medioid`, scratch in sc, errors prefixed with `who`; *n_batches (may be null) = batches run.  The caller has checked
+// the config, the order and the graph's edges.  Returns with the searcher's stream drained
+int build_graph_on_device(mse_searcher* s, ::mse_graph* g, const uint32_t* order_dev, size_t n_order, size_t batch, uint32_t medioid,
+                          const ::mse_build_config* cfg, BuildScratch& sc, const char* who, size_t* n_batches);
 // device memory the batched graph searches may spend on visited sets per launch: half of the free HBM, 256 MiB .. 64 GiB
 // (MSE_VISITED_BUDGET_KB overrides, for tests)
 size_t visited_budget_bytes();

@@ -131,11 +131,12 @@ def disk_greedy_search(searcher: Searcher, quantizer, codes, graph: IndexGraph, 
 
 
 DELETE_STATS = ("deleted", "lists_rewritten", "max_candidates", "lists_over_maxc")   # stats[0..4) of mse_graph_delete_rows
+INSERT_STATS = ("inserted", "batches")                                               # stats[0..2) of mse_graph_insert_rows
 
 
 class _RowDeletes:
-    """delete_rows / deleted / restore_rows of the two classes that wrap an mse_graph (include/mse.h "delete rows and repair the
-    graph")."""
+    """delete_rows / deleted / restore_rows / insert_rows of the two classes that wrap an mse_graph (include/mse.h "delete rows and
+    repair the graph", "insert rows into freed slots")."""
 
     def _graph_handle(self):
         h = getattr(self, "_h", None)
@@ -203,7 +204,8 @@ class _RowDeletes:
 
     def restore_rows(self, ids):
         """Give freed slots back (mse_graph_restore_rows): every id must be a deleted row, named once.  The rows count as live again
-        (has_url = 1) with EMPTY lists: write their new vectors, tell the base (rows_changed) and run build() over them."""
+        (has_url = 1) with EMPTY lists: write their new vectors, tell the base (rows_changed) and run build() over them.  insert_rows
+        does all of that, codes included, in one call under the graph's lock."""
         a = np.asarray(ids)
         if a.size and not np.issubdtype(a.dtype, np.integer):
             raise TypeError("ids must be an integer array")
@@ -212,6 +214,74 @@ class _RowDeletes:
             raise ValueError("row ids must be in 0 .. 2**32 - 1")
         i = np.ascontiguousarray(a, np.uint32)
         check(ffi.lib().mse_graph_restore_rows(self._graph_handle(), _p(i, C.c_uint32), i.size), "graph_restore_rows")
+
+
+    def insert_rows(self, searcher: Searcher, slots, rows, config, start, quantizer=None, codes=None, descriptors=None, has_url=None, batch=0):
+        """Put new vectors into free slots of the live index (mse_graph_insert_rows): rows, PQ codes, descriptors and flags are written and
+        the nodes linked, in one call that the request path sees wholly before or wholly after.
+        slots: integer ids of deleted rows, each once (capacity: upload spare rows with empty lists and delete_rows them).  rows: one
+        f16 row per slot -- a numpy array (np.float16 or uint16 bits), or anything with data_ptr() that lies on the searcher's device
+        (a torch tensor of 2-byte elements, contiguous: mse_graph_insert_rows_dev).  config: an IndexBuildConfig whose r is the graph's
+        stride.  start: the node the link searches start from (the medioid).  quantizer + codes: the index's ProductQuantizer and Codes,
+        both or neither; descriptors [m, n_desc] uint8 exactly when the codes carry descriptors.  has_url [m] (default: all 1).
+        batch: new nodes linked per group of launches (0 = default); the graph depends on it as build()'s does.
+        Returns {"inserted", "batches"}."""
+        if not isinstance(config, ffi.BuildConfig):
+            raise TypeError("config must be an IndexBuildConfig")
+        if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or batch < 0:
+            raise ValueError("batch must be a non-negative integer (0 = default)")
+        if searcher is None or getattr(searcher, "_h", None) is None:
+            raise MseError("insert_rows needs the searcher over the graph's rows")
+        if isinstance(start, bool) or not isinstance(start, (int, np.integer)) or not 0 <= start <= 0xFFFFFFFF:
+            raise ValueError("start must be a row id")
+        h = self._graph_handle()
+        sl = np.asarray(slots)
+        if sl.size and not np.issubdtype(sl.dtype, np.integer):
+            raise TypeError("slots must be an integer array")
+        sl = sl.reshape(-1)
+        if sl.size and (sl.min() < 0 or sl.max() > 0xFFFFFFFF):
+            raise ValueError("slots must be in 0 .. 2**32 - 1")
+        sl = np.ascontiguousarray(sl, np.uint32)
+        m = sl.size
+        vecs = getattr(searcher, "vecs", None)   # the width comes from the searcher's rows: a short array must not reach the library
+        if vecs is None or getattr(vecs, "_h", None) is None:
+            raise MseError("insert_rows needs the searcher over the graph's rows")
+        d = int(vecs.d_emb)
+        on_device = hasattr(rows, "data_ptr")
+        if on_device:
+            if not getattr(rows, "is_cuda", True):
+                raise TypeError("rows with data_ptr() must lie on the searcher's device")
+            if hasattr(rows, "is_contiguous") and not rows.is_contiguous():
+                raise ValueError("device rows must be contiguous")
+            if hasattr(rows, "element_size") and rows.element_size() != 2:
+                raise TypeError("device rows must be f16 (2-byte elements)")
+            n_elem = int(rows.numel())
+            if n_elem != m * d:
+                raise ValueError(f"rows must hold one row of the index's width per slot: {n_elem} elements for {m} slots")
+            rp = C.c_void_p(int(rows.data_ptr()))
+        else:
+            r = _bits(rows)
+            if r.size != m * d:
+                raise ValueError(f"rows must hold one row of the index's width per slot: {r.size} elements for {m} slots")
+            r = r.reshape(m, d)
+            rp = _p(r, C.c_uint16)
+        dp = up = None
+        if descriptors is not None:
+            de = np.ascontiguousarray(descriptors, np.uint8)
+            if m == 0 or de.size == 0 or de.size % m:
+                raise ValueError("descriptors must be [len(slots), n_desc]")
+            de = de.reshape(m, -1)
+            dp = _p(de, C.c_uint8)
+        if has_url is not None:
+            hu = np.ascontiguousarray(has_url, np.uint8).reshape(-1)
+            if hu.size != m:
+                raise ValueError("has_url has one entry per slot")
+            up = _p(hu, C.c_uint8)
+        out = (C.c_uint64 * 2)()
+        fn = ffi.lib().mse_graph_insert_rows_dev if on_device else ffi.lib().mse_graph_insert_rows
+        check(fn(searcher._h, h, quantizer._h if quantizer is not None else None, codes._h if codes is not None else None, _p(sl, C.c_uint32), m,
+                 rp, dp, up, int(start), C.byref(config), int(batch), out), "graph_insert_rows")
+        return {name: int(out[i]) for i, name in enumerate(INSERT_STATS)}
 
 
 class DeviceGraph(_RowDeletes):

@@ -201,6 +201,9 @@ SIGNATURES = {
     "mse_graph_delete_rows": (C.c_int, [vp, vp, vp, vp, sz, C.POINTER(C.c_uint64)]),
     "mse_graph_deleted": (C.c_int, [vp, u8p, C.POINTER(sz)]),
     "mse_graph_restore_rows": (C.c_int, [vp, u32p, sz]),
+    "mse_graph_insert_rows": (C.c_int, [vp, vp, vp, vp, u32p, sz, u16p, u8p, u8p, C.c_uint32, vp, sz, C.POINTER(C.c_uint64)]),
+    "mse_graph_insert_rows_dev": (C.c_int, [vp, vp, vp, vp, u32p, sz, vp, u8p, u8p, C.c_uint32, vp, sz, C.POINTER(C.c_uint64)]),
+    "mse_debug_base_norm_bits": (C.c_int, [vp, u32p]),
     "mse_graph_search_batch": (C.c_int, [vp, vp, u32p, u16p, sz, sz, C.c_int, C.c_uint32, u32p, i64p, u32p, u32p]),
     "mse_dedup_visited": (C.c_int, [vp, u32p, sz, C.c_float, u8p]),
     "mse_select_shard": (C.c_int, [f32p, sz, sz, f32p, C.POINTER(sz)]),
