@@ -123,6 +123,15 @@ int mse_merge_topk_packed_dev(mse_searcher* s, const void* gathered_blocks_dev, 
 /* Test hook: raw output of the matrix-core scan, out[g][q] = max over rows 32g..32g+31 of the MFMA score of query q
  * (nq <= 256, host arrays), so that tests can measure its distance from the exact-order scores. */
 int mse_debug_mfma_group_max(mse_searcher* s, const uint16_t* queries, size_t nq, float* out);
+/* Test hook: the selection tournament (the code every search ends in) over keys the caller supplies; host arrays, synchronous.
+ * kind: 0 i64, 1 f32, 3 u32.  layout: 0 query-major [nq][n] (nq_pad ignored); 1 element-strided [n][nq_pad]; 2 group-major float
+ * [n][nq_pad] as the matrix-core scan writes it (kind 1 only); nq_pad >= nq, columns past nq are never read.
+ * ids_out [nq][k]: the k best per query by (key descending, id ascending), padded with 0xFFFFFFFF; keys_out [nq][k]: their raw keys
+ * of `kind`, padded with INT64_MIN / -inf / 0; kth_out [nq]: the key the descent leaves behind as a floor for a later select, in the
+ * order-preserving unsigned domain (32-bit keys in the top half) -- never above the k-th best key, 0 when fewer than k keys exist.
+ * 1 <= k <= 2048; NaN keys are not ordered. */
+int mse_debug_select_topk(mse_searcher* s, int kind, int layout, const void* keys, size_t n, size_t nq, size_t nq_pad, size_t k,
+                          uint32_t* ids_out, void* keys_out, uint64_t* kth_out);
 /* HIP-event timing of the scan kernel (the HBM-bound kernel) on the searcher's stream: returns the
  * totals accumulated so far, then sets the mode: enable 0 = off, 1 = on, 2 = on and reset totals. */
 int mse_searcher_scan_timing(mse_searcher* s, int enable, double* total_ms, uint64_t* launches);

@@ -614,6 +614,40 @@ int mse_debug_mfma_group_max(mse_searcher* s, const uint16_t* queries, size_t nq
     return 0;
 }
 
+// test hook: descend() over keys the caller supplies, so that the tournament and the radix select can be checked on keys no search
+// produces (tests/test_gpu_topk_select.py).  The level-0 forms are the callers': query-major (exact_pass, the PQ gather), element-strided
+// (the batched PQ scan's u32 group maxima), group-major float (the MFMA rounds).  descend() hands keys_out to the level-0 select on
+// every path -- the only select when n <= DENSE_MAX, the last of the descent otherwise -- so the keys come back for every kind and
+// layout accepted here; everything else is refused.
+int mse_debug_select_topk(mse_searcher* s, int kind, int layout, const void* keys, size_t n, size_t nq, size_t nq_pad, size_t k,
+                          uint32_t* ids_out, void* keys_out, uint64_t* kth_out) {
+    if (!s) return fail("null searcher");
+    if (!keys || !ids_out || !keys_out || !kth_out) return fail("select_topk: null array");
+    if (k == 0 || k > (size_t)TOPK_KMAX) return fail("select_topk: k must be 1.." + std::to_string(TOPK_KMAX));
+    if (n == 0 || n > 0xFFFFFFFEull) return fail("select_topk: 1..2^32-2 keys per query (ids are u32)");
+    if (nq == 0 || nq > 65536) return fail("select_topk: 1..65536 queries");
+    if (kind != KEY_I64 && kind != KEY_F32 && kind != KEY_U32) return fail("select_topk: kind must be 0 (i64), 1 (f32) or 3 (u32)");
+    if (layout < 0 || layout > 2 || (layout == 2 && kind != KEY_F32)) return fail("select_topk: layout 0, 1, or 2 with f32 keys only");
+    if (layout == 0) nq_pad = nq;
+    if (nq_pad < nq || nq_pad > 65536) return fail("select_topk: nq_pad must be nq..65536");
+    const size_t es = kind == KEY_I64 ? 8 : 4;
+    DevBuf& in = layout == 0 ? s->scores : s->gmax;
+    if (in.ensure(n * nq_pad * es) || s->sel_keys.ensure(nq * k * es)) return -1;
+    MSE_HIP_TRY(hipMemcpyAsync(in.p, keys, n * nq_pad * es, hipMemcpyHostToDevice, s->stream));
+    const LevelRef l0 = layout == 0   ? LevelRef{(KeyKind)kind, in.p, n, 1, n, false, 0}
+                        : layout == 1 ? LevelRef{(KeyKind)kind, in.p, 1, nq_pad, n, false, 0}
+                                      : LevelRef{KEY_F32, in.p, 1, nq_pad, n, true, (int)nq_pad};
+    uint32_t* sel = nullptr;
+    s->last_kth = nullptr;
+    if (descend(s, l0, (int)nq, (int)k, &sel, s->sel_keys.p)) return -1;
+    if (!sel || !s->last_kth) return fail("select_topk: descend() left no selection behind");
+    MSE_HIP_TRY(hipMemcpyAsync(ids_out, sel, nq * k * 4, hipMemcpyDeviceToHost, s->stream));
+    MSE_HIP_TRY(hipMemcpyAsync(keys_out, s->sel_keys.p, nq * k * es, hipMemcpyDeviceToHost, s->stream));
+    MSE_HIP_TRY(hipMemcpyAsync(kth_out, s->last_kth, nq * 8, hipMemcpyDeviceToHost, s->stream));
+    MSE_HIP_TRY(hipStreamSynchronize(s->stream));
+    return 0;
+}
+
 // the base's coalescer, made on first use (null if it cannot be made: callers then answer directly)
 static mse_dispatcher* base_dispatcher(const mse_base* b) {
     std::lock_guard<std::mutex> g(b->disp_mu);

@@ -57,7 +57,8 @@ struct SelectArgs {
     // optional, per query, in the composite's score domain (sortable u64; 32-bit keys sit in the top half):
     // floor_hi: candidates whose score key is below it are skipped (the caller knows >= k candidates reach it -- e.g. the
     // k-th best key of the parent level, since every one of the k best parents has a child with exactly its key);
-    // kth_hi_out: receives the score key of the k-th best candidate (0 when fewer than k candidates exist).
+    // kth_hi_out: receives a lower bound of the score key of the k-th best candidate that at least k candidates reach -- the key
+    // itself, or the key with its low digits zeroed when the radix search ended early (0 when no more than k candidates exist).
     const unsigned long long* floor_hi = nullptr;
     unsigned long long* kth_hi_out = nullptr;
 };

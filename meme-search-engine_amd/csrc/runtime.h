@@ -111,7 +111,11 @@ struct mse_searcher {
     mse::DevBuf wq, wg, widx, wout;   // per-query widening of the MFMA pass: the compact set's queries, group maxima, indices, results
     mse::PinBuf margin_pin;   // certificate margins of an MFMA round on their way to the host
     mse::DevBuf thr;          // [2][nq] u64: k-th best score key of each tournament level, the floor of the level below
-    const unsigned long long* last_kth = nullptr;   // after descend(): k-th best level-0 key per query (sortable), or null
+    // after descend(): per query a LOWER BOUND of the k-th best level-0 key (sortable u64, 32-bit keys in the top half), or null.
+    // It is the radix select's threshold prefix: the k-th key itself when the search ran through every score digit, the k-th key
+    // with its low digits zeroed when a bucket was taken whole, 0 when no more than k entries exist.  At least k entries reach it,
+    // which is all a floor needs (api_pq.hip); tests/test_gpu_topk_select.py pins `<= k-th key`, not equality.
+    const unsigned long long* last_kth = nullptr;
     mse::DevBuf pool[16];     // scratch of the batched graph searches (kept between calls: no hipMalloc on the query path)
     mse::DevBuf del_scratch[10];   // scratch of mse_graph_delete_rows (graph_delete.hip), kept between calls for the same reason
     mse::DevBuf ins_scratch[8];    // scratch of mse_graph_insert_rows (graph_insert.hip): slots, staging slabs, codes, flags

@@ -93,6 +93,7 @@ SIGNATURES = {
     "mse_comm_search_dev": (C.c_int, [vp, vp, vp, sz, sz, C.c_int, C.c_uint64, vp, vp]),
     "mse_comm_last_timing": (C.c_int, [vp, C.POINTER(C.c_double)]),
     "mse_debug_mfma_group_max": (C.c_int, [vp, u16p, sz, f32p]),
+    "mse_debug_select_topk": (C.c_int, [vp, C.c_int, C.c_int, vp, sz, sz, sz, sz, u32p, vp, C.POINTER(C.c_uint64)]),
     "mse_searcher_scan_timing": (C.c_int, [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "mse_searcher_last_stats": (C.c_int, [vp, u32p, u32p]),
     "mse_index_new": (vp, [C.c_int]),

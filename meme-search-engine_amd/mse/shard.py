@@ -280,7 +280,7 @@ def merge_topk_numpy(scores, ids, k):
     for q in range(nq):
         valid = ids[q] != 0xFFFFFFFF
         s, i = scores[q][valid], ids[q][valid]
-        order = np.lexsort((i, -s))[:k]
+        order = np.lexsort((i, ~s))[:k]   # ~s = -s - 1 orders as -s does and cannot wrap (-INT64_MIN is INT64_MIN again)
         out_s[q, :order.size] = s[order]
         out_i[q, :order.size] = i[order]
     return out_s, out_i
