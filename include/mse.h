@@ -639,7 +639,7 @@ int mse_robust_prune(mse_searcher* s, const uint32_t* cand_ids, const int64_t* c
  *     sort by score, cut to cfg->maxc, the alpha walk, saturate_graph honoured.  An empty C gives an empty list.
  *  4. Every v in D ends with an empty list, has_url = 0 and a set bit in the graph's deleted map; a graph that had no has_url
  *     array gets one, all ones elsewhere.
- *  5. Rows, ids and codes do not move: ids stay stable, nothing is compacted.
+ *  5. Rows, ids and codes do not move: ids stay stable, nothing is compacted (mse_graph_compact below repacks an index).
  * What follows from the rule:
  *  - every candidate list reads only start-of-call lists, and a live node's list is written only by that node's own work, so the
  *    result does not depend on how the affected nodes are batched;
@@ -697,7 +697,7 @@ int mse_graph_restore_rows(mse_graph* g, const uint32_t* ids, size_t n_ids);
  *     descriptors, the linked adj / deg and the new has_url.
  * stats: [0] rows inserted, [1] batches run.  The call's scratch (a staging slab of at most 16384 rows and the link step's buffers)
  * stays with the searcher until mse_searcher_free, so that repeated small inserts allocate nothing while they hold the graph.
- * Not covered: growing n, compacting ids, the shard group, the on-disk writers, the flat index (mse_index). */
+ * Growing n and compacting ids: mse_graph_compact below.  Not covered: the shard group, the on-disk writers, the flat index (mse_index). */
 int mse_graph_insert_rows(mse_searcher* s, mse_graph* g, mse_pq* pq_or_null, mse_codes* codes_or_null, const uint32_t* slots, size_t n_rows,
                           const uint16_t* rows_f16 /* host [n_rows][d] */, const uint8_t* descriptors_or_null /* host [n_rows][n_desc] */,
                           const uint8_t* has_url_or_null /* host [n_rows] */, uint32_t start, const mse_build_config* cfg, size_t batch,
@@ -707,6 +707,47 @@ int mse_graph_insert_rows(mse_searcher* s, mse_graph* g, mse_pq* pq_or_null, mse
 int mse_graph_insert_rows_dev(mse_searcher* s, mse_graph* g, mse_pq* pq_or_null, mse_codes* codes_or_null, const uint32_t* slots, size_t n_rows,
                               const void* rows_f16_dev, const uint8_t* descriptors_or_null, const uint8_t* has_url_or_null, uint32_t start,
                               const mse_build_config* cfg, size_t batch, uint64_t stats[2]);
+/* ---- compact deleted rows away and grow capacity on the device ---------------------------------------------------------------------
+ * One call repacks a live index into a FRESH (base, codes, graph) triple of `capacity` rows, wholly on the device and out of place: the
+ * old handles are only read, everything that holds pointers into them (searchers, dispatchers, coalescer workers, shard groups) goes on
+ * working, and the caller swaps handles when it is ready and frees the old ones.  capacity = the live count compacts; capacity above the
+ * old length grows.  MEMORY PEAK: the old and the new index are resident together until the caller frees the old one.
+ *  1. n = mse_graph_len(g); a row is LIVE when its bit in the graph's deleted map is clear (a graph that was never deleted from: every
+ *     row).  Only the deleted map decides: a row with has_url = 0 is live.  s->base must be the rows the graph indexes: n rows, on the
+ *     graph's device, d a multiple of 8.  codes_or_null, if given, has n entries; codes_out is null exactly when codes_or_null is.
+ *  2. Live rows get the new ids 0 .. n_live - 1 in ascending order of their old ids: the renumbering is monotone, so every
+ *     (score desc, id asc) order falls the same way before and after.
+ *  3. Base: an owned base of `capacity` rows, row new = row old bit for bit, rows n_live .. capacity - 1 zero; its norm bound is
+ *     unmeasured (first use measures it, as for any upload).  Codes: `capacity` entries of the same code_size and n_desc, code and
+ *     descriptor bytes copied, the spare tail zero.
+ *  4. Graph: the same max_deg; the list of `new` is the list of `old` with every entry sent through the map, order and length
+ *     unchanged; entries at or past the length are 0, as mse_graph_new leaves an entry that was never written.  has_url is copied; a
+ *     graph that had none gets one (all ones for live rows) only when there is a spare tail.  The spare tail has empty lists,
+ *     has_url = 0 and set bits in the new deleted map, so mse_graph_deleted counts capacity - n_live and mse_graph_insert_rows accepts
+ *     those slots at once; without a spare tail the new graph has no deleted map, like a fresh upload.  The entry table, the dedup
+ *     threshold and the coalescer settings are NOT carried over: the caller sets them on the new graph, node ids through old_to_new.
+ *  5. old_to_new [n] (or null): the new id of each old row, 0xFFFFFFFF for a deleted one.  new_to_old [capacity] (or null): the old id
+ *     of each new row, 0xFFFFFFFF for a spare slot.  stats_out (or null): [0] n_live, [1] capacity, [2] list entries rewritten,
+ *     [3] bytes of rows moved = n_live x (2 d + code_size + n_desc).
+ *  6. Errors (mse_last_error names the check): a null s, g, base_out or graph_out, or codes and codes_out not given together;
+ *     capacity 0, below n_live or above 2^32 - 2; codes of another length; a base of another length or device; a live list that names
+ *     a deleted row or a row >= n (checked on the device before anything is handed back); an allocation failure (the message gives the
+ *     bytes asked for and the free device memory).  On any error nothing is returned, nothing is leaked, the out pointers are not
+ *     written and the old handles are bit for bit what they were.
+ *  7. Lock: the call holds the old graph's entry lock SHARED for its whole time on the device: mse_graph_delete_rows,
+ *     mse_graph_restore_rows and mse_graph_insert_rows on the old graph happen wholly before or wholly after it, request-path calls on
+ *     the old graph run beside it.  The calls outside that lock (mse_build_graph, mse_robust_stitch, mse_graph_random_fill, writes to a
+ *     wrapped base) are the caller's to keep out.  Everything runs on s's stream; the call returns with that stream drained.
+ * Not covered: an in-place variant (for an index above half of the device memory), the shard group, the on-disk writers, the flat
+ * index (mse_index). */
+int mse_graph_compact(mse_searcher* s, const mse_graph* g, const mse_codes* codes_or_null, size_t capacity, mse_base** base_out,
+                      mse_codes** codes_out, mse_graph** graph_out, uint32_t* old_to_new, uint32_t* new_to_old, uint64_t stats_out[4]);
+/* measurement hook of the row-gather kernel of mse_graph_compact (for scripts/graph_compact_probe.py): *last_gather_ms (or null)
+ * receives the HIP-event time of that kernel in the last mse_graph_compact made on s while the switch was on (0: none), then the
+ * switch is set (0 off, 1 on, 2 on and reset).  The kernel reads n_live and writes capacity rows of 2 d + code_size + n_desc bytes. */
+int mse_searcher_compact_timing(mse_searcher* s, int enable, double* last_gather_ms);
+/* D2H, for spot checks, like mse_base_read_rows: codes_out [n][code_size], desc_out_or_null [n][n_desc] */
+int mse_codes_read_rows(const mse_codes* c, size_t first, size_t n, uint8_t* codes_out, uint8_t* desc_out_or_null);
 /* test hook: the base's cached norm bound as float bits -- [0] largest row norm x 1.0001, [1] largest subnormal mass of a row
  * x 1.0001, [2] largest |component| -- measured first if it is not ready */
 int mse_debug_base_norm_bits(const mse_base* b, uint32_t out[3]);

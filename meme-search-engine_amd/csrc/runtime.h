@@ -134,6 +134,10 @@ struct mse_searcher {
     double beam_ms_total = 0.0;
     uint64_t beam_launches = 0, beam_queries = 0;
     mse::DevBuf beam_tot;
+    // optional measurement of mse_graph_compact's row-gather kernel (mse_searcher_compact_timing): HIP events around that launch, the
+    // last call's milliseconds
+    bool compact_timing = false;
+    double compact_gather_ms = 0.0;
     // event pairs of the PQ scan launches of one batch call (several per call on this searcher's stream), read when the call ends
     std::vector<hipEvent_t> ev_pool;
     size_t ev_used = 0;

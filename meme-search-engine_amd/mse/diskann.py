@@ -5,7 +5,7 @@ import numpy as np
 
 from . import ffi
 from .ffi import MseError, check, check_ptr
-from .vector import RowFilter, Searcher, _bits, _p
+from .vector import Codes, RowFilter, Searcher, VectorList, _bits, _p
 
 
 class NeighbourBuffer:
@@ -132,6 +132,7 @@ def disk_greedy_search(searcher: Searcher, quantizer, codes, graph: IndexGraph, 
 
 DELETE_STATS = ("deleted", "lists_rewritten", "max_candidates", "lists_over_maxc")   # stats[0..4) of mse_graph_delete_rows
 INSERT_STATS = ("inserted", "batches")                                               # stats[0..2) of mse_graph_insert_rows
+COMPACT_STATS = ("live", "capacity", "edges_rewritten", "bytes_moved")               # stats_out[0..4) of mse_graph_compact
 
 
 class _RowDeletes:
@@ -282,6 +283,73 @@ class _RowDeletes:
         check(fn(searcher._h, h, quantizer._h if quantizer is not None else None, codes._h if codes is not None else None, _p(sl, C.c_uint32), m,
                  rp, dp, up, int(start), C.byref(config), int(batch), out), "graph_insert_rows")
         return {name: int(out[i]) for i, name in enumerate(INSERT_STATS)}
+
+    def _live_count(self):
+        cnt = C.c_size_t()
+        check(ffi.lib().mse_graph_deleted(self._graph_handle(), None, C.byref(cnt)), "graph_deleted")
+        return self._n_rows() - int(cnt.value)
+
+    def _compact_once(self, searcher, codes, capacity):
+        h = self._graph_handle()
+        n = self._n_rows()
+        o2n = np.empty(n, np.uint32)
+        # (a capacity outside 1 .. 2^32 - 2 is refused by the call before it writes anything: no array is made for it)
+        n2o = np.empty(capacity, np.uint32) if 0 < capacity <= 0xFFFFFFFE else None
+        bo, co, go = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        out = (C.c_uint64 * 4)()
+        check(ffi.lib().mse_graph_compact(searcher._h, h, codes._h if codes is not None else None, capacity, C.byref(bo),
+                                          C.byref(co) if codes is not None else None, C.byref(go), _p(o2n, C.c_uint32),
+                                          _p(n2o, C.c_uint32) if n2o is not None else None, out), "graph_compact")
+        vecs = VectorList(bo.value)
+        new_codes = None
+        if codes is not None:
+            new_codes = Codes.__new__(Codes)
+            new_codes._h = co.value
+            new_codes.code_size, new_codes.n_desc = codes.code_size, codes.n_desc
+        g = object.__new__(type(self))
+        g._h = go.value
+        if isinstance(self, BuildGraph):
+            g.n, g.r = capacity, int(ffi.lib().mse_graph_max_degree(go.value))
+        g.compact_stats = {name: int(out[i]) for i, name in enumerate(COMPACT_STATS)}
+        return vecs, new_codes, g, o2n, n2o
+
+    def compact(self, searcher: Searcher, codes=None, capacity=None):
+        """Repack the live index into a fresh triple of `capacity` rows on the device (mse_graph_compact): the live rows renumbered densely
+        in their old order, the spare tail (capacity above the live count) marked deleted, ready for insert_rows.  Out of place: this
+        graph, the searcher's rows and `codes` are only read and stay valid; both indexes are resident until the old one is closed.
+        searcher: over the rows this graph indexes.  codes: the index's Codes, or None.
+        capacity: rows of the new triple.  None = the live count AS THE CALL FINDS IT UNDER THE GRAPH'S LOCK: the count is read first and
+        handed to the call; if a delete_rows / insert_rows / restore_rows on another thread changed it in between (the call reports the
+        live count it saw), that result is released and the call repeated, so the returned triple never has a spare tail:
+        len(vecs) == compact_stats["live"].  MseError if the count changes eight times in a row.
+        Returns (VectorList, Codes or None, graph of this class, old_to_new [n] uint32, new_to_old [capacity] uint32); 0xFFFFFFFF marks
+        a deleted row / a spare slot.  The new graph's stats are in its .compact_stats ({"live", "capacity", "edges_rewritten",
+        "bytes_moved"}).  The entry table, the dedup threshold and the coalescer settings are not carried over: set them on the new
+        graph, node ids through old_to_new."""
+        if searcher is None or getattr(searcher, "_h", None) is None:
+            raise MseError("compact needs the searcher over the graph's rows")
+        if codes is not None and getattr(codes, "_h", None) is None:
+            raise MseError("compact: the codes are closed")
+        self._graph_handle()
+        if capacity is not None:
+            if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or capacity < 0:
+                raise ValueError("capacity must be a non-negative integer")
+            return self._compact_once(searcher, codes, int(capacity))
+        for _ in range(8):
+            want = self._live_count()
+            try:
+                got = self._compact_once(searcher, codes, want)
+            except MseError:
+                if self._live_count() != want:      # an insert made the count outgrow the capacity meanwhile: again
+                    continue
+                raise
+            if got[2].compact_stats["live"] == want:
+                return got
+            got[2].close()                          # a delete slipped in between the count and the call: a spare tail nobody asked for
+            if got[1] is not None:
+                got[1].close()
+            got[0].close()
+        raise MseError("compact: the live count changed on every attempt; pass a capacity, or keep writers out")
 
 
 class DeviceGraph(_RowDeletes):

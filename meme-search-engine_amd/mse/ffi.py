@@ -204,6 +204,9 @@ SIGNATURES = {
     "mse_graph_restore_rows": (C.c_int, [vp, u32p, sz]),
     "mse_graph_insert_rows": (C.c_int, [vp, vp, vp, vp, u32p, sz, u16p, u8p, u8p, C.c_uint32, vp, sz, C.POINTER(C.c_uint64)]),
     "mse_graph_insert_rows_dev": (C.c_int, [vp, vp, vp, vp, u32p, sz, vp, u8p, u8p, C.c_uint32, vp, sz, C.POINTER(C.c_uint64)]),
+    "mse_graph_compact": (C.c_int, [vp, vp, vp, sz, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), u32p, u32p, C.POINTER(C.c_uint64)]),
+    "mse_searcher_compact_timing": (C.c_int, [vp, C.c_int, C.POINTER(C.c_double)]),
+    "mse_codes_read_rows": (C.c_int, [vp, sz, sz, u8p, u8p]),
     "mse_debug_base_norm_bits": (C.c_int, [vp, u32p]),
     "mse_graph_search_batch": (C.c_int, [vp, vp, u32p, u16p, sz, sz, C.c_int, C.c_uint32, u32p, i64p, u32p, u32p]),
     "mse_dedup_visited": (C.c_int, [vp, u32p, sz, C.c_float, u8p]),

@@ -184,6 +184,14 @@ class Searcher:
         return {"kernel_ms": out[0] / 1e3, "launches": int(out[1]), "queries": int(out[2]), "rows_scored": int(out[3]),
                 "nodes_fetched": int(out[4]), "adc_scored": int(out[5]), "iterations": int(out[6]), "iterations_replayed": int(out[7])}
 
+    def compact_timing(self, enable):
+        """Measurement hook of compact's row-gather kernel (mse_searcher_compact_timing): returns the HIP-event milliseconds of that
+        kernel in the last compact made on this searcher while the switch was on (0.0: none), then sets the switch (0 off, 1 on, 2 on
+        and reset)."""
+        ms = C.c_double()
+        check(ffi.lib().mse_searcher_compact_timing(self._h, int(enable), C.byref(ms)), "compact_timing")
+        return float(ms.value)
+
     def bruteforce_topk(self, queries, k, mode=MODE_AUTO, allow=None):
         """Brute-force scan + ranking of `evaluate` (query_disk_index.rs:262-273) for a query batch.
         Returns (scores int64 [nq,k], ids uint32 [nq,k]).  allow: a RowFilter or a boolean row mask -- top-k over those rows only."""
@@ -467,6 +475,7 @@ class Codes:
         else:
             nd, dp = 0, None
         self._h = check_ptr(ffi.lib().mse_codes_from_host(_p(codes, C.c_uint8), n, cs, dp, nd), "mse_codes_from_host")
+        self.code_size, self.n_desc = cs, nd
 
     @classmethod
     def quantize_base(cls, pq, vecs, descriptors=None):
@@ -479,10 +488,26 @@ class Codes:
         else:
             nd, dp = 0, None
         self._h = check_ptr(ffi.lib().mse_codes_quantize_base(pq._h, vecs._h, dp, nd), "mse_codes_quantize_base")
+        self.code_size, self.n_desc = pq.n_chunks, nd
         return self
 
     def __len__(self):
         return int(ffi.lib().mse_codes_len(self._h))
+
+    def read_rows(self, first, n, descriptors=False):
+        """Entries first .. first + n - 1 as they are in HBM (mse_codes_read_rows): codes [n, code_size] uint8, or with descriptors=True
+        (codes, descriptors [n, n_desc])."""
+        first, n = int(first), int(n)
+        if first < 0 or n < 0 or first + n > len(self):
+            raise ValueError("row range out of bounds")
+        cs, nd = self.code_size, self.n_desc
+        if descriptors and not nd:
+            raise MseError("the codes carry no descriptors")
+        codes = np.empty((n, cs), np.uint8)
+        desc = np.empty((n, nd), np.uint8) if descriptors else None
+        check(ffi.lib().mse_codes_read_rows(self._h, first, n, _p(codes, C.c_uint8), _p(desc, C.c_uint8) if descriptors else None),
+              "codes_read_rows")
+        return (codes, desc) if descriptors else codes
 
     def close(self):
         if self._h:
