@@ -380,6 +380,44 @@ int mse_pq_scan_sustained(mse_pq* pq, double* span_ms, uint64_t* scans);
  * sums, params_out [per_pass][4] = delta, c, eps, ok of each query's table. */
 int mse_debug_pq4_group_max(mse_pq* pq, const mse_codes* c, const float* luts, const float* scales, int n_valid, int per_pass,
                             uint32_t* out, double* params_out);
+/* ---- the flat scan over an allowed-row set (the post-filter of the reference's query_index, moved into the scan) -----------------
+ * Each call returns exactly what its unfiltered form returns on an mse_codes made of the allowed rows alone, in ascending id order, with
+ * the ids mapped back (a searcher's base is treated the same way).  The renumbering is monotone, so every (score desc, id asc) order
+ * falls the same way.  BOTH stages are filtered: the r best by ADC score (+ descriptor bias) are taken among the allowed rows, then the
+ * fp16 exact re-score and the top-k as in the unfiltered call.  Padding is INT64_MIN / MSE_ID_NONE when fewer than k rows are allowed;
+ * rows at or past mse_filter_len(f) are excluded.  A null filter, a filter longer than the codes or made on another device than the
+ * quantiser, and an unknown mode are errors and write nothing, like r or k out of range; the limits on r, k and nq are those of the
+ * unfiltered calls.  The filter must outlive the call.
+ *   MSE_PQ_FILTER_SCAN  the pass over all codes with masked group-maximum kernels (csrc/pq.hip): an excluded vector counts like one past
+ *                       the end of the codes, a group of 64 without an allowed vector is not loaded at all.  Batches share passes
+ *                       (eight, four, two queries) and certify the integer nomination exactly as unfiltered ones do.
+ *   MSE_PQ_FILTER_LIST  no scan: the ADC scores of the filter's ascending id list through the gather kernel of mse_pq_adc_gather (same
+ *                       arithmetic), then the same select, re-score and top-k; one query at a time.
+ *   MSE_PQ_FILTER_AUTO  asks mse_pq_filtered_plan(mse_codes_len(c), mse_filter_count(f), nq) and equals the explicit call at its answer.
+ * Results are identical in every mode.  No allowed row: all padding, nothing is launched.  Codec shapes other than 64 x 256 (which have
+ * no group-maximum scan) take the LIST path whatever the mode.  One-query calls run directly, not through the quantiser's coalescer.
+ * mse_pq_last_uncertified counts the repeats of filtered batch calls too; filtered batches never switch the handle back to four queries
+ * per pass (a sparse filter fails certificates for want of allowed vectors, not because of the data). */
+#define MSE_PQ_FILTER_AUTO 0
+#define MSE_PQ_FILTER_SCAN 1
+#define MSE_PQ_FILTER_LIST 2
+int mse_pq_scan_topk_filtered(mse_pq* pq, const mse_codes* c, const mse_filter* f, mse_searcher* s_or_null, const float* query_f32,
+                              const float* scales, size_t r, size_t k, int mode, int64_t* scores, uint32_t* ids);
+int mse_pq_scan_topk_batch_filtered(mse_pq* pq, const mse_codes* c, const mse_filter* f, mse_searcher* s_or_null, const float* queries_f32,
+                                    size_t nq, const float* scales, size_t r, size_t k, int mode, int64_t* scores, uint32_t* ids);
+int mse_pq_scan_topk_block_filtered(mse_pq* pq, const mse_codes* c, const mse_filter* f, mse_searcher* s_or_null, const float* queries_f32,
+                                    size_t nq, const float* scales, size_t r, size_t k, int mode, uint64_t id_offset, void* block_dev);
+/* Pure host function: *mode_out = MSE_PQ_FILTER_SCAN or _LIST for nq queries over n_codes rows of which `allowed` pass the filter.  The
+ * crossover comes from byte counts plus a fixed cost per LIST query (csrc/api_pq.hip); its two constants were set against one run of
+ * scripts/filtered_pq_probe.py and remain provisional.  It is monotone (once LIST is chosen, fewer allowed rows never flip it back) and
+ * LIST for allowed = 0.  allowed > n_codes and nq = 0 are errors. */
+int mse_pq_filtered_plan(size_t n_codes, size_t allowed, size_t nq, int* mode_out);
+/* test hooks: mse_debug_pq_group_max / mse_debug_pq4_group_max through the MASKED kernels -- the maximum over the ALLOWED vectors of each
+ * group; a group without one gives INT64_MIN (one and two queries per pass) or the zero-sum key 0 (four and eight). */
+int mse_debug_pq_group_max_filtered(mse_pq* pq, const mse_codes* c, const mse_filter* f, const float* lut0, const float* lut1,
+                                    const float* scales, int64_t* out0, int64_t* out1);
+int mse_debug_pq4_group_max_filtered(mse_pq* pq, const mse_codes* c, const mse_filter* f, const float* luts, const float* scales, int n_valid,
+                                     int per_pass, uint32_t* out, double* params_out);
 /* descriptor_product (src/query_disk_index.rs:135-142) for one id, host-side helper. */
 int64_t mse_descriptor_product(const float* scales, size_t n_descriptors, const uint8_t* descriptors, uint32_t id);
 
@@ -742,6 +780,13 @@ int mse_graph_insert_rows_dev(mse_searcher* s, mse_graph* g, mse_pq* pq_or_null,
  * index (mse_index). */
 int mse_graph_compact(mse_searcher* s, const mse_graph* g, const mse_codes* codes_or_null, size_t capacity, mse_base** base_out,
                       mse_codes** codes_out, mse_graph** graph_out, uint32_t* old_to_new, uint32_t* new_to_old, uint64_t stats_out[4]);
+/* The live rows of a graph as a row filter, so that the flat scans (mse_pq_scan_topk*_filtered, mse_bruteforce_topk_filtered_f16,
+ * mse_index_search_filtered) can serve a mutated index without compacting it.  Returns a fresh, immutable filter over mse_graph_len(g)
+ * rows (free it with mse_filter_free): a bit is set where the row is NOT in the graph's deleted map and -- with and_has_url != 0 and a
+ * has_url array present -- has_url != 0.  Built on the device; it is a SNAPSHOT, taken with the graph's entry lock held shared (as
+ * mse_graph_compact reads the graph): later deletes, restores and inserts need a new filter.  A graph that was never deleted from gives
+ * an all-ones filter.  NULL on error. */
+mse_filter* mse_graph_live_filter(const mse_graph* g, int and_has_url);
 /* measurement hook of the row-gather kernel of mse_graph_compact (for scripts/graph_compact_probe.py): *last_gather_ms (or null)
  * receives the HIP-event time of that kernel in the last mse_graph_compact made on s while the switch was on (0: none), then the
  * switch is set (0 off, 1 on, 2 on and reset).  The kernel reads n_live and writes capacity rows of 2 d + code_size + n_desc bytes. */

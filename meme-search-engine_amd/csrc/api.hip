@@ -809,6 +809,31 @@ void mse_filter_free(mse_filter* f) {
     if (f->ids) (void)hipFree(f->ids);
     delete f;
 }
+// The live rows of a graph as a filter: bit set where the row is not in the deleted map (and, with and_has_url and a has_url array, where
+// has_url != 0).  Built on the device -- the NOT of the deleted words, filter.hip's and_flags_kernel in place, then the usual compaction
+// -- under the graph's entry lock held shared, as mse_graph_compact reads it: a delete, restore or insert on another thread is wholly
+// before or wholly after the snapshot.  The filter is a fresh object and immutable; later changes of the graph do not reach it.
+mse_filter* mse_graph_live_filter(const mse_graph* g, int and_has_url) {
+    if (!g) { fail("graph_live_filter: null graph"); return nullptr; }
+    if (g->adj) {   // the filter belongs to the device the graph's arrays live on
+        hipPointerAttribute_t at{};
+        if (hipPointerGetAttributes(&at, g->adj) != hipSuccess) { (void)hipGetLastError(); fail("graph_live_filter: the graph's arrays are not device memory"); return nullptr; }
+        if (hipSetDevice(at.device) != hipSuccess) { fail("graph_live_filter: hipSetDevice failed"); return nullptr; }
+    }
+    mse_filter* f = nullptr;
+    {
+        g->entry_lock.lock_shared();
+        struct Hold { mse::SharedExclusive& l; ~Hold() { l.unlock_shared(); } } hold{g->entry_lock};
+        f = filter_alloc(g->n);
+        if (!f) return nullptr;
+        bool ok = launch_filter_live(g->deleted, g->n, f->n_words, f->words, nullptr) == 0;
+        if (ok && and_has_url && g->has_url) ok = launch_filter_and_flags(f->words, f->n_words, g->has_url, g->n, f->words, nullptr) == 0;
+        if (ok && hipStreamSynchronize(nullptr) != hipSuccess) { ok = false; fail("graph_live_filter: the device pass failed"); }
+        if (!ok) { mse_filter_free(f); return nullptr; }
+    }
+    return filter_finish(f);   // (reads the new bitmap only: the graph may change again)
+}
+
 size_t mse_filter_len(const mse_filter* f) { return f ? f->n_rows : 0; }
 size_t mse_filter_count(const mse_filter* f) { return f ? f->count : 0; }
 

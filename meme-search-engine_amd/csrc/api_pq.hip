@@ -520,9 +520,12 @@ static int prep_table(mse_pq* pq, mse_searcher* s, const float* query_dev, float
 
 // everything after the scan of one query.  gmax: the scan's group maxima [n_groups] (i64), or null when the codec shape has no
 // group-maximum scan (then every vector is scored here).
+// f (or null): the filter of a filtered call.  With gmax (the masked scan's maxima) the disallowed vectors of the nominated groups are
+// dropped at the expansion; without gmax -- the LIST mode, and every other codec shape under a filter -- the ADC scores of the filter's
+// ascending id list are taken by the gather kernel and the tournament runs over list positions, which order as their ids do.
 static int scan_tail_async(mse_pq* pq, const mse_codes* c, mse_searcher* s, const int64_t* gmax, const float* query_dev,
                            const float* lut_dev, uint16_t* qf16_dev, const float* scales_dev, size_t r, size_t k,
-                           int64_t* out_scores_dev, uint32_t* out_ids_dev) {
+                           int64_t* out_scores_dev, uint32_t* out_ids_dev, const mse_filter* f = nullptr) {
     hipStream_t st = s->stream;
     const size_t d = pq->d;
     const uint8_t* desc = scales_dev ? c->desc : nullptr;
@@ -537,7 +540,9 @@ static int scan_tail_async(mse_pq* pq, const mse_codes* c, mse_searcher* s, cons
         uint32_t* gsel = nullptr;
         LevelRef l0{KEY_I64, const_cast<int64_t*>(gmax), n_groups, 1, n_groups, false, 0};
         if (descend(s, l0, 1, (int)rg, &gsel, s->gkeys.p)) return -1;
-        if (launch_expand_groups(gsel, rg, rg, 64, c->n, s->cand_ids.as<uint32_t>(), rg * 64, 1, st)) return -1;
+        if (f ? launch_expand_groups_masked(gsel, rg, rg, 64, c->n, f->words, f->n_words, s->cand_ids.as<uint32_t>(), rg * 64, 1, st)
+              : launch_expand_groups(gsel, rg, rg, 64, c->n, s->cand_ids.as<uint32_t>(), rg * 64, 1, st)) return -1;
+        // (a dropped vector is ID_NONE: the gather kernel scores it INT64_MIN and the select skips it)
         if (launch_pq_adc(lut_dev, (int)pq->n_chunks, (int)pq->n_centroids, c->codes, c->n, s->cand_ids.as<uint32_t>(), rg * 64,
                           desc, (int)c->n_desc, scales_dev, s->cand_scores.as<int64_t>(), s->n_cu, st)) return -1;
         SelectArgs a{};
@@ -546,9 +551,20 @@ static int scan_tail_async(mse_pq* pq, const mse_codes* c, mse_searcher* s, cons
         // r group maxima reach the r-th best group's key, so r vectors do: the key is a floor for the select.  This leans on the
         // scan kernels and pq_adc_kernel producing the SAME i64 for a vector (same adds in the same order, bias added after the
         // conversion); tests/test_gpu_pq_index_graph.py::test_group_maxima_equal_the_gathered_scores pins exactly that.
+        // Under a filter the maxima are over ALLOWED vectors, so the argument holds as long as the r-th key belongs to a group with an
+        // allowed vector.  When fewer than r groups have one, the r-th key is INT64_MIN, whose sortable form is 0: a floor of 0 cuts
+        // nothing, and padding (ID_NONE) is skipped by the select before the floor is looked at (topk.hip), so it is never admitted.
         if (rg == r) a.floor_hi = s->last_kth;
         if (launch_select(a, st)) return -1;
         top_ids = s->out_ids.as<uint32_t>();
+    } else if (f) {
+        const size_t m = f->count;   // (> 0: the entry points answer an empty filter without a launch)
+        if (s->scores.ensure(m * 8)) return -1;
+        if (launch_pq_adc(lut_dev, (int)pq->n_chunks, (int)pq->n_centroids, c->codes, c->n, f->ids, m, desc, (int)c->n_desc,
+                          scales_dev, s->scores.as<int64_t>(), s->n_cu, st)) return -1;
+        LevelRef l0{KEY_I64, s->scores.p, m, 1, m, false, 0};
+        if (descend(s, l0, 1, (int)r, &top_ids, s->sel_keys.p)) return -1;
+        if (launch_map_positions(top_ids, r, f->ids, st)) return -1;
     } else {
         // other codec shapes: every vector's score, then the tournament over them
         if (s->scores.ensure(c->n * 8)) return -1;
@@ -586,10 +602,11 @@ static int scan_tail_async(mse_pq* pq, const mse_codes* c, mse_searcher* s, cons
 // prepared: lut_dev already holds this group's tables (the batch entry point builds all tables of a call in two launches)
 static int scan_topk_async(mse_pq* pq, const mse_codes* c, mse_searcher* s, const float* queries_dev, int n_q, float* t_dev,
                            float* lut_dev, uint16_t* qf16_dev, const float* scales_dev, size_t r, size_t k,
-                           int64_t* out_scores_dev, uint32_t* out_ids_dev, bool prepared = false) {
+                           int64_t* out_scores_dev, uint32_t* out_ids_dev, bool prepared = false, const mse_filter* f = nullptr,
+                           bool list = false /* filtered: skip the scan, score the filter's id list (scan_tail_async) */) {
     const size_t d = pq->d, lut_floats = pq->n_chunks * pq->n_centroids;
     const uint8_t* desc = scales_dev ? c->desc : nullptr;
-    const bool gm = pq_scan_gmax_supported((int)pq->n_chunks, (int)pq->n_centroids, desc, (int)c->n_desc, scales_dev);
+    const bool gm = !list && pq_scan_gmax_supported((int)pq->n_chunks, (int)pq->n_centroids, desc, (int)c->n_desc, scales_dev);
     for (int j = 0; j < n_q && !prepared; j++)
         if (prep_table(pq, s, queries_dev + j * d, t_dev + j * d, lut_dev + j * lut_floats)) return -1;
     const size_t n_groups = (c->n + 63) / 64;
@@ -600,12 +617,14 @@ static int scan_topk_async(mse_pq* pq, const mse_codes* c, mse_searcher* s, cons
         g0 = s->scores.as<int64_t>();
         g1 = s->gmax.as<int64_t>();
         if (n_q == 2) {
-            if (launch_pq_scan_gmax2(lut_dev, lut_dev + lut_floats, c->codes, c->n, desc, scales_dev, g0, g1, s->n_cu, s->stream)) return -1;
-        } else if (launch_pq_scan_gmax(lut_dev, c->codes, c->n, desc, scales_dev, g0, s->n_cu, s->stream)) return -1;
+            if (launch_pq_scan_gmax2(lut_dev, lut_dev + lut_floats, c->codes, c->n, desc, scales_dev, g0, g1, s->n_cu, s->stream,
+                                     f ? f->words : nullptr, f ? f->n_words : 0)) return -1;
+        } else if (launch_pq_scan_gmax(lut_dev, c->codes, c->n, desc, scales_dev, g0, s->n_cu, s->stream, f ? f->words : nullptr,
+                                       f ? f->n_words : 0)) return -1;
     }
     for (int j = 0; j < n_q; j++)
         if (scan_tail_async(pq, c, s, gm ? (j ? g1 : g0) : nullptr, queries_dev + j * d, lut_dev + j * lut_floats, qf16_dev, scales_dev,
-                            r, k, out_scores_dev + j * k, out_ids_dev + j * k)) return -1;
+                            r, k, out_scores_dev + j * k, out_ids_dev + j * k, f)) return -1;
     return 0;
 }
 
@@ -621,7 +640,7 @@ static int scan_topk_async(mse_pq* pq, const mse_codes* c, mse_searcher* s, cons
 static size_t pq_nominated(size_t r, int NQ) { return NQ == 4 ? r + std::max<size_t>(64, r / 2) : 2 * r + 112; }
 static int scan_topk4_async(mse_pq* pq, const mse_codes* c, mse_searcher* s, const float* queries_dev, float* t_dev, float* lut_dev,
                             uint16_t* qf16_dev, const float* scales_dev, size_t r, size_t k, int64_t* out_scores_dev,
-                            uint32_t* out_ids_dev, int* flags_dev, bool prepared, int NQ) {
+                            uint32_t* out_ids_dev, int* flags_dev, bool prepared, int NQ, const mse_filter* f = nullptr) {
     hipStream_t st = s->stream;
     const size_t d = pq->d, lut_floats = pq->n_chunks * pq->n_centroids;
     const uint8_t* desc = scales_dev ? c->desc : nullptr;
@@ -648,7 +667,8 @@ static int scan_topk4_async(mse_pq* pq, const mse_codes* c, mse_searcher* s, con
         s->ev_used += 2;
         MSE_HIP_TRY(hipEventRecord(te0, st));
     }
-    if (launch_pq_scan_gmax4(table, c->codes, c->n, desc, s->gmax.as<uint32_t>(), s->n_cu, st, NQ)) return -1;
+    if (launch_pq_scan_gmax4(table, c->codes, c->n, desc, s->gmax.as<uint32_t>(), s->n_cu, st, NQ, f ? f->words : nullptr, f ? f->n_words : 0))
+        return -1;
     if (te1) MSE_HIP_TRY(hipEventRecord(te1, st));
     // the NQ tails as ONE chain of launches with a query dimension (their kernels are latency-bound: four chains in a row cost more
     // than the scan); every buffer at its final size before the first kernel that uses it
@@ -680,7 +700,8 @@ static int scan_topk4_async(mse_pq* pq, const mse_codes* c, mse_searcher* s, con
     }
 #endif
     if (descend(s, l0, NQ, (int)n_sel, &gsel, s->gkeys.p)) return -1;                      // gsel [NQ][n_sel], gkeys u32 [NQ][n_sel]
-    if (launch_expand_groups(gsel, n_sel, n_nom, 64, c->n, s->cand_ids.as<uint32_t>(), n_cand, NQ, st)) return -1;
+    if (f ? launch_expand_groups_masked(gsel, n_sel, n_nom, 64, c->n, f->words, f->n_words, s->cand_ids.as<uint32_t>(), n_cand, NQ, st)
+          : launch_expand_groups(gsel, n_sel, n_nom, 64, c->n, s->cand_ids.as<uint32_t>(), n_cand, NQ, st)) return -1;
     if (launch_pq_adc(lut_dev, (int)pq->n_chunks, (int)pq->n_centroids, c->codes, c->n, s->cand_ids.as<uint32_t>(), n_cand, desc,
                       (int)c->n_desc, scales_dev, s->cand_scores.as<int64_t>(), s->n_cu, st, NQ, n_cand)) return -1;
     {
@@ -689,8 +710,11 @@ static int scan_topk4_async(mse_pq* pq, const mse_codes* c, mse_searcher* s, con
         a.n_list = n_cand; a.k = (int)r; a.out_ids = s->out_ids.as<uint32_t>(); a.out_keys = s->sel_keys.p; a.out_stride = r; a.nq = NQ;
         if (launch_select(a, st)) return -1;
     }
+    // the vectors that must exist among the nominated: min(r, rows) -- under a filter min(r, allowed rows).  The bound from the best
+    // excluded group stays sound there: its masked maximum bounds every ALLOWED vector outside the nominated groups, and a masked
+    // vector's key (the all-zero sum) is the smallest possible
     if (launch_pq4_certify(params, s->gkeys.as<uint32_t>(), (int)n_nom, (int)n_sel, s->out_ids.as<uint32_t>(), s->sel_keys.as<int64_t>(), r,
-                           (int)std::min(r, c->n), NQ, flags_dev, st)) return -1;
+                           (int)std::min(r, f ? f->count : c->n), NQ, flags_dev, st)) return -1;
     const uint32_t* top_ids = s->out_ids.as<uint32_t>();      // [NQ][r]
     const int64_t* top_scores = s->sel_keys.as<int64_t>();
     size_t top_stride = r;
@@ -714,8 +738,10 @@ static int scan_topk4_async(mse_pq* pq, const mse_codes* c, mse_searcher* s, con
 }
 
 // (a sharded scan hands its results over as a packed block on the device: launch_block_finish, topk.hip)
+// f (or null) / list: the filtered entry points further down (the unfiltered ones pass null and take exactly the launches they always took)
 static int pq_scan_topk_batch_impl(mse_pq* pq, const mse_codes* c, mse_searcher* s_or_null, const float* queries_f32, size_t nq,
-                                   const float* scales, size_t r, size_t k, int64_t* scores, uint32_t* ids, uint64_t id_offset, void* block_dev);
+                                   const float* scales, size_t r, size_t k, int64_t* scores, uint32_t* ids, uint64_t id_offset, void* block_dev,
+                                   const mse_filter* f = nullptr, bool list = false);
 
 int mse_pq_scan_topk_batch(mse_pq* pq, const mse_codes* c, mse_searcher* s_or_null, const float* queries_f32, size_t nq,
                            const float* scales, size_t r, size_t k, int64_t* scores, uint32_t* ids) {
@@ -730,7 +756,8 @@ int mse_pq_scan_topk_block(mse_pq* pq, const mse_codes* c, mse_searcher* s_or_nu
 }
 
 static int pq_scan_topk_batch_impl(mse_pq* pq, const mse_codes* c, mse_searcher* s_or_null, const float* queries_f32, size_t nq,
-                                   const float* scales, size_t r, size_t k, int64_t* scores, uint32_t* ids, uint64_t id_offset, void* block_dev) {
+                                   const float* scales, size_t r, size_t k, int64_t* scores, uint32_t* ids, uint64_t id_offset, void* block_dev,
+                                   const mse_filter* f, bool list) {
     if (!pq || !c) return fail("null quantiser or codes");
     if (c->code_size != pq->n_chunks) return fail("code size does not match the quantiser");
     if (k == 0 || nq == 0) return 0;
@@ -738,7 +765,7 @@ static int pq_scan_topk_batch_impl(mse_pq* pq, const mse_codes* c, mse_searcher*
     if (r > (size_t)TOPK_KMAX - 64) return fail("r too large (max 1984)");
     if (!block_dev)
         for (size_t i = 0; i < nq * k; i++) { scores[i] = INT64_MIN; ids[i] = MSE_ID_NONE; }
-    if (c->n == 0) {
+    if (c->n == 0 || (f && f->count == 0)) {   // (no allowed row: everything is padding, no scan is launched)
         if (block_dev) {   // an empty shard still hands over a block: all slots empty
             if (launch_block_finish(nullptr, nullptr, nq * k, 0, reinterpret_cast<int64_t*>(block_dev), reinterpret_cast<uint32_t*>(static_cast<char*>(block_dev) + nq * k * 8), nullptr)) return -1;
             MSE_HIP_TRY(hipStreamSynchronize(nullptr));
@@ -813,7 +840,8 @@ static int pq_scan_topk_batch_impl(mse_pq* pq, const mse_codes* c, mse_searcher*
             break;
         if (lanes[1] && hipStreamSynchronize(st) != hipSuccess) { fail("memset failed"); break; }
         const uint8_t* desc_dev = scales_dev ? c->desc : nullptr;
-        const bool four_ok = pq_scan_gmax_supported((int)pq->n_chunks, (int)pq->n_centroids, desc_dev, (int)c->n_desc, scales_dev) &&
+        // (a filtered LIST call shares no pass over the codes: its queries go one by one, still alternating between the streams)
+        const bool four_ok = !list && pq_scan_gmax_supported((int)pq->n_chunks, (int)pq->n_centroids, desc_dev, (int)c->n_desc, scales_dev) &&
                              r + std::max<size_t>(64, r / 2) + 1 <= (size_t)TOPK_KMAX;
         // eight per pass while the 8-bit certificate holds for this quantiser's data: a batch in which more than an eighth of the
         // eight-per-pass queries had to be repeated through the exact scan switches the handle back to four per pass for good
@@ -822,19 +850,19 @@ static int pq_scan_topk_batch_impl(mse_pq* pq, const mse_codes* c, mse_searcher*
         bool ok = true;
         size_t q = 0;
         for (size_t unit = 0; q < nq && ok; unit++) {
-            const int n_q = (eight_ok && nq - q >= 8) ? 8 : (four_ok && nq - q >= 4) ? 4 : nq - q >= 2 ? 2 : 1;
+            const int n_q = (eight_ok && nq - q >= 8) ? 8 : (four_ok && nq - q >= 4) ? 4 : (nq - q >= 2 && !list) ? 2 : 1;
             const int w = (int)(unit % (size_t)n_lanes);
             float* const tw = prep_all ? pq->b.as<float>() + q * d : w ? t2.as<float>() : pq->b.as<float>();     // (several lanes imply prep_all)
             float* const lw = prep_all ? pq->c.as<float>() + q * lut_floats_b : w ? lut2.as<float>() : pq->c.as<float>();
             uint16_t* const qw = qfs[w]->as<uint16_t>();
             if (n_q >= 4) {
                 ok = scan_topk4_async(pq, c, lanes[w], pq->a.as<float>() + q * d, tw, lw, qw, scales_dev, r, k, out_scores_dev + q * k,
-                                      out_ids_dev + q * k, flags_dev + q, prep_all, n_q) == 0;
+                                      out_ids_dev + q * k, flags_dev + q, prep_all, n_q, f) == 0;
                 if (n_q == 8) for (int j = 0; j < 8; j++) in_eight[q + j] = 1;
             }
             else
                 ok = scan_topk_async(pq, c, lanes[w], pq->a.as<float>() + q * d, n_q, tw, lw, qw, scales_dev, r, k,
-                                     out_scores_dev + q * k, out_ids_dev + q * k, prep_all) == 0;
+                                     out_scores_dev + q * k, out_ids_dev + q * k, prep_all, f, list) == 0;
             q += n_q;
         }
         for (int w = 1; w < n_lanes; w++)
@@ -849,13 +877,15 @@ static int pq_scan_topk_batch_impl(mse_pq* pq, const mse_codes* c, mse_searcher*
             pq->last_uncertified = 0;
             size_t n8 = 0, bad8 = 0;
             for (size_t j = 0; j < nq; j++) { n8 += in_eight[j]; bad8 += in_eight[j] && !flags[j]; }
-            if (n8 && bad8 * 8 > n8) pq->avoid8 = true;
+            // filtered batches are left out of this decision: a sparse filter legitimately fails more certificates (fewer than r allowed
+            // vectors among the nominated groups), which says nothing about the quantiser's data
+            if (!f && n8 && bad8 * 8 > n8) pq->avoid8 = true;
             for (size_t j = 0; j < nq && ok; j++)
                 if (!flags[j]) {
                     pq->last_uncertified++;
                     ok = scan_topk_async(pq, c, s, pq->a.as<float>() + j * d, 1, pq->b.as<float>() + (prep_all ? j * d : 0),
                                          pq->c.as<float>() + (prep_all ? j * lut_floats_b : 0), s->q_stage.as<uint16_t>(), scales_dev, r, k,
-                                         out_scores_dev + j * k, out_ids_dev + j * k, prep_all) == 0;
+                                         out_scores_dev + j * k, out_ids_dev + j * k, prep_all, f) == 0;
                 }
             if (!ok) { if (std::string(mse_last_error()).empty()) fail("scan failed"); break; }
         }
@@ -899,8 +929,27 @@ static int pq_scan_topk_batch_impl(mse_pq* pq, const mse_codes* c, mse_searcher*
 
 // test hook: the group maxima the flat scan nominates with -- lut1 == null: pq_scan64_kernel<true> for one table; otherwise
 // pq_scan64x2_kernel for the pair.  out0 / out1: [ceil(n / 64)] i64 on the host.
+static int check_pq_filter(const mse_pq* pq, const mse_codes* c, const mse_filter* f) {
+    if (!f) return fail("null filter");
+    if (f->n_rows > c->n) return fail("filter is longer than the codes (" + std::to_string(f->n_rows) + " > " + std::to_string(c->n) + " rows)");
+    if (f->device != pq->device) return fail("filter was made on another device than the quantiser's");   // no silent copy
+    return 0;
+}
+static int debug_pq_group_max(mse_pq* pq, const mse_codes* c, const mse_filter* f, const float* lut0, const float* lut1, const float* scales,
+                              int64_t* out0, int64_t* out1);
 int mse_debug_pq_group_max(mse_pq* pq, const mse_codes* c, const float* lut0, const float* lut1, const float* scales, int64_t* out0,
                            int64_t* out1) {
+    return debug_pq_group_max(pq, c, nullptr, lut0, lut1, scales, out0, out1);
+}
+// ... and the MASKED instantiations' maxima (INT64_MIN for a group without an allowed vector)
+int mse_debug_pq_group_max_filtered(mse_pq* pq, const mse_codes* c, const mse_filter* f, const float* lut0, const float* lut1,
+                                    const float* scales, int64_t* out0, int64_t* out1) {
+    if (!pq || !c) return fail("null argument");
+    if (check_pq_filter(pq, c, f)) return -1;
+    return debug_pq_group_max(pq, c, f, lut0, lut1, scales, out0, out1);
+}
+static int debug_pq_group_max(mse_pq* pq, const mse_codes* c, const mse_filter* f, const float* lut0, const float* lut1, const float* scales,
+                              int64_t* out0, int64_t* out1) {
     if (!pq || !c || !lut0 || !out0 || (lut1 && !out1)) return fail("null argument");
     if (c->code_size != pq->n_chunks) return fail("code size does not match the quantiser");
     const uint8_t* desc = (scales && c->n_desc) ? c->desc : nullptr;
@@ -918,8 +967,10 @@ int mse_debug_pq_group_max(mse_pq* pq, const mse_codes* c, const float* lut0, co
     if (desc) MSE_HIP_TRY(hipMemcpy(sc, scales, c->n_desc * 4, hipMemcpyHostToDevice));
     int64_t* g0 = pq->c.as<int64_t>();
     int64_t* g1 = g0 + n_groups;
-    const int rc = lut1 ? launch_pq_scan_gmax2(l0, l1, c->codes, c->n, desc, desc ? sc : nullptr, g0, g1, device_cu_count(), nullptr)
-                        : launch_pq_scan_gmax(l0, c->codes, c->n, desc, desc ? sc : nullptr, g0, device_cu_count(), nullptr);
+    const uint32_t* mw = f ? f->words : nullptr;
+    const size_t mn = f ? f->n_words : 0;
+    const int rc = lut1 ? launch_pq_scan_gmax2(l0, l1, c->codes, c->n, desc, desc ? sc : nullptr, g0, g1, device_cu_count(), nullptr, mw, mn)
+                        : launch_pq_scan_gmax(l0, c->codes, c->n, desc, desc ? sc : nullptr, g0, device_cu_count(), nullptr, mw, mn);
     if (rc) return -1;
     MSE_HIP_TRY(hipMemcpy(out0, g0, n_groups * 8, hipMemcpyDeviceToHost));
     if (lut1) MSE_HIP_TRY(hipMemcpy(out1, g1, n_groups * 8, hipMemcpyDeviceToHost));
@@ -983,8 +1034,21 @@ mse_codes* mse_codes_quantize_base(mse_pq* pq, const mse_base* b, const uint8_t*
 // test hook: the integer nomination scan by itself -- the four queries' group maxima (u32, [4][ceil(n / 64)]) and their
 // certificate parameters (params_out [4][4] = delta, c, eps, ok), so that a test can rebuild the 12-bit tables on the host and
 // check every maximum of the matrix-core scan against plain integer sums
+static int debug_pq4_group_max(mse_pq* pq, const mse_codes* c, const mse_filter* f, const float* luts4, const float* scales, int n_valid,
+                               int per_pass, uint32_t* out, double* params_out);
 int mse_debug_pq4_group_max(mse_pq* pq, const mse_codes* c, const float* luts4, const float* scales, int n_valid, int per_pass, uint32_t* out,
                             double* params_out) {
+    return debug_pq4_group_max(pq, c, nullptr, luts4, scales, n_valid, per_pass, out, params_out);
+}
+// ... and the MASKED instantiations' maxima (the zero-sum key 0 for a group without an allowed vector)
+int mse_debug_pq4_group_max_filtered(mse_pq* pq, const mse_codes* c, const mse_filter* f, const float* luts4, const float* scales, int n_valid,
+                                     int per_pass, uint32_t* out, double* params_out) {
+    if (!pq || !c) return fail("null argument");
+    if (check_pq_filter(pq, c, f)) return -1;
+    return debug_pq4_group_max(pq, c, f, luts4, scales, n_valid, per_pass, out, params_out);
+}
+static int debug_pq4_group_max(mse_pq* pq, const mse_codes* c, const mse_filter* f, const float* luts4, const float* scales, int n_valid,
+                               int per_pass, uint32_t* out, double* params_out) {
     if (!pq || !c || !luts4 || !out || !params_out) return fail("null argument");
     if (per_pass != 4 && per_pass != 8) return fail("per_pass must be 4 or 8");
     const size_t NQ = (size_t)per_pass;
@@ -1001,7 +1065,8 @@ int mse_debug_pq4_group_max(mse_pq* pq, const mse_codes* c, const float* luts4, 
     if (desc) MSE_HIP_TRY(hipMemcpy(sc, scales, 16, hipMemcpyHostToDevice));
     Pq4Params* params = reinterpret_cast<Pq4Params*>(pq->b.as<char>() + pq4_table_bytes());
     if (launch_pq4_table(pq->a.as<float>(), desc ? sc : nullptr, n_valid, pq->b.p, params, nullptr, per_pass)) return -1;
-    if (launch_pq_scan_gmax4(pq->b.p, c->codes, c->n, desc, pq->c.as<uint32_t>(), device_cu_count(), nullptr, per_pass)) return -1;
+    if (launch_pq_scan_gmax4(pq->b.p, c->codes, c->n, desc, pq->c.as<uint32_t>(), device_cu_count(), nullptr, per_pass, f ? f->words : nullptr,
+                             f ? f->n_words : 0)) return -1;
     Pq4Params ph[8];
     {   // the scan writes group-major [n_groups][NQ]; the hook hands out [NQ][n_groups]
         std::vector<uint32_t> gm(NQ * n_groups);
@@ -1089,6 +1154,71 @@ int mse_pq_scan_topk(mse_pq* pq, const mse_codes* c, mse_searcher* s_or_null, co
     q.queries = query_f32; q.nq = 1; q.k = k; q.out_a = scores; q.out_b = ids;
     q.aux0 = c; q.aux1 = s_or_null; q.aux2 = (scales && c->n_desc) ? scales : nullptr; q.aux_n = r;
     return pq->co->submit(q);
+}
+
+// ---- the flat scan over an allowed-row set (include/mse.h) ----
+// Where LIST overtakes SCAN.  The rule is a count of bytes:
+//   SCAN streams 64 code bytes + 4 descriptor bytes for every one of the n rows, once per PASS; a batch of nq queries makes
+//        nq / 8 passes of eight, then one of four, one pair and one single for what is left (pq_scan_topk_batch_impl);
+//   LIST gathers one 64-byte code row + 4 descriptor bytes per allowed row PER QUERY.  A gathered 64-byte row occupies half of a
+//        128-byte line, so unless its neighbour is allowed too it moves twice its size: PQ_LIST_BYTE_COST = 2.
+// That alone -- LIST when nq * allowed * 2 <= passes * n -- was the first, unmeasured form.  Measured once (scripts/filtered_pq_probe.py,
+// profiles/filtered_pq_probe.json: one MI355X, 1e7 codes, r 200) the curves cross at allowed / n = 0.42 for one query (the rule: 0.5,
+// i.e. a byte cost of 2.4 against the assumed 2: kept), but at 0.020 for eight and 0.0022 for thirty-two queries where the rule said
+// 0.0625 for both: a LIST query is a chain of small launches (gather, tournament, map, re-score) that costs ~0.04 ms whatever the
+// list's length and does not overlap its neighbours the way the tails of batched scans do.  So a FIXED cost per LIST query was added,
+// in streamed-byte equivalents: PQ_LIST_FIXED_BYTES = 1.2e6 rows x 68 B.  With it the rule gives 0.44 / 0.0025 / 0.0025 at the three
+// batch sizes: right for 1 and 32, cautious for 8 (between 0.0025 and 0.02 it keeps the masked scan, which is at most 12 % slower
+// there).  One box, one size: both constants stay PROVISIONAL; at 1e8 codes the fixed term matters a tenth as much.
+// Monotone in `allowed` by construction; an index below 1.2e6 rows always scans (unless nothing is allowed).
+static constexpr double PQ_ROW_BYTES = 68.0, PQ_LIST_BYTE_COST = 2.0, PQ_LIST_FIXED_BYTES = 1.2e6 * 68.0;
+int mse_pq_filtered_plan(size_t n_codes, size_t allowed, size_t nq, int* mode_out) {
+    if (!mode_out) return fail("pq_filtered_plan: null argument");
+    if (allowed > n_codes) return fail("pq_filtered_plan: more allowed rows than codes");
+    if (nq == 0) return fail("pq_filtered_plan: nq must be positive");
+    const size_t rem = nq % 8;
+    const size_t passes = nq / 8 + (rem >= 4 ? 1 : 0) + ((rem % 4) >= 2 ? 1 : 0) + (rem % 2);
+    // (in double: the products pass 2^64 only far beyond any real call, but the comparison must not wrap)
+    const double list_cost = (double)nq * ((double)allowed * PQ_ROW_BYTES * PQ_LIST_BYTE_COST + PQ_LIST_FIXED_BYTES);
+    const double scan_cost = (double)passes * (double)n_codes * PQ_ROW_BYTES;
+    *mode_out = (allowed == 0 || list_cost <= scan_cost) ? MSE_PQ_FILTER_LIST : MSE_PQ_FILTER_SCAN;
+    return 0;
+}
+
+// argument checks of the three filtered entry points: all before anything is written; *list = the resolved mode is LIST
+static int pq_filtered_args(mse_pq* pq, const mse_codes* c, const mse_filter* f, const mse_searcher* s, size_t nq, size_t r, size_t k, int mode,
+                            bool* list) {
+    if (!pq || !c) return fail("null quantiser or codes");
+    if (check_pq_filter(pq, c, f)) return -1;
+    if (mode != MSE_PQ_FILTER_AUTO && mode != MSE_PQ_FILTER_SCAN && mode != MSE_PQ_FILTER_LIST) return fail("unknown mode");
+    if (c->code_size != pq->n_chunks) return fail("code size does not match the quantiser");
+    if (std::max(r, k) > (size_t)TOPK_KMAX - 64) return fail("r too large (max 1984)");
+    if (s && s->base && s->base->n != c->n) return fail("base and codes differ in length");
+    if (s && s->base && s->base->d != pq->d) return fail("base width differs from the quantiser");
+    if (mode == MSE_PQ_FILTER_AUTO && nq && mse_pq_filtered_plan(c->n, f->count, nq, &mode)) return -1;
+    *list = mode == MSE_PQ_FILTER_LIST;
+    return 0;
+}
+int mse_pq_scan_topk_batch_filtered(mse_pq* pq, const mse_codes* c, const mse_filter* f, mse_searcher* s_or_null, const float* queries_f32,
+                                    size_t nq, const float* scales, size_t r, size_t k, int mode, int64_t* scores, uint32_t* ids) {
+    bool list = false;
+    if (pq_filtered_args(pq, c, f, s_or_null, nq, r, k, mode, &list)) return -1;
+    if (nq == 0 || k == 0) return 0;
+    if (!queries_f32 || !scores || !ids) return fail("null argument");
+    return pq_scan_topk_batch_impl(pq, c, s_or_null, queries_f32, nq, scales, r, k, scores, ids, 0, nullptr, f, list);
+}
+// (one query per call: straight to the batch path -- filtered calls do not meet in the quantiser's coalescer)
+int mse_pq_scan_topk_filtered(mse_pq* pq, const mse_codes* c, const mse_filter* f, mse_searcher* s_or_null, const float* query_f32,
+                              const float* scales, size_t r, size_t k, int mode, int64_t* scores, uint32_t* ids) {
+    return mse_pq_scan_topk_batch_filtered(pq, c, f, s_or_null, query_f32, 1, scales, r, k, mode, scores, ids);
+}
+int mse_pq_scan_topk_block_filtered(mse_pq* pq, const mse_codes* c, const mse_filter* f, mse_searcher* s_or_null, const float* queries_f32,
+                                    size_t nq, const float* scales, size_t r, size_t k, int mode, uint64_t id_offset, void* block_dev) {
+    bool list = false;
+    if (pq_filtered_args(pq, c, f, s_or_null, nq, r, k, mode, &list)) return -1;
+    if (nq == 0 || k == 0) return 0;
+    if (!queries_f32 || !block_dev) return fail("null argument");
+    return pq_scan_topk_batch_impl(pq, c, s_or_null, queries_f32, nq, scales, r, k, nullptr, nullptr, id_offset, block_dev, f, list);
 }
 
 int64_t mse_descriptor_product(const float* scales, size_t n_descriptors, const uint8_t* descriptors, uint32_t id) {

@@ -126,6 +126,20 @@ __global__ void and_flags_kernel(const uint32_t* __restrict__ words, size_t n_wo
     out[w] = in & keep;
 }
 
+// out[w] = NOT deleted[w] for the rows below n_rows (deleted == null: all ones), zero past them: the live rows of a graph as a filter's
+// bitmap (mse_graph_live_filter).  deleted has ceil(n_rows / 32) words, out n_words >= that (the filter's tile padding).
+__global__ void live_words_kernel(const uint32_t* __restrict__ deleted, size_t n_rows, size_t n_words, uint32_t* __restrict__ out) {
+    const size_t w = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= n_words) return;
+    const size_t r0 = w * 32;
+    uint32_t v = 0u;
+    if (r0 < n_rows) {
+        v = deleted ? ~deleted[w] : 0xffffffffu;
+        if (r0 + 32 > n_rows) v &= 0xffffffffu >> (32 - (n_rows - r0));
+    }
+    out[w] = v;
+}
+
 // scores[j][p] += descriptor_product(scales[j], row ids[p]) for the nq (<= 8) queries of a list pass: per term the f32 product is
 // truncated to fixed point, the terms are summed as integers (the beam kernel's bias(pt); src/query_disk_index.rs:135-142).  A row's
 // descriptor bytes are read once for all queries.  The sum wraps like the reference's release build (unsigned add: no overflow trap).
@@ -151,6 +165,13 @@ __global__ void list_bias_kernel(const uint32_t* __restrict__ ids, size_t n, con
 int launch_filter_and_flags(const uint32_t* words, size_t n_words, const uint8_t* has_url, size_t n_rows, uint32_t* out, hipStream_t stream) {
     if (n_words == 0) return 0;
     hipLaunchKernelGGL(and_flags_kernel, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, stream, words, n_words, has_url, n_rows, out);
+    MSE_HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_filter_live(const uint32_t* deleted, size_t n_rows, size_t n_words, uint32_t* out, hipStream_t stream) {
+    if (n_words == 0) return 0;
+    hipLaunchKernelGGL(live_words_kernel, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, stream, deleted, n_rows, n_words, out);
     MSE_HIP_TRY(hipGetLastError());
     return 0;
 }

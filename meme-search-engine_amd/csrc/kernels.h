@@ -105,16 +105,20 @@ int launch_pq_adc(const float* lut, int n_chunks, int n_centroids, const uint8_t
                   const uint32_t* ids, size_t n, const uint8_t* desc, int n_desc, const float* scales, int64_t* out,
                   int n_cu, hipStream_t stream, int nq = 1, size_t q_stride = 0);
 bool pq_scan_gmax_supported(int n_chunks, int n_centroids, const uint8_t* desc, int n_desc, const float* scales);
+// mask (all three group-maximum scans): the bitmap words of an mse_filter -- the masked instantiation, where a vector whose bit is clear
+// (or at / past 32 * mask_words) counts like one past the end of the codes; null: the unfiltered kernel, launched exactly as ever
 int launch_pq_scan_gmax(const float* lut, const uint8_t* codes, size_t n, const uint8_t* desc, const float* scales,
-                        int64_t* gmax, int n_cu, hipStream_t stream);
+                        int64_t* gmax, int n_cu, hipStream_t stream, const uint32_t* mask = nullptr, size_t mask_words = 0);
 int launch_pq_scan_gmax2(const float* lut0, const float* lut1, const uint8_t* codes, size_t n, const uint8_t* desc,
-                         const float* scales, int64_t* gmax0, int64_t* gmax1, int n_cu, hipStream_t stream);
+                         const float* scales, int64_t* gmax0, int64_t* gmax1, int n_cu, hipStream_t stream, const uint32_t* mask = nullptr,
+                         size_t mask_words = 0);
 // four queries per pass: 12-bit integer nomination tables + certificate (pq.hip)
 struct Pq4Params { double delta, c, eps; int ok; };
 size_t pq4_table_bytes();
 int launch_pq4_table(const float* luts, const float* scales, int n_valid, void* table, Pq4Params* params, hipStream_t stream, int nq = 4);
 int launch_pq_scan_gmax4(const void* table, const uint8_t* codes, size_t n, const uint8_t* desc, uint32_t* gmax, int n_cu,
-                         hipStream_t stream, int nq = 4);   // nq = 4: 12-bit tables, 8: 8-bit tables; gmax [n_groups][nq] (group-major)
+                         hipStream_t stream, int nq = 4,    // nq = 4: 12-bit tables, 8: 8-bit tables; gmax [n_groups][nq] (group-major)
+                         const uint32_t* mask = nullptr, size_t mask_words = 0);
 int launch_pq4_certify(const Pq4Params* params, const uint32_t* group_keys, int n_nominated, int n_sel, const uint32_t* top_ids,
                        const int64_t* top_scores, size_t top_stride, int r, int nq, int* flag, hipStream_t stream);
 int launch_add_descriptor(const uint32_t* ids, size_t n, const uint8_t* desc, int n_desc, size_t n_codes,
@@ -143,6 +147,8 @@ int launch_filter_compact(const uint32_t* words, size_t n_words, uint32_t* ids_o
 // launch_expand_groups, with ID_NONE for rows whose bit is clear (or at / past 32 * n_words)
 int launch_expand_groups_masked(const uint32_t* parents, size_t par_stride, size_t n_par, int group, size_t n_rows, const uint32_t* words,
                                 size_t n_words, uint32_t* ids, size_t ids_stride, int nq, hipStream_t stream);
+// out[w] = NOT deleted[w] below n_rows (deleted null: all ones), zero at and past n_rows: a graph's live rows as a filter bitmap of n_words words
+int launch_filter_live(const uint32_t* deleted, size_t n_rows, size_t n_words, uint32_t* out, hipStream_t stream);
 // sel[i] = list[sel[i]] (ID_NONE stays): positions in the filter's id list -> row ids
 int launch_map_positions(uint32_t* sel, size_t n, const uint32_t* list, hipStream_t stream);
 // out[w] = words[w] AND (has_url != 0 for the word's 32 rows; rows at or past n_rows excluded): the rows a filtered LIST search may return

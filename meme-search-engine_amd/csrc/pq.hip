@@ -414,10 +414,34 @@ template <typename T, int ENTRY> __device__ __forceinline__ void gather16(const 
     for (int c = 0; c < 16; c++) e[c] = *lds_at<T>(off[c] + (Q * 16 + c) * 256 * ENTRY);
 }
 
-template <bool GMAX>
+// Filtered scans (MASKED instantiations of the three group-maximum kernels below).  A group of 64 vectors has ONE 64-bit mask: words
+// 2g and 2g + 1 of the filter's bitmap (filter.hip: one u32 per 32 rows, LSB first, zero-padded to whole 256-row tiles), bit l = vector
+// 64 g + l is allowed.  The filter may be shorter than the codes: a group at or past mask_groups = n_words / 2 is fully excluded and its
+// words are never read.  An excluded vector contributes what a vector past the end of the codes contributes (INT64_MIN, or the all-zero
+// integer sum); a group whose mask is zero issues no code or descriptor load at all and stores that minimum.
+// The mask is wave-uniform and the bitmap immutable (mse_filter), so it is read through the CONSTANT address space: a scalar (SMEM) load,
+// counted by lgkmcnt -- it never enters vmcnt, which pq_scan64_kernel counts by hand.
+__device__ __forceinline__ uint64_t group_mask(const uint32_t* mask, size_t mask_groups, size_t g) {
+    if (g >= mask_groups) return 0ull;
+    typedef const __attribute__((address_space(4))) uint64_t* cptr;
+    return reinterpret_cast<cptr>((uintptr_t)mask)[g];
+}
+
+// lanes[lane] ? r : INT64_MIN, with the wave-uniform mask used AS the lane predicate of two v_cndmask (no per-lane shift of the mask,
+// no extra live registers: pq_scan64x2_kernel has none to spare)
+__device__ __forceinline__ int64_t keep_allowed(int64_t r, uint64_t lanes) {
+    uint32_t lo = (uint32_t)(uint64_t)r, hi = (uint32_t)((uint64_t)r >> 32);
+    const uint32_t min_hi = 0x80000000u;
+    asm("v_cndmask_b32_e64 %0, 0, %0, %2\n\tv_cndmask_b32_e64 %1, %3, %1, %2" : "+v"(lo), "+v"(hi) : "s"(lanes), "v"(min_hi));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+template <bool GMAX, bool MASKED = false>
 __global__ __launch_bounds__(PQS_WAVES * 64) void pq_scan64_kernel(const float* __restrict__ lut, const uint8_t* __restrict__ codes,
                                                                   size_t n, const uint8_t* __restrict__ desc /* [n][4] or null */,
-                                                                  const float* __restrict__ scales, int64_t* __restrict__ out) {
+                                                                  const float* __restrict__ scales, int64_t* __restrict__ out,
+                                                                  const uint32_t* mask = nullptr, size_t mask_groups = 0) {
+    static_assert(GMAX || !MASKED, "the masked scan keeps group maxima only");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* s_lut = reinterpret_cast<float*>(smem);
     require_lds_base_zero(smem);
@@ -448,10 +472,28 @@ __global__ __launch_bounds__(PQS_WAVES * 64) void pq_scan64_kernel(const float* 
         for (int j = 0; j < 4; j++) pq_dma16(base, voff[j], stage_lds + j * 1024);
         if (desc) pq_dma4(desc + gi * 256, (uint32_t)(lane * 4), stage_lds + 4096);
     };
-    if (grp < ngroups) issue(grp);
+    // MASKED: the same pipeline, with the DMA of a group issued only when its mask is non-zero.  The hand count holds because every
+    // iteration, skipped or not, still issues in this order: [wait + LDS reads, unless skipped] -> the NEXT group's DMAs (if that
+    // group has an allowed vector) -> exactly ONE result store.  So at the wait of a group that was fetched, its 4 (+1) DMAs are
+    // followed by exactly one younger VMEM operation -- the previous iteration's store (a skipped iteration stores the minimum) --
+    // and vmcnt(1) covers them; a skipped group waits for nothing and has nothing in flight.  The mask words come by scalar loads
+    // (group_mask), outside vmcnt.
+    uint64_t m_cur = ~0ull, m_next = ~0ull;
+    if constexpr (MASKED) m_cur = grp < ngroups ? group_mask(mask, mask_groups, grp) : 0ull;
+    if (grp < ngroups && (!MASKED || m_cur != 0ull)) issue(grp);
     const int rsw = (lane >> 3) & 3;
     bool first = true;
     for (; grp < ngroups; grp += stride) {
+        if constexpr (MASKED) {
+            m_next = grp + stride < ngroups ? group_mask(mask, mask_groups, grp + stride) : 0ull;
+            if (m_cur == 0ull) {     // no allowed vector: nothing was fetched for this group
+                if (m_next != 0ull) issue(grp + stride);
+                if (lane == 0) out[grp] = INT64_MIN;
+                first = false;       // (the next wait has this store behind its DMAs, like any other)
+                m_cur = m_next;
+                continue;
+            }
+        }
         if (first) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(1)" ::: "memory");   // the one younger operation is the previous result store
         first = false;
@@ -460,7 +502,7 @@ __global__ __launch_bounds__(PQS_WAVES * 64) void pq_scan64_kernel(const float* 
         for (int p = 0; p < 4; p++) w4[p] = *reinterpret_cast<const uint4*>(stage + lane * 64 + ((p ^ rsw) * 16));
         const uint32_t dw = desc ? *reinterpret_cast<const uint32_t*>(stage + 4096 + lane * 4) : 0u;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // rows are in registers: the staging area may be refilled
-        if (grp + stride < ngroups) issue(grp + stride);
+        if (grp + stride < ngroups && (!MASKED || m_next != 0ull)) issue(grp + stride);
         const uint32_t w[16] = {w4[0].x, w4[0].y, w4[0].z, w4[0].w, w4[1].x, w4[1].y, w4[1].z, w4[1].w,
                                 w4[2].x, w4[2].y, w4[2].z, w4[2].w, w4[3].x, w4[3].y, w4[3].z, w4[3].w};
         float s = 0.0f;
@@ -482,6 +524,10 @@ __global__ __launch_bounds__(PQS_WAVES * 64) void pq_scan64_kernel(const float* 
         }
         if (GMAX) {
             if (v >= n) r = INT64_MIN;
+            if constexpr (MASKED) {
+                r = keep_allowed(r, m_cur);
+                m_cur = m_next;
+            }
 #pragma unroll
             for (int o = 32; o >= 1; o >>= 1) {
                 const int64_t other = __shfl_xor(r, o);
@@ -507,11 +553,12 @@ __global__ __launch_bounds__(PQS_WAVES * 64) void pq_scan64_kernel(const float* 
 // LDS-DMA staging (8 waves x 4 KiB) measured 3 % slower at 2e7 codes and was dropped.
 constexpr int PQ2_LUT_BYTES = 64 * 256 * 8;
 constexpr int PQ2_WAVES = 12;
-template <int NW>
+template <int NW, bool MASKED = false>
 __global__ __launch_bounds__(NW * 64) void pq_scan64x2_kernel(const float* __restrict__ lut0, const float* __restrict__ lut1,
                                                               const uint8_t* __restrict__ codes, size_t n,
                                                               const uint8_t* __restrict__ desc, const float* __restrict__ scales,
-                                                              int64_t* __restrict__ out0, int64_t* __restrict__ out1) {
+                                                              int64_t* __restrict__ out0, int64_t* __restrict__ out1,
+                                                              const uint32_t* mask = nullptr, size_t mask_groups = 0) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float2* s_lut2 = reinterpret_cast<float2*>(smem);
     require_lds_base_zero(smem);
@@ -538,11 +585,23 @@ __global__ __launch_bounds__(NW * 64) void pq_scan64x2_kernel(const float* __res
     };
     uint4 nx[4];
     uint32_t dw_next = 0;
-    if (grp < ngroups) load_rows(grp, nx, dw_next);
+    // MASKED: a group's rows are loaded only when its mask (wave-uniform, group_mask) is non-zero; a group without an allowed vector
+    // stores INT64_MIN for both queries and touches neither codes nor descriptors
+    uint64_t m_cur = ~0ull, m_next = ~0ull;
+    if constexpr (MASKED) m_cur = grp < ngroups ? group_mask(mask, mask_groups, grp) : 0ull;
+    if (grp < ngroups && (!MASKED || m_cur != 0ull)) load_rows(grp, nx, dw_next);
     for (; grp < ngroups; grp += stride) {
+        if constexpr (MASKED) m_next = grp + stride < ngroups ? group_mask(mask, mask_groups, grp + stride) : 0ull;
         uint4 w4[4] = {nx[0], nx[1], nx[2], nx[3]};
         const uint32_t dw = dw_next;
-        if (grp + stride < ngroups) load_rows(grp + stride, nx, dw_next);
+        if (grp + stride < ngroups && (!MASKED || m_next != 0ull)) load_rows(grp + stride, nx, dw_next);
+        if constexpr (MASKED) {
+            if (m_cur == 0ull) {     // (w4 / dw hold nothing: no row of this group was loaded)
+                if (lane == 0) { out0[grp] = INT64_MIN; out1[grp] = INT64_MIN; }
+                m_cur = m_next;
+                continue;
+            }
+        }
         const uint32_t w[16] = {w4[0].x, w4[0].y, w4[0].z, w4[0].w, w4[1].x, w4[1].y, w4[1].z, w4[1].w,
                                 w4[2].x, w4[2].y, w4[2].z, w4[2].w, w4[3].x, w4[3].y, w4[3].z, w4[3].w};
         float s0 = 0.0f, s1 = 0.0f;
@@ -564,6 +623,11 @@ __global__ __launch_bounds__(NW * 64) void pq_scan64x2_kernel(const float* __res
             r0 += bias; r1 += bias;
         }
         if (v >= n) { r0 = INT64_MIN; r1 = INT64_MIN; }
+        if constexpr (MASKED) {
+            r0 = keep_allowed(r0, m_cur);
+            r1 = keep_allowed(r1, m_cur);
+            m_cur = m_next;
+        }
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) {
             const int64_t o0 = __shfl_xor(r0, o), o1 = __shfl_xor(r1, o);
@@ -736,9 +800,10 @@ typedef uint32_t u32x2v __attribute__((ext_vector_type(2)));
 //   NQ = 8 (round 4): the pass is HBM-bound with every on-chip unit under 55 %, so the same instruction stream serves EIGHT
 //   queries when an entry holds one byte per query (8-bit tables, B = identity): twice the queries per byte of codes read.  The
 //   coarser step (delta x 16) widens the certificate's band; the caller nominates more groups for it (api_pq.hip).
-template <int NW, int NQ>
+template <int NW, int NQ, bool MASKED = false>
 __global__ __launch_bounds__(NW * 64) void pq_scan64x4_kernel(const uint4* __restrict__ table, const uint8_t* __restrict__ codes, size_t n,
-                                                             const uint8_t* __restrict__ desc, uint32_t* __restrict__ out, size_t n_groups) {
+                                                             const uint8_t* __restrict__ desc, uint32_t* __restrict__ out, size_t n_groups,
+                                                             const uint32_t* mask = nullptr, size_t mask_groups = 0) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     require_lds_base_zero(smem);
     {
@@ -797,13 +862,26 @@ __global__ __launch_bounds__(NW * 64) void pq_scan64x4_kernel(const uint4* __res
             dnx[sb] = (desc && vec < n) ? reinterpret_cast<const uint32_t*>(desc)[vec] : 0u;
         }
     };
-    if (grp < n_groups) load_rows(grp);
+    // MASKED: a group's rows are loaded only when its mask (wave-uniform, group_mask) is non-zero; a group without an allowed vector
+    // stores the all-zero sum (key 0, the smallest possible) and touches neither codes nor descriptors
+    uint64_t m_cur = ~0ull, m_next = ~0ull;
+    if constexpr (MASKED) m_cur = grp < n_groups ? group_mask(mask, mask_groups, grp) : 0ull;
+    if (grp < n_groups && (!MASKED || m_cur != 0ull)) load_rows(grp);
     for (; grp < n_groups; grp += stride) {
+        if constexpr (MASKED) {
+            m_next = grp + stride < n_groups ? group_mask(mask, mask_groups, grp + stride) : 0ull;
+            if (m_cur == 0ull) {
+                if (m_next != 0ull) load_rows(grp + stride);
+                if (lane < NQ) out[grp * NQ + lane] = 0u;
+                m_cur = m_next;
+                continue;
+            }
+        }
         u32x4v x[4];
         uint32_t dw[4];
 #pragma unroll
         for (int i = 0; i < 4; i++) { x[i] = nx[i]; dw[i] = dnx[i]; }
-        if (grp + stride < n_groups) load_rows(grp + stride);
+        if (grp + stride < n_groups && (!MASKED || m_next != 0ull)) load_rows(grp + stride);
         int rows[16];
 #pragma unroll
         for (int pr = 0; pr < 2; pr++) {      // two blocks of 16 vectors at a time: two independent accumulator chains
@@ -863,6 +941,17 @@ __global__ __launch_bounds__(NW * 64) void pq_scan64x4_kernel(const uint4* __res
 #pragma unroll
             for (int j = 0; j < 16; j++)
                 if (grp * 64 + (j >> 2) * 16 + 4 * g + (j & 3) >= n) rows[j] = -bias;
+        }
+        if constexpr (MASKED) {
+            if (m_cur != ~0ull) {    // rows[j] is vector (j >> 2) * 16 + 4 g + (j & 3) of the group: an excluded one counts as the all-zero sum
+                const uint32_t lo = (uint32_t)m_cur >> (4 * g), hi = (uint32_t)(m_cur >> 32) >> (4 * g);
+#pragma unroll
+                for (int j = 0; j < 16; j++) {
+                    const uint32_t half = (j >> 2) < 2 ? lo : hi;
+                    if (!((half >> (((j >> 2) & 1) * 16 + (j & 3))) & 1u)) rows[j] = -bias;
+                }
+            }
+            m_cur = m_next;
         }
         int best = max(rows[0], rows[1]);
 #pragma unroll
@@ -1014,8 +1103,17 @@ static size_t scan_cus(int n_cu) { return n_cu >= 64 ? (size_t)(n_cu - 8) : (siz
 
 // group maxima of a full scan: gmax[g] = max ADC score (+ descriptor bias) of vectors 64g .. 64g+63 (INT64_MIN past the end)
 int launch_pq_scan_gmax(const float* lut, const uint8_t* codes, size_t n, const uint8_t* desc, const float* scales,
-                        int64_t* gmax, int n_cu, hipStream_t stream) {
+                        int64_t* gmax, int n_cu, hipStream_t stream, const uint32_t* mask, size_t mask_words) {
     if (n == 0) return 0;
+    if (mask) {     // the masked instantiation: same grid, same LDS (mask_words / 2 groups have mask words)
+        MSE_DYN_LDS((pq_scan64_kernel<true, true>), PQS_LDS);
+        const size_t mgroups = (n + 63) / 64;
+        const unsigned mblocks = (unsigned)std::min<size_t>((mgroups + PQS_WAVES - 1) / PQS_WAVES, scan_cus(n_cu));
+        hipLaunchKernelGGL((pq_scan64_kernel<true, true>), dim3(mblocks), dim3(PQS_WAVES * 64), PQS_LDS, stream, lut, codes, n,
+                           (desc && scales) ? desc : nullptr, scales, gmax, mask, mask_words / 2);
+        MSE_HIP_TRY(hipGetLastError());
+        return 0;
+    }
     MSE_DYN_LDS(pq_scan64_kernel<true>, PQS_LDS);
     const size_t groups = (n + 63) / 64;
     // one 133-KiB workgroup per CU, on all but ONE CU PER XCD: the kernels of another query's tail (radix selects, ~50 KiB of LDS
@@ -1032,10 +1130,19 @@ int launch_pq_scan_gmax(const float* lut, const uint8_t* codes, size_t n, const 
 
 // the same for TWO queries in one pass over the codes (pq_scan64x2_kernel); scales are shared by the two queries (one request)
 int launch_pq_scan_gmax2(const float* lut0, const float* lut1, const uint8_t* codes, size_t n, const uint8_t* desc,
-                         const float* scales, int64_t* gmax0, int64_t* gmax1, int n_cu, hipStream_t stream) {
+                         const float* scales, int64_t* gmax0, int64_t* gmax1, int n_cu, hipStream_t stream, const uint32_t* mask,
+                         size_t mask_words) {
     if (n == 0) return 0;
     const size_t groups = (n + 63) / 64;
     const size_t cus = scan_cus(n_cu);   // one CU per XCD stays free for the previous pair's tail (see above)
+    if (mask) {
+        MSE_DYN_LDS((pq_scan64x2_kernel<PQ2_WAVES, true>), PQ2_LUT_BYTES);
+        const unsigned mblocks = (unsigned)std::min<size_t>((groups + PQ2_WAVES - 1) / PQ2_WAVES, cus);
+        hipLaunchKernelGGL((pq_scan64x2_kernel<PQ2_WAVES, true>), dim3(mblocks), dim3(PQ2_WAVES * 64), PQ2_LUT_BYTES, stream, lut0, lut1, codes,
+                           n, (desc && scales) ? desc : nullptr, scales, gmax0, gmax1, mask, mask_words / 2);
+        MSE_HIP_TRY(hipGetLastError());
+        return 0;
+    }
     MSE_DYN_LDS(pq_scan64x2_kernel<PQ2_WAVES>, PQ2_LUT_BYTES);
     const unsigned blocks = (unsigned)std::min<size_t>((groups + PQ2_WAVES - 1) / PQ2_WAVES, cus);
     hipLaunchKernelGGL(pq_scan64x2_kernel<PQ2_WAVES>, dim3(blocks), dim3(PQ2_WAVES * 64), PQ2_LUT_BYTES, stream, lut0, lut1, codes, n,
@@ -1065,12 +1172,26 @@ int launch_pq4_table(const float* luts, const float* scales, int n_valid, void* 
     return 0;
 }
 int launch_pq_scan_gmax4(const void* table, const uint8_t* codes, size_t n, const uint8_t* desc, uint32_t* gmax, int n_cu,
-                         hipStream_t stream, int nq) {
+                         hipStream_t stream, int nq, const uint32_t* mask, size_t mask_words) {
     if (n == 0) return 0;
     if (nq != 4 && nq != 8) return fail("pq scan: 4 or 8 queries per pass");
     const size_t groups = (n + 63) / 64;
     const size_t cus = scan_cus(n_cu);
     const unsigned blocks = (unsigned)std::min<size_t>((groups + PQ4_WAVES - 1) / PQ4_WAVES, cus);
+    if (mask && nq == 4) {
+        MSE_DYN_LDS((pq_scan64x4_kernel<PQ4_WAVES, 4, true>), Pq4Layout<4>::TABLE_BYTES);
+        hipLaunchKernelGGL((pq_scan64x4_kernel<PQ4_WAVES, 4, true>), dim3(blocks), dim3(PQ4_WAVES * 64), Pq4Layout<4>::TABLE_BYTES, stream,
+                           reinterpret_cast<const uint4*>(table), codes, n, desc, gmax, groups, mask, mask_words / 2);
+        MSE_HIP_TRY(hipGetLastError());
+        return 0;
+    }
+    if (mask) {
+        MSE_DYN_LDS((pq_scan64x4_kernel<PQ4_WAVES, 8, true>), Pq4Layout<8>::TABLE_BYTES);
+        hipLaunchKernelGGL((pq_scan64x4_kernel<PQ4_WAVES, 8, true>), dim3(blocks), dim3(PQ4_WAVES * 64), Pq4Layout<8>::TABLE_BYTES, stream,
+                           reinterpret_cast<const uint4*>(table), codes, n, desc, gmax, groups, mask, mask_words / 2);
+        MSE_HIP_TRY(hipGetLastError());
+        return 0;
+    }
     if (nq == 4) {
         MSE_DYN_LDS((pq_scan64x4_kernel<PQ4_WAVES, 4>), Pq4Layout<4>::TABLE_BYTES);
         hipLaunchKernelGGL((pq_scan64x4_kernel<PQ4_WAVES, 4>), dim3(blocks), dim3(PQ4_WAVES * 64), Pq4Layout<4>::TABLE_BYTES, stream,

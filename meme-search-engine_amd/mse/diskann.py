@@ -156,6 +156,14 @@ class _RowDeletes:
         check(ffi.lib().mse_graph_to_host(h, _p(adj, C.c_uint32), _p(deg, C.c_uint32)), "graph_to_host")
         return IndexGraph(adj, deg)
 
+    def live_filter(self, and_has_url=False) -> RowFilter:
+        """The graph's live rows as a RowFilter (mse_graph_live_filter): a row is allowed when it is not in the deleted map and -- with
+        and_has_url, on a graph that has has_url flags -- its flag is set.  Built on the device; a snapshot: deletes, restores and
+        inserts made later need a new filter.  With it ProductQuantizer.scan_topk*_filtered and Searcher.bruteforce_topk(allow=...)
+        serve a mutated index without compact()."""
+        return RowFilter.from_handle(check_ptr(ffi.lib().mse_graph_live_filter(self._graph_handle(), int(bool(and_has_url))),
+                                               "graph_live_filter"))
+
     def delete_rows(self, searcher: Searcher, ids_or_filter, config, batch=0):
         """Remove rows from the live graph and repair the lists that pointed at them, on the device (mse_graph_delete_rows).
         ids_or_filter: a RowFilter over the graph's rows whose SET bits name the rows to remove, a boolean mask with one entry per row, or

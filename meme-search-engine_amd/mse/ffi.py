@@ -129,6 +129,13 @@ SIGNATURES = {
     "mse_pq_last_uncertified": (C.c_uint32, [vp]),
     "mse_debug_pq_group_max": (C.c_int, [vp, vp, f32p, f32p, f32p, i64p, i64p]),
     "mse_debug_pq4_group_max": (C.c_int, [vp, vp, f32p, f32p, C.c_int, C.c_int, u32p, C.POINTER(C.c_double)]),
+    "mse_pq_scan_topk_filtered": (C.c_int, [vp, vp, vp, vp, f32p, f32p, sz, sz, C.c_int, i64p, u32p]),
+    "mse_pq_scan_topk_batch_filtered": (C.c_int, [vp, vp, vp, vp, f32p, sz, f32p, sz, sz, C.c_int, i64p, u32p]),
+    "mse_pq_scan_topk_block_filtered": (C.c_int, [vp, vp, vp, vp, f32p, sz, f32p, sz, sz, C.c_int, C.c_uint64, vp]),
+    "mse_pq_filtered_plan": (C.c_int, [sz, sz, sz, C.POINTER(C.c_int)]),
+    "mse_debug_pq_group_max_filtered": (C.c_int, [vp, vp, vp, f32p, f32p, f32p, i64p, i64p]),
+    "mse_debug_pq4_group_max_filtered": (C.c_int, [vp, vp, vp, f32p, f32p, C.c_int, C.c_int, u32p, C.POINTER(C.c_double)]),
+    "mse_graph_live_filter": (vp, [vp, C.c_int]),
     "mse_descriptor_product": (C.c_int64, [f32p, sz, u8p, C.c_uint32]),
     "mse_nb_new": (vp, [sz]),
     "mse_nb_free": (None, [vp]),

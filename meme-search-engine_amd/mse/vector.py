@@ -135,6 +135,13 @@ class RowFilter:
             raise TypeError("allowed must be a boolean mask or an integer id array")
 
     @classmethod
+    def from_handle(cls, handle):
+        """Adopt an mse_filter* made by the library (mse_graph_live_filter): the RowFilter owns and frees it."""
+        f = cls.__new__(cls)
+        f._h = handle
+        return f
+
+    @classmethod
     def wrap(cls, allow):
         """(filter, owned): a RowFilter as it is, anything else made into one (and owned by the caller, to close)."""
         if isinstance(allow, RowFilter):
@@ -329,6 +336,10 @@ class Dispatcher:
             pass
 
 
+# mode of the filtered flat scan (MSE_PQ_FILTER_*)
+PQ_FILTER_MODES = {"auto": 0, "scan": 1, "list": 2}
+
+
 class QueryLUT:
     """vector.rs:316-317: chunk-major table [n_chunks][n_centroids] of f32."""
 
@@ -416,6 +427,81 @@ class ProductQuantizer:
                                                _p(q, C.c_float), q.shape[0], _p(sc, C.c_float) if sc is not None else None, r, k,
                                                _p(scores, C.c_int64), _p(ids, C.c_uint32)), "pq_scan_topk_batch")
         return scores, ids
+
+    def scan_topk_filtered(self, codes, allow, query_f32, r, k, searcher=None, scales=None, mode="auto"):
+        """scan_topk over the rows `allow` (a RowFilter or a boolean row mask) lets through: exactly scan_topk on codes (and base rows)
+        made of the allowed rows alone, ids mapped back.  mode: "auto", "scan" (masked pass over all codes) or "list" (ADC over the
+        filter's id list); results are identical."""
+        s, i = self.scan_topk_batch_filtered(codes, allow, np.ascontiguousarray(query_f32, np.float32).reshape(1, self.n_dims), r, k,
+                                             searcher, scales, mode, _one=True)
+        return s[0], i[0]
+
+    def scan_topk_batch_filtered(self, codes, allow, queries_f32, r, k, searcher=None, scales=None, mode="auto", _one=False):
+        """scan_topk_batch over the rows `allow` lets through -> ([nq,k], [nq,k]), padded INT64_MIN / 0xFFFFFFFF."""
+        q = np.ascontiguousarray(queries_f32, np.float32).reshape(-1, self.n_dims)
+        sc = None if scales is None else np.ascontiguousarray(scales, np.float32)
+        scores = np.empty((q.shape[0], k), np.int64)
+        ids = np.empty((q.shape[0], k), np.uint32)
+        f, owned = RowFilter.wrap(allow)
+        try:
+            sh = searcher._h if searcher is not None else None
+            scp = _p(sc, C.c_float) if sc is not None else None
+            if _one:
+                check(ffi.lib().mse_pq_scan_topk_filtered(self._h, codes._h, f._h, sh, _p(q, C.c_float), scp, r, k, PQ_FILTER_MODES[mode],
+                                                          _p(scores, C.c_int64), _p(ids, C.c_uint32)), "pq_scan_topk_filtered")
+            else:
+                check(ffi.lib().mse_pq_scan_topk_batch_filtered(self._h, codes._h, f._h, sh, _p(q, C.c_float), q.shape[0], scp, r, k,
+                                                                PQ_FILTER_MODES[mode], _p(scores, C.c_int64), _p(ids, C.c_uint32)),
+                      "pq_scan_topk_batch_filtered")
+        finally:
+            if owned:
+                f.close()
+        return scores, ids
+
+    @staticmethod
+    def filtered_plan(n, allowed, nq):
+        """What mode="auto" picks for nq queries over n codes of which `allowed` pass the filter: "scan" or "list" (host only)."""
+        m = C.c_int()
+        check(ffi.lib().mse_pq_filtered_plan(n, allowed, nq, C.byref(m)), "pq_filtered_plan")
+        return {v: name for name, v in PQ_FILTER_MODES.items()}[m.value]
+
+    def debug_group_max_filtered(self, codes, allow, lut0, lut1=None, scales=None):
+        """Test hook: debug_group_max through the masked kernels (INT64_MIN for a group without an allowed vector)."""
+        ng = (len(codes) + 63) // 64
+        l0 = np.ascontiguousarray(lut0, np.float32)
+        l1 = None if lut1 is None else np.ascontiguousarray(lut1, np.float32)
+        sc = None if scales is None else np.ascontiguousarray(scales, np.float32)
+        o0 = np.empty(ng, np.int64)
+        o1 = np.empty(ng, np.int64) if l1 is not None else None
+        f, owned = RowFilter.wrap(allow)
+        try:
+            check(ffi.lib().mse_debug_pq_group_max_filtered(self._h, codes._h, f._h, _p(l0, C.c_float),
+                                                            _p(l1, C.c_float) if l1 is not None else None,
+                                                            _p(sc, C.c_float) if sc is not None else None, _p(o0, C.c_int64),
+                                                            _p(o1, C.c_int64) if o1 is not None else None), "debug_pq_group_max_filtered")
+        finally:
+            if owned:
+                f.close()
+        return (o0, o1) if l1 is not None else o0
+
+    def debug_group_max4_filtered(self, codes, allow, luts, scales=None, n_valid=None, per_pass=4):
+        """Test hook: the integer nomination scan through the masked kernels -> (maxima u32 [per_pass, groups], params [per_pass, 4] =
+        delta, c, eps, ok); a group without an allowed vector gives the zero-sum key 0."""
+        ng = (len(codes) + 63) // 64
+        lt = np.ascontiguousarray(luts, np.float32).reshape(per_pass, 64 * 256)
+        sc = None if scales is None else np.ascontiguousarray(scales, np.float32)
+        out = np.zeros((per_pass, ng), np.uint32)
+        params = np.zeros((per_pass, 4), np.float64)
+        f, owned = RowFilter.wrap(allow)
+        try:
+            check(ffi.lib().mse_debug_pq4_group_max_filtered(self._h, codes._h, f._h, _p(lt, C.c_float),
+                                                             _p(sc, C.c_float) if sc is not None else None,
+                                                             per_pass if n_valid is None else n_valid, per_pass, _p(out, C.c_uint32),
+                                                             _p(params, C.c_double)), "debug_pq4_group_max_filtered")
+        finally:
+            if owned:
+                f.close()
+        return out, params
 
     def scan_timing(self, enable):
         """HIP-event totals of the four-query scan kernel so far -> (total_ms, launches); then set mode (0 off, 1 on, 2 on + reset)."""
