@@ -787,6 +787,51 @@ int mse_graph_compact(mse_searcher* s, const mse_graph* g, const mse_codes* code
  * mse_graph_compact reads the graph): later deletes, restores and inserts need a new filter.  A graph that was never deleted from gives
  * an all-ones filter.  NULL on error. */
 mse_filter* mse_graph_live_filter(const mse_graph* g, int and_has_url);
+
+/* ---- row filters as values: set algebra, predicates over resident data, read-back (FAISS IDSelectorAnd/Or/XOr/Not, range_search) ----
+ * Every creator below builds its result on the device and returns a FRESH immutable filter -- bitmap padded with zero words to whole
+ * 256-row tiles, ascending id list, count -- or NULL with mse_last_error, and then has made nothing.  Operands are never modified and
+ * may be freed at once afterwards.  Creators block until the filter is complete.  mse_filter_from_scores runs on the searcher's stream
+ * and uses its scratch (one call per searcher at a time); the others use the null stream, like mse_filter_from_ids.
+ * Lengths: a filter reads as zeros at and past its own mse_filter_len (the rule of the searches).  No result has a set bit at or past
+ * its own length.  Devices: operands made on different devices are an error, not a copy; a result lives with its operands (from_descriptors:
+ * where the codes' descriptor bytes live; from_scores: on the base's device; from_bits_dev: where the bits live), and that device is the
+ * calling thread's current device afterwards, as after mse_graph_live_filter.
+ * Memory: these creators size the id list by the count (count pass, then write pass): a result holds n_rows / 8 bytes of bitmap and
+ * 4 x count bytes of ids.  (mse_filter_from_bits / _from_ids / mse_graph_live_filter keep n_rows x 4 bytes of id list whatever the count.)
+ *   mse_filter_combine           a OP b over max(len a, len b) rows; the shorter operand reads as zeros.  An op outside 0..3 is an error.
+ *   mse_filter_not               NOT a over n_rows rows (0 = mse_filter_len(a)); n_rows < mse_filter_len(a) is an error; the rows in
+ *                                [len a, n_rows) come out allowed.
+ *   mse_filter_from_descriptors  over mse_codes_len(c) rows: bit r is set iff lo[j] <= desc[r][j] <= hi[j] for EVERY channel j of the
+ *                                codes' n_descriptors (lo, hi: host arrays of that many bytes, inclusive; lo[j] > hi[j] allows nothing).
+ *                                Reads the descriptor bytes as they are on the device now (after mse_graph_insert_rows: the new rows').
+ *                                Codes without descriptor bytes, or with more than 8 per row, are an error.
+ *   mse_filter_from_scores       over mse_base_len rows: bit r is set iff fast_dot(row r, query) >= threshold -- the reference-order i64
+ *                                score, exactly what mse_bruteforce_scores_f16 returns (saturation and NaN as there: threshold INT64_MIN
+ *                                allows every row) -- AND, with `within`, r is allowed by it.  `within` must be on the base's device and not
+ *                                longer than the base.  Widths: those of mse_bruteforce_scores_f16.  A null query is an error.
+ *   mse_filter_from_bits_dev     mse_filter_from_bits of a bitmap that is already in device memory ((n_rows + 7) / 8 bytes, same layout;
+ *                                bits past n_rows are ignored).  Host memory is an error.
+ * Read-back (blocking; both return non-zero and write nothing on error):
+ *   mse_filter_to_bits           writes exactly (mse_filter_len(f) + 7) / 8 bytes in the from_bits layout; a null buffer is an error.
+ *   mse_filter_read_ids          the allowed ids number first .. first + n of the ascending list; first + n > mse_filter_count(f) is an
+ *                                error. */
+#define MSE_FILTER_AND    0   /* a & b  */
+#define MSE_FILTER_OR     1   /* a | b  */
+#define MSE_FILTER_XOR    2   /* a ^ b  */
+#define MSE_FILTER_ANDNOT 3   /* a & ~b */
+mse_filter* mse_filter_combine(const mse_filter* a, const mse_filter* b, int op);
+mse_filter* mse_filter_not(const mse_filter* a, size_t n_rows);
+mse_filter* mse_filter_from_descriptors(const mse_codes* c, const uint8_t* lo, const uint8_t* hi);
+mse_filter* mse_filter_from_scores(mse_searcher* s, const uint16_t* query_f16, int64_t threshold, const mse_filter* within_or_null);
+mse_filter* mse_filter_from_bits_dev(const void* bits_dev, size_t n_rows);
+int mse_filter_to_bits(const mse_filter* f, uint8_t* bits);
+int mse_filter_read_ids(const mse_filter* f, size_t first, size_t n, uint32_t* out);
+/* measurement hook of the creators above (for scripts/filter_ops_probe.py): *last_ms (or null) receives the HIP-event time of the kernel
+ * that wrote the bitmap in the last creator call made while the switch was on -- the combine / descriptor / threshold kernel alone (for
+ * from_bits_dev: clear, copy and tail mask), without the count and write passes and without from_scores' scan -- then the switch is set
+ * (0 off, 1 on, 2 on and reset).  Process-wide; while it is on every creator call waits for its kernel once more. */
+int mse_filter_kernel_timing(int enable, double* last_ms);
 /* measurement hook of the row-gather kernel of mse_graph_compact (for scripts/graph_compact_probe.py): *last_gather_ms (or null)
  * receives the HIP-event time of that kernel in the last mse_graph_compact made on s while the switch was on (0: none), then the
  * switch is set (0 off, 1 on, 2 on and reset).  The kernel reads n_live and writes capacity rows of 2 d + code_size + n_desc bytes. */

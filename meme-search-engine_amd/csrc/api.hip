@@ -3,6 +3,7 @@
 #include "../../include/mse.h"
 #include "runtime.h"
 #include <algorithm>
+#include <atomic>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -836,6 +837,172 @@ mse_filter* mse_graph_live_filter(const mse_graph* g, int and_has_url) {
 
 size_t mse_filter_len(const mse_filter* f) { return f ? f->n_rows : 0; }
 size_t mse_filter_count(const mse_filter* f) { return f ? f->count : 0; }
+
+// ---- filters as values: set algebra, descriptor predicates, score thresholds, read-back (filter.hip) -----------------------------
+// filter_finish with the id list sized by the count (count pass, read-back, allocation, write pass): what the creators below make holds
+// count x 4 bytes of ids, not n_rows x 4.  `st`: the stream the bitmap was written on.  Frees f on failure.
+static mse_filter* filter_finish_counted(mse_filter* f, hipStream_t st = nullptr) {
+    DevBuf scratch;
+    unsigned long long count = 0;
+    bool ok = scratch.ensure(filter_compact_scratch_bytes(f->n_words) + 8) == 0;
+    unsigned long long* count_dev = scratch.as<unsigned long long>();
+    ok = ok && launch_filter_count(f->words, f->n_words, count_dev, scratch.as<char>() + 8, st) == 0;
+    if (ok && (hipMemcpyAsync(&count, count_dev, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) {
+        ok = false; fail("filter: the count pass failed");
+    }
+    if (ok && hipMalloc((void**)&f->ids, std::max<size_t>((size_t)count, 1) * 4) != hipSuccess) { ok = false; fail("hipMalloc failed for the filter"); }
+    ok = ok && launch_filter_write_ids(f->words, f->n_words, scratch.as<char>() + 8, f->ids, st) == 0;
+    if (ok && hipStreamSynchronize(st) != hipSuccess) { ok = false; fail("filter: the compaction failed"); }
+    if (!ok) { mse_filter_free(f); return nullptr; }
+    f->count = (size_t)count;
+    return f;
+}
+
+// the device `p` lives on becomes the thread's current device (as mse_graph_live_filter finds the graph's); 0, or -1 with the error set
+static int enter_device_of(const void* p, const char* who) {
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice) {
+        (void)hipGetLastError();
+        return fail(std::string(who) + ": not device memory");
+    }
+    if (hipSetDevice(at.device) != hipSuccess) return fail(std::string(who) + ": hipSetDevice failed");
+    return 0;
+}
+
+// measurement hook (mse_filter_kernel_timing, for scripts/filter_ops_probe.py): while the switch is on, HIP events around the kernel
+// that writes a new filter's bitmap -- not the count and write passes of filter_finish_counted, not from_scores' scan
+static std::atomic<int> g_filter_timing{0};
+static std::atomic<double> g_filter_kernel_ms{0.0};
+struct FilterKernelTimer {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipStream_t st;
+    explicit FilterKernelTimer(hipStream_t stream) : st(stream) {
+        if (!g_filter_timing.load()) return;
+        if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess || hipEventRecord(e0, st) != hipSuccess) drop();
+    }
+    void stop() {
+        float ms = 0.0f;
+        if (e0 && hipEventRecord(e1, st) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess)
+            g_filter_kernel_ms.store(ms);
+    }
+    void drop() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        e0 = e1 = nullptr;
+        (void)hipGetLastError();
+    }
+    ~FilterKernelTimer() { drop(); }
+};
+
+int mse_filter_kernel_timing(int enable, double* last_ms) {
+    if (last_ms) *last_ms = g_filter_kernel_ms.load();
+    if (enable == 2) g_filter_kernel_ms.store(0.0);
+    g_filter_timing.store(enable ? 1 : 0);
+    return 0;
+}
+
+static mse_filter* filter_binary(const mse_filter* a, const mse_filter* b, int op, size_t n_rows) {
+    if (hipSetDevice(a->device) != hipSuccess) { fail("filter: hipSetDevice failed"); return nullptr; }
+    mse_filter* f = filter_alloc(n_rows);
+    if (!f) return nullptr;
+    FilterKernelTimer tm(nullptr);
+    if (launch_filter_combine(a->words, a->n_words, b ? b->words : nullptr, b ? b->n_words : 0, op, n_rows, f->n_words, f->words, nullptr)) {
+        mse_filter_free(f); return nullptr;
+    }
+    tm.stop();
+    return filter_finish_counted(f);
+}
+
+mse_filter* mse_filter_combine(const mse_filter* a, const mse_filter* b, int op) {
+    if (!a || !b) { fail("filter_combine: null filter"); return nullptr; }
+    if (op < MSE_FILTER_AND || op > MSE_FILTER_ANDNOT) { fail("filter_combine: unknown op " + std::to_string(op)); return nullptr; }
+    if (a->device != b->device) { fail("filter_combine: the filters were made on different devices"); return nullptr; }   // no silent copy
+    return filter_binary(a, b, op, std::max(a->n_rows, b->n_rows));
+}
+
+mse_filter* mse_filter_not(const mse_filter* a, size_t n_rows) {
+    if (!a) { fail("filter_not: null filter"); return nullptr; }
+    if (n_rows == 0) n_rows = a->n_rows;
+    if (n_rows < a->n_rows) {
+        fail("filter_not: n_rows " + std::to_string(n_rows) + " is below the filter's " + std::to_string(a->n_rows) + " rows");
+        return nullptr;
+    }
+    return filter_binary(a, nullptr, 4, n_rows);
+}
+
+mse_filter* mse_filter_from_descriptors(const mse_codes* c, const uint8_t* lo, const uint8_t* hi) {
+    if (!c || !lo || !hi) { fail("filter_from_descriptors: null codes or bounds"); return nullptr; }
+    if (!c->n_desc || !c->desc) { fail("filter_from_descriptors: the codes carry no descriptor bytes"); return nullptr; }
+    if (c->n_desc > 8) { fail("filter_from_descriptors: at most 8 descriptor bytes per row"); return nullptr; }
+    if (enter_device_of(c->desc, "filter_from_descriptors")) return nullptr;
+    uint64_t lo8 = 0, hi8 = 0;
+    for (size_t j = 0; j < c->n_desc; j++) { lo8 |= (uint64_t)lo[j] << (8 * j); hi8 |= (uint64_t)hi[j] << (8 * j); }
+    mse_filter* f = filter_alloc(c->n);
+    if (!f) return nullptr;
+    FilterKernelTimer tm(nullptr);
+    if (launch_filter_desc_range(c->desc, (int)c->n_desc, c->n, lo8, hi8, f->n_words, f->words, nullptr)) { mse_filter_free(f); return nullptr; }
+    tm.stop();
+    return filter_finish_counted(f);
+}
+
+mse_filter* mse_filter_from_scores(mse_searcher* s, const uint16_t* query, int64_t threshold, const mse_filter* within) {
+    if (!s || !s->base) { fail("filter_from_scores: null searcher"); return nullptr; }
+    if (!query) { fail("filter_from_scores: null query"); return nullptr; }
+    const mse_base* b = s->base;
+    if (within && check_filter(b, within)) return nullptr;
+    if (hipSetDevice(b->device) != hipSuccess) { fail("filter_from_scores: hipSetDevice failed"); return nullptr; }
+    mse_filter* f = filter_alloc(b->n);
+    if (!f) return nullptr;
+    const size_t d = b->d;
+    bool ok = true;
+    if (b->n) {   // the one query staged and scored as mse_bruteforce_scores_f16 does it, then the threshold pass over s->scores
+        ok = s->q_stage.ensure(8 * d * 2) == 0 && s->scores.ensure(b->n * 8) == 0;
+        if (ok && (hipMemsetAsync(s->q_stage.p, 0, 8 * d * 2, s->stream) != hipSuccess ||
+                   hipMemcpyAsync(s->q_stage.p, query, d * 2, hipMemcpyHostToDevice, s->stream) != hipSuccess)) {
+            ok = false; fail("filter_from_scores: staging the query failed");
+        }
+        ok = ok && launch_scan_exact(b->dev, b->n, (int)d, s->q_stage.p, 1, false, s->scores.as<int64_t>(), b->n, nullptr, s->n_cu, s->stream) == 0;
+        FilterKernelTimer tm(s->stream);
+        ok = ok && launch_filter_score_threshold(s->scores.as<int64_t>(), b->n, threshold, within ? within->words : nullptr,
+                                                 within ? within->n_words : 0, f->n_words, f->words, s->stream) == 0;
+        if (ok) tm.stop();
+    }
+    if (!ok) { (void)hipStreamSynchronize(s->stream); mse_filter_free(f); return nullptr; }
+    return filter_finish_counted(f, s->stream);
+}
+
+mse_filter* mse_filter_from_bits_dev(const void* bits_dev, size_t n_rows) {
+    if (!bits_dev && n_rows) { fail("filter_from_bits_dev: null bitmap"); return nullptr; }
+    if (n_rows && enter_device_of(bits_dev, "filter_from_bits_dev")) return nullptr;
+    mse_filter* f = filter_alloc(n_rows);
+    if (!f) return nullptr;
+    FilterKernelTimer tm(nullptr);
+    bool ok = hipMemsetAsync(f->words, 0, std::max<size_t>(f->n_words, 1) * 4, nullptr) == hipSuccess;
+    if (ok && n_rows) ok = hipMemcpyAsync(f->words, bits_dev, (n_rows + 7) / 8, hipMemcpyDeviceToDevice, nullptr) == hipSuccess;
+    if (!ok) { mse_filter_free(f); fail("filter_from_bits_dev: the device copy failed"); return nullptr; }
+    if (launch_filter_mask_tail(f->words, n_rows, nullptr)) { mse_filter_free(f); return nullptr; }
+    tm.stop();
+    return filter_finish_counted(f);
+}
+
+int mse_filter_to_bits(const mse_filter* f, uint8_t* bits) {
+    if (!f) return fail("filter_to_bits: null filter");
+    if (!bits) return fail("filter_to_bits: null buffer");
+    if (f->n_rows == 0) return 0;
+    if (hipMemcpy(bits, f->words, (f->n_rows + 7) / 8, hipMemcpyDeviceToHost) != hipSuccess) return fail("filter_to_bits: the read-back failed");
+    return 0;
+}
+
+int mse_filter_read_ids(const mse_filter* f, size_t first, size_t n, uint32_t* out) {
+    if (!f) return fail("filter_read_ids: null filter");
+    if (first > f->count || n > f->count - first)
+        return fail("filter_read_ids: [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(n) + ") is past the filter's " +
+                    std::to_string(f->count) + " allowed rows");
+    if (n == 0) return 0;
+    if (!out) return fail("filter_read_ids: null buffer");
+    if (hipMemcpy(out, f->ids + first, n * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail("filter_read_ids: the read-back failed");
+    return 0;
+}
 
 
 

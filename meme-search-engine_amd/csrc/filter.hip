@@ -160,7 +160,139 @@ __global__ void list_bias_kernel(const uint32_t* __restrict__ ids, size_t n, con
     }
 }
 
+// ---- filters as values (mse_filter_combine / _not / _from_descriptors / _from_scores / _from_bits_dev) -------------------------------
+// Every kernel below writes all n_words words of the new bitmap (the tile padding included, as zeros) and no bit at or past n_rows.
+
+// the bits of word w that speak for rows below n_rows
+__device__ __forceinline__ uint32_t row_mask(size_t w, size_t n_rows) {
+    const size_t r0 = w * 32;
+    if (r0 >= n_rows) return 0u;
+    return r0 + 32 > n_rows ? 0xffffffffu >> (32 - (n_rows - r0)) : 0xffffffffu;
+}
+
+// out[w] = a[w] OP b[w] over the rows below n_rows; an operand reads as zero at and past its own words.  OP: MSE_FILTER_AND .. _ANDNOT,
+// 4 = NOT a (b unused).  One thread per word.
+template <int OP>
+__global__ void combine_words_kernel(const uint32_t* __restrict__ a, size_t a_words, const uint32_t* __restrict__ b, size_t b_words,
+                                     size_t n_rows, size_t n_words, uint32_t* __restrict__ out) {
+    const size_t w = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= n_words) return;
+    const uint32_t x = w < a_words ? a[w] : 0u;
+    const uint32_t y = OP != 4 && w < b_words ? b[w] : 0u;
+    const uint32_t v = OP == 0 ? x & y : OP == 1 ? x | y : OP == 2 ? x ^ y : OP == 3 ? x & ~y : ~x;
+    out[w] = v & row_mask(w, n_rows);
+}
+
+// the two words of this wave's 64 rows, from each lane's verdict on its row; lane 0 stores them (8-byte aligned: the pair index is even)
+__device__ __forceinline__ void store_ballot(bool pass, size_t pair, uint32_t* __restrict__ out) {
+    const unsigned long long m = __ballot(pass);
+    if ((threadIdx.x & 63) == 0) *reinterpret_cast<uint2*>(out + pair * 2) = make_uint2((uint32_t)m, (uint32_t)(m >> 32));
+}
+
+// bit r = lo[j] <= desc[r][j] <= hi[j] for every j < n_desc (bounds: byte j of lo / hi).  One wave per 64 rows, one lane per row, a block
+// of four waves per 256-row tile of the bitmap (grid = n_words / 8).  WORD: n_desc == 4, the row's bytes are one aligned 4-byte load.
+template <bool WORD>
+__global__ __launch_bounds__(256) void desc_range_kernel(const uint8_t* __restrict__ desc, int n_desc, size_t n_rows, uint64_t lo, uint64_t hi,
+                                                         uint32_t* __restrict__ out) {
+    const size_t r = (size_t)blockIdx.x * 256 + threadIdx.x;
+    bool pass = r < n_rows;
+    if (pass) {
+        if (WORD) {
+            const uint32_t v = reinterpret_cast<const uint32_t*>(desc)[r];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const uint32_t x = (v >> (8 * j)) & 0xffu;
+                pass = pass && x >= (uint32_t)((lo >> (8 * j)) & 0xffu) && x <= (uint32_t)((hi >> (8 * j)) & 0xffu);
+            }
+        } else {
+            const uint8_t* dp = desc + r * (size_t)n_desc;
+            for (int j = 0; j < n_desc; j++) {
+                const uint32_t x = dp[j];
+                pass = pass && x >= (uint32_t)((lo >> (8 * j)) & 0xffu) && x <= (uint32_t)((hi >> (8 * j)) & 0xffu);
+            }
+        }
+    }
+    store_ballot(pass, r >> 6, out);
+}
+
+// bit r = scores[r] >= threshold, AND the bit of `within` (null: all rows; zero at and past its words).  Same shape as desc_range_kernel.
+__global__ __launch_bounds__(256) void score_threshold_kernel(const int64_t* __restrict__ scores, size_t n_rows, int64_t threshold,
+                                                              const uint32_t* __restrict__ within, size_t within_words,
+                                                              uint32_t* __restrict__ out) {
+    const size_t r = (size_t)blockIdx.x * 256 + threadIdx.x;
+    bool pass = r < n_rows && scores[r] >= threshold;
+    if (pass && within) pass = (r >> 5) < within_words && ((within[r >> 5] >> (r & 31)) & 1u);
+    store_ballot(pass, r >> 6, out);
+}
+
+// clears the bits at and past n_rows in the word that holds row n_rows (n_rows % 32 != 0)
+__global__ void mask_tail_kernel(uint32_t* __restrict__ words, size_t n_rows) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) words[n_rows >> 5] &= (1u << (n_rows & 31)) - 1u;
+}
+
 }  // namespace
+
+int launch_filter_combine(const uint32_t* a, size_t a_words, const uint32_t* b, size_t b_words, int op, size_t n_rows, size_t n_words,
+                          uint32_t* out, hipStream_t stream) {
+    if (n_words == 0) return 0;
+    const dim3 grid((unsigned)((n_words + 255) / 256)), block(256);
+    switch (op) {
+#define MSE_COMBINE(OP) case OP: hipLaunchKernelGGL(combine_words_kernel<OP>, grid, block, 0, stream, a, a_words, b, b_words, n_rows, n_words, out); break;
+        MSE_COMBINE(0) MSE_COMBINE(1) MSE_COMBINE(2) MSE_COMBINE(3) MSE_COMBINE(4)
+#undef MSE_COMBINE
+        default: return fail("filter combine: unknown op");
+    }
+    MSE_HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_filter_desc_range(const uint8_t* desc, int n_desc, size_t n_rows, uint64_t lo, uint64_t hi, size_t n_words, uint32_t* out,
+                             hipStream_t stream) {
+    if (n_words == 0) return 0;
+    if (n_desc < 1 || n_desc > 8) return fail("filter from descriptors: 1 to 8 descriptor bytes per row");
+    if (n_words % 8 || n_words * 32 < n_rows) return fail("filter from descriptors: the bitmap is not whole tiles over the rows");
+    const dim3 grid((unsigned)(n_words / 8)), block(256);
+    if (n_desc == 4) hipLaunchKernelGGL(desc_range_kernel<true>, grid, block, 0, stream, desc, n_desc, n_rows, lo, hi, out);
+    else hipLaunchKernelGGL(desc_range_kernel<false>, grid, block, 0, stream, desc, n_desc, n_rows, lo, hi, out);
+    MSE_HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_filter_score_threshold(const int64_t* scores, size_t n_rows, int64_t threshold, const uint32_t* within, size_t within_words,
+                                  size_t n_words, uint32_t* out, hipStream_t stream) {
+    if (n_words == 0) return 0;
+    if (n_words % 8 || n_words * 32 < n_rows) return fail("filter from scores: the bitmap is not whole tiles over the rows");
+    hipLaunchKernelGGL(score_threshold_kernel, dim3((unsigned)(n_words / 8)), dim3(256), 0, stream, scores, n_rows, threshold, within,
+                       within_words, out);
+    MSE_HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_filter_mask_tail(uint32_t* words, size_t n_rows, hipStream_t stream) {
+    if (n_rows % 32 == 0) return 0;
+    hipLaunchKernelGGL(mask_tail_kernel, dim3(1), dim3(64), 0, stream, words, n_rows);
+    MSE_HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_filter_count(const uint32_t* words, size_t n_words, unsigned long long* count_dev, void* scratch, hipStream_t stream) {
+    const size_t nb = std::max<size_t>((n_words + CB - 1) / CB, 1);
+    if (nb > 0x7fffffffull) return fail("filter: too many rows");
+    unsigned long long* offsets = reinterpret_cast<unsigned long long*>(scratch);
+    uint32_t* counts = reinterpret_cast<uint32_t*>(offsets + nb);
+    hipLaunchKernelGGL(count_blocks_kernel, dim3((unsigned)nb), dim3(CB), 0, stream, words, n_words, counts);
+    hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(CB), 0, stream, counts, nb, offsets, count_dev);
+    MSE_HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_filter_write_ids(const uint32_t* words, size_t n_words, const void* scratch, uint32_t* ids_out, hipStream_t stream) {
+    const size_t nb = std::max<size_t>((n_words + CB - 1) / CB, 1);
+    hipLaunchKernelGGL(compact_kernel, dim3((unsigned)nb), dim3(CB), 0, stream, words, n_words,
+                       reinterpret_cast<const unsigned long long*>(scratch), ids_out);
+    MSE_HIP_TRY(hipGetLastError());
+    return 0;
+}
 
 int launch_filter_and_flags(const uint32_t* words, size_t n_words, const uint8_t* has_url, size_t n_rows, uint32_t* out, hipStream_t stream) {
     if (n_words == 0) return 0;

@@ -144,6 +144,22 @@ int launch_filter_or_ids(uint32_t* words, size_t n_words, const uint32_t* ids, s
 size_t filter_compact_scratch_bytes(size_t n_words);
 int launch_filter_compact(const uint32_t* words, size_t n_words, uint32_t* ids_out, unsigned long long* count_dev, void* scratch,
                           hipStream_t stream);
+// launch_filter_compact in two steps, for an id list sized by the count: *count_dev = set bits and the block offsets into scratch
+// (filter_compact_scratch_bytes), then -- same words, same scratch -- the ascending ids into ids_out (room for *count_dev of them)
+int launch_filter_count(const uint32_t* words, size_t n_words, unsigned long long* count_dev, void* scratch, hipStream_t stream);
+int launch_filter_write_ids(const uint32_t* words, size_t n_words, const void* scratch, uint32_t* ids_out, hipStream_t stream);
+// Filters as values.  Each writes all n_words words of `out` (whole 256-row tiles over n_rows) and no bit at or past n_rows.
+// out = a OP b (op: MSE_FILTER_AND / OR / XOR / ANDNOT; 4 = NOT a, b unused); an operand reads as zero at and past its own words
+int launch_filter_combine(const uint32_t* a, size_t a_words, const uint32_t* b, size_t b_words, int op, size_t n_rows, size_t n_words,
+                          uint32_t* out, hipStream_t stream);
+// bit r = byte j of lo <= desc[r][j] <= byte j of hi for every j < n_desc (1 .. 8)
+int launch_filter_desc_range(const uint8_t* desc, int n_desc, size_t n_rows, uint64_t lo, uint64_t hi, size_t n_words, uint32_t* out,
+                             hipStream_t stream);
+// bit r = scores[r] >= threshold AND bit r of within (null: every row; zero at and past within_words)
+int launch_filter_score_threshold(const int64_t* scores, size_t n_rows, int64_t threshold, const uint32_t* within, size_t within_words,
+                                  size_t n_words, uint32_t* out, hipStream_t stream);
+// clears the bits at and past n_rows in the word that holds row n_rows
+int launch_filter_mask_tail(uint32_t* words, size_t n_rows, hipStream_t stream);
 // launch_expand_groups, with ID_NONE for rows whose bit is clear (or at / past 32 * n_words)
 int launch_expand_groups_masked(const uint32_t* parents, size_t par_stride, size_t n_par, int group, size_t n_rows, const uint32_t* words,
                                 size_t n_words, uint32_t* ids, size_t ids_stride, int nq, hipStream_t stream);

@@ -136,6 +136,14 @@ SIGNATURES = {
     "mse_debug_pq_group_max_filtered": (C.c_int, [vp, vp, vp, f32p, f32p, f32p, i64p, i64p]),
     "mse_debug_pq4_group_max_filtered": (C.c_int, [vp, vp, vp, f32p, f32p, C.c_int, C.c_int, u32p, C.POINTER(C.c_double)]),
     "mse_graph_live_filter": (vp, [vp, C.c_int]),
+    "mse_filter_combine": (vp, [vp, vp, C.c_int]),
+    "mse_filter_not": (vp, [vp, sz]),
+    "mse_filter_from_descriptors": (vp, [vp, u8p, u8p]),
+    "mse_filter_from_scores": (vp, [vp, u16p, C.c_int64, vp]),
+    "mse_filter_from_bits_dev": (vp, [vp, sz]),
+    "mse_filter_to_bits": (C.c_int, [vp, u8p]),
+    "mse_filter_read_ids": (C.c_int, [vp, sz, sz, u32p]),
+    "mse_filter_kernel_timing": (C.c_int, [C.c_int, C.POINTER(C.c_double)]),
     "mse_descriptor_product": (C.c_int64, [f32p, sz, u8p, C.c_uint32]),
     "mse_nb_new": (vp, [sz]),
     "mse_nb_free": (None, [vp]),

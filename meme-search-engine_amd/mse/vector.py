@@ -113,7 +113,8 @@ class VectorList:
 class RowFilter:
     """Allowed-row set of the filtered search (mse_filter): `allowed` is a boolean array of n_rows entries, or an integer array of
     row ids (duplicates allowed; then n_rows is required).  The bitmap lives on the current device and is immutable.  len() is
-    n_rows; .count the allowed rows."""
+    n_rows; .count the allowed rows.  Filters are values: a & b, a | b, a ^ b, a - b (and-not), ~a and invert(n_rows) build new ones on
+    the device, as do from_descriptors, from_scores and from_device_bits; to_mask() and ids() read one back."""
 
     def __init__(self, allowed, n_rows=None):
         a = np.asarray(allowed)
@@ -154,6 +155,87 @@ class RowFilter:
     @property
     def count(self):
         return int(ffi.lib().mse_filter_count(self._h))
+
+    # ---- filters as values: every result is a fresh RowFilter built on the device; the operands stay as they are -------------------
+
+    @classmethod
+    def from_descriptors(cls, codes, ranges):
+        """The rows of `codes` (a Codes with descriptor bytes) whose descriptor bytes lie in `ranges`: {channel: (lo, hi)}, inclusive;
+        channels that are not named are unconstrained (0 .. 255), lo > hi allows nothing.  Reads the bytes as they are in HBM now."""
+        nd = int(codes.n_desc)
+        lo, hi = np.zeros(max(nd, 1), np.uint8), np.full(max(nd, 1), 255, np.uint8)
+        for ch, (a, b) in dict(ranges).items():
+            if not 0 <= int(ch) < nd:
+                raise ValueError(f"descriptor channel {ch} is not in 0 .. {nd - 1}")
+            if not (0 <= int(a) <= 255 and 0 <= int(b) <= 255):
+                raise ValueError(f"descriptor bounds must be in 0 .. 255, got ({a}, {b})")
+            lo[int(ch)], hi[int(ch)] = int(a), int(b)
+        return cls.from_handle(check_ptr(ffi.lib().mse_filter_from_descriptors(codes._h, _p(lo, C.c_uint8), _p(hi, C.c_uint8)),
+                                         "mse_filter_from_descriptors"))
+
+    @classmethod
+    def from_scores(cls, searcher, query, threshold, within=None):
+        """The rows of the searcher's base whose reference-order i64 score against `query` (what Searcher.scores returns) is at least
+        `threshold`, and -- with `within`, a RowFilter -- that `within` allows: the range search."""
+        if within is not None and not isinstance(within, RowFilter):
+            raise TypeError("within must be a RowFilter")
+        q = None if query is None else _bits(query).reshape(-1)
+        if q is not None and q.size != searcher.vecs.d_emb:
+            raise ValueError("the query must have the base's width")
+        return cls.from_handle(check_ptr(ffi.lib().mse_filter_from_scores(searcher._h, None if q is None else _p(q, C.c_uint16), int(threshold),
+                                                                          None if within is None else within._h), "mse_filter_from_scores"))
+
+    @classmethod
+    def from_device_bits(cls, ptr, n_rows):
+        """A filter from a packed bitmap that already lives in device memory (`ptr`: its address; (n_rows + 7) // 8 bytes, LSB first,
+        as numpy.packbits(..., bitorder="little"); bits past n_rows are ignored)."""
+        return cls.from_handle(check_ptr(ffi.lib().mse_filter_from_bits_dev(ptr, int(n_rows)), "mse_filter_from_bits_dev"))
+
+    def _combine(self, other, op):
+        if not isinstance(other, RowFilter):
+            return NotImplemented
+        return RowFilter.from_handle(check_ptr(ffi.lib().mse_filter_combine(self._h, other._h, op), "mse_filter_combine"))
+
+    def __and__(self, other):
+        return self._combine(other, 0)
+
+    def __or__(self, other):
+        return self._combine(other, 1)
+
+    def __xor__(self, other):
+        return self._combine(other, 2)
+
+    def __sub__(self, other):
+        """self AND NOT other"""
+        return self._combine(other, 3)
+
+    def invert(self, n_rows=None):
+        """NOT self over n_rows rows (default len(self); not fewer): rows at or past len(self) come out allowed."""
+        n = len(self) if n_rows is None else int(n_rows)
+        if n < 0:
+            raise ValueError("n_rows must not be negative")
+        if n == 0 and len(self):
+            raise MseError("mse_filter_not: n_rows 0 is below the filter's rows")   # 0 means len(self) in the C call
+        return RowFilter.from_handle(check_ptr(ffi.lib().mse_filter_not(self._h, n), "mse_filter_not"))
+
+    def __invert__(self):
+        return self.invert()
+
+    def to_mask(self):
+        """The allowed rows as a boolean array of len(self) entries."""
+        n = len(self)
+        bits = np.zeros((n + 7) // 8 + 1, np.uint8)   # one spare byte: the call writes exactly (n + 7) // 8
+        check(ffi.lib().mse_filter_to_bits(self._h, _p(bits, C.c_uint8)), "mse_filter_to_bits")
+        return np.unpackbits(bits[:(n + 7) // 8], count=n, bitorder="little").astype(bool)
+
+    def ids(self, first=0, n=None):
+        """The allowed row ids, ascending (uint32): all of them, or n of them from position `first`."""
+        n = self.count - int(first) if n is None else int(n)
+        if first < 0 or n < 0:
+            raise ValueError("first and n must not be negative")
+        out = np.empty(n, np.uint32)
+        check(ffi.lib().mse_filter_read_ids(self._h, int(first), n, _p(out, C.c_uint32)), "mse_filter_read_ids")
+        return out
 
     def close(self):
         if self._h:
