@@ -832,6 +832,82 @@ int mse_filter_read_ids(const mse_filter* f, size_t first, size_t n, uint32_t* o
  * from_bits_dev: clear, copy and tail mask), without the count and write passes and without from_scores' scan -- then the switch is set
  * (0 off, 1 on, 2 on and reset).  Process-wide; while it is on every creator call waits for its kernel once more. */
 int mse_filter_kernel_timing(int enable, double* last_ms);
+/* ---- row filters across shards: a filter over GLOBAL row ids cut into per-shard filters over LOCAL ids on the device, and back -------
+ * (no reference counterpart: the reference post-filters one address space, src/query_disk_index.rs:172.)  Both creators follow the rules
+ * of the creators above -- fresh immutable filter, id list sized by the count, NULL with mse_last_error and nothing made on error, null
+ * stream, blocking -- except that the calling thread's current device is the same after the call as before it.
+ *   mse_filter_slice   over n_rows LOCAL rows: bit r = bit first_row + r of f, zero where that is at or past mse_filter_len(f).  The rule
+ *                      per word: out[w] = funnel(in[w0 + w], in[w0 + w + 1]) >> (first_row & 31), w0 = first_row >> 5, masked to n_rows;
+ *                      first_row need not be a multiple of 32 (2 999 rows over 4 shards start at 750, 1 500 and 2 250).  device: where
+ *                      the result lives, -1 = f's device; for another device the word range the slice reads goes over by ONE peer copy
+ *                      and is sliced there.  n_rows = 0 and a null filter are errors.
+ *   mse_filter_concat  the inverse, over n_rows GLOBAL rows: part i occupies rows [first_rows[i], first_rows[i] + mse_filter_len(parts[i]));
+ *                      rows no part covers read as zero.  Parts that overlap, a part that reaches past n_rows, a null part and n_rows = 0
+ *                      are errors; parts may come in any order and may share a boundary word.  device: -1 = the first part's device; a
+ *                      part on another device comes over by one peer copy of its words. */
+mse_filter* mse_filter_slice(const mse_filter* f, uint64_t first_row, size_t n_rows, int device);
+mse_filter* mse_filter_concat(const mse_filter* const* parts, const uint64_t* first_rows, size_t n_parts, size_t n_rows, int device);
+/* mse_shard_filter: one LOCAL filter per shard of a group, each on its shard's device -- what the filtered searches of the group take.
+ *   mse_shard_group_filter             mse_filter_slice of `global` at each shard's first row and length.  A filter shorter than the group
+ *                                      excludes the rows past it; one longer than max(first row + rows) over the shards is an error.
+ *   mse_shard_group_filter_from_local  a copy of per_shard[g] for every shard g; each must have its shard's length and device.
+ *   mse_shard_group_live_filter        mse_graph_live_filter(graph, and_has_url) of every shard's attached graph: the rows that deletes
+ *                                      through the shards' graphs have left.  A shard without a graph is an error.
+ *   mse_shard_filter_count             allowed rows, summed over the shards;  _n_shards: its parts
+ *   mse_shard_filter_shard             shard g's local filter, BORROWED (it lives as long as the shard filter)
+ *   mse_shard_filter_global            mse_filter_concat of the parts at their first rows over max(first row + rows) rows on `device`
+ *                                      (-1: shard 0's): a fresh mse_filter, the caller's to free
+ * A shard filter remembers the layout it was made for: every call that re-fills a shard (mse_shard_group_generate, _load_host,
+ * _set_shard_device) starts a new layout, and a shard filter of an older layout -- or of another group -- is refused by every call that
+ * takes one.  It is immutable, holds no reference to the group, and must outlive the calls it is passed to.
+ * The filtered searches: the unfiltered call's contract and protocol with every shard's local step replaced by its filtered form over the
+ * shard's part.  A null shard filter, a stale or foreign one, an unknown mode / regime are errors; on any argument error nothing is written.
+ *   mse_shard_group_search_filtered(_dev)  local step mse_bruteforce_topk_filtered_f16_dev(part g, id_offset = first row).  Equals
+ *                                          mse_bruteforce_topk_filtered_f16 over one base of all rows with the global filter, bit for bit,
+ *                                          in every mode; padding INT64_MIN / MSE_ID_NONE when fewer than k rows are allowed overall.
+ *   mse_shard_group_pq_scan_topk_filtered  phase A = mse_pq_scan_topk_block_filtered(part g, r, r) per shard, phase B unchanged (every member
+ *                                          of the merged top-r is allowed by construction; empty slots stay empty).  Equals
+ *                                          mse_pq_scan_topk_batch_filtered over unsharded codes, bit for bit, in MSE_PQ_FILTER_SCAN, _LIST
+ *                                          and _AUTO; AUTO is resolved PER SHARD by mse_pq_filtered_plan from that shard's codes and count.
+ *   mse_shard_group_query_topk_filtered    every shard runs mse_disk_query_topk_block_filtered on its graph and part; the answer is the
+ *                                          (score desc, id asc) merge of the per-shard mse_disk_query_topk_filtered answers.  Under
+ *                                          MSE_FILTERED_AUTO EACH SHARD resolves mse_filtered_plan from its own rows and count, so shards
+ *                                          of one call may run different regimes and effective search lists.
+ * A shard whose part allows no row launches nothing and hands over padding. */
+typedef struct mse_shard_filter mse_shard_filter;
+mse_shard_filter* mse_shard_group_filter(mse_shard_group* g, const mse_filter* global);
+mse_shard_filter* mse_shard_group_filter_from_local(mse_shard_group* g, const mse_filter* const* per_shard);
+mse_shard_filter* mse_shard_group_live_filter(mse_shard_group* g, int and_has_url);
+void mse_shard_filter_free(mse_shard_filter* sf);
+size_t mse_shard_filter_count(const mse_shard_filter* sf);
+size_t mse_shard_filter_n_shards(const mse_shard_filter* sf);
+const mse_filter* mse_shard_filter_shard(const mse_shard_filter* sf, size_t shard);
+mse_filter* mse_shard_filter_global(const mse_shard_filter* sf, int device);
+int mse_shard_group_search_filtered(mse_shard_group* g, const mse_shard_filter* sf, const uint16_t* queries, size_t nq, size_t k, int mode,
+                                    int64_t* scores, uint32_t* ids);
+int mse_shard_group_search_filtered_dev(mse_shard_group* g, const mse_shard_filter* sf, const void* queries_dev, size_t nq, size_t k, int mode,
+                                        void* scores_dev, void* ids_dev);
+int mse_shard_group_pq_scan_topk_filtered(mse_shard_group* g, const mse_shard_filter* sf, const float* queries_f32, const float* scales, size_t nq,
+                                          size_t r, size_t k, int mode, int64_t* scores, uint32_t* ids);
+int mse_shard_group_query_topk_filtered(mse_shard_group* g, const mse_shard_filter* sf, const uint16_t* queries, const float* luts,
+                                        const float* scales, size_t nq, int disable_pq, size_t beamwidth, size_t search_list, size_t k, int regime,
+                                        int64_t* scores, uint32_t* ids);
+/* mse_disk_query_topk_block over has_url AND allowed: the filtered request path (regimes and AUTO plan of mse_disk_query_topk_filtered) with
+ * the results left on the device as a packed block, ids + id_offset; never coalesced.  The LIST regime writes the block directly. */
+int mse_disk_query_topk_block_filtered(mse_searcher* s, mse_pq* pq, const mse_codes* c, const mse_graph* g, const mse_filter* f, int regime,
+                                       const uint32_t* starts, const uint16_t* queries, const float* luts, const float* scales, size_t nq,
+                                       int disable_pq, size_t beamwidth, size_t search_list, size_t k, uint64_t id_offset, void* block_dev,
+                                       uint32_t* n_visited, uint32_t* cmps, uint32_t* pq_cmps);
+/* One process per GPU: the filtered forms of mse_comm_search_dev / _pq_scan_topk / _query_topk.  f is THIS RANK's LOCAL filter -- the caller's
+ * mse_filter_slice(global, first_row, rows of the rank, the rank's device) -- over the rank's rows; every rank must make the call. */
+int mse_comm_search_filtered_dev(mse_comm* c, mse_searcher* s, const mse_filter* f, const void* queries_dev, size_t nq, size_t k, int mode,
+                                 uint64_t id_offset, void* scores_dev, void* ids_dev);
+int mse_comm_pq_scan_topk_filtered(mse_comm* c, mse_pq* pq, const mse_codes* codes, mse_searcher* s, const mse_filter* f, const float* queries_f32,
+                                   const float* scales, size_t nq, size_t r, size_t k, int mode, uint64_t first_row, void* scores_dev,
+                                   void* ids_dev);
+int mse_comm_query_topk_filtered(mse_comm* c, mse_searcher* s, mse_pq* pq, const mse_codes* codes, const mse_graph* g, const mse_filter* f,
+                                 int regime, const uint16_t* queries, const float* luts, const float* scales, size_t nq, int disable_pq,
+                                 size_t beamwidth, size_t search_list, size_t k, uint64_t first_row, void* scores_dev, void* ids_dev);
 /* measurement hook of the row-gather kernel of mse_graph_compact (for scripts/graph_compact_probe.py): *last_gather_ms (or null)
  * receives the HIP-event time of that kernel in the last mse_graph_compact made on s while the switch was on (0: none), then the
  * switch is set (0 off, 1 on, 2 on and reset).  The kernel reads n_live and writes capacity rows of 2 d + code_size + n_desc bytes. */

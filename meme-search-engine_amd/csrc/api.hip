@@ -1004,6 +1004,107 @@ int mse_filter_read_ids(const mse_filter* f, size_t first, size_t n, uint32_t* o
     return 0;
 }
 
+// ---- a filter over GLOBAL rows cut into filters over LOCAL rows, and back (filter.hip slice_words_kernel / place_words_kernel) ----------
+// the thread's current device for the length of a call that must build on another one
+struct DeviceScope {
+    int prev = -1;
+    bool ok = false;
+    explicit DeviceScope(int device) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        ok = hipSetDevice(device) == hipSuccess;
+    }
+    ~DeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
+static int resolve_filter_device(int device, int own, const char* who) {
+    if (device < 0) return own;
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || device >= n_dev) { fail(std::string(who) + ": device ordinal out of range"); return -1; }
+    return device;
+}
+
+mse_filter* mse_filter_slice(const mse_filter* src, uint64_t first_row, size_t n_rows, int device) {
+    if (!src) { fail("filter_slice: null filter"); return nullptr; }
+    if (n_rows == 0) { fail("filter_slice: n_rows must be positive"); return nullptr; }
+    if (first_row > 0xFFFFFFFEull) { fail("filter_slice: row ids are u32: first_row is too large"); return nullptr; }
+    const int dev = resolve_filter_device(device, src->device, "filter_slice");
+    if (dev < 0) return nullptr;
+    DeviceScope scope(dev);
+    if (!scope.ok) { fail("filter_slice: hipSetDevice failed"); return nullptr; }
+    mse_filter* f = filter_alloc(n_rows);
+    if (!f) return nullptr;
+    const uint32_t* in = src->words;
+    size_t in_words = src->n_words, in_rows = src->n_rows;
+    uint64_t first = first_row;
+    DevBuf range;   // another device: the word range the slice reads comes over by ONE peer copy and is sliced here
+    if (dev != src->device) {
+        const size_t w0 = std::min<size_t>((size_t)(first_row >> 5), src->n_words);
+        const size_t nw = std::min<size_t>(src->n_words - w0, (n_rows + 31) / 32 + 1);
+        if (range.ensure(std::max<size_t>(nw, 1) * 4)) { mse_filter_free(f); return nullptr; }
+        if (nw && hipMemcpyPeer(range.p, dev, src->words + w0, src->device, nw * 4) != hipSuccess) {
+            (void)hipGetLastError();
+            mse_filter_free(f); fail("filter_slice: the peer copy failed"); return nullptr;
+        }
+        in = range.as<uint32_t>(); in_words = nw;
+        in_rows = src->n_rows > w0 * 32 ? src->n_rows - w0 * 32 : 0;
+        first = first_row - (uint64_t)w0 * 32;
+    }
+    FilterKernelTimer tm(nullptr);
+    if (launch_filter_slice(in, in_words, in_rows, first, n_rows, f->n_words, f->words, nullptr)) { mse_filter_free(f); return nullptr; }
+    tm.stop();
+    return filter_finish_counted(f);   // (blocks: `range` is free to go afterwards)
+}
+
+mse_filter* mse_filter_concat(const mse_filter* const* parts, const uint64_t* first_rows, size_t n_parts, size_t n_rows, int device) {
+    if (n_parts && (!parts || !first_rows)) { fail("filter_concat: null argument"); return nullptr; }
+    if (n_rows == 0) { fail("filter_concat: n_rows must be positive"); return nullptr; }
+    std::vector<std::pair<uint64_t, uint64_t>> spans;   // [first, end) of the parts that hold rows
+    for (size_t i = 0; i < n_parts; i++) {
+        if (!parts[i]) { fail("filter_concat: null part " + std::to_string(i)); return nullptr; }
+        const uint64_t len = parts[i]->n_rows;
+        if (first_rows[i] > n_rows || len > n_rows - first_rows[i]) {
+            fail("filter_concat: part " + std::to_string(i) + " reaches past the result's " + std::to_string(n_rows) + " rows");
+            return nullptr;
+        }
+        if (len) spans.emplace_back(first_rows[i], first_rows[i] + len);
+    }
+    std::sort(spans.begin(), spans.end());
+    for (size_t i = 1; i < spans.size(); i++)
+        if (spans[i].first < spans[i - 1].second) { fail("filter_concat: parts overlap at row " + std::to_string(spans[i].first)); return nullptr; }
+    int own = 0;
+    if (n_parts) own = parts[0]->device;
+    else if (hipGetDevice(&own) != hipSuccess) own = 0;
+    const int dev = resolve_filter_device(device, own, "filter_concat");
+    if (dev < 0) return nullptr;
+    DeviceScope scope(dev);
+    if (!scope.ok) { fail("filter_concat: hipSetDevice failed"); return nullptr; }
+    mse_filter* f = filter_alloc(n_rows);
+    if (!f) return nullptr;
+    // all on the null stream, one launch per part: parts that share a boundary word meet in launch order
+    FilterKernelTimer tm(nullptr);
+    bool ok = hipMemsetAsync(f->words, 0, std::max<size_t>(f->n_words, 1) * 4, nullptr) == hipSuccess;
+    if (!ok) fail("filter_concat: clearing the bitmap failed");
+    std::vector<DevBuf> staged(n_parts);   // parts of another device: their words come over by one peer copy each
+    for (size_t i = 0; ok && i < n_parts; i++) {
+        const mse_filter* p = parts[i];
+        if (p->n_rows == 0) continue;
+        const uint32_t* words = p->words;
+        if (p->device != dev) {
+            const size_t nw = (p->n_rows + 31) / 32;
+            ok = staged[i].ensure(nw * 4) == 0;
+            if (ok && hipMemcpyPeer(staged[i].p, dev, p->words, p->device, nw * 4) != hipSuccess) {
+                (void)hipGetLastError();
+                ok = false; fail("filter_concat: the peer copy failed");
+            }
+            words = staged[i].as<uint32_t>();
+        }
+        ok = ok && launch_filter_place(words, p->n_rows, first_rows[i], n_rows, f->words, nullptr) == 0;
+    }
+    if (!ok) { (void)hipStreamSynchronize(nullptr); mse_filter_free(f); return nullptr; }
+    tm.stop();
+    return filter_finish_counted(f);
+}
+
 
 
 int mse_bruteforce_topk_filtered_f16_dev(mse_searcher* s, const mse_filter* f, const void* queries_dev, size_t nq, size_t k, int mode,

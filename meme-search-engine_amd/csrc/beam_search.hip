@@ -1364,7 +1364,7 @@ int list_run(const SearchIn& in, const FusedQuery& fz) {
     const size_t nq = in.nq, d = b->d, k = fz.k;
     if (!f) return fail("disk_query_topk_filtered: null filter");
     if (check_filter(b, f) || check_list_regime(in) || check_k(k)) return -1;
-    if (fz.dev_sc || (!fz.dst && (!fz.ids || !fz.scores))) return fail("disk_query_topk: bad k / outputs");
+    if (!fz.dev_sc && !fz.dst && (!fz.ids || !fz.scores)) return fail("disk_query_topk: bad k / outputs");
     if (nq == 0) return 0;
     hipStream_t st = s->stream;
     const bool bias = in.scales && in.c->n_desc && in.c->desc;
@@ -1406,11 +1406,28 @@ int list_run(const SearchIn& in, const FusedQuery& fz) {
             MSE_HIP_TRY(hipMemsetAsync(s->q_stage.p, 0, (size_t)8 * d * 2, st));
             MSE_HIP_TRY(hipMemcpyAsync(s->q_stage.p, dq.as<uint16_t>() + q0 * d, (size_t)nqp * d * 2, hipMemcpyDeviceToDevice, st));
             const ListBias lb{in.c ? in.c->desc : nullptr, (int)n_desc, dsc.as<float>() + q0 * n_desc};
-            if (exact_pass_list(s, nqp, (int)k, 0, os.as<int64_t>() + q0 * k, oi.as<uint32_t>() + q0 * k, k, ids, n_el, bias ? &lb : nullptr)) return -1;
+            // a shard's hand-over: straight into the two halves of its packed block, the shard's first row added to the ids
+            int64_t* o_sc = fz.dev_sc ? fz.dev_sc + q0 * k : os.as<int64_t>() + q0 * k;
+            uint32_t* o_id = fz.dev_sc ? fz.dev_ids + q0 * k : oi.as<uint32_t>() + q0 * k;
+            if (exact_pass_list(s, nqp, (int)k, fz.dev_sc ? fz.id_offset : 0, o_sc, o_id, k, ids, n_el, bias ? &lb : nullptr)) return -1;
         }
-        MSE_HIP_TRY(hipMemcpyAsync(h_sc.data(), os.p, nq * k * 8, hipMemcpyDeviceToHost, st));
-        MSE_HIP_TRY(hipMemcpyAsync(h_id.data(), oi.p, nq * k * 4, hipMemcpyDeviceToHost, st));
+        if (!fz.dev_sc) {
+            MSE_HIP_TRY(hipMemcpyAsync(h_sc.data(), os.p, nq * k * 8, hipMemcpyDeviceToHost, st));
+            MSE_HIP_TRY(hipMemcpyAsync(h_id.data(), oi.p, nq * k * 4, hipMemcpyDeviceToHost, st));
+        }
         MSE_HIP_TRY(hipStreamSynchronize(st));
+    } else if (fz.dev_sc) {   // no eligible row: the block is all padding
+        MSE_HIP_TRY(hipMemcpyAsync(fz.dev_sc, h_sc.data(), nq * k * 8, hipMemcpyHostToDevice, st));
+        MSE_HIP_TRY(hipMemcpyAsync(fz.dev_ids, h_id.data(), nq * k * 4, hipMemcpyHostToDevice, st));
+        MSE_HIP_TRY(hipStreamSynchronize(st));
+    }
+    if (fz.dev_sc) {   // only the counters travel to the host
+        for (size_t q = 0; q < nq; q++) {
+            if (fz.n_visited) fz.n_visited[q] = (uint32_t)n_el;
+            if (fz.cmps) fz.cmps[q] = (uint32_t)n_el;
+            if (fz.pq_cmps) fz.pq_cmps[q] = 0;
+        }
+        return 0;
     }
     for (size_t q = 0; q < nq; q++) {
         const QueryDst o = fz.dst ? fz.dst[q]
@@ -1947,6 +1964,24 @@ int mse_disk_query_topk_block(mse_searcher* s, mse_pq* pq, const mse_codes* c, c
     fz.dev_ids = reinterpret_cast<uint32_t*>(static_cast<char*>(block_dev) + nq * k * 8);
     fz.id_offset = id_offset;
     return fused_run(SearchIn{s, pq, c, g, starts, queries, nullptr, luts, scales, nq, disable_pq, beamwidth, search_list}, fz);
+}
+
+// mse_disk_query_topk_block over has_url AND allowed: the filtered request path (mse_disk_query_topk_filtered: same regimes, same plan
+// under AUTO) with the shard's hand-over; never coalesced.
+int mse_disk_query_topk_block_filtered(mse_searcher* s, mse_pq* pq, const mse_codes* c, const mse_graph* g, const mse_filter* f, int regime,
+                                       const uint32_t* starts, const uint16_t* queries, const float* luts, const float* scales, size_t nq,
+                                       int disable_pq, size_t beamwidth, size_t search_list, size_t k, uint64_t id_offset, void* block_dev,
+                                       uint32_t* n_visited, uint32_t* cmps, uint32_t* pq_cmps) {
+    if (!g || !queries || !block_dev) return fail("disk_query_topk_block: null argument");
+    SearchIn in{s, pq, c, g, starts, queries, nullptr, luts, scales, nq, disable_pq, beamwidth, search_list, f};
+    if (filtered_resolve(in, regime)) return -1;
+    if (nq == 0) return 0;
+    if (check_k(k)) return -1;
+    FusedQuery fz = fused_out(k, nullptr, nullptr, n_visited, cmps, pq_cmps);
+    fz.dev_sc = reinterpret_cast<int64_t*>(block_dev);
+    fz.dev_ids = reinterpret_cast<uint32_t*>(static_cast<char*>(block_dev) + nq * k * 8);
+    fz.id_offset = id_offset;
+    return fused_run(in, fz);
 }
 
 int mse_graph_set_dedup(mse_graph* g, float threshold) {

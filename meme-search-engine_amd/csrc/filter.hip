@@ -230,7 +230,63 @@ __global__ void mask_tail_kernel(uint32_t* __restrict__ words, size_t n_rows) {
     if (blockIdx.x == 0 && threadIdx.x == 0) words[n_rows >> 5] &= (1u << (n_rows & 31)) - 1u;
 }
 
+// ---- a global filter cut into per-shard ones and back (mse_filter_slice / mse_filter_concat) ---------------------------------------------
+
+// out[w] = rows first_row + 32 w .. first_row + 32 w + 31 of `in`: the funnel of in[w0 + w] and in[w0 + w + 1] shifted right by
+// first_row & 31, w0 = first_row >> 5 (a 64-bit shift: shift 0 is no special case).  `in` reads as zero at and past its in_words words and
+// at and past its in_rows rows; the result is masked to n_rows, so the tile padding comes out as zero words.  One thread per output word.
+__global__ void slice_words_kernel(const uint32_t* __restrict__ in, size_t in_words, size_t in_rows, uint64_t first_row, size_t n_rows,
+                                   size_t n_words, uint32_t* __restrict__ out) {
+    const size_t w = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= n_words) return;
+    const uint32_t keep = row_mask(w, n_rows);
+    uint32_t v = 0u;
+    if (keep) {
+        const size_t s = (size_t)(first_row >> 5) + w;
+        const uint32_t lo = s < in_words ? in[s] & row_mask(s, in_rows) : 0u;
+        const uint32_t hi = s + 1 < in_words ? in[s + 1] & row_mask(s + 1, in_rows) : 0u;
+        v = (uint32_t)((((uint64_t)hi << 32) | lo) >> (first_row & 31)) & keep;
+    }
+    out[w] = v;
+}
+
+// The inverse: ORs `part` (part_rows rows), shifted left by first_row & 31, into out from word first_row >> 5 on.  Thread j owns the
+// destination word (first_row >> 5) + j -- the funnel of part[j - 1] and part[j] -- so a launch needs no atomics, and the parts of one
+// bitmap are placed by one launch each on ONE stream: two parts that share a boundary word meet in launch order.  out is n_rows rows of a
+// zero-initialised bitmap; nothing is written at or past them.  part_words + 1 threads, part_words = ceil(part_rows / 32).
+__global__ void place_words_kernel(const uint32_t* __restrict__ part, size_t part_rows, uint64_t first_row, size_t n_rows,
+                                   uint32_t* __restrict__ out) {
+    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t part_words = (part_rows + 31) / 32;
+    if (j > part_words) return;
+    const size_t dst = (size_t)(first_row >> 5) + j;
+    const uint32_t keep = row_mask(dst, n_rows);
+    if (!keep) return;
+    const uint32_t cur = j < part_words ? part[j] & row_mask(j, part_rows) : 0u;
+    const uint32_t prev = j > 0 ? part[j - 1] & row_mask(j - 1, part_rows) : 0u;
+    const uint32_t v = (uint32_t)((((uint64_t)cur << 32) | prev) >> (32 - (first_row & 31))) & keep;
+    if (v) out[dst] |= v;
+}
+
 }  // namespace
+
+int launch_filter_slice(const uint32_t* in, size_t in_words, size_t in_rows, uint64_t first_row, size_t n_rows, size_t n_words, uint32_t* out,
+                        hipStream_t stream) {
+    if (n_words == 0) return 0;
+    hipLaunchKernelGGL(slice_words_kernel, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, stream, in, in_words, in_rows, first_row,
+                       n_rows, n_words, out);
+    MSE_HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_filter_place(const uint32_t* part, size_t part_rows, uint64_t first_row, size_t n_rows, uint32_t* out, hipStream_t stream) {
+    if (part_rows == 0) return 0;
+    if (first_row > n_rows || part_rows > n_rows - first_row) return fail("filter concat: a part reaches past the result's rows");
+    const size_t threads = (part_rows + 31) / 32 + 1;
+    hipLaunchKernelGGL(place_words_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, part, part_rows, first_row, n_rows, out);
+    MSE_HIP_TRY(hipGetLastError());
+    return 0;
+}
 
 int launch_filter_combine(const uint32_t* a, size_t a_words, const uint32_t* b, size_t b_words, int op, size_t n_rows, size_t n_words,
                           uint32_t* out, hipStream_t stream) {

@@ -160,6 +160,13 @@ int launch_filter_score_threshold(const int64_t* scores, size_t n_rows, int64_t 
                                   size_t n_words, uint32_t* out, hipStream_t stream);
 // clears the bits at and past n_rows in the word that holds row n_rows
 int launch_filter_mask_tail(uint32_t* words, size_t n_rows, hipStream_t stream);
+// out (n_words words, whole tiles over n_rows) = rows first_row .. first_row + n_rows of `in`, which reads as zero at and past its in_words
+// words and its in_rows rows (mse_filter_slice)
+int launch_filter_slice(const uint32_t* in, size_t in_words, size_t in_rows, uint64_t first_row, size_t n_rows, size_t n_words, uint32_t* out,
+                        hipStream_t stream);
+// out (a zero-initialised bitmap over n_rows rows) |= part (part_rows rows) at row first_row; a part past n_rows is an error.  The parts of
+// one bitmap go on ONE stream, one launch each: parts sharing a boundary word then need no atomics (mse_filter_concat)
+int launch_filter_place(const uint32_t* part, size_t part_rows, uint64_t first_row, size_t n_rows, uint32_t* out, hipStream_t stream);
 // launch_expand_groups, with ID_NONE for rows whose bit is clear (or at / past 32 * n_words)
 int launch_expand_groups_masked(const uint32_t* parents, size_t par_stride, size_t n_par, int group, size_t n_rows, const uint32_t* words,
                                 size_t n_words, uint32_t* ids, size_t ids_stride, int nq, hipStream_t stream);

@@ -154,6 +154,9 @@ struct mse_shard_group {
     int rccl_ranks = 0;                 // as ncclCommCount reports them
     hipEvent_t ev_merge[2] = {nullptr, nullptr};
     double last_ms[4] = {0, 0, 0, 0};   // last search: max local search, max exchange, merge, wall
+    // stamp of the rows the shards hold now: every call that re-fills a shard takes a new one (process-wide counter, so two groups never
+    // share a stamp); an mse_shard_filter carries the stamp it was cut for and is refused under any other (guarded by call_mu)
+    uint64_t layout = 0;
 
     void worker(size_t g) {
         (void)hipSetDevice(shards[g].device);
@@ -193,6 +196,15 @@ struct mse_shard_group {
             if (shards[g].rc) return fail("shard " + std::to_string(g) + ": " + shards[g].err);
         return 0;
     }
+};
+
+static std::atomic<uint64_t> g_layout_stamp{0};
+
+// one local filter per shard of a group, each on its shard's device (include/mse.h)
+struct mse_shard_filter {
+    uint64_t layout = 0;                  // the group's stamp when it was made
+    std::vector<mse_filter*> parts;       // owned; part g speaks the LOCAL ids of shard g
+    std::vector<uint64_t> first_rows;     // global id of each part's row 0
 };
 
 // contiguous split, remainder spread over the first shards (the same rule as the host mirror's shard_range)
@@ -320,6 +332,7 @@ int mse_shard_group_generate(mse_shard_group* G, uint32_t seed, uint64_t first_r
     if (!G) return fail("null shard group");
     if (first_row + total_rows > 0xFFFFFFFEull) return fail("row ids are u32: too many rows");
     std::lock_guard<std::mutex> call(G->call_mu);
+    G->layout = ++g_layout_stamp;
     return G->run([=](size_t g) -> int {
         size_t lo, hi;
         shard_range(total_rows, g, G->shards.size(), &lo, &hi);
@@ -331,6 +344,7 @@ int mse_shard_group_load_host(mse_shard_group* G, const uint16_t* rows, size_t t
     if (!G) return fail("null shard group");
     if (total_rows > 0xFFFFFFFEull) return fail("row ids are u32: too many rows");
     std::lock_guard<std::mutex> call(G->call_mu);
+    G->layout = ++g_layout_stamp;
     return G->run([=](size_t g) -> int {
         size_t lo, hi;
         shard_range(total_rows, g, G->shards.size(), &lo, &hi);
@@ -343,6 +357,7 @@ int mse_shard_group_set_shard_device(mse_shard_group* G, size_t shard, const voi
     if (shard >= G->shards.size()) return fail("shard index out of range");
     if (first_row + n_rows > 0xFFFFFFFEull) return fail("row ids are u32: too many rows");
     std::lock_guard<std::mutex> call(G->call_mu);
+    G->layout = ++g_layout_stamp;
     return G->run([=](size_t g) -> int {
         if (g != shard) return 0;
         return install(G->shards[g], mse_base_wrap_device(rows_dev, n_rows, G->d), (size_t)first_row);
@@ -508,6 +523,31 @@ static LocalFn bruteforce_local(size_t nq, size_t k, int mode) {
     };
 }
 
+// the same over the shard's slice of a shard filter (mse_bruteforce_topk_filtered_f16_dev: the slice speaks local ids, the block global ones)
+static LocalFn bruteforce_local_filtered(const mse_shard_group* G, const mse_shard_filter* sf, size_t nq, size_t k, int mode) {
+    return [=](Shard& sh, const void* q, char* blk) -> int {
+        return mse_bruteforce_topk_filtered_f16_dev(sh.searcher, sf->parts[(size_t)(&sh - G->shards.data())], q, nq, k, mode, sh.first_row, blk,
+                                                    blk + nq * k * 8);
+    };
+}
+
+// A shard filter may be used on the group as it is now: made for this layout (not another group's, not from before a re-fill), one part per
+// shard, each of its shard's length and on its device.  The caller holds G->call_mu.  0, or -1 with the error set
+static int check_shard_filter(const mse_shard_group* G, const mse_shard_filter* sf) {
+    if (!sf) return fail("shard group: null shard filter");
+    if (sf->layout != G->layout || sf->parts.size() != G->shards.size())
+        return fail("shard group: the shard filter was made for another group, or before the group's rows were replaced");
+    for (size_t g = 0; g < G->shards.size(); g++) {
+        const Shard& sh = G->shards[g];
+        const mse_filter* f = sf->parts[g];
+        if (!sh.base || !f || f->n_rows != sh.base->n || f->device != sh.device || sf->first_rows[g] != sh.first_row)
+            return fail("shard group: the shard filter does not fit shard " + std::to_string(g));
+    }
+    return 0;
+}
+
+static bool known_mode(int mode) { return mode == MSE_MODE_AUTO || mode == MSE_MODE_EXACT || mode == MSE_MODE_MFMA; }
+
 extern "C" {
 
 // queries_dev: [nq][d] f16 on the ROOT device (device of shard 0), complete before the call; outputs [nq][k] on the root device.
@@ -519,6 +559,44 @@ int mse_shard_group_search_dev(mse_shard_group* G, const void* queries_dev, size
     if (k > (size_t)TOPK_KMAX - 64) return fail("k too large (max 1984)");
     std::lock_guard<std::mutex> call(G->call_mu);
     return search_dev_locked(G, queries_dev, nq * G->d * 2, nq, k, k, bruteforce_local(nq, k, mode), scores_dev, ids_dev);
+}
+
+int mse_shard_group_search_filtered_dev(mse_shard_group* G, const mse_shard_filter* sf, const void* queries_dev, size_t nq, size_t k, int mode,
+                                        void* scores_dev, void* ids_dev) {
+    if (!G) return fail("null shard group");
+    if (!sf) return fail("shard group: null shard filter");
+    if (!known_mode(mode)) return fail("unknown mode");
+    if (k > (size_t)TOPK_KMAX - 64) return fail("k too large (max 1984)");
+    std::lock_guard<std::mutex> call(G->call_mu);
+    if (check_shard_filter(G, sf)) return -1;
+    if (nq == 0 || k == 0) return 0;
+    if (!queries_dev || !scores_dev || !ids_dev) return fail("shard group: null argument");
+    return search_dev_locked(G, queries_dev, nq * G->d * 2, nq, k, k, bruteforce_local_filtered(G, sf, nq, k, mode), scores_dev, ids_dev);
+}
+
+int mse_shard_group_search_filtered(mse_shard_group* G, const mse_shard_filter* sf, const uint16_t* queries, size_t nq, size_t k, int mode,
+                                    int64_t* scores, uint32_t* ids) {
+    if (!G) return fail("null shard group");
+    if (!sf) return fail("shard group: null shard filter");
+    if (!known_mode(mode)) return fail("unknown mode");
+    if (k > (size_t)TOPK_KMAX - 64) return fail("k too large (max 1984)");
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    int rc = 0;
+    {
+        std::lock_guard<std::mutex> call(G->call_mu);   // one lock across the check, upload, search and download (mse_shard_group_search)
+        if (check_shard_filter(G, sf)) return -1;
+        if (nq == 0 || k == 0) return 0;
+        if (!queries || !scores || !ids) return fail("shard group: null argument");
+        MSE_HIP_TRY(hipSetDevice(G->root_device));
+        rc = G->q_root.ensure(nq * G->d * 2) || G->out_s.ensure(nq * k * 8) || G->out_i.ensure(nq * k * 4);
+        if (!rc && hipMemcpy(G->q_root.p, queries, nq * G->d * 2, hipMemcpyHostToDevice) != hipSuccess) rc = fail("query upload failed");
+        if (!rc) rc = search_dev_locked(G, G->q_root.p, nq * G->d * 2, nq, k, k, bruteforce_local_filtered(G, sf, nq, k, mode), G->out_s.p, G->out_i.p);
+        if (!rc && (hipMemcpy(scores, G->out_s.p, nq * k * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+                    hipMemcpy(ids, G->out_i.p, nq * k * 4, hipMemcpyDeviceToHost) != hipSuccess)) rc = fail("result download failed");
+    }
+    (void)hipSetDevice(prev);
+    return rc;
 }
 
 int mse_shard_group_search(mse_shard_group* G, const uint16_t* queries, size_t nq, size_t k, int mode, int64_t* scores,
@@ -598,8 +676,10 @@ static int pq_rescore_members(const mse_base* b, const mse_codes* codes, uint64_
 //   B  every shard: exact score (+ descriptor bias) of ITS members of that top-r, (INT64_MIN, none) for the others'
 //                                                                   -> exchange -> top-k by (exact score desc, id asc)
 // Records exchanged: 2 x shards x nq x r x 12 bytes (r = 200, 32 queries, 8 shards: 1.2 MB in all).
-int mse_shard_group_pq_scan_topk(mse_shard_group* G, const float* queries_f32, const float* scales, size_t nq, size_t r, size_t k,
-                                 int64_t* scores, uint32_t* ids) {
+// sf: the allowed rows (null: all; then `mode` is unused) -- phase A becomes mse_pq_scan_topk_block_filtered over the shard's slice, and
+// phase B stays as it is: every member of the merged top-r is allowed by construction
+static int pq_scan_topk_impl(mse_shard_group* G, const mse_shard_filter* sf, int mode, const float* queries_f32, const float* scales, size_t nq,
+                             size_t r, size_t k, int64_t* scores, uint32_t* ids) {
     if (!G || !queries_f32 || !scores || !ids) return fail("shard group pq scan: null argument");
     if (nq == 0 || k == 0) return 0;
     if (r < k) r = k;
@@ -613,6 +693,7 @@ int mse_shard_group_pq_scan_topk(mse_shard_group* G, const float* queries_f32, c
     int rc = 0;
     {
         std::lock_guard<std::mutex> call(G->call_mu);
+        if (sf && check_shard_filter(G, sf)) { (void)hipSetDevice(prev); return -1; }
         // root staging: [f16 queries nq x d][merged top-r ids nq x r][scales n_desc f32] -- phase B's payload, one buffer so that a shard
         // that cannot map the root's memory gets it in one peer copy
         const size_t off_ids = (nq * d * 2 + 255) & ~(size_t)255, off_sc = (off_ids + nq * r * 4 + 255) & ~(size_t)255;
@@ -628,6 +709,9 @@ int mse_shard_group_pq_scan_topk(mse_shard_group* G, const float* queries_f32, c
         // phase A: the index's top-r by ADC (+ bias)
         if (!rc)
             rc = search_dev_locked(G, nullptr, 0, nq, r, r, [=](Shard& sh, const void*, char* blk) -> int {
+                if (sf)   // (AUTO resolves per shard, from the shard's own codes and count)
+                    return mse_pq_scan_topk_block_filtered(sh.pq, sh.codes, sf->parts[(size_t)(&sh - G->shards.data())], nullptr, queries_f32, nq,
+                                                           bias ? scales : nullptr, r, r, mode, sh.first_row, blk);
                 return mse_pq_scan_topk_block(sh.pq, sh.codes, nullptr, queries_f32, nq, bias ? scales : nullptr, r, r, sh.first_row, blk);
             }, G->out_s.p, G->out_i.p);
         double tA[4] = {G->last_ms[0], G->last_ms[1], G->last_ms[2], G->last_ms[3]};
@@ -648,13 +732,31 @@ int mse_shard_group_pq_scan_topk(mse_shard_group* G, const float* queries_f32, c
     return rc;
 }
 
+int mse_shard_group_pq_scan_topk(mse_shard_group* G, const float* queries_f32, const float* scales, size_t nq, size_t r, size_t k,
+                                 int64_t* scores, uint32_t* ids) {
+    return pq_scan_topk_impl(G, nullptr, 0, queries_f32, scales, nq, r, k, scores, ids);
+}
+
+int mse_shard_group_pq_scan_topk_filtered(mse_shard_group* G, const mse_shard_filter* sf, const float* queries_f32, const float* scales, size_t nq,
+                                          size_t r, size_t k, int mode, int64_t* scores, uint32_t* ids) {
+    if (!G) return fail("shard group pq scan: null argument");
+    if (!sf) return fail("shard group: null shard filter");
+    if (mode != MSE_PQ_FILTER_AUTO && mode != MSE_PQ_FILTER_SCAN && mode != MSE_PQ_FILTER_LIST) return fail("unknown mode");
+    {
+        std::lock_guard<std::mutex> call(G->call_mu);   // (a stale filter is refused even by a call that has nothing to do)
+        if (check_shard_filter(G, sf)) return -1;
+    }
+    return pq_scan_topk_impl(G, sf, mode, queries_f32, scales, nq, r, k, scores, ids);
+}
+
 // The graph index sharded: ONE Vamana graph per shard over its own rows (the reference's shards are exactly that:
 // src/generate_index_shard.rs builds a shard's graph over the shard's vectors).  Every shard answers the whole query batch from ITS
 // graph -- entry by its own entry table, query_disk_index::greedy_search, the k best visited records (mse_disk_query_topk_block) --
 // and the blocks meet in the one exchange: the merged result is the merge of the per-shard searches.  queries: f16 [nq][d] host rows;
 // neighbours scored exactly (disable_pq = 1) or by ADC through the shard's codec and codes with tables from `luts` ([nq][64*256] f32).
-int mse_shard_group_query_topk(mse_shard_group* G, const uint16_t* queries, const float* luts, const float* scales, size_t nq, int disable_pq,
-                               size_t beamwidth, size_t search_list, size_t k, int64_t* scores, uint32_t* ids) {
+// sf: the allowed rows (null: all; then `regime` is unused) -- every shard runs mse_disk_query_topk_block_filtered over its slice
+static int query_topk_impl(mse_shard_group* G, const mse_shard_filter* sf, int regime, const uint16_t* queries, const float* luts, const float* scales,
+                           size_t nq, int disable_pq, size_t beamwidth, size_t search_list, size_t k, int64_t* scores, uint32_t* ids) {
     if (!G || !queries || !scores || !ids) return fail("shard group query: null argument");
     if (nq == 0 || k == 0) return 0;
     if (k > (size_t)TOPK_KMAX - 64) return fail("k too large (max 1984)");
@@ -668,10 +770,15 @@ int mse_shard_group_query_topk(mse_shard_group* G, const uint16_t* queries, cons
     int rc = 0;
     {
         std::lock_guard<std::mutex> call(G->call_mu);
+        if (sf && check_shard_filter(G, sf)) { (void)hipSetDevice(prev); return -1; }
         rc = G->q_root.ensure(nq * G->d * 2) || G->out_s.ensure(nq * k * 8) || G->out_i.ensure(nq * k * 4);
         if (!rc && hipMemcpy(G->q_root.p, queries, nq * G->d * 2, hipMemcpyHostToDevice) != hipSuccess) rc = fail("query upload failed");
         if (!rc)
             rc = search_dev_locked(G, G->q_root.p, nq * G->d * 2, nq, k, k, [=](Shard& sh, const void* q, char* blk) -> int {
+                if (sf)   // (AUTO: each shard's plan from its own rows and count)
+                    return mse_disk_query_topk_block_filtered(sh.searcher, sh.pq, sh.codes, sh.graph, sf->parts[(size_t)(&sh - G->shards.data())], regime,
+                                                              nullptr, static_cast<const uint16_t*>(q), luts, scales, nq, disable_pq, beamwidth,
+                                                              search_list, k, sh.first_row, blk, nullptr, nullptr, nullptr);
                 return mse_disk_query_topk_block(sh.searcher, sh.pq, sh.codes, sh.graph, nullptr, static_cast<const uint16_t*>(q), luts, scales, nq, disable_pq,
                                                  beamwidth, search_list, k, sh.first_row, blk, nullptr, nullptr, nullptr);
             }, G->out_s.p, G->out_i.p);
@@ -680,6 +787,117 @@ int mse_shard_group_query_topk(mse_shard_group* G, const uint16_t* queries, cons
     }
     (void)hipSetDevice(prev);
     return rc;
+}
+
+int mse_shard_group_query_topk(mse_shard_group* G, const uint16_t* queries, const float* luts, const float* scales, size_t nq, int disable_pq,
+                               size_t beamwidth, size_t search_list, size_t k, int64_t* scores, uint32_t* ids) {
+    return query_topk_impl(G, nullptr, 0, queries, luts, scales, nq, disable_pq, beamwidth, search_list, k, scores, ids);
+}
+
+int mse_shard_group_query_topk_filtered(mse_shard_group* G, const mse_shard_filter* sf, const uint16_t* queries, const float* luts, const float* scales,
+                                        size_t nq, int disable_pq, size_t beamwidth, size_t search_list, size_t k, int regime, int64_t* scores,
+                                        uint32_t* ids) {
+    if (!G) return fail("shard group query: null argument");
+    if (!sf) return fail("shard group: null shard filter");
+    if (regime != MSE_FILTERED_AUTO && regime != MSE_FILTERED_GRAPH && regime != MSE_FILTERED_LIST) return fail("shard group query: unknown regime");
+    {
+        std::lock_guard<std::mutex> call(G->call_mu);
+        if (check_shard_filter(G, sf)) return -1;
+    }
+    return query_topk_impl(G, sf, regime, queries, luts, scales, nq, disable_pq, beamwidth, search_list, k, scores, ids);
+}
+
+// ---- shard filters: a row filter per shard, each on its shard's device (include/mse.h) ------------------------------------------------
+void mse_shard_filter_free(mse_shard_filter* sf) {
+    if (!sf) return;
+    for (mse_filter* f : sf->parts) mse_filter_free(f);
+    delete sf;
+}
+
+// one part per shard, made by make(shard index, shard) on the shard's own thread (and device), after fits() -- a check of the whole request
+// against the group as it is (may be empty) -- has passed; the caller does NOT hold call_mu
+static mse_shard_filter* shard_filter_make(mse_shard_group* G, const std::function<int()>& fits,
+                                           const std::function<mse_filter*(size_t, Shard&)>& make) {
+    std::lock_guard<std::mutex> call(G->call_mu);
+    for (const Shard& s : G->shards) if (!s.base) { fail("shard group: a shard holds no rows yet"); return nullptr; }
+    if (fits && fits()) return nullptr;
+    mse_shard_filter* sf = new (std::nothrow) mse_shard_filter();
+    if (!sf) { fail("out of host memory"); return nullptr; }
+    try {
+        sf->parts.assign(G->shards.size(), nullptr);
+        sf->first_rows.assign(G->shards.size(), 0);
+    } catch (const std::bad_alloc&) {
+        delete sf; fail("out of host memory"); return nullptr;
+    }
+    sf->layout = G->layout;
+    const int rc = G->run([&](size_t g) -> int {
+        Shard& sh = G->shards[g];
+        sf->first_rows[g] = sh.first_row;
+        mse_filter* f = make(g, sh);
+        if (!f) return -1;
+        sf->parts[g] = f;
+        if (f->n_rows != sh.base->n || f->device != sh.device) return fail("the filter does not fit the shard's rows / device");
+        return 0;
+    });
+    if (rc) { const std::string why = mse_last_error(); mse_shard_filter_free(sf); set_error(why); return nullptr; }
+    return sf;
+}
+
+// rows [0, n) of src as a filter on `device`; a shard without rows gets the empty filter (mse_filter_slice makes no filter of no rows)
+static mse_filter* slice_or_empty(const mse_filter* src, uint64_t first_row, size_t n, int device) {
+    if (n) return mse_filter_slice(src, first_row, n, device);
+    if (hipSetDevice(device) != hipSuccess) { fail("shard group: hipSetDevice failed"); return nullptr; }
+    return mse_filter_from_bits(nullptr, 0);
+}
+
+mse_shard_filter* mse_shard_group_filter(mse_shard_group* G, const mse_filter* global) {
+    if (!G || !global) { fail("shard group filter: null argument"); return nullptr; }
+    return shard_filter_make(G, [=]() -> int {
+        uint64_t end = 0;
+        for (const Shard& sh : G->shards) end = std::max<uint64_t>(end, sh.first_row + sh.base->n);
+        if (global->n_rows > end)
+            return fail("shard group: the filter is longer than the group (" + std::to_string(global->n_rows) + " > " + std::to_string(end) + " rows)");
+        return 0;
+    }, [=](size_t, Shard& sh) -> mse_filter* { return slice_or_empty(global, sh.first_row, sh.base->n, sh.device); });
+}
+
+mse_shard_filter* mse_shard_group_filter_from_local(mse_shard_group* G, const mse_filter* const* per_shard) {
+    if (!G || !per_shard) { fail("shard group filter: null argument"); return nullptr; }
+    return shard_filter_make(G, nullptr, [=](size_t g, Shard& sh) -> mse_filter* {
+        const mse_filter* f = per_shard[g];
+        if (!f) { fail("null filter"); return nullptr; }
+        if (f->n_rows != sh.base->n) {
+            fail("the filter has " + std::to_string(f->n_rows) + " rows, the shard " + std::to_string(sh.base->n));
+            return nullptr;
+        }
+        if (f->device != sh.device) { fail("the filter was made on another device than the shard's"); return nullptr; }
+        return slice_or_empty(f, 0, sh.base->n, sh.device);
+    });
+}
+
+mse_shard_filter* mse_shard_group_live_filter(mse_shard_group* G, int and_has_url) {
+    if (!G) { fail("shard group filter: null argument"); return nullptr; }
+    return shard_filter_make(G, nullptr, [=](size_t, Shard& sh) -> mse_filter* {
+        if (!sh.graph) { fail("no graph attached (mse_shard_group_attach_graph)"); return nullptr; }
+        return mse_graph_live_filter(sh.graph, and_has_url);
+    });
+}
+
+size_t mse_shard_filter_count(const mse_shard_filter* sf) {
+    size_t n = 0;
+    if (sf) for (const mse_filter* f : sf->parts) n += f->count;
+    return n;
+}
+size_t mse_shard_filter_n_shards(const mse_shard_filter* sf) { return sf ? sf->parts.size() : 0; }
+const mse_filter* mse_shard_filter_shard(const mse_shard_filter* sf, size_t shard) {
+    if (!sf || shard >= sf->parts.size()) { fail("shard filter: shard index out of range"); return nullptr; }
+    return sf->parts[shard];
+}
+mse_filter* mse_shard_filter_global(const mse_shard_filter* sf, int device) {
+    if (!sf) { fail("shard filter: null argument"); return nullptr; }
+    uint64_t end = 0;
+    for (size_t g = 0; g < sf->parts.size(); g++) end = std::max<uint64_t>(end, sf->first_rows[g] + sf->parts[g]->n_rows);
+    return mse_filter_concat(sf->parts.data(), sf->first_rows.data(), sf->parts.size(), (size_t)end, device);
 }
 
 int mse_shard_group_set_exchange(mse_shard_group* G, int kind) {
@@ -747,8 +965,9 @@ int mse_comm_size(const mse_comm* c) {
 
 // local search over this rank's shard + ONE all-gather of the packed records + merge; outputs [nq][k] on this rank's device,
 // identical on every rank.  Asynchronous on the searcher's stream after the local search (which synchronises internally).
-int mse_comm_search_dev(mse_comm* c, mse_searcher* s, const void* queries_dev, size_t nq, size_t k, int mode,
-                        uint64_t id_offset, void* scores_dev, void* ids_dev) {
+// f: this rank's LOCAL filter (null: the unfiltered search)
+static int comm_search_impl(mse_comm* c, mse_searcher* s, const mse_filter* f, const void* queries_dev, size_t nq, size_t k, int mode,
+                            uint64_t id_offset, void* scores_dev, void* ids_dev) {
     if (!c || !s) return fail("null communicator / searcher");
     if (nq == 0 || k == 0) return 0;
     if (k > (size_t)TOPK_KMAX - 64) return fail("k too large (max 1984)");
@@ -758,7 +977,8 @@ int mse_comm_search_dev(mse_comm* c, mse_searcher* s, const void* queries_dev, s
     for (hipEvent_t& e : c->ev) if (!e) MSE_HIP_TRY(hipEventCreate(&e));
     c->timed = false;
     MSE_HIP_TRY(hipEventRecord(c->ev[0], s->stream));
-    if (mse_bruteforce_topk_f16_dev(s, queries_dev, nq, k, mode, id_offset, blk, blk + nq * k * 8)) return -1;
+    if (f ? mse_bruteforce_topk_filtered_f16_dev(s, f, queries_dev, nq, k, mode, id_offset, blk, blk + nq * k * 8)
+          : mse_bruteforce_topk_f16_dev(s, queries_dev, nq, k, mode, id_offset, blk, blk + nq * k * 8)) return -1;
     MSE_HIP_TRY(hipEventRecord(c->ev[1], s->stream));
     const int rc = rccl().AllGather(blk, c->gathered.p, B, /*ncclInt8*/ 0, c->comm, s->stream);
     if (rc) return rccl_fail("ncclAllGather", rc);
@@ -767,6 +987,22 @@ int mse_comm_search_dev(mse_comm* c, mse_searcher* s, const void* queries_dev, s
     MSE_HIP_TRY(hipEventRecord(c->ev[3], s->stream));
     c->timed = true;
     return 0;
+}
+
+int mse_comm_search_dev(mse_comm* c, mse_searcher* s, const void* queries_dev, size_t nq, size_t k, int mode,
+                        uint64_t id_offset, void* scores_dev, void* ids_dev) {
+    return comm_search_impl(c, s, nullptr, queries_dev, nq, k, mode, id_offset, scores_dev, ids_dev);
+}
+
+// mse_comm_search_dev over this rank's LOCAL filter (the caller's mse_filter_slice of the global one at id_offset): every rank's filtered
+// top-k, ONE all-gather, merge.  The argument checks come before the collective: a rank that fails them leaves the others waiting, as any
+// rank that does not call does.
+int mse_comm_search_filtered_dev(mse_comm* c, mse_searcher* s, const mse_filter* f, const void* queries_dev, size_t nq, size_t k, int mode,
+                                 uint64_t id_offset, void* scores_dev, void* ids_dev) {
+    if (!c || !s) return fail("null communicator / searcher");
+    if (check_filter(s->base, f)) return -1;
+    if (!known_mode(mode)) return fail("unknown mode");
+    return comm_search_impl(c, s, f, queries_dev, nq, k, mode, id_offset, scores_dev, ids_dev);
 }
 
 // The exchange alone: this rank's packed block ([nq*k_in] i64 scores | [nq*k_in] u32 GLOBAL ids, on its device, complete on the
@@ -786,8 +1022,8 @@ int mse_comm_exchange_dev(mse_comm* c, mse_searcher* s, const void* block_dev, s
 // One rank of the sharded PQ scan + exact re-rank (the protocol of mse_shard_group_pq_scan_topk): this rank's codes / rows start at
 // global row first_row; queries_f32 [nq][d] and scales [n_desc] are host memory, the same on every rank.  Outputs [nq][k] on this
 // rank's device, identical on every rank, complete on return.
-int mse_comm_pq_scan_topk(mse_comm* c, mse_pq* pq, const mse_codes* codes, mse_searcher* s, const float* queries_f32, const float* scales,
-                          size_t nq, size_t r, size_t k, uint64_t first_row, void* scores_dev, void* ids_dev) {
+static int comm_pq_scan_impl(mse_comm* c, mse_pq* pq, const mse_codes* codes, mse_searcher* s, const mse_filter* f, int mode, const float* queries_f32,
+                             const float* scales, size_t nq, size_t r, size_t k, uint64_t first_row, void* scores_dev, void* ids_dev) {
     if (!c || !pq || !codes || !s || !s->base || !queries_f32) return fail("comm pq scan: null argument");
     if (nq == 0 || k == 0) return 0;
     if (r < k) r = k;
@@ -800,7 +1036,9 @@ int mse_comm_pq_scan_topk(mse_comm* c, mse_pq* pq, const mse_codes* codes, mse_s
     const size_t o_ms = B, o_mi = o_ms + n * 8, o_q32 = (o_mi + n * 4 + 255) & ~(size_t)255, o_q16 = o_q32 + nq * d * 4, o_sc = (o_q16 + nq * d * 2 + 255) & ~(size_t)255;
     if (c->local.ensure(o_sc + n_desc * 4 + 64)) return -1;
     char* w = c->local.as<char>();
-    if (mse_pq_scan_topk_block(pq, codes, nullptr, queries_f32, nq, bias ? scales : nullptr, r, r, first_row, w)) return -1;   // phase A, complete on return
+    // phase A, complete on return
+    if (f ? mse_pq_scan_topk_block_filtered(pq, codes, f, nullptr, queries_f32, nq, bias ? scales : nullptr, r, r, mode, first_row, w)
+          : mse_pq_scan_topk_block(pq, codes, nullptr, queries_f32, nq, bias ? scales : nullptr, r, r, first_row, w)) return -1;
     if (mse_comm_exchange_dev(c, s, w, nq, r, r, w + o_ms, w + o_mi)) return -1;
     MSE_HIP_TRY(hipMemcpyAsync(w + o_q32, queries_f32, nq * d * 4, hipMemcpyHostToDevice, st));
     if (launch_f32_to_f16(reinterpret_cast<const float*>(w + o_q32), nq * d, reinterpret_cast<uint16_t*>(w + o_q16), st)) return -1;
@@ -810,6 +1048,20 @@ int mse_comm_pq_scan_topk(mse_comm* c, mse_pq* pq, const mse_codes* codes, mse_s
     if (mse_comm_exchange_dev(c, s, w, nq, r, k, scores_dev, ids_dev)) return -1;
     MSE_HIP_TRY(hipStreamSynchronize(st));
     return 0;
+}
+
+int mse_comm_pq_scan_topk(mse_comm* c, mse_pq* pq, const mse_codes* codes, mse_searcher* s, const float* queries_f32, const float* scales,
+                          size_t nq, size_t r, size_t k, uint64_t first_row, void* scores_dev, void* ids_dev) {
+    return comm_pq_scan_impl(c, pq, codes, s, nullptr, 0, queries_f32, scales, nq, r, k, first_row, scores_dev, ids_dev);
+}
+
+// The same over this rank's LOCAL filter (mse_shard_group_pq_scan_topk_filtered's protocol: phase A filtered, phase B unchanged)
+int mse_comm_pq_scan_topk_filtered(mse_comm* c, mse_pq* pq, const mse_codes* codes, mse_searcher* s, const mse_filter* f, const float* queries_f32,
+                                   const float* scales, size_t nq, size_t r, size_t k, int mode, uint64_t first_row, void* scores_dev,
+                                   void* ids_dev) {
+    if (!f) return fail("comm pq scan: null filter");
+    if (mode != MSE_PQ_FILTER_AUTO && mode != MSE_PQ_FILTER_SCAN && mode != MSE_PQ_FILTER_LIST) return fail("unknown mode");
+    return comm_pq_scan_impl(c, pq, codes, s, f, mode, queries_f32, scales, nq, r, k, first_row, scores_dev, ids_dev);
 }
 
 // One rank of the sharded graph index (mse_shard_group_query_topk's protocol): this rank's graph over its own rows answers the batch,
@@ -823,6 +1075,22 @@ int mse_comm_query_topk(mse_comm* c, mse_searcher* s, mse_pq* pq, const mse_code
     if (c->local.ensure(block_bytes(nq, k))) return -1;
     if (mse_disk_query_topk_block(s, pq, codes, g, nullptr, queries, luts, scales, nq, disable_pq, beamwidth, search_list, k, first_row, c->local.p,
                                   nullptr, nullptr, nullptr)) return -1;
+    if (mse_comm_exchange_dev(c, s, c->local.p, nq, k, k, scores_dev, ids_dev)) return -1;
+    MSE_HIP_TRY(hipStreamSynchronize(s->stream));
+    return 0;
+}
+
+// The same over this rank's LOCAL filter: mse_disk_query_topk_block_filtered, ONE all-gather, merge
+int mse_comm_query_topk_filtered(mse_comm* c, mse_searcher* s, mse_pq* pq, const mse_codes* codes, const mse_graph* g, const mse_filter* f,
+                                 int regime, const uint16_t* queries, const float* luts, const float* scales, size_t nq, int disable_pq,
+                                 size_t beamwidth, size_t search_list, size_t k, uint64_t first_row, void* scores_dev, void* ids_dev) {
+    if (!c || !s || !g || !queries) return fail("comm query: null argument");
+    if (!f) return fail("comm query: null filter");
+    if (nq == 0 || k == 0) return 0;
+    if (k > (size_t)TOPK_KMAX - 64) return fail("k too large (max 1984)");
+    if (c->local.ensure(block_bytes(nq, k))) return -1;
+    if (mse_disk_query_topk_block_filtered(s, pq, codes, g, f, regime, nullptr, queries, luts, scales, nq, disable_pq, beamwidth, search_list, k,
+                                           first_row, c->local.p, nullptr, nullptr, nullptr)) return -1;
     if (mse_comm_exchange_dev(c, s, c->local.p, nq, k, k, scores_dev, ids_dev)) return -1;
     MSE_HIP_TRY(hipStreamSynchronize(s->stream));
     return 0;

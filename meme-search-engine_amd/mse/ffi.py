@@ -144,6 +144,25 @@ SIGNATURES = {
     "mse_filter_to_bits": (C.c_int, [vp, u8p]),
     "mse_filter_read_ids": (C.c_int, [vp, sz, sz, u32p]),
     "mse_filter_kernel_timing": (C.c_int, [C.c_int, C.POINTER(C.c_double)]),
+    "mse_filter_slice": (vp, [vp, C.c_uint64, sz, C.c_int]),
+    "mse_filter_concat": (vp, [C.POINTER(vp), C.POINTER(C.c_uint64), sz, sz, C.c_int]),
+    "mse_shard_group_filter": (vp, [vp, vp]),
+    "mse_shard_group_filter_from_local": (vp, [vp, C.POINTER(vp)]),
+    "mse_shard_group_live_filter": (vp, [vp, C.c_int]),
+    "mse_shard_filter_free": (None, [vp]),
+    "mse_shard_filter_count": (sz, [vp]),
+    "mse_shard_filter_n_shards": (sz, [vp]),
+    "mse_shard_filter_shard": (vp, [vp, sz]),
+    "mse_shard_filter_global": (vp, [vp, C.c_int]),
+    "mse_shard_group_search_filtered": (C.c_int, [vp, vp, u16p, sz, sz, C.c_int, i64p, u32p]),
+    "mse_shard_group_search_filtered_dev": (C.c_int, [vp, vp, vp, sz, sz, C.c_int, vp, vp]),
+    "mse_shard_group_pq_scan_topk_filtered": (C.c_int, [vp, vp, f32p, f32p, sz, sz, sz, C.c_int, i64p, u32p]),
+    "mse_shard_group_query_topk_filtered": (C.c_int, [vp, vp, u16p, f32p, f32p, sz, C.c_int, sz, sz, sz, C.c_int, i64p, u32p]),
+    "mse_disk_query_topk_block_filtered": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, u32p, u16p, f32p, f32p, sz, C.c_int, sz, sz, sz, C.c_uint64, vp,
+                                                     u32p, u32p, u32p]),
+    "mse_comm_search_filtered_dev": (C.c_int, [vp, vp, vp, vp, sz, sz, C.c_int, C.c_uint64, vp, vp]),
+    "mse_comm_pq_scan_topk_filtered": (C.c_int, [vp, vp, vp, vp, vp, f32p, f32p, sz, sz, sz, C.c_int, C.c_uint64, vp, vp]),
+    "mse_comm_query_topk_filtered": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, u16p, f32p, f32p, sz, C.c_int, sz, sz, sz, C.c_uint64, vp, vp]),
     "mse_descriptor_product": (C.c_int64, [f32p, sz, u8p, C.c_uint32]),
     "mse_nb_new": (vp, [sz]),
     "mse_nb_free": (None, [vp]),

@@ -21,7 +21,8 @@ import numpy as np
 
 from . import ffi
 from .ffi import check, check_ptr
-from .vector import MODE_AUTO, Searcher, _bits, _p
+from .diskann import REGIMES
+from .vector import MODE_AUTO, PQ_FILTER_MODES, RowFilter, Searcher, _bits, _p
 
 
 class _BorrowedSearcher(Searcher):
@@ -52,6 +53,62 @@ class _BorrowedVectorList:
 
     def close(self):
         self._h = None
+
+
+class _BorrowedFilter(RowFilter):
+    """A shard's local filter, owned by its ShardFilter (which it keeps alive)."""
+
+    def __init__(self, handle, owner):   # noqa: D401 -- no creator call: the shard filter made it
+        self._h = handle
+        self._owner = owner
+
+    def close(self):
+        self._h = None
+        self._owner = None
+
+
+class ShardFilter:
+    """One local RowFilter per shard of a ShardGroup, each on its shard's device (mse_shard_filter): made by ShardGroup.filter,
+    .filter_from_local or .live_filter, taken by the group's *_filtered searches.  It belongs to the layout of the group it was made
+    for: after generate / load_host / set_shard_device the group refuses it."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @property
+    def count(self):
+        """Allowed rows over all shards."""
+        return int(ffi.lib().mse_shard_filter_count(self._h))
+
+    @property
+    def n_shards(self):
+        return int(ffi.lib().mse_shard_filter_n_shards(self._h))
+
+    def shard(self, g):
+        """Shard g's filter over its LOCAL rows (borrowed: valid while this ShardFilter is open)."""
+        return _BorrowedFilter(check_ptr(ffi.lib().mse_shard_filter_shard(self._h, int(g)), "mse_shard_filter_shard"), self)
+
+    def to_global(self, device=None):
+        """The parts joined at their shards' first rows: a fresh RowFilter over GLOBAL rows (RowFilter.concat)."""
+        return RowFilter.from_handle(check_ptr(ffi.lib().mse_shard_filter_global(self._h, -1 if device is None else int(device)),
+                                               "mse_shard_filter_global"))
+
+    def close(self):
+        if self._h:
+            ffi.lib().mse_shard_filter_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _shard_filter_handle(sf):
+    if not isinstance(sf, ShardFilter):
+        raise TypeError("the filtered searches of a ShardGroup take a ShardFilter (ShardGroup.filter / .filter_from_local / .live_filter)")
+    return sf._h
 
 
 class ShardGroup:
@@ -104,6 +161,75 @@ class ShardGroup:
 
     def bruteforce_topk_dev(self, queries_dev, nq, k, scores_dev, ids_dev, mode=MODE_AUTO):
         check(ffi.lib().mse_shard_group_search_dev(self._h, queries_dev, nq, k, mode, scores_dev, ids_dev), "mse_shard_group_search_dev")
+
+    # ---- row filters across the shards ----
+    def filter(self, row_filter):
+        """A RowFilter over GLOBAL rows cut into one filter per shard, on the devices (mse_shard_group_filter).  Shorter than the group:
+        the rows past it are excluded; longer: an error."""
+        if not isinstance(row_filter, RowFilter):
+            raise TypeError("row_filter must be a RowFilter")
+        return ShardFilter(check_ptr(ffi.lib().mse_shard_group_filter(self._h, row_filter._h), "mse_shard_group_filter"))
+
+    def filter_from_local(self, per_shard):
+        """One RowFilter per shard, each over its shard's LOCAL rows and on its device; they are copied."""
+        per_shard = list(per_shard)
+        if len(per_shard) != self.n_shards:
+            raise ValueError("one filter per shard")
+        if any(not isinstance(f, RowFilter) for f in per_shard):
+            raise TypeError("per_shard must hold RowFilters")
+        hs = (C.c_void_p * len(per_shard))(*[f._h for f in per_shard])
+        return ShardFilter(check_ptr(ffi.lib().mse_shard_group_filter_from_local(self._h, hs), "mse_shard_group_filter_from_local"))
+
+    def live_filter(self, and_has_url=False):
+        """DeviceGraph.live_filter of every shard's attached graph: what deletes through the shards' graphs have left."""
+        return ShardFilter(check_ptr(ffi.lib().mse_shard_group_live_filter(self._h, int(bool(and_has_url))), "mse_shard_group_live_filter"))
+
+    def bruteforce_topk_filtered(self, shard_filter, queries, k, mode=MODE_AUTO):
+        """bruteforce_topk over the rows the ShardFilter allows; equals Searcher.bruteforce_topk(allow=the global filter) over all rows."""
+        sf = _shard_filter_handle(shard_filter)
+        q = _bits(queries).reshape(-1, self.d)
+        nq = q.shape[0]
+        scores = np.empty((nq, k), np.int64)
+        ids = np.empty((nq, k), np.uint32)
+        check(ffi.lib().mse_shard_group_search_filtered(self._h, sf, _p(q, C.c_uint16), nq, k, mode, _p(scores, C.c_int64), _p(ids, C.c_uint32)),
+              "mse_shard_group_search_filtered")
+        return scores, ids
+
+    def bruteforce_topk_filtered_dev(self, shard_filter, queries_dev, nq, k, scores_dev, ids_dev, mode=MODE_AUTO):
+        check(ffi.lib().mse_shard_group_search_filtered_dev(self._h, _shard_filter_handle(shard_filter), queries_dev, nq, k, mode, scores_dev, ids_dev),
+              "mse_shard_group_search_filtered_dev")
+
+    def pq_scan_topk_filtered(self, shard_filter, queries_f32, r, k, scales=None, mode="auto"):
+        """pq_scan_topk over the allowed rows: ProductQuantizer.scan_topk_batch_filtered over the unsharded codes, bit for bit.  mode
+        "auto" is resolved per shard, from the shard's own codes and count."""
+        sf = _shard_filter_handle(shard_filter)
+        q = np.ascontiguousarray(queries_f32, np.float32).reshape(-1, self.d)
+        nq = q.shape[0]
+        sc = None if scales is None else np.ascontiguousarray(scales, np.float32).reshape(-1)
+        scores, ids = np.empty((nq, k), np.int64), np.empty((nq, k), np.uint32)
+        check(ffi.lib().mse_shard_group_pq_scan_topk_filtered(self._h, sf, _p(q, C.c_float), _p(sc, C.c_float) if sc is not None else None, nq, int(r),
+                                                              int(k), PQ_FILTER_MODES[mode], _p(scores, C.c_int64), _p(ids, C.c_uint32)),
+              "mse_shard_group_pq_scan_topk_filtered")
+        return scores, ids
+
+    def query_topk_filtered(self, shard_filter, queries, k, luts=None, scales=None, disable_pq=True, beamwidth=4, search_list=64, regime="auto"):
+        """query_topk over has_url AND allowed on every shard's graph: the merge of the per-shard disk_query_topk(allow=...) answers.
+        regime "auto": every shard plans for itself, from its own rows and count."""
+        sf = _shard_filter_handle(shard_filter)
+        q = _bits(queries).reshape(-1, self.d)
+        nq = q.shape[0]
+        tables = None if luts is None else np.ascontiguousarray(luts, np.float32).reshape(nq, -1)
+        sc = None
+        if scales is not None:
+            sc = np.ascontiguousarray(scales, np.float32)
+            if sc.ndim == 1:
+                sc = np.ascontiguousarray(np.broadcast_to(sc, (nq, sc.size)))
+        scores, ids = np.empty((nq, k), np.int64), np.empty((nq, k), np.uint32)
+        check(ffi.lib().mse_shard_group_query_topk_filtered(self._h, sf, _p(q, C.c_uint16), _p(tables, C.c_float) if tables is not None else None,
+                                                            _p(sc, C.c_float) if sc is not None else None, nq, int(bool(disable_pq)), int(beamwidth),
+                                                            int(search_list), int(k), REGIMES[regime], _p(scores, C.c_int64), _p(ids, C.c_uint32)),
+              "mse_shard_group_query_topk_filtered")
+        return scores, ids
 
     # ---- the approximate-search paths over the same shards ----
     def base(self, shard):
@@ -242,6 +368,35 @@ class Comm:
                                             dgraph._h, q_ptr, _p(tables, C.c_float) if tables is not None else None,
                                             _p(sc, C.c_float) if sc is not None else None, nq, int(bool(disable_pq)), int(beamwidth), int(search_list),
                                             int(k), int(first_row), scores_dev, ids_dev), "mse_comm_query_topk")
+
+    # ---- the filtered forms: row_filter is THIS RANK's local filter, RowFilter.slice(first_row, rows of the rank) of the global one ----
+    def search_filtered_dev(self, searcher, row_filter, queries_dev, nq, k, scores_dev, ids_dev, mode=MODE_AUTO, id_offset=0):
+        check(ffi.lib().mse_comm_search_filtered_dev(self._h, searcher._h, row_filter._h, queries_dev, nq, k, mode, id_offset, scores_dev, ids_dev),
+              "mse_comm_search_filtered_dev")
+
+    def pq_scan_topk_filtered(self, quantizer, codes, searcher, row_filter, queries_f32, r, k, first_row, scores_dev, ids_dev, scales=None,
+                              mode="auto"):
+        q = np.ascontiguousarray(queries_f32, np.float32).reshape(-1, quantizer.n_dims)
+        sc = None if scales is None else np.ascontiguousarray(scales, np.float32).reshape(-1)
+        check(ffi.lib().mse_comm_pq_scan_topk_filtered(self._h, quantizer._h, codes._h, searcher._h, row_filter._h, _p(q, C.c_float),
+                                                       _p(sc, C.c_float) if sc is not None else None, q.shape[0], int(r), int(k),
+                                                       PQ_FILTER_MODES[mode], int(first_row), scores_dev, ids_dev), "mse_comm_pq_scan_topk_filtered")
+
+    def query_topk_filtered(self, searcher, dgraph, row_filter, queries, k, first_row, scores_dev, ids_dev, quantizer=None, codes=None, luts=None,
+                            scales=None, disable_pq=True, beamwidth=4, search_list=64, regime="auto"):
+        if isinstance(queries, tuple):
+            q_ptr, nq = C.cast(C.c_void_p(int(queries[0])), C.POINTER(C.c_uint16)), int(queries[1])
+        else:
+            q = _bits(queries)
+            q = q.reshape(-1, q.shape[-1])
+            nq, q_ptr = q.shape[0], _p(q, C.c_uint16)
+        tables = None if luts is None else np.ascontiguousarray(luts, np.float32).reshape(nq, -1)
+        sc = None if scales is None else np.ascontiguousarray(scales, np.float32)
+        check(ffi.lib().mse_comm_query_topk_filtered(self._h, searcher._h, quantizer._h if quantizer is not None else None,
+                                                     codes._h if codes is not None else None, dgraph._h, row_filter._h, REGIMES[regime], q_ptr,
+                                                     _p(tables, C.c_float) if tables is not None else None,
+                                                     _p(sc, C.c_float) if sc is not None else None, nq, int(bool(disable_pq)), int(beamwidth),
+                                                     int(search_list), int(k), int(first_row), scores_dev, ids_dev), "mse_comm_query_topk_filtered")
 
     def last_timing(self):
         """This rank's last search_dev in ms (waits for it): local search, all-gather (incl. waiting for the slowest rank), merge."""

@@ -191,6 +191,31 @@ class RowFilter:
         as numpy.packbits(..., bitorder="little"); bits past n_rows are ignored)."""
         return cls.from_handle(check_ptr(ffi.lib().mse_filter_from_bits_dev(ptr, int(n_rows)), "mse_filter_from_bits_dev"))
 
+    def slice(self, first_row, n_rows, device=None):
+        """Rows first_row .. first_row + n_rows of this filter as a fresh filter over n_rows LOCAL rows (mse_filter_slice): bit r is bit
+        first_row + r of self, zero where that is at or past len(self).  first_row need not be a multiple of 32.  device: where the
+        result lives (default: with self; another device costs one peer copy of the word range)."""
+        if first_row < 0 or n_rows < 0:
+            raise ValueError("first_row and n_rows must not be negative")
+        return RowFilter.from_handle(check_ptr(ffi.lib().mse_filter_slice(self._h, int(first_row), int(n_rows), -1 if device is None else int(device)),
+                                               "mse_filter_slice"))
+
+    @classmethod
+    def concat(cls, parts, first_rows, n_rows, device=None):
+        """The inverse of slice (mse_filter_concat): a fresh filter over n_rows GLOBAL rows in which parts[i] occupies the rows from
+        first_rows[i] on; rows no part covers are excluded.  Parts must not overlap or reach past n_rows."""
+        parts = list(parts)
+        if len(parts) != len(first_rows):
+            raise ValueError("one first row per part")
+        if any(not isinstance(p, RowFilter) for p in parts):
+            raise TypeError("parts must be RowFilters")
+        if n_rows < 0 or any(int(r) < 0 for r in first_rows):
+            raise ValueError("rows must not be negative")
+        hs = (C.c_void_p * max(len(parts), 1))(*[p._h for p in parts])
+        fr = (C.c_uint64 * max(len(parts), 1))(*[int(r) for r in first_rows])
+        return cls.from_handle(check_ptr(ffi.lib().mse_filter_concat(hs, fr, len(parts), int(n_rows), -1 if device is None else int(device)),
+                                         "mse_filter_concat"))
+
     def _combine(self, other, op):
         if not isinstance(other, RowFilter):
             return NotImplemented
