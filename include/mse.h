@@ -138,6 +138,18 @@ int mse_searcher_scan_timing(mse_searcher* s, int enable, double* total_ms, uint
 /* statistics of the last MFMA-mode call: number of queries whose certificate needed a wider
  * candidate set, and the widest group count used. */
 int mse_searcher_last_stats(const mse_searcher* s, uint32_t* n_widened, uint32_t* max_groups);
+/* Thresholded group maxima of the 320-query matrix-core pass (unfiltered search, 257 .. 320 queries per pass): a strided sample of
+ * the rows gives each query a rigorous threshold, and the scan of the other rows keeps a group maximum only where it exceeds it,
+ * in a per-query list, instead of writing a dense array of maxima.  Answers are the same either way.
+ * mode 0: auto (used when the base is large enough for two launches to pay and k is small enough for the lists), 1: off,
+ * 2: forced (the size rule is skipped, never what correctness needs: a sample of at least k groups).
+ * stride: every stride-th 256-row tile is the sample; stride - 1 must be a power of two (3 .. 1025); 0 keeps the current value (33).
+ * capacity: survivors kept per query; 0 keeps the current value (8192).  A pass in which a query has more falls back to the dense
+ * array: it costs time, never correctness. */
+int mse_searcher_set_sparse_maxima(mse_searcher* s, int mode, uint32_t stride, uint32_t capacity);
+/* of the last MFMA-mode call: passes that took the thresholded path, how many of them fell back to the dense array (a list
+ * overflowed), and the longest survivor list seen (it may exceed the capacity: that is the overflow). */
+int mse_searcher_sparse_stats(const mse_searcher* s, uint32_t* passes, uint32_t* fallbacks, uint32_t* longest_list);
 
 /* ---- filtered brute-force search: top-k over an allowed-row set (FAISS SearchParameters.sel / IDSelector) -----------------
  * A filter is one bit per row, kept on the device that was current on the calling thread when it was made, padded with zero bits

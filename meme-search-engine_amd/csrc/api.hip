@@ -211,8 +211,59 @@ static size_t mfma_call_tile(const mse_base* b, size_t k) {
 // and the kg0 groups re-scored per query are then twice as many rows.
 // The queries are read where the caller has them: the scan's pack kernel writes the padding of the last pass as zeros, and the norms,
 // the re-score and the widening only ever touch the nq_pass real rows.
+// Thresholded group maxima (`sparse`, the 320-query unmasked pass with 64-row groups only).  The dense array of group
+// maxima is 4 B x 320 per 64 rows written by the scan and read back once by the tournament, and all but a few hundred entries per query
+// are never looked at again.  Instead: launch A scans every S-th 256-row tile (the sample) with the dense epilogue into a small array;
+// the tournament over it gives G_k, the k-th best sample group maximum of each query; tau_q = the float below G_k - 3 eps_q (topk.hip
+// sparse_tau_kernel has the argument: no row of a group whose maximum is <= tau_q can be in the exact top k, not even as a tie);
+// launch B scans the other tiles and appends (group, maximum) to the query's list only where maximum > tau_q.  The round then picks
+// its kg best groups from the list, and the certificate's bound is max(last chosen key, tau_q): what is not on the list is <= tau_q.
+// Widening takes more of the same list; a list used up leaves tau_q, which certifies by construction.  A query whose survivors exceed
+// the list capacity (an unrepresentative sample, heavily duplicated rows) sets *overflow: the caller runs the pass again the dense way.
+struct SparsePlan {
+    uint32_t stride = 0, cap = 0, shift = 0;
+    size_t n_a = 0, n_b = 0, n_sg = 0;   // sample tiles, other tiles, sample groups that exist
+};
+static bool sparse_plan(const mse_searcher* s, int nq_pass, int k, const mse_filter* f, SparsePlan* p) {
+    const mse_base* b = s->base;
+    const int d = (int)b->d;
+    if (s->sparse_mode == 1 || f || mfma_query_tile(d) != 320 || nq_pass > 320 || mfma_pad(nq_pass, d) != 320 || mfma_group_rows(320) != 64) return false;
+    const uint32_t S = s->sparse_stride;
+    const size_t n_tiles = (b->n + 255) / 256, n_groups = (b->n + 63) / 64;
+    p->stride = S; p->cap = s->sparse_cap;
+    p->shift = 0;
+    while ((1u << p->shift) < S - 1) p->shift++;
+    p->n_a = (n_tiles + S - 1) / S;
+    p->n_b = n_tiles - p->n_a;
+    p->n_sg = (p->n_a - 1) * 4 + std::min<size_t>(4, n_groups - (p->n_a - 1) * (size_t)S * 4);
+    // what correctness needs: G_k must exist, i.e. the sample holds k groups
+    if (n_tiles < 2 || p->n_sg < (size_t)k) return false;
+    if (s->sparse_mode == 2) return true;
+    // auto: each launch keeps every CU busy for at least eight tiles (a second launch costs the drain and fill of the persistent grid,
+    // about one tile per CU); the sample holds four times the groups a round re-scores, so that G_k is a typical k-th maximum; and the
+    // survivors expected of random rows, about k * S per query, fit the list four times over
+    const size_t kg0 = std::min<size_t>(std::max(k + 8, 16), TOPK_KMAX);
+    return p->n_a >= (size_t)8 * s->n_cu && p->n_sg >= 4 * kg0 && (size_t)4 * k * S <= p->cap;
+}
+
+static int mfma_pass_run(mse_searcher* s, const uint16_t* q_dev, int nq_pass, int k, uint64_t id_offset,
+                         int64_t* out_scores, uint32_t* out_ids, size_t out_stride, const mse_filter* f, const SparsePlan* sp, bool* overflow);
+
 static int mfma_pass(mse_searcher* s, const uint16_t* q_dev, int nq_pass, int k, uint64_t id_offset,
                      int64_t* out_scores, uint32_t* out_ids, size_t out_stride, const mse_filter* f = nullptr) {
+    SparsePlan plan;
+    if (sparse_plan(s, nq_pass, k, f, &plan)) {
+        bool overflow = false;
+        s->last_sparse_passes++;
+        if (mfma_pass_run(s, q_dev, nq_pass, k, id_offset, out_scores, out_ids, out_stride, f, &plan, &overflow)) return -1;
+        if (!overflow) return 0;
+        s->last_sparse_fallbacks++;
+    }
+    return mfma_pass_run(s, q_dev, nq_pass, k, id_offset, out_scores, out_ids, out_stride, f, nullptr, nullptr);
+}
+
+static int mfma_pass_run(mse_searcher* s, const uint16_t* q_dev, int nq_pass, int k, uint64_t id_offset,
+                         int64_t* out_scores, uint32_t* out_ids, size_t out_stride, const mse_filter* f, const SparsePlan* sp, bool* overflow) {
     const mse_base* b = s->base;
     hipStream_t st = s->stream;
     const int d = (int)b->d;
@@ -229,24 +280,55 @@ static int mfma_pass(mse_searcher* s, const uint16_t* q_dev, int nq_pass, int k,
     }
     const int gr = tile == 320 && (!rem || nq_pad - n_full * tile == 320) ? mfma_group_rows(320) : GROUP_ROWS;
     const size_t n_groups = (b->n + gr - 1) / gr;
-    if (s->gmax.ensure(n_groups * (size_t)nq_pad * 4)) return -1;
+    if (!sp && s->gmax.ensure(n_groups * (size_t)nq_pad * 4)) return -1;
     // the full passes go out as ONE launch (a small base has few row tiles: its passes fill the chip side by side), then the remainder
     const size_t one_tile_packed = (size_t)(d / 64) * tile * 128;
     if (s->qpacked.ensure(std::max(mfma_packed_bytes(d), (size_t)std::max(n_full, 1) * one_tile_packed))) return -1;
     const uint32_t* mask = f ? f->words : nullptr;
     const size_t mask_words = f ? f->n_words : 0;
-    if (n_full &&
+    if (s->eps.ensure((size_t)nq_pass * 8) || s->margin.ensure((size_t)nq_pass * 8)) return -1;   // second halves: the widening's compact set
+    // the sparse form's lists: thresholds, counts, group ids, maxima (SparsePlan above)
+    struct ListSrc { const uint32_t* ids; const float* keys; const uint32_t* counts; const float* tau; };
+    ListSrc lists{};
+    const uint32_t cap = sp ? sp->cap : 0;
+    if (sp) {
+        if (s->sp_dense.ensure(sp->n_a * 4 * (size_t)320 * 4) || s->sp_lists.ensure((size_t)320 * 8 + (size_t)320 * cap * 8) ||
+            s->sp_pin.ensure((size_t)320 * 4, 4096)) return -1;
+        float* tau = s->sp_lists.as<float>();
+        uint32_t* counts = reinterpret_cast<uint32_t*>(tau + 320);
+        uint32_t* ids = counts + 320;
+        float* keys = reinterpret_cast<float*>(ids + (size_t)320 * cap);
+        lists = ListSrc{ids, keys, counts, tau};
+        ScanSparse a;
+        a.n_tiles = sp->n_a; a.mul = sp->stride; a.shift = 63; a.add = 0;
+        if (launch_scan_mfma_tiles(b->dev, b->n, d, q_dev, nq_pass, true, s->qpacked.p, a, s->sp_dense.as<float>(), s->n_cu, st,
+                                   s->timing ? s->ev0 : nullptr, nullptr)) return -1;
+        if (launch_query_eps(q_dev, nq_pass, d, b->norm_bits_dev, 2.8e-4f, s->eps.as<float>(), st)) return -1;
+        if (s->gkeys.ensure((size_t)nq_pass * k * 4)) return -1;
+        uint32_t* ssel = nullptr;
+        LevelRef ls0{KEY_F32, s->sp_dense.p, 1, (size_t)320, sp->n_sg, true, 320};
+        if (descend(s, ls0, nq_pass, k, &ssel, s->gkeys.p)) return -1;
+        if (launch_sparse_tau(s->gkeys.as<float>(), (size_t)k, k, s->eps.as<float>(), nq_pass, 320, tau, counts, st)) return -1;
+        if (launch_sparse_append_sample(s->sp_dense.as<float>(), 320, sp->n_sg, nq_pass, sp->stride, tau, counts, ids, keys, cap, st)) return -1;
+        ScanSparse bb;
+        bb.n_tiles = sp->n_b; bb.mul = 1; bb.shift = sp->shift; bb.add = 1;   // the j-th tile that is no multiple of S: j + j / (S - 1) + 1
+        bb.tau = tau; bb.counts = counts; bb.ids = ids; bb.keys = keys; bb.cap = cap;
+        if (launch_scan_mfma_tiles(b->dev, b->n, d, q_dev, nq_pass, false, s->qpacked.p, bb, nullptr, s->n_cu, st, nullptr,
+                                   s->timing ? s->ev1 : nullptr)) return -1;
+        // the counts reach the host with the first round's margins (its synchronisation)
+        MSE_HIP_TRY(hipMemcpyAsync(s->sp_pin.p, counts, (size_t)320 * 4, hipMemcpyDeviceToHost, st));
+    }
+    if (!sp && n_full &&
         launch_scan_mfma(b->dev, b->n, d, q_dev, tile, s->qpacked.p, s->gmax.as<float>(), s->n_cu, st,
                          s->timing ? s->ev0 : nullptr, s->timing && !rem ? s->ev1 : nullptr, nq_pad, n_full, mask, mask_words, n_full * tile, gr)) return -1;
-    if (rem &&
+    if (!sp && rem &&
         launch_scan_mfma(b->dev, b->n, d, q_dev + (size_t)n_full * tile * d, nq_pad - n_full * tile, s->qpacked.p,
                          s->gmax.as<float>() + n_full * tile, s->n_cu, st, s->timing && !n_full ? s->ev0 : nullptr,
                          s->timing ? s->ev1 : nullptr, nq_pad, 1, mask, mask_words, rem, gr)) return -1;
     bool timing_pending = s->timing;
-    if (s->eps.ensure((size_t)nq_pass * 8) || s->margin.ensure((size_t)nq_pass * 8)) return -1;   // second halves: the widening's compact set
     // |mfma score - exact-order score| <= 2 * gamma_1151 * sum|x_i q_i| <= 1.4e-4 * |x||q|; doubled again
-    // because the matrix core's internal rounding is not documented.
-    if (launch_query_eps(q_dev, nq_pass, d, b->norm_bits_dev, 2.8e-4f, s->eps.as<float>(), st))
+    // because the matrix core's internal rounding is not documented.  (The sparse form needed it for its thresholds already.)
+    if (!sp && launch_query_eps(q_dev, nq_pass, d, b->norm_bits_dev, 2.8e-4f, s->eps.as<float>(), st))
         return -1;
 
     // the margins come back into pinned memory: a true asynchronous copy, then the one synchronisation that ends the round
@@ -257,12 +339,22 @@ static int mfma_pass(mse_searcher* s, const uint16_t* q_dev, int nq_pass, int k,
     // One round of: tournament over the group maxima -> the kg best groups' rows re-scored exactly -> exact top-k -> certificate.
     // gm: group maxima [n_groups][gm_pad] of the nq queries in `qs` ([nq][d] f16); results go to dst_* with stride dst_stride;
     // margins (> 0 = certified) come back in margin_h[0..nq).
-    auto round = [&](const float* gm, int gm_pad, const uint16_t* qs, int nq, int kg_eff, const float* eps_dev, float* margin_dev,
+    // ls (the sparse form): the kg best groups come from the queries' lists instead of a tournament over gm
+    auto round = [&](const float* gm, int gm_pad, const ListSrc* ls, const uint16_t* qs, int nq, int kg_eff, const float* eps_dev, float* margin_dev,
                      int64_t* dst_s, uint32_t* dst_i, size_t dst_stride, uint64_t id_off) -> int {
         if (s->gkeys.ensure((size_t)nq * kg_eff * 4)) return -1;
         uint32_t* gsel = nullptr;
-        LevelRef l0{KEY_F32, gm, 1, (size_t)gm_pad, n_groups, true, gm_pad};
-        if (descend(s, l0, nq, kg_eff, &gsel, s->gkeys.p)) return -1;
+        if (ls) {
+            if (s->sel_a.ensure((size_t)nq * kg_eff * 4)) return -1;
+            gsel = s->sel_a.as<uint32_t>();
+            SelectArgs a{};
+            a.kind = KEY_F32; a.list_ids = ls->ids; a.list_keys = ls->keys; a.list_stride = cap; a.n_list = cap; a.list_count = ls->counts;
+            a.k = kg_eff; a.out_ids = gsel; a.out_keys = s->gkeys.p; a.out_stride = kg_eff; a.nq = nq;
+            if (launch_select(a, st)) return -1;
+        } else {
+            LevelRef l0{KEY_F32, gm, 1, (size_t)gm_pad, n_groups, true, gm_pad};
+            if (descend(s, l0, nq, kg_eff, &gsel, s->gkeys.p)) return -1;
+        }
         const size_t n_cand = (size_t)kg_eff * gr;
         if (s->cand_ids.ensure((size_t)nq * n_cand * 4) || s->cand_scores.ensure((size_t)nq * n_cand * 8)) return -1;
         if (f ? launch_expand_groups_masked(gsel, kg_eff, kg_eff, gr, b->n, f->words, f->n_words, s->cand_ids.as<uint32_t>(), n_cand,
@@ -278,18 +370,26 @@ static int mfma_pass(mse_searcher* s, const uint16_t* q_dev, int nq_pass, int k,
         a.out_keys = s->sel_keys.p; a.out_stride = k; a.nq = nq;
         if (launch_select(a, st)) return -1;
         if (launch_finalize(s->misc.as<uint32_t>(), s->sel_keys.as<int64_t>(), k, k, nq, id_off, dst_s, dst_i, dst_stride,
-                            s->gkeys.as<float>(), kg_eff, kg_eff, n_groups, eps_dev, margin_dev, st)) return -1;
+                            s->gkeys.as<float>(), kg_eff, kg_eff, n_groups, eps_dev, margin_dev, st, ls ? ls->tau : nullptr)) return -1;
         MSE_HIP_TRY(hipMemcpyAsync(margin_h, margin_dev, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
         MSE_HIP_TRY(hipStreamSynchronize(st));
         s->last_max_groups = std::max<uint32_t>(s->last_max_groups, (uint32_t)kg_eff);
         return 0;
     };
-    if (round(s->gmax.as<float>(), nq_pad, q_dev, nq_pass, kg0, s->eps.as<float>(), s->margin.as<float>(), out_scores,
-              out_ids, out_stride, id_offset)) return -1;
+    if (round(sp ? nullptr : s->gmax.as<float>(), nq_pad, sp ? &lists : nullptr, q_dev, nq_pass, kg0, s->eps.as<float>(), s->margin.as<float>(),
+              out_scores, out_ids, out_stride, id_offset)) return -1;
     if (timing_pending) {
+        // (the sparse form: from the start of launch A to the end of launch B, the small kernels between them included)
         float ms = 0.0f;
         if (hipEventElapsedTime(&ms, s->ev0, s->ev1) == hipSuccess) { s->scan_ms_total += ms; s->scan_launches++; }
         timing_pending = false;
+    }
+    const uint32_t* const counts_h = sp ? s->sp_pin.as<uint32_t>() : nullptr;
+    if (sp) {
+        uint32_t longest = 0;
+        for (int i = 0; i < nq_pass; i++) longest = std::max(longest, counts_h[i]);
+        s->last_sparse_max_list = std::max(s->last_sparse_max_list, longest);
+        if (longest > cap) { *overflow = true; return 0; }   // a list lost survivors: nothing of this attempt stands
     }
     std::vector<uint32_t> bad;
     for (int i = 0; i < nq_pass; i++)
@@ -300,13 +400,24 @@ static int mfma_pass(mse_searcher* s, const uint16_t* q_dev, int nq_pass, int k,
     // columns of the group maxima, their query rows.  Widening then costs what those few queries cost -- not a 4x, 16x, 64x larger
     // re-score for all 256 (a clustered 1e8-row set: 84 ms per pass of 256 queries instead of 58, before this).
     const int nb = (int)bad.size(), nbp = (nb + 31) / 32 * 32;
-    if (s->widx.ensure((size_t)nb * 5) || s->wq.ensure((size_t)(nb + 8) * d * 2) || s->wg.ensure(n_groups * (size_t)nbp * 4) ||
+    if (s->widx.ensure((size_t)nb * 5) || s->wq.ensure((size_t)(nb + 8) * d * 2) || (!sp && s->wg.ensure(n_groups * (size_t)nbp * 4)) ||
         s->wout.ensure((size_t)std::max(nb, 8) * k * 12)) return -1;
     uint32_t* idx_dev = s->widx.as<uint32_t>();
     uint8_t* take_dev = reinterpret_cast<uint8_t*>(idx_dev + nb);
     MSE_HIP_TRY(hipMemcpyAsync(idx_dev, bad.data(), (size_t)nb * 4, hipMemcpyHostToDevice, st));
     if (launch_gather_rows16(q_dev, (size_t)d * 2, idx_dev, nb, s->wq.p, st)) return -1;
-    if (launch_gather_columns(s->gmax.as<float>(), nq_pad, n_groups, idx_dev, nb, s->wg.as<float>(), nbp, st)) return -1;
+    ListSrc wlists{};
+    size_t longest_bad = 0;   // the sparse form: the longest list of the compact set -- more groups than that widen nothing
+    if (sp) {
+        if (s->sp_wlists.ensure((size_t)nb * 8 + (size_t)nb * cap * 8)) return -1;
+        float* tau = s->sp_wlists.as<float>();
+        uint32_t* counts = reinterpret_cast<uint32_t*>(tau + nb);
+        uint32_t* ids = counts + nb;
+        float* keys = reinterpret_cast<float*>(ids + (size_t)nb * cap);
+        wlists = ListSrc{ids, keys, counts, tau};
+        if (launch_sparse_gather_lists(lists.ids, lists.keys, lists.counts, lists.tau, cap, idx_dev, nb, ids, keys, counts, tau, st)) return -1;
+        for (uint32_t i : bad) longest_bad = std::max<size_t>(longest_bad, counts_h[i]);
+    } else if (launch_gather_columns(s->gmax.as<float>(), nq_pad, n_groups, idx_dev, nb, s->wg.as<float>(), nbp, st)) return -1;
     float* eps2 = s->eps.as<float>() + nq_pass;
     float* margin2 = s->margin.as<float>() + nq_pass;
     if (launch_query_eps(s->wq.as<uint16_t>(), nb, d, b->norm_bits_dev, 2.8e-4f, eps2, st)) return -1;
@@ -316,7 +427,8 @@ static int mfma_pass(mse_searcher* s, const uint16_t* q_dev, int nq_pass, int k,
     int kg = kg0 * 4;
     for (;;) {
         const int kg_eff = (int)std::min<size_t>(kg, TOPK_KMAX);
-        if (round(s->wg.as<float>(), nbp, s->wq.as<uint16_t>(), nb, kg_eff, eps2, margin2, w_s, w_i, (size_t)k, id_offset)) return -1;
+        if (round(sp ? nullptr : s->wg.as<float>(), nbp, sp ? &wlists : nullptr, s->wq.as<uint16_t>(), nb, kg_eff, eps2, margin2, w_s, w_i, (size_t)k,
+                  id_offset)) return -1;
         // rows of the queries certified in this round (or examined completely) go to their places
         std::vector<uint8_t> take(nb, 0);
         int still = 0;
@@ -328,7 +440,9 @@ static int mfma_pass(mse_searcher* s, const uint16_t* q_dev, int nq_pass, int k,
         if (launch_scatter_topk(idx_dev, take_dev, nb, k, w_s, w_i, out_scores, out_ids, out_stride, st)) return -1;
         MSE_HIP_TRY(hipStreamSynchronize(st));   // `take` is a stack-owned source
         if (still == 0) return 0;
-        if (kg_eff >= TOPK_KMAX) break;
+        // (a list used up leaves the threshold as the bound, which certifies by construction: the second test is a safety net that
+        // sends what is still open -- a k-th score saturated to INT64_MIN, which proves nothing -- to the exact scan)
+        if (kg_eff >= TOPK_KMAX || (sp && (size_t)kg_eff >= longest_bad)) break;
         kg = kg_eff * 4;
     }
     // cannot widen further: the exact scan for what is left, 8 queries at a time
@@ -547,6 +661,24 @@ int mse_searcher_last_stats(const mse_searcher* s, uint32_t* n_widened, uint32_t
     if (max_groups) *max_groups = s->last_max_groups;
     return 0;
 }
+int mse_searcher_set_sparse_maxima(mse_searcher* s, int mode, uint32_t stride, uint32_t capacity) {
+    if (!s) return fail("null searcher");
+    if (mode < 0 || mode > 2) return fail("sparse maxima: mode 0 (auto), 1 (off) or 2 (forced)");
+    if (stride && (stride < 3 || stride > 1025 || ((stride - 1) & (stride - 2)) != 0))
+        return fail("sparse maxima: the sample stride must be 2^j + 1, 3 .. 1025");
+    if (capacity > (1u << 20)) return fail("sparse maxima: at most 2^20 survivors per query");
+    s->sparse_mode = mode;
+    if (stride) s->sparse_stride = stride;
+    if (capacity) s->sparse_cap = capacity;
+    return 0;
+}
+int mse_searcher_sparse_stats(const mse_searcher* s, uint32_t* passes, uint32_t* fallbacks, uint32_t* longest_list) {
+    if (!s) return fail("null searcher");
+    if (passes) *passes = s->last_sparse_passes;
+    if (fallbacks) *fallbacks = s->last_sparse_fallbacks;
+    if (longest_list) *longest_list = s->last_sparse_max_list;
+    return 0;
+}
 
 size_t mse_queries_per_pass_max(size_t d) { return d && d % 64 == 0 ? (size_t)mfma_query_tile((int)d) : 0; }
 
@@ -573,6 +705,7 @@ int mse_bruteforce_topk_f16_dev(mse_searcher* s, const void* queries_dev, size_t
     if (mode == MSE_MODE_AUTO) mode = nq <= 8 ? MSE_MODE_EXACT : MSE_MODE_MFMA;
     s->last_widened = 0;
     s->last_max_groups = 0;
+    s->last_sparse_passes = s->last_sparse_fallbacks = s->last_sparse_max_list = 0;
     if (b->n == 0) return fill_empty(s, nq, k, out_scores, out_ids);   // nothing to score
     if (mode == MSE_MODE_EXACT) {
         for (size_t q0 = 0; q0 < nq; q0 += 8) {
@@ -1121,6 +1254,7 @@ int mse_bruteforce_topk_filtered_f16_dev(mse_searcher* s, const mse_filter* f, c
     const uint16_t* q = reinterpret_cast<const uint16_t*>(queries_dev);
     s->last_widened = 0;
     s->last_max_groups = 0;
+    s->last_sparse_passes = s->last_sparse_fallbacks = s->last_sparse_max_list = 0;
     if (f->count == 0) return fill_empty(s, nq, k, out_scores, out_ids);   // nothing allowed
     // MODE_EXACT: the filtered exact pass.  MODE_MFMA: the masked matrix-core scan.  MODE_AUTO: the exact pass on the sparse side of the
     // crossover; otherwise the unfiltered rule (the coalescer's, dispatch.hip): the masked scan for more than 8 queries, and for any

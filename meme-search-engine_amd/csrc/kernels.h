@@ -49,6 +49,7 @@ struct SelectArgs {
     size_t list_stride, n_list;
     size_t list_chunk = 0, list_chunk_stride = 0;  // if list_chunk != 0: candidate c lives at (c / chunk) * chunk_stride + c % chunk
     size_t list_id_chunk_stride = 0;               // chunk stride of list_ids when it differs from that of list_keys (0 = the same)
+    const uint32_t* list_count = nullptr;          // optional, per query: only the first min(list_count[q], n_list) candidates exist
     int k;                   // number to select (<= TOPK_KMAX)
     uint32_t* out_ids;       // [nq][out_stride], best first, padded with ID_NONE
     void* out_keys;          // optional: raw keys (same type as `in`) of the selected, [nq][out_stride]
@@ -75,7 +76,19 @@ int launch_expand_groups(const uint32_t* parents, size_t par_stride, size_t n_pa
 int launch_finalize(const uint32_t* sel_ids, const int64_t* sel_scores, size_t sel_stride, int k, int nq,
                     uint64_t id_offset, int64_t* out_scores, uint32_t* out_ids, size_t out_stride,
                     const float* group_keys, size_t gk_stride, int kg, size_t n_groups, const float* eps,
-                    float* margin, hipStream_t stream);
+                    float* margin, hipStream_t stream, const float* tau = nullptr /* per query: the bound is max(worst chosen key, tau) */);
+
+// Thresholded group maxima (api.hip mfma_pass, the sparse form of the 320-query pass).  counts [nq_pad], ids / keys [nq_pad][cap].
+// tau[q] = the next float below gk[q][k - 1] - 3 eps[q] for q < nq (gk: the k best sample maxima, best first), +inf for the padding
+// columns up to nq_pad; counts[0 .. nq_pad) = 0
+int launch_sparse_tau(const float* gk, size_t gk_stride, int k, const float* eps, int nq, int nq_pad, float* tau, uint32_t* counts, hipStream_t stream);
+// the sample's survivors: entry (sg, q) of the sample's dense maxima [n_sg][nq_pad] above tau[q] is appended to list q as group
+// (sg / 4) * 4 * stride + sg % 4 (the sample is every stride-th 256-row tile = four 64-row groups)
+int launch_sparse_append_sample(const float* dense, int nq_pad, size_t n_sg, int nq, uint32_t stride, const float* tau, uint32_t* counts,
+                                uint32_t* ids, float* keys, uint32_t cap, hipStream_t stream);
+// lists, counts (clamped to cap) and thresholds of the queries idx[0 .. nb) as a compact set
+int launch_sparse_gather_lists(const uint32_t* ids, const float* keys, const uint32_t* counts, const float* tau, uint32_t cap, const uint32_t* idx,
+                               int nb, uint32_t* out_ids, float* out_keys, uint32_t* out_counts, float* out_tau, hipStream_t stream);
 
 // certificate margin for f32 keys: margin[q] = sel_keys[q][k-1] - (group_keys[q][kg-1] + eps[q])   (flat index)
 int launch_margin_f32(const uint32_t* sel_ids, const float* sel_keys, size_t sel_stride, int k, int nq, const float* group_keys,
@@ -225,6 +238,22 @@ int launch_scan_mfma(const uint16_t* base, size_t n_rows, int d, const uint16_t*
                                          zeros.  -1 = all n_pass x nq_pad */,
                      int group_rows = GROUP_ROWS /* base rows per written maximum: 32, or 64 (nq_pad 320 only) */);
                      // events bracket the scan kernel only
+// One launch of the 320-query search kernel (64 rows per maximum, unmasked) over a SUBSET of the 256-row tiles: launch tile v of
+// n_tiles is base tile v * mul + (v >> shift) + add.  tau == nullptr: the dense epilogue, into group_max [4 n_tiles][stride] indexed
+// by the launch's own groups 4 v + rg.  tau != nullptr: a group maximum above tau[column] is appended to that column's list as
+// (base group, maximum) -- counts[column] counts every survivor, stored or not; nothing dense is written.
+struct ScanSparse {
+    size_t n_tiles = 0;
+    uint32_t mul = 1, shift = 63, add = 0;
+    const float* tau = nullptr;
+    uint32_t* counts = nullptr;
+    uint32_t* ids = nullptr;
+    float* keys = nullptr;
+    uint32_t cap = 0;
+};
+// pack: re-tile the queries first (the first launch of a pass); the later launches of the pass reuse packed_scratch
+int launch_scan_mfma_tiles(const uint16_t* base, size_t n_rows, int d, const uint16_t* queries_dev, int nq_rows, bool pack, void* packed_scratch,
+                           const ScanSparse& sp, float* group_max, int n_cu, hipStream_t stream, hipEvent_t ev_begin, hipEvent_t ev_end);
 size_t mfma_packed_bytes(int d);
 int mfma_query_tile(int d);  // most queries one pass handles at width d (320 or 256)
 int mfma_pad(int nq, int d);   // padded query count of a pass of nq <= 256 queries: 128, 192 or 256

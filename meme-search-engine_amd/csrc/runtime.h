@@ -121,6 +121,15 @@ struct mse_searcher {
     mse::DevBuf ins_scratch[8];    // scratch of mse_graph_insert_rows (graph_insert.hip): slots, staging slabs, codes, flags
     mse::BuildScratch ins_build;   // ... and of its link step
     uint32_t last_widened = 0, last_max_groups = 0;
+    // thresholded group maxima of the 320-query pass (api.hip mfma_pass; mse_searcher_set_sparse_maxima): mode 0 auto, 1 off, 2 forced;
+    // every sparse_stride-th 256-row tile is the sample (stride - 1 a power of two); sparse_cap survivors per query at most
+    int sparse_mode = 0;
+    uint32_t sparse_stride = 33, sparse_cap = 8192;
+    uint32_t last_sparse_passes = 0, last_sparse_fallbacks = 0, last_sparse_max_list = 0;   // of the last MFMA-mode call, as last_widened
+    mse::DevBuf sp_dense;     // the sample's dense maxima [sample groups][320]
+    mse::DevBuf sp_lists;     // thresholds [320] f32 | survivor counts [320] u32 | group ids [320][cap] u32 | maxima [320][cap] f32
+    mse::DevBuf sp_wlists;    // the same for the widening's compact set
+    mse::PinBuf sp_pin;       // the survivor counts on their way to the host
     // optional HIP-event timing of the dominant (scan) kernel, for bench.py's roofline line
     bool timing = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;

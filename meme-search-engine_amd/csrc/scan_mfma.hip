@@ -63,6 +63,7 @@
 #include "common.h"
 #include "kernels.h"
 #include <cstdlib>
+#include <algorithm>
 #include <type_traits>
 
 namespace mse {
@@ -350,12 +351,22 @@ __device__ unsigned long long g_scan_prof[4];
 __device__ __forceinline__ uint32_t memtime() { return (uint32_t)__builtin_amdgcn_s_memtime(); }   // deltas fit 32 bits
 #endif
 
+// The trailing pack is empty (the plain kernel), the filter's bitmap and word count (the masked form), or one ScanSparse (the tile-subset
+// form of the 320-query search pass, kernels.h): its tile map is three scalars, its epilogue dense or thresholded by a uniform branch.
+template <typename... M> struct is_tile_subset : std::false_type {};
+template <> struct is_tile_subset<ScanSparse> : std::true_type {};
+template <typename... M> __device__ __forceinline__ ScanSparse tile_subset_of(const M&...) { return ScanSparse{}; }
+__device__ __forceinline__ ScanSparse tile_subset_of(const ScanSparse& sp) { return sp; }
+
 template <int S, int MF, int PROF = 0, int BN = 256, int GR = 32, typename... Mask>
 __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __restrict__ base, size_t n_rows, int d,
                                                              const uint4* __restrict__ packed_ro,
                                                              float* __restrict__ gmax, int nq_pad, size_t n_tiles, uint32_t y_packed, uint32_t y_cols,
                                                              Mask... mask) {
+    constexpr bool SPF = is_tile_subset<Mask...>::value;
+    constexpr bool MASKED = sizeof...(Mask) != 0 && !SPF;
     static_assert(sizeof...(Mask) == 0 || (MF == 16 && PROF == 0), "the masked form is the product kernel's");
+    static_assert(!SPF || (BN == 320 && GR == 64), "a tile subset: the 320-query search pass only");
     static_assert(BN == 256 || (BN == 320 && MF == 16 && S == 2), "320 queries: 16x16x32 tiles on the two-stage ring only");
     static_assert(GR == 32 || (GR == 64 && MF == 16), "rows per written maximum: 32, or the wave's 64");
     constexpr int HALF = BN / 2;             // queries of one query half
@@ -367,7 +378,8 @@ __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __r
     constexpr int RG_BYTES = 64 * 128;       // one K block of a row group
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
+    // (the tile-subset form has no register to spare for its epilogue's addressing: it keeps the wave index in a scalar)
+    const int lane = tid & 63, wave = is_tile_subset<Mask...>::value ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
     const int rg = wave >> 1, qh = wave & 1;
     const int nkb = d / KB;
     const size_t row_bytes = (size_t)d * 2;
@@ -377,8 +389,13 @@ __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __r
     gmax += (size_t)blockIdx.y * y_cols;   // batched passes (launch_scan_mfma n_pass > 1): pass y has its own query tiles and columns
     const char* const packed = reinterpret_cast<const char*>(packed_ro + (size_t)blockIdx.y * y_packed) + (size_t)(wave * QI * 64 + lane) * 16;
 
-    size_t tile = blockIdx.x;
-    if (tile >= n_tiles) return;
+    // vt counts the tiles of this launch, tile is the base's: the same thing unless the launch covers a subset
+    const ScanSparse sp = tile_subset_of(mask...);
+    const size_t n_vt = SPF ? sp.n_tiles : n_tiles;
+    auto tile_of = [&](size_t v) -> size_t { return SPF ? v * sp.mul + (v >> sp.shift) + sp.add : v; };
+    size_t vt = blockIdx.x;
+    if (vt >= n_vt) return;
+    size_t tile = tile_of(vt);
 
     // this wave's DMA share of a K block: rows qh*32 + 8u + (lane>>3) of the row group, u = 0..3
     auto src_ptr = [&](size_t t, int u) -> const char* {
@@ -428,8 +445,9 @@ __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __r
 #pragma unroll
                 for (int r = 0; r < NACC; r++) acc[rt][ct][r] = 0.0f;
 
-        const size_t next_tile = tile + gridDim.x;
-        const bool has_next_tile = next_tile < n_tiles;
+        const size_t next_vt = vt + gridDim.x;
+        const size_t next_tile = tile_of(next_vt);
+        const bool has_next_tile = next_vt < n_vt;
 #pragma unroll
         for (int u = 0; u < 4; u++) rn[u] = has_next_tile ? src_ptr(next_tile, u) : rp[u];
 
@@ -474,7 +492,7 @@ __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __r
                         int pc = -1;   // the DMA piece issued in front of MFMA group t (t is a constant of the unrolled loop)
                         // row pieces before groups 1-4, query pieces before 6, 8, ...; the masked form keeps the every-other-group
                         // order of PROF = 5: with the early order it spills two registers (12 B of scratch)
-                        if constexpr (S == 2 && PROF != 4 && PROF != 5 && sizeof...(Mask) == 0) {
+                        if constexpr (S == 2 && PROF != 4 && PROF != 5 && !MASKED) {
                             if (t >= 1 && t <= 4) pc = t - 1;
                             else if (t >= 6 && (t - 6) % 2 == 0 && (t - 6) / 2 < QI) pc = 4 + (t - 6) / 2;
                         } else if (t >= 1 && (t - 1) % STEP == 0 && (t - 1) / STEP < QI + 4) pc = (t - 1) / STEP;
@@ -514,7 +532,7 @@ __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __r
         }
 
         // epilogue: per query column, max over each 32-row group of this wave (two groups), or over all 64 rows (GR = 64)
-        if constexpr (sizeof...(Mask) != 0 && GR == 32) {
+        if constexpr (MASKED && GR == 32) {
             // acc[2 p + h][ct][r] of lane (i, g) holds row 16 h + 4 g + r of group p (LDS row = row of the row group, src_ptr)
 #pragma unroll
             for (int p = 0; p < 2; p++) {
@@ -536,14 +554,26 @@ __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __r
             // masked form: bit 4 rt + r of `allowed` = this lane's row 16 rt + 4 g + r of the wave (acc[rt][.][r]) is an allowed row; an
             // excluded row enters the maximum as MASKED_OUT (selected here, not written into the accumulators: that form spills)
             uint32_t allowed = 0xFFFFu;
-            if constexpr (sizeof...(Mask) != 0) {
+            if constexpr (MASKED) {
                 const uint32_t w0 = group_word(group * 2, mask...) >> (4 * g), w1 = group_word(group * 2 + 1, mask...) >> (4 * g);
                 allowed = (w0 & 15u) | ((w0 >> 16 & 15u) << 4) | ((w1 & 15u) << 8) | ((w1 >> 16 & 15u) << 12);
             }
             auto av = [&](int rt, int ct, int r) {
-                if constexpr (sizeof...(Mask) != 0) return (allowed >> (4 * rt + r)) & 1u ? acc[rt][ct][r] : MASKED_OUT;
+                if constexpr (MASKED) return (allowed >> (4 * rt + r)) & 1u ? acc[rt][ct][r] : MASKED_OUT;
                 else return acc[rt][ct][r];
             };
+            // tile-subset form, thresholded: this lane's thresholds, columns (g + 4 j) * 16 + i of the wave's half (1280 B per pass: cache hits)
+            float tq[3] = {0.0f, 0.0f, 0.0f};
+            uint32_t cbase = (uint32_t)(qh * HALF + i);   // this lane's column of column tile 0
+            if constexpr (SPF) {
+                // opaque: everything addressed from it is worked out here, in the epilogue -- hoisted out of the tile loop, ten list
+                // offsets per lane would have to live through the main loop, which has no register to spare
+                asm volatile("" : "+v"(cbase));
+                if (sp.tau) {
+#pragma unroll
+                    for (int j = 0; j < 3; j++) tq[j] = g + 4 * j < NCTW ? sp.tau[cbase + (g + 4 * j) * MF] : __builtin_inff();
+                }
+            }
 #pragma unroll
             for (int ct = 0; ct < NCTW; ct++) {
                 float m = fmaxf(fmaxf(av(0, ct, 0), av(0, ct, 1)), fmaxf(av(0, ct, 2), av(0, ct, 3)));
@@ -552,6 +582,29 @@ __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __r
                     m = fmaxf(m, fmaxf(fmaxf(av(rt, ct, 0), av(rt, ct, 1)), fmaxf(av(rt, ct, 2), av(rt, ct, 3))));
                 m = fmaxf(m, __shfl_xor(m, 16));
                 m = fmaxf(m, __shfl_xor(m, 32));
+#ifdef MSE_DEV_KERNELS
+                if constexpr (PROF == 6) { asm volatile("" ::"v"(m)); continue; }   // timing ablation: the maxima are formed and not stored
+#endif
+                if constexpr (SPF) {
+                    if (sp.tau) {
+                        // thresholded: the few maxima above the column's threshold go to the column's list, nothing else is written.
+                        // Every lane of a column holds m: lane group ct & 3 speaks for column tile ct (its thresholds are in tq)
+                        const uint32_t col = cbase + ct * MF;
+                        if (g == (ct & 3) && group < n_groups && m > tq[ct >> 2]) {
+                            uint32_t one;
+                            asm volatile("v_mov_b32 %0, 1" : "=v"(one));   // made here, not kept in a register through the main loop
+                            const uint32_t pos = atomicAdd(&sp.counts[col], one);
+                            if (pos < sp.cap) {
+                                sp.ids[col * sp.cap + pos] = (uint32_t)group;
+                                sp.keys[col * sp.cap + pos] = m;
+                            }
+                        }
+                    } else if (g == 0 && group < n_groups) {
+                        gmax[(vt * 4 + rg) * (size_t)nq_pad + cbase + ct * MF] = m;   // the launch's own groups: a small dense array
+                    }
+                    __builtin_amdgcn_sched_barrier(0);   // one column tile at a time: the accumulators free their registers as they go
+                    continue;
+                }
                 if (g == 0 && group < n_groups) gmax[group * (size_t)nq_pad + qh * HALF + ct * MF + i] = m;
             }
         } else {
@@ -578,6 +631,7 @@ __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __r
         }
 
         if (!has_next_tile) break;
+        vt = next_vt;
         tile = next_tile;
 #pragma unroll
         for (int u = 0; u < 4; u++) rp[u] = rn[u];
@@ -817,7 +871,8 @@ size_t mfma_packed_bytes(int d) { return (size_t)(d / KB) * 320 * 128; }
 #endif
 int mfma_group_rows(int nq_pad) {
 #ifdef MSE_DEV_KERNELS
-    if (getenv("MSE_SCAN_2D") || getenv("MSE_SCAN_ABL")) return 32;
+    // MSE_SCAN_ABL=32 is the ablation of the 64-row form itself (no stores of group maxima) and keeps its groups
+    if (getenv("MSE_SCAN_2D") || (getenv("MSE_SCAN_ABL") && atoi(getenv("MSE_SCAN_ABL")) != 32)) return 32;
 #endif
     return nq_pad == 320 ? MSE_GROUP_ROWS_320 : 32;
 }
@@ -883,6 +938,10 @@ int launch_scan_mfma(const uint16_t* base, size_t n_rows, int d, const uint16_t*
     else if (nq_pad == 256 && S == 3 && v2d == 17) rc = launch_2s<3>(grid, stream, base, n_rows, d, packed, group_max, gs);
     else if (nq_pad == 256 && S == 3 && v2d == 32) rc = launch_2d<3, 32>(grid, stream, base, n_rows, d, packed, group_max, gs);
     }
+    // MSE_SCAN_ABL=32: the 320-query search kernel (64 rows per maximum) WITHOUT its stores of group maxima -- what the dense array
+    // of maxima costs the scan (profiles/sparse_maxima_ab.txt); the array keeps whatever an earlier, unablated step left in it
+    if (!mask && group_rows == 64 && nq_pad == 320 && getenv("MSE_SCAN_ABL") && atoi(getenv("MSE_SCAN_ABL")) == 32)
+        rc = launch_2d<2, 16, 6, 320, 64>(grid, stream, base, n_rows, d, packed, group_max, gs);
     if (rc != -2) {
         if (rc) return rc;
         if (ev_end) MSE_HIP_TRY(hipEventRecord(ev_end, stream));
@@ -899,6 +958,8 @@ int launch_scan_mfma(const uint16_t* base, size_t n_rows, int d, const uint16_t*
         // group_rows = 64 (the search passes): one maximum per wave's 64 rows instead of two per 32 -- half the array of group maxima,
         // half the 64-byte partial stores, half of what the tournament's first level reads back.  Code object of that form: 255 VGPRs
         // unmasked and masked (the mask is applied by selection in the epilogue), 0 spilled, 0 scratch.
+        // The tile-subset form of that kernel (launch_scan_mfma_tiles, the sparse maxima of api.hip mfma_pass): scan_mfma2d_kernel<2, 16,
+        // 0, 320, 64, ScanSparse>: VGPRs: 252, ScratchSize [bytes/lane]: 0, Occupancy [waves/SIMD]: 2, SGPRs Spill: 0, VGPRs Spill: 0.
         if (group_rows == 64) rc = run([&](auto... m) { return launch_2d<2, 16, 0, 320, 64>(grid, stream, base, n_rows, d, packed, group_max, gs, m...); });
         else rc = run([&](auto... m) { return launch_2d<2, 16, 0, 320>(grid, stream, base, n_rows, d, packed, group_max, gs, m...); });
     } else if (nq_pad == 192) {
@@ -915,6 +976,32 @@ int launch_scan_mfma(const uint16_t* base, size_t n_rows, int d, const uint16_t*
         else rc = run([&](auto... m) { return launch_variant<1, 16, 0>(grid, stream, base, n_rows, d, packed, group_max, gs, m...); });
     }
     if (rc) return rc;
+    if (ev_end) MSE_HIP_TRY(hipEventRecord(ev_end, stream));
+    return 0;
+}
+
+int launch_scan_mfma_tiles(const uint16_t* base, size_t n_rows, int d, const uint16_t* queries_dev, int nq_rows, bool pack, void* packed_scratch,
+                           const ScanSparse& sp, float* group_max, int n_cu, hipStream_t stream, hipEvent_t ev_begin, hipEvent_t ev_end) {
+    if (n_rows == 0) return 0;
+    if (d % 64 != 0 || d <= 0 || d > D_MAX || (d / KB) % 2 != 0) return fail("scan_mfma_tiles: the 320-query pass needs an even number of K blocks");
+    if (sp.tau ? !(sp.counts && sp.ids && sp.keys && sp.cap) : !group_max) return fail("scan_mfma_tiles: no place for the maxima");
+    constexpr int BN = 320;
+    uint4* packed = reinterpret_cast<uint4*>(packed_scratch);
+    if (pack) hipLaunchKernelGGL(pack_queries_kernel, dim3(64, 1), dim3(256), 0, stream, queries_dev, d, BN, nq_rows, packed);
+    if (ev_begin) MSE_HIP_TRY(hipEventRecord(ev_begin, stream));
+    if (sp.n_tiles) {
+        // Code object of this form (hipcc --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage): 252 VGPRs, 92 SGPRs, 0 spilled,
+        // 0 scratch, 2 waves per SIMD (with the wave index in a vector register and the list offsets hoisted out of the tile loop it
+        // spilled 2 to 46 registers: see the kernel's epilogue)
+        auto kernel = scan_mfma2d_kernel<2, 16, 0, BN, 64, ScanSparse>;
+        const size_t lds = 2 * (size_t)(BN * 128) + (size_t)4 * 2 * 8192;
+        const size_t n_tiles = (n_rows + TILE_ROWS - 1) / TILE_ROWS;
+        const size_t grid = std::min<size_t>((size_t)n_cu, sp.n_tiles);
+        MSE_DYN_LDS(kernel, lds);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)grid, 1), dim3(W * 64), lds, stream, base, n_rows, d, (const uint4*)packed, group_max, BN, n_tiles,
+                           0u, 0u, sp);
+        MSE_HIP_TRY(hipGetLastError());
+    }
     if (ev_end) MSE_HIP_TRY(hipEventRecord(ev_end, stream));
     return 0;
 }

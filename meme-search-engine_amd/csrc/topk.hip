@@ -169,7 +169,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_kernel(SelectArgs a, size_
     const uint32_t* list_ids = use_list ? a.list_ids + (size_t)q * a.list_stride : nullptr;
     const T* list_keys = use_list ? reinterpret_cast<const T*>(a.list_keys) + (size_t)q * a.list_stride : nullptr;
     size_t M;
-    if (use_list) M = a.n_list;
+    if (use_list) M = a.list_count ? (size_t)min((unsigned long long)a.list_count[q], (unsigned long long)a.n_list) : a.n_list;
     else if (use_par) M = a.n_par * (size_t)a.fanout;
     else M = a.n_in;
 
@@ -416,7 +416,7 @@ __global__ void finalize_kernel(const uint32_t* __restrict__ sel_ids, const int6
                                 size_t sel_stride, int k, int nq, uint64_t id_offset, int64_t* __restrict__ out_scores,
                                 uint32_t* __restrict__ out_ids, size_t out_stride, const float* __restrict__ group_keys,
                                 size_t gk_stride, int kg, size_t n_groups, const float* __restrict__ eps,
-                                float* __restrict__ margin) {
+                                float* __restrict__ margin, const float* __restrict__ tau) {
     const int q = blockIdx.x;
     for (int i = threadIdx.x; i < k; i += blockDim.x) {
         const uint32_t id = sel_ids[(size_t)q * sel_stride + i];
@@ -431,7 +431,10 @@ __global__ void finalize_kernel(const uint32_t* __restrict__ sel_ids, const int6
         if ((size_t)kg >= n_groups) {
             m = __builtin_inff();  // every group was re-scored exactly
         } else {
-            const float g = group_keys[(size_t)q * gk_stride + (kg - 1)];
+            // thresholded group maxima (tau): the groups that never reached the list are at most tau[q], and a list shorter than kg
+            // leaves -inf in its last chosen key: the bound is then tau[q] itself
+            float g = group_keys[(size_t)q * gk_stride + (kg - 1)];
+            if (tau) g = fmaxf(g, tau[q]);
             const uint32_t idk = sel_ids[(size_t)q * sel_stride + (k - 1)];
             // a k-th score of INT64_MIN (saturated fixed point) proves nothing: a row outside the groups that also saturates ties with
             // it and may have the lower id -- only examining every group decides
@@ -605,14 +608,83 @@ int launch_scatter_topk(const uint32_t* idx, const uint8_t* take, int nb, int k,
 int launch_finalize(const uint32_t* sel_ids, const int64_t* sel_scores, size_t sel_stride, int k, int nq,
                     uint64_t id_offset, int64_t* out_scores, uint32_t* out_ids, size_t out_stride,
                     const float* group_keys, size_t gk_stride, int kg, size_t n_groups, const float* eps,
-                    float* margin, hipStream_t stream) {
+                    float* margin, hipStream_t stream, const float* tau) {
     if (nq == 0 || k == 0) return 0;
     hipLaunchKernelGGL(finalize_kernel, dim3(nq), dim3(256), 0, stream, sel_ids, sel_scores, sel_stride, k, nq,
-                       id_offset, out_scores, out_ids, out_stride, group_keys, gk_stride, kg, n_groups, eps, margin);
+                       id_offset, out_scores, out_ids, out_stride, group_keys, gk_stride, kg, n_groups, eps, margin, tau);
     MSE_HIP_TRY(hipGetLastError());
     return 0;
 }
 
+// ---- thresholded group maxima (api.hip mfma_pass): threshold, the sample's survivors, the widening's compact lists
+__device__ __forceinline__ float next_below(float t) {   // the next float below t; -inf and NaN stay
+    if (!(t > -__builtin_inff())) return t;
+    if (t == 0.0f) return __uint_as_float(0x80000001u);
+    const uint32_t b = __float_as_uint(t);
+    return __uint_as_float(t > 0.0f ? b - 1u : b + 1u);
+}
+__global__ void sparse_tau_kernel(const float* __restrict__ gk, size_t gk_stride, int k, const float* __restrict__ eps, int nq, int nq_pad,
+                                  float* __restrict__ tau, uint32_t* __restrict__ counts) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nq_pad) return;
+    counts[q] = 0u;
+    // G_k = gk[q][k - 1]: k distinct sample groups, hence k distinct rows, have matrix-core scores >= G_k, so the exact k-th score is
+    // >= G_k - eps.  A row of a group whose maximum is <= tau < G_k - 2 eps has an exact score < G_k - eps: not in the top k, not
+    // even as a tie.  The third eps covers the rounding of the subtraction (an ulp of G_k is far below eps unless eps is 0, and then
+    // next_below keeps the inequality strict).  Fewer than k sample groups: G_k = -inf, everything survives.
+    tau[q] = q < nq ? next_below(gk[(size_t)q * gk_stride + (k - 1)] - 3.0f * eps[q]) : __builtin_inff();
+}
+__global__ void sparse_append_sample_kernel(const float* __restrict__ dense, int nq_pad, size_t n_sg, int nq, uint32_t stride,
+                                            const float* __restrict__ tau, uint32_t* __restrict__ counts, uint32_t* __restrict__ ids,
+                                            float* __restrict__ keys, uint32_t cap) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t sg = t / (size_t)nq_pad;
+    const uint32_t q = (uint32_t)(t % (size_t)nq_pad);
+    if (sg >= n_sg || q >= (uint32_t)nq) return;
+    const float m = dense[t];
+    if (!(m > tau[q])) return;
+    const uint32_t pos = atomicAdd(&counts[q], 1u);
+    if (pos < cap) {
+        ids[(size_t)q * cap + pos] = (uint32_t)((sg >> 2) * 4 * stride + (sg & 3));
+        keys[(size_t)q * cap + pos] = m;
+    }
+}
+__global__ void sparse_gather_lists_kernel(const uint32_t* __restrict__ ids, const float* __restrict__ keys, const uint32_t* __restrict__ counts,
+                                           const float* __restrict__ tau, uint32_t cap, const uint32_t* __restrict__ idx,
+                                           uint32_t* __restrict__ out_ids, float* __restrict__ out_keys, uint32_t* __restrict__ out_counts,
+                                           float* __restrict__ out_tau) {
+    const int j = blockIdx.x;
+    const uint32_t q = idx[j];
+    const uint32_t n = counts[q] < cap ? counts[q] : cap;
+    if (threadIdx.x == 0) { out_counts[j] = n; out_tau[j] = tau[q]; }
+    for (uint32_t c = threadIdx.x; c < n; c += blockDim.x) {
+        out_ids[(size_t)j * cap + c] = ids[(size_t)q * cap + c];
+        out_keys[(size_t)j * cap + c] = keys[(size_t)q * cap + c];
+    }
+}
+int launch_sparse_tau(const float* gk, size_t gk_stride, int k, const float* eps, int nq, int nq_pad, float* tau, uint32_t* counts, hipStream_t stream) {
+    if (nq_pad == 0) return 0;
+    hipLaunchKernelGGL(sparse_tau_kernel, dim3((nq_pad + 63) / 64), dim3(64), 0, stream, gk, gk_stride, k, eps, nq, nq_pad, tau, counts);
+    MSE_HIP_TRY(hipGetLastError());
+    return 0;
+}
+int launch_sparse_append_sample(const float* dense, int nq_pad, size_t n_sg, int nq, uint32_t stride, const float* tau, uint32_t* counts,
+                                uint32_t* ids, float* keys, uint32_t cap, hipStream_t stream) {
+    const size_t total = n_sg * (size_t)nq_pad;
+    if (total == 0) return 0;
+    hipLaunchKernelGGL(sparse_append_sample_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, dense, nq_pad, n_sg, nq, stride,
+                       tau, counts, ids, keys, cap);
+    MSE_HIP_TRY(hipGetLastError());
+    return 0;
+}
+int launch_sparse_gather_lists(const uint32_t* ids, const float* keys, const uint32_t* counts, const float* tau, uint32_t cap, const uint32_t* idx,
+                               int nb, uint32_t* out_ids, float* out_keys, uint32_t* out_counts, float* out_tau, hipStream_t stream) {
+    if (nb == 0) return 0;
+    hipLaunchKernelGGL(sparse_gather_lists_kernel, dim3(nb), dim3(256), 0, stream, ids, keys, counts, tau, cap, idx, out_ids, out_keys,
+                       out_counts, out_tau);
+    MSE_HIP_TRY(hipGetLastError());
+    return 0;
+}
 
 // hand-over of a shard's results as a packed block: out_sc[i] = sc[i], out_ids[i] = ids[i] + id_offset; an empty slot (id ID_NONE, or
 // sc == nullptr: nothing to hand over) becomes (INT64_MIN, ID_NONE)

@@ -96,6 +96,8 @@ SIGNATURES = {
     "mse_debug_select_topk": (C.c_int, [vp, C.c_int, C.c_int, vp, sz, sz, sz, sz, u32p, vp, C.POINTER(C.c_uint64)]),
     "mse_searcher_scan_timing": (C.c_int, [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "mse_searcher_last_stats": (C.c_int, [vp, u32p, u32p]),
+    "mse_searcher_set_sparse_maxima": (C.c_int, [vp, C.c_int, C.c_uint32, C.c_uint32]),
+    "mse_searcher_sparse_stats": (C.c_int, [vp, u32p, u32p, u32p]),
     "mse_index_new": (vp, [C.c_int]),
     "mse_index_free": (None, [vp]),
     "mse_index_add": (C.c_int, [vp, f32p, sz]),

@@ -15,6 +15,7 @@ SCALE = 4294967296.0  # vector.rs:46
 ID_NONE = 0xFFFFFFFF
 
 MODE_AUTO, MODE_EXACT, MODE_MFMA = 0, 1, 2
+SPARSE_AUTO, SPARSE_OFF, SPARSE_FORCED = 0, 1, 2   # Searcher.set_sparse_maxima
 
 
 def _bits(a):
@@ -380,7 +381,16 @@ class Searcher:
     def last_stats(self):
         a, b = C.c_uint32(), C.c_uint32()
         check(ffi.lib().mse_searcher_last_stats(self._h, C.byref(a), C.byref(b)), "last_stats")
-        return {"widened_queries": int(a.value), "max_groups": int(b.value)}
+        p, f, n = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        check(ffi.lib().mse_searcher_sparse_stats(self._h, C.byref(p), C.byref(f), C.byref(n)), "sparse_stats")
+        return {"widened_queries": int(a.value), "max_groups": int(b.value), "sparse_passes": int(p.value),
+                "sparse_fallbacks": int(f.value), "sparse_longest_list": int(n.value)}
+
+    def set_sparse_maxima(self, mode="auto", stride=0, capacity=0):
+        """Thresholded group maxima of the 320-query pass (include/mse.h mse_searcher_set_sparse_maxima): mode "auto", "off" or
+        "forced" (or SPARSE_AUTO / SPARSE_OFF / SPARSE_FORCED); stride and capacity 0 keep their current values."""
+        mode = {"auto": SPARSE_AUTO, "off": SPARSE_OFF, "forced": SPARSE_FORCED}.get(mode, mode)
+        check(ffi.lib().mse_searcher_set_sparse_maxima(self._h, int(mode), int(stride), int(capacity)), "set_sparse_maxima")
 
     def close(self):
         if self._h:
