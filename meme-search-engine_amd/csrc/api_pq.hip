@@ -67,7 +67,7 @@ namespace {
 
 // <= 8 f32 queries against every row in the stated FAISS order (scan_exact.hip, QF32), tournament, ids + f32 keys into
 // out_ids / out_keys ([nq][out_stride], ID_NONE-padded)
-// With a filter (non-empty, no longer than the index): its allowed rows only, through its ascending id list (api.hip exact_pass).
+// With a filter (non-empty, no longer than the index): its allowed rows only, through its ascending id list (bruteforce.hip exact_pass).
 int index_pass_exact(mse_index* idx, const float* q32_dev, int nqp, int k, uint32_t* out_ids, float* out_keys, size_t out_stride,
                      const mse_filter* f = nullptr) {
     mse_searcher* s = idx->scratch;
@@ -90,10 +90,10 @@ int index_pass_exact(mse_index* idx, const float* q32_dev, int nqp, int k, uint3
 
 // Up to 256 f32 queries in ONE pass over the rows.  The matrix cores score f16 roundings of the queries and only nominate:
 // group maxima -> tournament -> the rows of the best groups re-scored with the f32 query in the stated order -> top k ->
-// certificate.  The bound on what the nomination can have missed is the f16 scan's (api.hip mfma_pass) plus the query
+// certificate.  The bound on what the nomination can have missed is the f16 scan's (bruteforce.hip mfma_pass) plus the query
 // rounding, |x . (q - f16(q))| <= |x| |q - f16(q)| (measured per query, not assumed).  A query whose certificate fails widens
 // its candidate set and finally repeats through the exact pass: answers equal index_pass_exact's.
-// With a filter: the masked scan, excluded rows dropped at candidate expansion, the filtered exact pass as the fallback (api.hip mfma_pass).
+// With a filter: the masked scan, excluded rows dropped at candidate expansion, the filtered exact pass as the fallback (bruteforce.hip mfma_pass).
 int index_pass_mfma(mse_index* idx, const float* q32_dev, int nqp, int k, uint32_t* out_ids, float* out_keys, size_t out_stride,
                     const mse_filter* f = nullptr) {
     mse_searcher* s = idx->scratch;
@@ -148,7 +148,7 @@ int index_pass_mfma(mse_index* idx, const float* q32_dev, int nqp, int k, uint32
         if (!(margin_h[i] > 0.0f)) bad.push_back((uint32_t)i);
     if (bad.empty() || (size_t)kg0 >= n_groups) return 0;
     s->last_widened = std::max<uint32_t>(s->last_widened, (uint32_t)bad.size());
-    // only the queries whose certificate failed go on, as a compact set (api.hip mfma_pass has the same structure)
+    // only the queries whose certificate failed go on, as a compact set (bruteforce.hip mfma_pass has the same structure)
     const int nb = (int)bad.size(), nbp = (nb + 31) / 32 * 32;
     if (s->widx.ensure((size_t)nb * 5) || s->wq.ensure((size_t)nb * d * 6) || s->wg.ensure(n_groups * (size_t)nbp * 4) ||
         s->wout.ensure((size_t)nb * k * 8)) return -1;
@@ -212,7 +212,7 @@ int index_run_group(mse_index* idx, DispatchReq* const* reqs, size_t n_req) {
     s->last_widened = 0; s->last_max_groups = 0;
     // same rule as the f16 dispatcher (dispatch.hip): the matrix-core pass for more than 8 queries, and for any count once the
     // rows have outgrown the caches
-    // (filtered: the id-list pass on the sparse side of the crossover, api.hip filter_sparse)
+    // (filtered: the id-list pass on the sparse side of the crossover, bruteforce.hip filter_sparse)
     const bool mfma = (total > 8 || n >= ((size_t)1 << 22)) && !(f && filter_sparse(&idx->view, f, total));
     const size_t tile = mfma ? (size_t)mfma_query_tile((int)d) : 8;
     for (size_t q0 = 0; q0 < total; q0 += tile) {

@@ -1353,7 +1353,7 @@ int filtered_resolve(SearchIn& in, int regime) {
 }
 
 // The LIST regime: no traversal.  The eligible rows -- allowed by the filter AND carrying a url -- are scored exactly through their
-// ascending id list, 8 queries per pass (the sparse path of the filtered brute-force search, api.hip), the descriptor bias is added
+// ascending id list, 8 queries per pass (the sparse path of the filtered brute-force search, bruteforce.hip), the descriptor bias is added
 // before the selection, and the tournament picks the k best by (score desc, id asc).  An ineligible row is absent, not merely low.
 // Counters: n_visited = cmps = eligible rows, pq_cmps = 0.  Results go where the fused request path's go (fz.dst or the contiguous arrays).
 int list_run(const SearchIn& in, const FusedQuery& fz) {

@@ -518,15 +518,11 @@ int run_group(mse_dispatcher* D, DispatchReq* const* reqs, size_t n_req) {
         o += reqs[i]->nq * d * 2;
     }
     MSE_HIP_TRY(hipMemcpyAsync(D->q_dev.p, D->pin.p, in_bytes, hipMemcpyHostToDevice, st));
-    // a pass of the matrix-core scan costs less than the exact-order pass once the rows no longer fit the caches, whatever the
-    // query count (40 ms against 54 ms at 1e8 rows); below that the exact pass has the shorter tail.  Same answers either way.
-    const int mode = (total > 8 || b->n >= ((size_t)1 << 22)) ? MSE_MODE_MFMA : MSE_MODE_EXACT;
     int64_t* sc_dev = D->out_dev.as<int64_t>();
     uint32_t* id_dev = reinterpret_cast<uint32_t*>(D->out_dev.as<char>() + sc_bytes);
-    // a group shares one filter (its key, aux0; run_batch): the filtered search picks its own path by the same rule and the crossover
+    // a group shares one filter (its key, aux0; run_batch), or has none; the path is the coalescer's side of the AUTO rule
     const mse_filter* f = static_cast<const mse_filter*>(reqs[0]->aux0);
-    if (f ? mse_bruteforce_topk_filtered_f16_dev(s, f, D->q_dev.p, total, kmax, MSE_MODE_AUTO, 0, sc_dev, id_dev)
-          : mse_bruteforce_topk_f16_dev(s, D->q_dev.p, total, kmax, mode, 0, sc_dev, id_dev)) return -1;
+    if (bruteforce_topk_dev(s, f, D->q_dev.p, total, kmax, bruteforce_auto_mode(b, f, total, true), 0, sc_dev, id_dev)) return -1;
     MSE_HIP_TRY(hipMemcpyAsync(D->pin.p, D->out_dev.p, out_bytes, hipMemcpyDeviceToHost, st));
     MSE_HIP_TRY(hipStreamSynchronize(st));
     const int64_t* sc = reinterpret_cast<const int64_t*>(p);

@@ -78,7 +78,7 @@ int launch_finalize(const uint32_t* sel_ids, const int64_t* sel_scores, size_t s
                     const float* group_keys, size_t gk_stride, int kg, size_t n_groups, const float* eps,
                     float* margin, hipStream_t stream, const float* tau = nullptr /* per query: the bound is max(worst chosen key, tau) */);
 
-// Thresholded group maxima (api.hip mfma_pass, the sparse form of the 320-query pass).  counts [nq_pad], ids / keys [nq_pad][cap].
+// Thresholded group maxima (bruteforce.hip mfma_pass, the sparse form of the 320-query pass).  counts [nq_pad], ids / keys [nq_pad][cap].
 // tau[q] = the next float below gk[q][k - 1] - 3 eps[q] for q < nq (gk: the k best sample maxima, best first), +inf for the padding
 // columns up to nq_pad; counts[0 .. nq_pad) = 0
 int launch_sparse_tau(const float* gk, size_t gk_stride, int k, const float* eps, int nq, int nq_pad, float* tau, uint32_t* counts, hipStream_t stream);

@@ -121,7 +121,7 @@ struct mse_searcher {
     mse::DevBuf ins_scratch[8];    // scratch of mse_graph_insert_rows (graph_insert.hip): slots, staging slabs, codes, flags
     mse::BuildScratch ins_build;   // ... and of its link step
     uint32_t last_widened = 0, last_max_groups = 0;
-    // thresholded group maxima of the 320-query pass (api.hip mfma_pass; mse_searcher_set_sparse_maxima): mode 0 auto, 1 off, 2 forced;
+    // thresholded group maxima of the 320-query pass (bruteforce.hip mfma_pass; mse_searcher_set_sparse_maxima): mode 0 auto, 1 off, 2 forced;
     // every sparse_stride-th 256-row tile is the sample (stride - 1 a power of two); sparse_cap survivors per query at most
     int sparse_mode = 0;
     uint32_t sparse_stride = 33, sparse_cap = 8192;
@@ -188,10 +188,16 @@ struct mse_codes {
 };
 
 namespace mse {
-// a filter may be used on base b: same device, no longer than the rows (api.hip); 0, or -1 with the error set
+// a filter may be used on base b: same device, no longer than the rows (filter_api.hip); 0, or -1 with the error set
 int check_filter(const mse_base* b, const mse_filter* f);
-// the sparse side of the crossover: nq queries through the filter's id list cost less than the masked scan over all rows (api.hip)
+// the sparse side of the crossover: nq queries through the filter's id list cost less than the masked scan over all rows (bruteforce.hip)
 bool filter_sparse(const mse_base* b, const mse_filter* f, size_t nq);
+// what MSE_MODE_AUTO resolves to for nq queries (f: the call's filter or null; coalesced: the call is a pass of the base's coalescer) --
+// the one statement of the rule (bruteforce.hip)
+int bruteforce_auto_mode(const mse_base* b, const mse_filter* f, size_t nq, bool coalesced);
+// the body of mse_bruteforce_topk_f16_dev (f = null) and mse_bruteforce_topk_filtered_f16_dev, validation included (bruteforce.hip)
+int bruteforce_topk_dev(mse_searcher* s, const mse_filter* f, const void* queries_dev, size_t nq, size_t k, int mode, uint64_t id_offset,
+                        void* scores_dev, void* ids_dev);
 // One exact pass of <= 8 queries (staged, padded, in s->q_stage) over the rows ids[0 .. n) -- ascending; null: rows 0 .. n -- and the
 // exact top-k of each: i64 scores in the reference order, (score desc, id asc), padding INT64_MIN / ID_NONE; a row that is not listed is
 // absent.  bias (optional, needs ids): the descriptor product of every listed row is added to its score before the selection.

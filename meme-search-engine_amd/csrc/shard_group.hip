@@ -516,18 +516,12 @@ static int bring_up_rccl(mse_shard_group* G) {
     return 0;
 }
 
-// the brute-force local step: exact top-k of the shard's rows with global ids (the shard's first row added)
-static LocalFn bruteforce_local(size_t nq, size_t k, int mode) {
+// the brute-force local step: exact top-k of the shard's rows -- of those its slice of sf allows (null: all; the slice speaks local ids) --
+// with global ids (the shard's first row added)
+static LocalFn bruteforce_local(const mse_shard_group* G, const mse_shard_filter* sf, size_t nq, size_t k, int mode) {
     return [=](Shard& sh, const void* q, char* blk) -> int {
-        return mse_bruteforce_topk_f16_dev(sh.searcher, q, nq, k, mode, sh.first_row, blk, blk + nq * k * 8);
-    };
-}
-
-// the same over the shard's slice of a shard filter (mse_bruteforce_topk_filtered_f16_dev: the slice speaks local ids, the block global ones)
-static LocalFn bruteforce_local_filtered(const mse_shard_group* G, const mse_shard_filter* sf, size_t nq, size_t k, int mode) {
-    return [=](Shard& sh, const void* q, char* blk) -> int {
-        return mse_bruteforce_topk_filtered_f16_dev(sh.searcher, sf->parts[(size_t)(&sh - G->shards.data())], q, nq, k, mode, sh.first_row, blk,
-                                                    blk + nq * k * 8);
+        const mse_filter* f = sf ? sf->parts[(size_t)(&sh - G->shards.data())] : nullptr;
+        return bruteforce_topk_dev(sh.searcher, f, q, nq, k, mode, sh.first_row, blk, blk + nq * k * 8);
     };
 }
 
@@ -548,78 +542,77 @@ static int check_shard_filter(const mse_shard_group* G, const mse_shard_filter* 
 
 static bool known_mode(int mode) { return mode == MSE_MODE_AUTO || mode == MSE_MODE_EXACT || mode == MSE_MODE_MFMA; }
 
-extern "C" {
+// The brute-force entry points, sf = null being the unfiltered search.  One order of checks for all four: the group, the mode and k before
+// the lock; under it the shard filter (a stale one is refused even by a call that has nothing to do), nothing to do, null arrays.
+static int check_search(const mse_shard_group* G, int mode, size_t k) {
+    if (!G) return fail("null shard group");
+    if (!known_mode(mode)) return fail("unknown mode");
+    if (k > (size_t)TOPK_KMAX - 64) return fail("k too large (max 1984)");
+    return 0;
+}
+// the caller holds G->call_mu: -1 with the error set, 0 = nothing to do, 1 = go on
+static int check_search_locked(const mse_shard_group* G, const mse_shard_filter* sf, const void* queries, size_t nq, size_t k, const void* scores,
+                               const void* ids) {
+    if (sf && check_shard_filter(G, sf)) return -1;
+    if (nq == 0 || k == 0) return 0;
+    if (!queries || !scores || !ids) return fail("shard group: null argument");
+    return 1;
+}
 
 // queries_dev: [nq][d] f16 on the ROOT device (device of shard 0), complete before the call; outputs [nq][k] on the root device.
 // Returns when the merged result is complete.
+static int search_dev_impl(mse_shard_group* G, const mse_shard_filter* sf, const void* queries_dev, size_t nq, size_t k, int mode,
+                           void* scores_dev, void* ids_dev) {
+    if (check_search(G, mode, k)) return -1;
+    std::lock_guard<std::mutex> call(G->call_mu);
+    if (const int go = check_search_locked(G, sf, queries_dev, nq, k, scores_dev, ids_dev); go <= 0) return go;
+    return search_dev_locked(G, queries_dev, nq * G->d * 2, nq, k, k, bruteforce_local(G, sf, nq, k, mode), scores_dev, ids_dev);
+}
+
+// the host form.  ONE lock across the check, upload, search and download: two host threads on the same group must not see each other's
+// queries in q_root or each other's answers in out_s / out_i
+static int search_impl(mse_shard_group* G, const mse_shard_filter* sf, const uint16_t* queries, size_t nq, size_t k, int mode, int64_t* scores,
+                       uint32_t* ids) {
+    if (check_search(G, mode, k)) return -1;
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    int rc = 0;
+    {
+        std::lock_guard<std::mutex> call(G->call_mu);
+        if (const int go = check_search_locked(G, sf, queries, nq, k, scores, ids); go <= 0) return go;
+        MSE_HIP_TRY(hipSetDevice(G->root_device));
+        rc = G->q_root.ensure(nq * G->d * 2) || G->out_s.ensure(nq * k * 8) || G->out_i.ensure(nq * k * 4);
+        if (!rc && hipMemcpy(G->q_root.p, queries, nq * G->d * 2, hipMemcpyHostToDevice) != hipSuccess) rc = fail("query upload failed");
+        if (!rc) rc = search_dev_locked(G, G->q_root.p, nq * G->d * 2, nq, k, k, bruteforce_local(G, sf, nq, k, mode), G->out_s.p, G->out_i.p);
+        if (!rc && (hipMemcpy(scores, G->out_s.p, nq * k * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+                    hipMemcpy(ids, G->out_i.p, nq * k * 4, hipMemcpyDeviceToHost) != hipSuccess)) rc = fail("result download failed");
+    }
+    (void)hipSetDevice(prev);
+    return rc;
+}
+
+extern "C" {
+
 int mse_shard_group_search_dev(mse_shard_group* G, const void* queries_dev, size_t nq, size_t k, int mode,
                                void* scores_dev, void* ids_dev) {
-    if (!G) return fail("null shard group");
-    if (nq == 0 || k == 0) return 0;
-    if (k > (size_t)TOPK_KMAX - 64) return fail("k too large (max 1984)");
-    std::lock_guard<std::mutex> call(G->call_mu);
-    return search_dev_locked(G, queries_dev, nq * G->d * 2, nq, k, k, bruteforce_local(nq, k, mode), scores_dev, ids_dev);
+    return search_dev_impl(G, nullptr, queries_dev, nq, k, mode, scores_dev, ids_dev);
 }
 
 int mse_shard_group_search_filtered_dev(mse_shard_group* G, const mse_shard_filter* sf, const void* queries_dev, size_t nq, size_t k, int mode,
                                         void* scores_dev, void* ids_dev) {
-    if (!G) return fail("null shard group");
-    if (!sf) return fail("shard group: null shard filter");
-    if (!known_mode(mode)) return fail("unknown mode");
-    if (k > (size_t)TOPK_KMAX - 64) return fail("k too large (max 1984)");
-    std::lock_guard<std::mutex> call(G->call_mu);
-    if (check_shard_filter(G, sf)) return -1;
-    if (nq == 0 || k == 0) return 0;
-    if (!queries_dev || !scores_dev || !ids_dev) return fail("shard group: null argument");
-    return search_dev_locked(G, queries_dev, nq * G->d * 2, nq, k, k, bruteforce_local_filtered(G, sf, nq, k, mode), scores_dev, ids_dev);
+    if (G && !sf) return fail("shard group: null shard filter");
+    return search_dev_impl(G, sf, queries_dev, nq, k, mode, scores_dev, ids_dev);
 }
 
 int mse_shard_group_search_filtered(mse_shard_group* G, const mse_shard_filter* sf, const uint16_t* queries, size_t nq, size_t k, int mode,
                                     int64_t* scores, uint32_t* ids) {
-    if (!G) return fail("null shard group");
-    if (!sf) return fail("shard group: null shard filter");
-    if (!known_mode(mode)) return fail("unknown mode");
-    if (k > (size_t)TOPK_KMAX - 64) return fail("k too large (max 1984)");
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    int rc = 0;
-    {
-        std::lock_guard<std::mutex> call(G->call_mu);   // one lock across the check, upload, search and download (mse_shard_group_search)
-        if (check_shard_filter(G, sf)) return -1;
-        if (nq == 0 || k == 0) return 0;
-        if (!queries || !scores || !ids) return fail("shard group: null argument");
-        MSE_HIP_TRY(hipSetDevice(G->root_device));
-        rc = G->q_root.ensure(nq * G->d * 2) || G->out_s.ensure(nq * k * 8) || G->out_i.ensure(nq * k * 4);
-        if (!rc && hipMemcpy(G->q_root.p, queries, nq * G->d * 2, hipMemcpyHostToDevice) != hipSuccess) rc = fail("query upload failed");
-        if (!rc) rc = search_dev_locked(G, G->q_root.p, nq * G->d * 2, nq, k, k, bruteforce_local_filtered(G, sf, nq, k, mode), G->out_s.p, G->out_i.p);
-        if (!rc && (hipMemcpy(scores, G->out_s.p, nq * k * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-                    hipMemcpy(ids, G->out_i.p, nq * k * 4, hipMemcpyDeviceToHost) != hipSuccess)) rc = fail("result download failed");
-    }
-    (void)hipSetDevice(prev);
-    return rc;
+    if (G && !sf) return fail("shard group: null shard filter");
+    return search_impl(G, sf, queries, nq, k, mode, scores, ids);
 }
 
 int mse_shard_group_search(mse_shard_group* G, const uint16_t* queries, size_t nq, size_t k, int mode, int64_t* scores,
                            uint32_t* ids) {
-    if (!G) return fail("null shard group");
-    if (nq == 0 || k == 0) return 0;
-    if (k > (size_t)TOPK_KMAX - 64) return fail("k too large (max 1984)");
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    MSE_HIP_TRY(hipSetDevice(G->root_device));
-    int rc = 0;
-    {
-        // ONE lock across upload, search and download: two host threads on the same group must not see each other's queries
-        // in q_root or each other's answers in out_s / out_i
-        std::lock_guard<std::mutex> call(G->call_mu);
-        rc = G->q_root.ensure(nq * G->d * 2) || G->out_s.ensure(nq * k * 8) || G->out_i.ensure(nq * k * 4);
-        if (!rc && hipMemcpy(G->q_root.p, queries, nq * G->d * 2, hipMemcpyHostToDevice) != hipSuccess) rc = fail("query upload failed");
-        if (!rc) rc = search_dev_locked(G, G->q_root.p, nq * G->d * 2, nq, k, k, bruteforce_local(nq, k, mode), G->out_s.p, G->out_i.p);
-        if (!rc && (hipMemcpy(scores, G->out_s.p, nq * k * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-                    hipMemcpy(ids, G->out_i.p, nq * k * 4, hipMemcpyDeviceToHost) != hipSuccess)) rc = fail("result download failed");
-    }
-    (void)hipSetDevice(prev);
-    return rc;
+    return search_impl(G, nullptr, queries, nq, k, mode, scores, ids);
 }
 
 // ---- the approximate-search paths over the same shards (round 5; SURVEY 8(e): "rows (and their PQ codes / descriptors)") ---------
@@ -977,8 +970,7 @@ static int comm_search_impl(mse_comm* c, mse_searcher* s, const mse_filter* f, c
     for (hipEvent_t& e : c->ev) if (!e) MSE_HIP_TRY(hipEventCreate(&e));
     c->timed = false;
     MSE_HIP_TRY(hipEventRecord(c->ev[0], s->stream));
-    if (f ? mse_bruteforce_topk_filtered_f16_dev(s, f, queries_dev, nq, k, mode, id_offset, blk, blk + nq * k * 8)
-          : mse_bruteforce_topk_f16_dev(s, queries_dev, nq, k, mode, id_offset, blk, blk + nq * k * 8)) return -1;
+    if (bruteforce_topk_dev(s, f, queries_dev, nq, k, mode, id_offset, blk, blk + nq * k * 8)) return -1;
     MSE_HIP_TRY(hipEventRecord(c->ev[1], s->stream));
     const int rc = rccl().AllGather(blk, c->gathered.p, B, /*ncclInt8*/ 0, c->comm, s->stream);
     if (rc) return rccl_fail("ncclAllGather", rc);

@@ -58,7 +58,7 @@ def main():
         res["sparse_1q_ms"][str(count)] = {"sparse": float(np.median(sp)), "masked_scan": float(np.median(sc)),
                                            "speedup": float(np.median(sc) / np.median(sp))}
         f.close()
-    # the crossover: the id-list pass (MODE_EXACT) against the masked scan (MODE_MFMA) around the boundary of the rule in api.hip
+    # the crossover: the id-list pass (MODE_EXACT) against the masked scan (MODE_MFMA) around the boundary of the rule in bruteforce.hip
     # (filter_sparse: count x ceil(nq / 8) x 3 <= rows x ceil(nq / pass width) x 2), and what the rule picks
     tile = mse.ffi.lib().mse_queries_per_pass_max(1152)
     res["crossover"] = []

@@ -115,7 +115,7 @@ def test_wide_passes_at_other_widths(gpu, mse, orc, d, nq):
 @pytest.mark.parametrize("n,nq,k", [(300, 2000, 1), (4096, 1500, 3), (33, 700, 5)])
 def test_many_queries_against_a_small_base(gpu, mse, orc, n, nq, k):
     # a small base takes all its queries in ONE matrix-core call: the full passes side by side in one launch, the remainder after
-    # them, one tournament / re-score / certificate over all queries (api.hip mfma_call_tile; the request path's entry step)
+    # them, one tournament / re-score / certificate over all queries (bruteforce.hip mfma_call_tile; the request path's entry step)
     base = orc.gen_rows_f16(SEED_BASE, 0, n)
     q = orc.gen_rows_f16(SEED_QUERY, 0, nq)
     s = mse.Searcher(mse.VectorList.from_f16s(base, D))
@@ -253,7 +253,7 @@ def test_full_size_properties_1e7(gpu, mse, orc):
 
 def test_mfma_error_bound_is_measured_not_assumed(gpu, mse, orc):
     """The exactness certificate of the batched scan rests on |MFMA score - exact-order score| <= eps * |q| * |x| with
-    eps = 2.8e-4 (api.hip mfma_pass / DESIGN 3.1).  Measure the left side: a 1e7-row base in which every row is repeated 32
+    eps = 2.8e-4 (bruteforce.hip mfma_pass / DESIGN 3.1).  Measure the left side: a 1e7-row base in which every row is repeated 32
     times, so that the scan's per-32-row maximum IS the row's MFMA score, against the exact-order scores of the 312 500
     distinct rows, for 128 and 256 queries (40 M and 80 M (row, query) pairs).  The bound must hold with a margin of 4."""
     import ctypes as C

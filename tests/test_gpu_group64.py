@@ -1,5 +1,5 @@
 """The 320-query pass of the matrix-core scan writes ONE group maximum per 64 rows (the rows one wave owns), where every other pass writes
-one per 32 (scan_mfma.hip scan_mfma2d_kernel GR = 64, api.hip mfma_pass).  Pinned down here at 257 and 320 queries, the counts that take
+one per 32 (scan_mfma.hip scan_mfma2d_kernel GR = 64, bruteforce.hip mfma_pass).  Pinned down here at 257 and 320 queries, the counts that take
 that pass: bases that are whole tiles, that end 1 .. 255 rows into a tile (on either side of a 32- and a 64-row group boundary) and that
 are smaller than one tile; the widening, which then re-scores 64-row groups; filters seen from a 64-row group (one allowed row, none,
 allowed rows in its second half only); the debug hook, which must go on returning 32-row maxima; and two shards on one device.
@@ -11,7 +11,7 @@ from conftest import SEED_BASE, SEED_QUERY
 
 pytestmark = pytest.mark.gpu
 D = 1152
-EPS = 2.8e-4   # api.hip mfma_pass -> launch_query_eps: |matrix-core score - exact-order score| <= EPS * |q| * max |x|
+EPS = 2.8e-4   # bruteforce.hip mfma_pass -> launch_query_eps: |matrix-core score - exact-order score| <= EPS * |q| * max |x|
 
 
 def check_both_modes(mse, orc, base, q, k):

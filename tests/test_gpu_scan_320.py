@@ -10,7 +10,7 @@ from conftest import SEED_BASE, SEED_QUERY
 
 pytestmark = pytest.mark.gpu
 D = 1152
-EPS = 2.8e-4   # api.hip mfma_pass -> launch_query_eps: |matrix-core score - exact-order score| <= EPS * |q| * max |x|
+EPS = 2.8e-4   # bruteforce.hip mfma_pass -> launch_query_eps: |matrix-core score - exact-order score| <= EPS * |q| * max |x|
 
 
 def subset_oracle(orc, base, mask, q, k):

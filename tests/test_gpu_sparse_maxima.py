@@ -1,4 +1,4 @@
-"""Thresholded group maxima of the 320-query pass (api.hip mfma_pass): every S-th 256-row tile is scanned first and gives
+"""Thresholded group maxima of the 320-query pass (bruteforce.hip mfma_pass): every S-th 256-row tile is scanned first and gives
 each query a threshold tau; the scan of the other tiles keeps a group maximum only above tau, in a per-query list.  The answers must be
 what the dense array of maxima gives: every case runs the search forced-sparse, forced-off and in the exact mode and wants equal ids and
 i64 scores, and the oracle's where it is computed (all of these bases are small enough).
