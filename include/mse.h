@@ -178,6 +178,59 @@ int mse_bruteforce_topk_filtered_f16(mse_searcher* s, const mse_filter* f, const
 int mse_bruteforce_topk_filtered_f16_dev(mse_searcher* s, const mse_filter* f, const void* queries_dev, size_t nq, size_t k,
                                          int mode, uint64_t id_offset, void* scores_dev, void* ids_dev);
 
+/* ---- grouped search: one result per group, collapsed on the device ("collapse" / "grouping search" of other engines) --------------
+ * The reference's small-scale server walks its ranked rows and keeps the first frame of each video only (src/main.rs:902-917:
+ * `seen_videos.insert(container)` drops every later frame of a container already seen), so that asking for k yields "however many
+ * distinct items were among the best k rows".  Here the same step runs on the device and returns k GROUPS.
+ * A grouping gives every row a u32 group id.  MSE_GROUP_NONE: the row is a group of its own.  Any other id must be below n_rows (number
+ * the groups densely, or use the row id of any member); an id that breaks this is an error at creation and nothing is made.  The array is
+ * copied to the device that is current on the calling thread (from_dev: the device the array lives on, which becomes current) and
+ * validated and counted there.  A grouping may be SHORTER than the base or index it is used on (rows at or past mse_groups_len are groups
+ * of their own -- the flat index grows under add), not longer, and not on another device: the rules of filters.
+ * Contract, met bit for bit by every path: for one query order all eligible rows (all rows, or the filter's allowed rows) by the
+ * search's own total order -- (score desc, id asc) for the f16 brute force, (distance desc, label asc) for the flat index.  A row is
+ * its group's REPRESENTATIVE if no earlier row has the same group.  The answer is the first k representatives with their own scores and
+ * ids, padded with INT64_MIN / MSE_ID_NONE (flat index: -FLT_MAX / -1) when fewer than k groups have an eligible row.  So: under a
+ * filter a group whose best row is disallowed is represented by its best ALLOWED row; a non-representative is never returned, not even
+ * to fill a short list; with every row MSE_GROUP_NONE the answer is the ungrouped answer.
+ * How: MSE_MODE_MFMA runs the ordinary (masked) search for k' = max(2k, k + 64) candidates and collapses the ranked
+ * list in one workgroup per query; a prefix of the total order collapses to a prefix of the collapsed order, so a query with k
+ * representatives -- or a list that came back short -- is answered exactly.  The others go on as a compact set with k' eightfold per
+ * round up to the selection limit (1984), and what is still short takes the DENSE path, as every query of MSE_MODE_EXACT does: over all scores of the query the best row of each group
+ * by integer atomics (bit-reproducible), every other grouped row out of the ranking, then the ordinary selection.  Dense-path scratch:
+ * the exact pass's 8 bytes per query per eligible row, plus 12 bytes (flat index: 8) per query per row of the GROUPING, bounded to 1 GiB
+ * per pass by taking fewer than 8 queries per pass once the grouping exceeds 1.1e7 rows.
+ * Rows whose own score saturates to INT64_MIN rank last in any case and tie with the rows the dense path takes out of the ranking; it
+ * completes a short list from them in id order with one workgroup per query, which is slow and meant for that degenerate case only.
+ * (The flat index takes rows out with the all-ones f32 pattern, a NaN below every other key that no dot product produces.) */
+#define MSE_GROUP_NONE 0xFFFFFFFFu
+typedef struct mse_groups mse_groups;
+mse_groups* mse_groups_from_host(const uint32_t* group_of, size_t n_rows);     /* copies; validated on the device */
+mse_groups* mse_groups_from_dev(const void* group_of_dev, size_t n_rows);      /* copies */
+void   mse_groups_free(mse_groups* g);
+size_t mse_groups_len(const mse_groups* g);
+size_t mse_groups_count(const mse_groups* g);   /* distinct ids + MSE_GROUP_NONE rows: the most results a search can return */
+/* f may be NULL (all rows).  Arguments, modes, limits (k <= 1984), padding and error order as the filtered calls; a null grouping is an
+ * error (after the searcher's checks), a grouping that does not fit is one after the filter's.  Groups are looked up by LOCAL row id:
+ * id_offset is added only on the way out.  Host calls run on the caller's searcher in every mode (not through the base's coalescer).
+ * The _dev form synchronises the searcher's stream (the prefix path decides on the host who goes on); on return the answers are complete. */
+int mse_bruteforce_topk_grouped_f16(mse_searcher* s, const mse_groups* g, const mse_filter* f, const uint16_t* queries,
+                                    size_t nq, size_t k, int mode, int64_t* scores, uint32_t* ids);
+int mse_bruteforce_topk_grouped_f16_dev(mse_searcher* s, const mse_groups* g, const mse_filter* f, const void* queries_dev,
+                                        size_t nq, size_t k, int mode, uint64_t id_offset, void* scores_dev, void* ids_dev);
+/* of the last grouped call on s: queries answered from the first candidate prefix, from a widened prefix, by the dense path */
+int mse_searcher_grouped_stats(const mse_searcher* s, uint32_t out[3]);
+/* Measurement hook (scripts/grouped_search_probe.py), as mse_searcher_scan_timing: out (or null) receives the HIP-event milliseconds
+ * accumulated by the grouped calls on s while the switch was on -- [0] the collapse kernel of the prefix rounds; of the dense passes
+ * [1] the score pass, [2] the group atomics and the demotion, [3] the selection with its collapse -- then sets the switch (0 off, 1 on,
+ * 2 on and reset).  While it is on every dense pass ends with a synchronisation. */
+int mse_searcher_grouped_timing(mse_searcher* s, int enable, double out[4]);
+/* Test hook, like mse_debug_select_topk: the collapse kernel alone over caller-supplied ranked id lists.
+ * ids [nq][n_list] best first, MSE_ID_NONE padding at the tail only, n_list <= 2048.  kept_pos [nq][k]: positions in the list of the
+ * first k representatives (MSE_ID_NONE padded); n_reps [nq]: representatives in the whole list.  Host arrays, synchronous. */
+int mse_debug_collapse_topk(mse_searcher* s, const mse_groups* g, const uint32_t* ids, size_t n_list, size_t nq, size_t k,
+                            uint32_t* kept_pos, uint32_t* n_reps);
+
 /* ---- cross-thread query coalescer ----------------------------------------------------------
  * The reference serves ONE query per request from many threads at once: `index.search(&query, k)` under a shared read
  * guard per HTTP request (src/main.rs:896-934,1043-1049), and a thread per core with its own Scratch, one search per
@@ -331,6 +384,11 @@ int mse_index_search(mse_index* idx, const float* queries, size_t nq, size_t k, 
  * rows are excluded), not longer; a null filter is an error.  Coalesced with the searches of the same filter object. */
 int mse_index_search_filtered(mse_index* idx, const mse_filter* f, const float* queries, size_t nq, size_t k,
                               float* distances, int64_t* labels);
+/* mse_index_search with one result per group of g (the grouped-search contract above, in the index's order (distance desc, label asc)):
+ * the query_index walk of src/main.rs:902-917 on the device.  f may be NULL.  g may be shorter than the index (rows added since are
+ * groups of their own), not longer.  Coalesced like every search: requests share a pass when filter AND grouping are the same objects. */
+int mse_index_search_grouped(mse_index* idx, const mse_groups* g, const mse_filter* f, const float* queries, size_t nq,
+                             size_t k, float* distances, int64_t* labels);
 int mse_index_stats(mse_index* idx, uint64_t out[6]);     /* as mse_dispatcher_stats */
 
 /* ---- product quantiser: diskann::vector::ProductQuantizer (vector.rs:308-406) ------------ */

@@ -68,8 +68,12 @@ namespace {
 // <= 8 f32 queries against every row in the stated FAISS order (scan_exact.hip, QF32), tournament, ids + f32 keys into
 // out_ids / out_keys ([nq][out_stride], ID_NONE-padded)
 // With a filter (non-empty, no longer than the index): its allowed rows only, through its ascending id list (bruteforce.hip exact_pass).
+// With a grouping: the dense path of the grouped search (bruteforce.hip grouped_dense_pass, on f32 keys) -- the best row of every group
+// by ONE 8-byte atomic max of (order-preserving key << 32) | ~row per row, which decides distance and label at once; every other
+// grouped row drops out of the ranking; the selection's k results are collapsed (a demoted row that fills a short list comes after its
+// own representative) and go to row dst_rows[j] (device; null: j) of the outputs.
 int index_pass_exact(mse_index* idx, const float* q32_dev, int nqp, int k, uint32_t* out_ids, float* out_keys, size_t out_stride,
-                     const mse_filter* f = nullptr) {
+                     const mse_filter* f = nullptr, const mse_groups* g = nullptr, const uint32_t* dst_rows = nullptr) {
     mse_searcher* s = idx->scratch;
     hipStream_t st = s->stream;
     const size_t d = idx->d, n = f ? f->count : idx->n;
@@ -78,11 +82,22 @@ int index_pass_exact(mse_index* idx, const float* q32_dev, int nqp, int k, uint3
     MSE_HIP_TRY(hipMemcpyAsync(s->q_stage.p, q32_dev, (size_t)nqp * d * 4, hipMemcpyDeviceToDevice, st));
     if (launch_scan_exact(idx->codes, n, (int)d, s->q_stage.p, nqp, true, nullptr, n, s->scores.as<float>(), s->n_cu, st,
                           f ? f->ids : nullptr)) return -1;
+    if (g && g->n_rows) {
+        if (s->grp_best.ensure((size_t)nqp * g->n_rows * 8)) return -1;
+        if (launch_dense_group_best(true, s->scores.p, n, n, f ? f->ids : nullptr, g->group_of, g->n_rows, nqp, s->grp_best.as<unsigned long long>(),
+                                    nullptr, nullptr, st)) return -1;
+    }
     if (s->sel_keys.ensure((size_t)nqp * k * 4)) return -1;
     uint32_t* sel = nullptr;
     LevelRef l0{KEY_F32, s->scores.p, n, 1, n, false, 0};
     if (descend(s, l0, nqp, k, &sel, s->sel_keys.p)) return -1;
     if (f && launch_map_positions(sel, (size_t)nqp * k, f->ids, st)) return -1;
+    if (g) {
+        if (s->grp_pos.ensure((size_t)nqp * k * 4) || s->grp_reps.ensure((size_t)nqp * 4)) return -1;
+        if (launch_collapse(sel, (size_t)k, (size_t)k, g->group_of, g->n_rows, k, nqp, s->grp_pos.as<uint32_t>(), s->grp_reps.as<uint32_t>(), st)) return -1;
+        return launch_collapse_gather(s->grp_pos.as<uint32_t>(), k, sel, (size_t)k, s->sel_keys.p, (size_t)k, 4, nqp, 0, dst_rows, nullptr, out_keys,
+                                      out_ids, out_stride, st);
+    }
     MSE_HIP_TRY(hipMemcpy2DAsync(out_ids, out_stride * 4, sel, (size_t)k * 4, (size_t)k * 4, nqp, hipMemcpyDeviceToDevice, st));
     MSE_HIP_TRY(hipMemcpy2DAsync(out_keys, out_stride * 4, s->sel_keys.p, (size_t)k * 4, (size_t)k * 4, nqp, hipMemcpyDeviceToDevice, st));
     return 0;
@@ -192,6 +207,49 @@ int index_pass_mfma(mse_index* idx, const float* q32_dev, int nqp, int k, uint32
     return 0;
 }
 
+// The grouped search over the `total` gathered queries (idx->q32), k results each into ids_dev / keys_dev [total][k]: the sequence of
+// bruteforce.hip grouped_topk_dev on f32 keys.  The exact regime holds every distance, so it takes the dense path at once; the
+// matrix-core regime runs the rounds of the prefix path (grouped_prefix_drive) and sends what they leave to the dense path.
+int index_run_grouped(mse_index* idx, const mse_groups* g, const mse_filter* f, size_t total, int k, bool mfma, uint32_t* ids_dev, float* keys_dev) {
+    mse_searcher* s = idx->scratch;
+    hipStream_t st = s->stream;
+    const size_t d = idx->d;
+    const float* q32 = idx->q32.as<float>();
+    const size_t dtile = (size_t)dense_pass_queries(g->n_rows, 8);
+    s->last_grouped[0] = s->last_grouped[1] = s->last_grouped[2] = 0;
+    if (!mfma) {
+        for (size_t q0 = 0; q0 < total; q0 += dtile) {
+            const int m = (int)std::min(dtile, total - q0);
+            if (index_pass_exact(idx, q32 + q0 * d, m, k, ids_dev + q0 * k, keys_dev + q0 * k, (size_t)k, f, g)) return -1;
+        }
+        s->last_grouped[2] = (uint32_t)total;
+        return 0;
+    }
+    const size_t tile = (size_t)mfma_query_tile((int)d);
+    auto round = [&](const void* qv, size_t nq, size_t kp, const std::vector<uint32_t>* dst, std::vector<uint32_t>* open,
+                     std::vector<uint32_t>* reps) -> int {
+        const float* qs = reinterpret_cast<const float*>(qv);
+        if (s->grp_ids.ensure(nq * kp * 4) || s->grp_keys.ensure(nq * kp * 4)) return -1;
+        for (size_t q0 = 0; q0 < nq; q0 += tile) {
+            const int m = (int)std::min(tile, nq - q0);
+            if (index_pass_mfma(idx, qs + q0 * d, m, (int)kp, s->grp_ids.as<uint32_t>() + q0 * kp, s->grp_keys.as<float>() + q0 * kp, kp, f)) return -1;
+        }
+        return grouped_collapse_round(s, g, 4, nq, kp, k, 0, dst, keys_dev, ids_dev, (size_t)k, open, reps);
+    };
+    auto dense = [&](const void* qv, size_t nr, const std::vector<uint32_t>& dst) -> int {
+        const float* qs = reinterpret_cast<const float*>(qv);
+        if (s->grp_idx.ensure(8 * 4)) return -1;
+        for (size_t q0 = 0; q0 < nr; q0 += dtile) {
+            const int m = (int)std::min(dtile, nr - q0);
+            MSE_HIP_TRY(hipMemcpyAsync(s->grp_idx.p, dst.data() + q0, (size_t)m * 4, hipMemcpyHostToDevice, st));
+            if (index_pass_exact(idx, qs + q0 * d, m, k, ids_dev, keys_dev, (size_t)k, f, g, s->grp_idx.as<uint32_t>())) return -1;
+            MSE_HIP_TRY(hipStreamSynchronize(st));   // the indices are replaced by the next pass
+        }
+        return 0;
+    };
+    return grouped_prefix_drive(s, q32, d * 4, total, (size_t)k, round, dense);
+}
+
 // one engine call for a group of requests (worker thread; every caller of the group holds the shared lock)
 int index_run_group(mse_index* idx, DispatchReq* const* reqs, size_t n_req) {
     mse_searcher* s = idx->scratch;
@@ -200,6 +258,7 @@ int index_run_group(mse_index* idx, DispatchReq* const* reqs, size_t n_req) {
     size_t total = 0, kmax = 0;
     for (size_t i = 0; i < n_req; i++) { total += reqs[i]->nq; kmax = std::max(kmax, reqs[i]->k); }
     const mse_filter* f = static_cast<const mse_filter*>(reqs[0]->aux0);   // the group's filter (its key, index_run_batch), or null
+    const mse_groups* grp = static_cast<const mse_groups*>(reqs[0]->aux1);   // ... and its grouping, or null
     if (total == 0 || kmax == 0 || n == 0 || (f && f->count == 0)) return 0;   // outputs were pre-filled with "nothing found"
     const size_t in_bytes = total * d * 4, out_bytes = total * kmax * 8;
     if (idx->pin.ensure(std::max(in_bytes, out_bytes), (size_t)1 << 20)) return -1;
@@ -215,7 +274,8 @@ int index_run_group(mse_index* idx, DispatchReq* const* reqs, size_t n_req) {
     // (filtered: the id-list pass on the sparse side of the crossover, bruteforce.hip filter_sparse)
     const bool mfma = (total > 8 || n >= ((size_t)1 << 22)) && !(f && filter_sparse(&idx->view, f, total));
     const size_t tile = mfma ? (size_t)mfma_query_tile((int)d) : 8;
-    for (size_t q0 = 0; q0 < total; q0 += tile) {
+    if (grp && index_run_grouped(idx, grp, f, total, (int)kmax, mfma, ids_dev, keys_dev)) return -1;
+    for (size_t q0 = 0; !grp && q0 < total; q0 += tile) {
         const int m = (int)std::min(tile, total - q0);
         const int rc = mfma ? index_pass_mfma(idx, idx->q32.as<float>() + q0 * d, m, (int)kmax, ids_dev + q0 * kmax, keys_dev + q0 * kmax, kmax, f)
                             : index_pass_exact(idx, idx->q32.as<float>() + q0 * d, m, (int)kmax, ids_dev + q0 * kmax, keys_dev + q0 * kmax, kmax, f);
@@ -245,15 +305,16 @@ void index_run_batch(mse_index* idx, std::vector<DispatchReq*>& batch) {
         idx->retried_alone += run_shared(group, [idx](DispatchReq* const* reqs, size_t n) { return index_run_group(idx, reqs, n); });
     };
     bool filtered = false;
-    for (const DispatchReq* r : batch) filtered = filtered || r->aux0;
-    if (!filtered) { run(batch); return; }   // unfiltered requests only: one group, as always
-    // requests share a pass only with requests of the same filter object (null = unfiltered)
-    for_each_shared_group(batch, [](const DispatchReq& a, const DispatchReq& b) { return a.aux0 == b.aux0; }, run);
+    for (const DispatchReq* r : batch) filtered = filtered || r->aux0 || r->aux1;
+    if (!filtered) { run(batch); return; }   // unfiltered, ungrouped requests only: one group, as always
+    // requests share a pass only with requests of the same filter object (null = unfiltered) and the same grouping object (null = ungrouped)
+    for_each_shared_group(batch, [](const DispatchReq& a, const DispatchReq& b) { return a.aux0 == b.aux0 && a.aux1 == b.aux1; }, run);
 }
 
 }  // namespace
 
-static int index_search(mse_index* idx, const mse_filter* f, const float* queries, size_t nq, size_t k, float* distances, int64_t* labels) {
+static int index_search(mse_index* idx, const mse_filter* f, const float* queries, size_t nq, size_t k, float* distances, int64_t* labels,
+                        const mse_groups* g = nullptr) {
     if (!idx) return fail("null index");
     if (nq == 0 || k == 0) return 0;
     if (!queries || !distances || !labels) return fail("null argument");
@@ -262,9 +323,10 @@ static int index_search(mse_index* idx, const mse_filter* f, const float* querie
     // with the searches of the same filter object: DispatchReq::aux0 is the group key)
     idx->rw.lock_shared();
     if (f && check_filter(&idx->view, f)) { idx->rw.unlock_shared(); return -1; }   // rows past the filter are excluded; add only grows
+    if (g && check_groups(&idx->view, g)) { idx->rw.unlock_shared(); return -1; }   // rows past the grouping are groups of their own
     for (size_t i = 0; i < nq * k; i++) { distances[i] = -FLT_MAX; labels[i] = -1; }
     DispatchReq r;
-    r.queries = queries; r.nq = nq; r.k = k; r.out_a = distances; r.out_b = labels; r.aux0 = f;
+    r.queries = queries; r.nq = nq; r.k = k; r.out_a = distances; r.out_b = labels; r.aux0 = f; r.aux1 = g;
     const int rc = idx->co->submit(r);
     idx->rw.unlock_shared();
     return rc;
@@ -351,6 +413,13 @@ int mse_index_search_filtered(mse_index* idx, const mse_filter* f, const float* 
     if (!idx) return fail("null index");
     if (!f) return fail("null filter");
     return index_search(idx, f, queries, nq, k, distances, labels);
+}
+
+int mse_index_search_grouped(mse_index* idx, const mse_groups* g, const mse_filter* f, const float* queries, size_t nq, size_t k, float* distances,
+                             int64_t* labels) {
+    if (!idx) return fail("null index");
+    if (!g) return fail("null grouping");
+    return index_search(idx, f, queries, nq, k, distances, labels, g);
 }
 
 int mse_index_stats(mse_index* idx, uint64_t out[6]) {

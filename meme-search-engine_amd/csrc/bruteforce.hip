@@ -39,8 +39,7 @@ int exact_pass_list(mse_searcher* s, int nq_pass, int k, uint64_t id_offset, int
 // s->q_stage.  With a filter (non-empty, no longer than the base): the filter's allowed rows only, scanned through its ascending id list;
 // level 0 then holds list positions, so an excluded row is absent -- not merely low: an allowed row whose score saturates to INT64_MIN
 // still ranks -- and (score desc, position asc) is (score desc, id asc).  The selected positions are mapped back to row ids before the finish.
-static int exact_pass(mse_searcher* s, const mse_filter* f, const uint16_t* q_dev, const uint32_t* pick, int nq_pass, int k, uint64_t id_offset,
-                      int64_t* out_scores, uint32_t* out_ids, size_t out_stride) {
+static int stage_exact_queries(mse_searcher* s, const uint16_t* q_dev, const uint32_t* pick, int nq_pass) {
     const size_t row = s->base->d * 2;
     if (s->q_stage.ensure(8 * row)) return -1;
     MSE_HIP_TRY(hipMemsetAsync(s->q_stage.p, 0, 8 * row, s->stream));
@@ -48,6 +47,12 @@ static int exact_pass(mse_searcher* s, const mse_filter* f, const uint16_t* q_de
     for (int j = 0; pick && j < nq_pass; j++)
         MSE_HIP_TRY(hipMemcpyAsync(s->q_stage.as<char>() + j * row, reinterpret_cast<const char*>(q_dev) + pick[j] * row, row,
                                    hipMemcpyDeviceToDevice, s->stream));
+    return 0;
+}
+
+static int exact_pass(mse_searcher* s, const mse_filter* f, const uint16_t* q_dev, const uint32_t* pick, int nq_pass, int k, uint64_t id_offset,
+                      int64_t* out_scores, uint32_t* out_ids, size_t out_stride) {
+    if (stage_exact_queries(s, q_dev, pick, nq_pass)) return -1;
     return exact_pass_list(s, nq_pass, k, id_offset, out_scores, out_ids, out_stride, f ? f->ids : nullptr, f ? f->count : s->base->n, nullptr);
 }
 
@@ -427,11 +432,12 @@ static mse_dispatcher* base_dispatcher(const mse_base* b) {
 // a searcher the brute-force search can run on: it exists and has rows behind it (a scratch searcher has none)
 static int check_searcher(const mse_searcher* s) { return !s ? fail("null searcher") : !s->base ? fail("searcher has no base") : 0; }
 
-// The one validation order of the four entry points, f = null being the unfiltered search: -1 with the error set, 0 = nothing to do,
+// The one validation order of the entry points, f = null being the unfiltered and g = null the ungrouped search: -1 with the error set, 0 = nothing to do,
 // 1 = go on.  (The filter before the counts: a filter that does not fit is an error even of a call that asks for nothing.)
-static int check_call(const mse_searcher* s, const mse_filter* f, size_t nq, size_t k, int mode) {
+static int check_call(const mse_searcher* s, const mse_filter* f, size_t nq, size_t k, int mode, const mse_groups* g = nullptr) {
     if (check_searcher(s)) return -1;
     if (f && check_filter(s->base, f)) return -1;
+    if (g && check_groups(s->base, g)) return -1;
     if (nq == 0 || k == 0) return 0;
     if (k > (size_t)TOPK_KMAX - 64) return fail("k too large (max 1984)");
     if (mode != MSE_MODE_AUTO && mode != MSE_MODE_EXACT && mode != MSE_MODE_MFMA) return fail("unknown mode");
@@ -487,6 +493,216 @@ static int bruteforce_topk_host(mse_searcher* s, const mse_filter* f, const uint
     return 0;
 }
 
+// ---- grouped search: one result per group (include/mse.h mse_groups) ------------------------------------------------
+// a grouped entry point that was handed no grouping: an error of its own, in the grouping's place of the validation order
+static int null_groups(const mse_searcher* s) { return check_searcher(s) ? -1 : fail("null grouping"); }
+
+// The dense path for one pass of <= dense_pass_queries queries (rows pick[..] of q_dev, or its first nq_pass): the exact pass's scan
+// leaves every eligible row's score in level 0; the group step (group.hip) finds each group's best row and drops every other grouped
+// row to INT64_MIN; the tournament then ranks representatives before everything it has to, and the collapse of its k results removes
+// the demoted rows that filled a short list -- each comes after its own representative, which has the higher score or the lower id.
+// Under a filter level 0 holds list positions: the group step maps them through the filter's ids.  Results to row dst_rows[j] (device;
+// null: j) of the outputs.
+// Representatives whose own score saturates to INT64_MIN tie with the demoted rows and can be crowded off the list: a short list is
+// completed from them afterwards (group.hip dense_complete_kernel).
+static int grouped_dense_pass(mse_searcher* s, const mse_groups* g, const mse_filter* f, const uint16_t* q_dev, const uint32_t* pick, int nq_pass,
+                              int k, uint64_t id_offset, const uint32_t* dst_rows, int64_t* out_scores, uint32_t* out_ids, size_t out_stride) {
+    const mse_base* b = s->base;
+    hipStream_t st = s->stream;
+    const uint32_t* list = f ? f->ids : nullptr;
+    const size_t n = f ? f->count : b->n;
+    if (stage_exact_queries(s, q_dev, pick, nq_pass)) return -1;
+    if (s->scores.ensure((size_t)nq_pass * n * 8)) return -1;
+    const bool tm = s->grp_timing;
+    if (tm) MSE_HIP_TRY(hipEventRecord(s->grp_ev[0], st));
+    if (launch_scan_exact(b->dev, n, (int)b->d, s->q_stage.p, nq_pass, false, s->scores.as<int64_t>(), n, nullptr, s->n_cu, st, list)) return -1;
+    if (tm) MSE_HIP_TRY(hipEventRecord(s->grp_ev[1], st));
+    unsigned long long* best = nullptr;
+    uint32_t *best_id = nullptr, *n_sat = nullptr;
+    if (g->n_rows) {   // group table: best keys [nq][g_len] u64 | best ids [nq][g_len] u32 | saturated representatives [nq] u32
+        if (s->grp_best.ensure((size_t)nq_pass * g->n_rows * 12 + (size_t)nq_pass * 4)) return -1;
+        best = s->grp_best.as<unsigned long long>();
+        best_id = reinterpret_cast<uint32_t*>(best + (size_t)nq_pass * g->n_rows);
+        n_sat = best_id + (size_t)nq_pass * g->n_rows;
+        if (launch_dense_group_best(false, s->scores.p, n, n, list, g->group_of, g->n_rows, nq_pass, best, best_id, n_sat, st)) return -1;
+    }
+    if (tm) MSE_HIP_TRY(hipEventRecord(s->grp_ev[2], st));
+    if (s->sel_keys.ensure((size_t)nq_pass * k * 8) || s->grp_pos.ensure((size_t)nq_pass * k * 4) || s->grp_reps.ensure((size_t)nq_pass * 4)) return -1;
+    uint32_t* sel = nullptr;
+    LevelRef l0{KEY_I64, s->scores.p, n, 1, n, false, 0};
+    if (descend(s, l0, nq_pass, k, &sel, s->sel_keys.p)) return -1;
+    if (list && launch_map_positions(sel, (size_t)nq_pass * k, list, st)) return -1;
+    uint32_t *kept = s->grp_pos.as<uint32_t>(), *reps = s->grp_reps.as<uint32_t>();
+    if (launch_collapse(sel, (size_t)k, (size_t)k, g->group_of, g->n_rows, k, nq_pass, kept, reps, st)) return -1;
+    if (launch_collapse_gather(kept, k, sel, (size_t)k, s->sel_keys.p, (size_t)k, 8, nq_pass, id_offset, dst_rows, nullptr, out_scores, out_ids,
+                               out_stride, st)) return -1;
+    if (launch_dense_complete(s->scores.as<int64_t>(), n, n, list, g->group_of, g->n_rows, best_id, n_sat, kept, reps, s->sel_keys.as<int64_t>(), k,
+                              nq_pass, id_offset, dst_rows, out_scores, out_ids, out_stride, st)) return -1;
+    if (tm) {
+        MSE_HIP_TRY(hipEventRecord(s->grp_ev[3], st));
+        MSE_HIP_TRY(hipEventSynchronize(s->grp_ev[3]));
+        for (int i = 0; i < 3; i++) {
+            float ms = 0.0f;
+            if (hipEventElapsedTime(&ms, s->grp_ev[i], s->grp_ev[i + 1]) == hipSuccess) s->grp_ms[i + 1] += ms;
+        }
+    }
+    return 0;
+}
+
+// the dense path for the nq queries at q_dev, pass by pass; results to rows dst[..] of the outputs (null: in place)
+static int grouped_dense(mse_searcher* s, const mse_groups* g, const mse_filter* f, const uint16_t* q_dev, const std::vector<uint32_t>* dst, size_t nq,
+                         int k, uint64_t id_offset, int64_t* out_scores, uint32_t* out_ids) {
+    const size_t tile = (size_t)dense_pass_queries(g->n_rows, 12);
+    if (dst && s->grp_idx.ensure(8 * 4)) return -1;
+    for (size_t q0 = 0; q0 < nq; q0 += tile) {
+        const int nqp = (int)std::min(tile, nq - q0);
+        const uint16_t* qs = q_dev + q0 * s->base->d;
+        if (!dst) {
+            if (grouped_dense_pass(s, g, f, qs, nullptr, nqp, k, id_offset, nullptr, out_scores + q0 * k, out_ids + q0 * k, (size_t)k)) return -1;
+            continue;
+        }
+        MSE_HIP_TRY(hipMemcpyAsync(s->grp_idx.p, dst->data() + q0, (size_t)nqp * 4, hipMemcpyHostToDevice, s->stream));
+        if (grouped_dense_pass(s, g, f, qs, nullptr, nqp, k, id_offset, s->grp_idx.as<uint32_t>(), out_scores, out_ids, (size_t)k)) return -1;
+        MSE_HIP_TRY(hipStreamSynchronize(s->stream));   // the indices are replaced by the next pass
+    }
+    return 0;
+}
+
+// The second half of a round of the prefix path (the first: an ordinary search for kp candidates per query into s->grp_ids [nq][kp] and
+// s->grp_keys, payload key_bytes 8 = i64 or 4 = f32): the collapse of every list, and -- for the queries that are done: k representatives,
+// or a list that came back short, i.e. every eligible row was seen -- the first k representatives into row dst[q] (null: q) of the
+// outputs.  A prefix of the total order collapses to a prefix of the collapsed order, so these answers are exact.  open_out: the
+// queries that are not done; open_reps: how many representatives each of them has so far.  Ends with the stream drained.
+int grouped_collapse_round(mse_searcher* s, const mse_groups* g, int key_bytes, size_t nq, size_t kp, int k, uint64_t id_offset,
+                           const std::vector<uint32_t>* dst, void* out_keys, uint32_t* out_ids, size_t out_stride, std::vector<uint32_t>* open_out,
+                           std::vector<uint32_t>* open_reps) {
+    hipStream_t st = s->stream;
+    if (s->grp_pos.ensure(nq * k * 4) || s->grp_reps.ensure(nq * 4) || s->grp_idx.ensure(nq * 5) || s->grp_pin.ensure(nq * 8, 4096)) return -1;
+    uint32_t* ids = s->grp_ids.as<uint32_t>();
+    if (s->grp_timing) MSE_HIP_TRY(hipEventRecord(s->grp_ev[0], st));
+    if (launch_collapse(ids, kp, kp, g->group_of, g->n_rows, k, (int)nq, s->grp_pos.as<uint32_t>(), s->grp_reps.as<uint32_t>(), st)) return -1;
+    if (s->grp_timing) MSE_HIP_TRY(hipEventRecord(s->grp_ev[1], st));
+    uint32_t* reps_h = s->grp_pin.as<uint32_t>();
+    uint32_t* tail_h = reps_h + nq;
+    MSE_HIP_TRY(hipMemcpyAsync(reps_h, s->grp_reps.p, nq * 4, hipMemcpyDeviceToHost, st));
+    MSE_HIP_TRY(hipMemcpy2DAsync(tail_h, 4, ids + (kp - 1), kp * 4, 4, nq, hipMemcpyDeviceToHost, st));
+    MSE_HIP_TRY(hipStreamSynchronize(st));
+    if (s->grp_timing) {
+        float ms = 0.0f;
+        if (hipEventElapsedTime(&ms, s->grp_ev[0], s->grp_ev[1]) == hipSuccess) s->grp_ms[0] += ms;
+    }
+    std::vector<uint8_t> take(nq, 0);
+    for (size_t i = 0; i < nq; i++) {
+        if (reps_h[i] >= (uint32_t)k || tail_h[i] == ID_NONE) take[i] = 1;
+        else { open_out->push_back((uint32_t)i); open_reps->push_back(reps_h[i]); }
+    }
+    uint32_t* dst_dev = s->grp_idx.as<uint32_t>();
+    uint8_t* take_dev = reinterpret_cast<uint8_t*>(dst_dev + nq);
+    if (dst) MSE_HIP_TRY(hipMemcpyAsync(dst_dev, dst->data(), nq * 4, hipMemcpyHostToDevice, st));
+    MSE_HIP_TRY(hipMemcpyAsync(take_dev, take.data(), nq, hipMemcpyHostToDevice, st));
+    if (launch_collapse_gather(s->grp_pos.as<uint32_t>(), k, ids, kp, s->grp_keys.p, kp, key_bytes, (int)nq, id_offset, dst ? dst_dev : nullptr,
+                               take_dev, out_keys, out_ids, out_stride, st)) return -1;
+    MSE_HIP_TRY(hipStreamSynchronize(st));   // `take` is a stack-owned source
+    return 0;
+}
+
+// One round of the brute force's prefix path: the ordinary (masked) matrix-core search of the nq queries at qs with kp candidates each.
+static int grouped_prefix_round(mse_searcher* s, const mse_groups* g, const mse_filter* f, const uint16_t* qs, size_t nq, size_t kp, int k,
+                                uint64_t id_offset, const std::vector<uint32_t>* dst, int64_t* out_scores, uint32_t* out_ids,
+                                std::vector<uint32_t>* open_out, std::vector<uint32_t>* open_reps) {
+    if (s->grp_ids.ensure(nq * kp * 4) || s->grp_keys.ensure(nq * kp * 8)) return -1;
+    if (bruteforce_topk_dev(s, f, qs, nq, kp, MSE_MODE_MFMA, 0, s->grp_keys.p, s->grp_ids.p)) return -1;
+    return grouped_collapse_round(s, g, 8, nq, kp, k, id_offset, dst, out_scores, out_ids, (size_t)k, open_out, open_reps);
+}
+
+// The prefix path's rounds.  k' starts at max(2k, k + 64) -- a grouping of mean size 2 or less is done there -- and grows eightfold per
+// round up to the selection limit (1984); after each round the queries still short are carried on as a COMPACT set (rows of row_bytes,
+// a multiple of 16), so a longer prefix is paid for by the queries that need it only.  Eightfold: a round costs a pass over the rows plus
+// a re-score that grows with k', so few rounds.  A query leaves for the dense path when the last round left it open -- or EARLY, when
+// its r representatives among k' candidates say that not even 1984 will do: new groups only get rarer down the ranking, so k' x k / r
+// candidates is the least it needs (a cost heuristic only: either path gives the same answer; measured at 1e7 rows, a query in a
+// 99.9 % group otherwise paid three useless rounds, the last of them dearer than its dense pass).  The dense set is gathered from the
+// ORIGINAL queries -- a query's output row is its index there -- and handed to `dense` with those rows.
+int grouped_prefix_drive(mse_searcher* s, const void* q, size_t row_bytes, size_t nq, size_t k, const GroupedRound& round, const GroupedDense& dense) {
+    const size_t k_top = (size_t)TOPK_KMAX - 64;
+    size_t kp = std::min(k_top, std::max(2 * k, k + 64));
+    const void* cur = q;
+    size_t n_cur = nq;
+    std::vector<uint32_t> rows;         // output row of each query of the current set (empty: its own index)
+    std::vector<uint32_t> dense_rows;   // the queries for the dense path
+    for (int r = 0;; r++) {
+        std::vector<uint32_t> open, reps, go;
+        if (round(cur, n_cur, kp, rows.empty() ? nullptr : &rows, &open, &reps)) return -1;
+        s->last_grouped[r ? 1 : 0] += (uint32_t)(n_cur - open.size());
+        for (size_t j = 0; j < open.size(); j++) {
+            if (kp >= k_top || (uint64_t)kp * k > (uint64_t)k_top * std::max<uint32_t>(reps[j], 1)) dense_rows.push_back(rows.empty() ? open[j] : rows[open[j]]);
+            else go.push_back(open[j]);
+        }
+        if (go.empty()) break;
+        const size_t nb = go.size();
+        DevBuf& set = (r & 1) ? s->grp_q2 : s->grp_q;   // (the current set is read while the next is written)
+        if (set.ensure(nb * row_bytes) || s->grp_idx.ensure(nb * 4)) return -1;
+        MSE_HIP_TRY(hipMemcpyAsync(s->grp_idx.p, go.data(), nb * 4, hipMemcpyHostToDevice, s->stream));
+        if (launch_gather_rows16(cur, row_bytes, s->grp_idx.as<uint32_t>(), (int)nb, set.p, s->stream)) return -1;
+        MSE_HIP_TRY(hipStreamSynchronize(s->stream));   // `go` is a stack-owned source, and grp_idx is the next round's
+        for (uint32_t& j : go) j = rows.empty() ? j : rows[j];
+        rows.swap(go);
+        cur = set.p;
+        n_cur = nb;
+        kp = std::min(k_top, kp * 8);
+    }
+    if (dense_rows.empty()) return 0;
+    const size_t nd = dense_rows.size();
+    s->last_grouped[2] = (uint32_t)nd;
+    if (s->grp_q.ensure(nd * row_bytes) || s->grp_idx.ensure(nd * 4)) return -1;
+    MSE_HIP_TRY(hipMemcpyAsync(s->grp_idx.p, dense_rows.data(), nd * 4, hipMemcpyHostToDevice, s->stream));
+    if (launch_gather_rows16(q, row_bytes, s->grp_idx.as<uint32_t>(), (int)nd, s->grp_q.p, s->stream)) return -1;
+    MSE_HIP_TRY(hipStreamSynchronize(s->stream));
+    return dense(s->grp_q.p, nd, dense_rows);
+}
+
+// The device form of the grouped search.  MODE_EXACT: the exact pass holds every score, so the dense path at once.  MODE_MFMA: the
+// prefix path (grouped_prefix_drive), the dense path for what it leaves.  MODE_AUTO: bruteforce_auto_mode's direct rule.
+int grouped_topk_dev(mse_searcher* s, const mse_groups* g, const mse_filter* f, const void* queries_dev, size_t nq, size_t k, int mode,
+                     uint64_t id_offset, void* scores_dev, void* ids_dev) {
+    if (const int go = check_call(s, f, nq, k, mode, g); go <= 0) return go;
+    const mse_base* b = s->base;
+    int64_t* out_scores = reinterpret_cast<int64_t*>(scores_dev);
+    uint32_t* out_ids = reinterpret_cast<uint32_t*>(ids_dev);
+    const uint16_t* q = reinterpret_cast<const uint16_t*>(queries_dev);
+    s->last_grouped[0] = s->last_grouped[1] = s->last_grouped[2] = 0;
+    const size_t eligible = f ? f->count : b->n;
+    if (eligible == 0) return fill_empty(s, nq, k, out_scores, out_ids);
+    if (mode == MSE_MODE_AUTO) mode = bruteforce_auto_mode(b, f, nq, false);
+    if (mode == MSE_MODE_EXACT) {
+        s->last_grouped[2] = (uint32_t)nq;
+        return grouped_dense(s, g, f, q, nullptr, nq, (int)k, id_offset, out_scores, out_ids);
+    }
+    return grouped_prefix_drive(
+        s, q, b->d * 2, nq, k,
+        [&](const void* qs, size_t n, size_t kp, const std::vector<uint32_t>* dst, std::vector<uint32_t>* open, std::vector<uint32_t>* reps) {
+            return grouped_prefix_round(s, g, f, reinterpret_cast<const uint16_t*>(qs), n, kp, (int)k, id_offset, dst, out_scores, out_ids, open, reps);
+        },
+        [&](const void* qs, size_t n, const std::vector<uint32_t>& dst) {
+            return grouped_dense(s, g, f, reinterpret_cast<const uint16_t*>(qs), &dst, n, (int)k, id_offset, out_scores, out_ids);
+        });
+}
+
+// The host form: on the caller's searcher in every mode (the base's coalescer groups requests by filter only).
+static int grouped_topk_host(mse_searcher* s, const mse_groups* g, const mse_filter* f, const uint16_t* queries, size_t nq, size_t k, int mode,
+                             int64_t* scores, uint32_t* ids) {
+    if (const int go = check_call(s, f, nq, k, mode, g); go <= 0) return go;
+    const size_t d = s->base->d;
+    DevBuf qd;
+    if (qd.ensure(nq * d * 2) || s->out_scores.ensure(nq * k * 8) || s->out_ids.ensure(nq * k * 4)) return -1;
+    MSE_HIP_TRY(hipMemcpyAsync(qd.p, queries, nq * d * 2, hipMemcpyHostToDevice, s->stream));
+    if (grouped_topk_dev(s, g, f, qd.p, nq, k, mode, 0, s->out_scores.p, s->out_ids.p)) return -1;
+    MSE_HIP_TRY(hipMemcpyAsync(scores, s->out_scores.p, nq * k * 8, hipMemcpyDeviceToHost, s->stream));
+    MSE_HIP_TRY(hipMemcpyAsync(ids, s->out_ids.p, nq * k * 4, hipMemcpyDeviceToHost, s->stream));
+    MSE_HIP_TRY(hipStreamSynchronize(s->stream));
+    return 0;
+}
+
 }  // namespace mse
 
 using namespace mse;
@@ -511,6 +727,18 @@ int mse_bruteforce_topk_filtered_f16(mse_searcher* s, const mse_filter* f, const
                                      int64_t* scores, uint32_t* ids) {
     if (!f) return null_filter(s);
     return bruteforce_topk_host(s, f, queries, nq, k, mode, scores, ids);
+}
+
+int mse_bruteforce_topk_grouped_f16(mse_searcher* s, const mse_groups* g, const mse_filter* f, const uint16_t* queries, size_t nq, size_t k, int mode,
+                                    int64_t* scores, uint32_t* ids) {
+    if (!g) return null_groups(s);
+    return grouped_topk_host(s, g, f, queries, nq, k, mode, scores, ids);
+}
+
+int mse_bruteforce_topk_grouped_f16_dev(mse_searcher* s, const mse_groups* g, const mse_filter* f, const void* queries_dev, size_t nq, size_t k,
+                                        int mode, uint64_t id_offset, void* scores_dev, void* ids_dev) {
+    if (!g) return null_groups(s);
+    return grouped_topk_dev(s, g, f, queries_dev, nq, k, mode, id_offset, scores_dev, ids_dev);
 }
 
 int mse_bruteforce_scores_f16(mse_searcher* s, const uint16_t* query, int64_t* scores) {

@@ -1,0 +1,135 @@
+// C ABI (include/mse.h): row groupings as objects, and the collapse kernel's test hook.  The kernels are in group.hip; the searches that
+// take a grouping are in bruteforce.hip and api_pq.hip.
+#include "../../include/mse.h"
+#include "runtime.h"
+#include <algorithm>
+#include <new>
+
+namespace mse {
+
+int check_groups(const mse_base* b, const mse_groups* g) {
+    if (!g) return fail("null grouping");
+    if (g->n_rows > b->n) return fail("grouping is longer than the base (" + std::to_string(g->n_rows) + " > " + std::to_string(b->n) + " rows)");
+    if (g->device != b->device) return fail("grouping was made on another device than the base's");   // no silent copy
+    return 0;
+}
+
+// The dense path keeps, per query of a pass, one table entry per row of the grouping: at most 1 GiB of it per pass, so fewer than the
+// exact pass's 8 queries once the grouping is long (12-byte entries: 8 queries up to 1.1e7 rows, one query from 9e7 rows on).
+int dense_pass_queries(size_t g_len, size_t bytes) {
+    const size_t fit = ((size_t)1 << 30) / (std::max<size_t>(g_len, 1) * bytes);
+    return (int)std::min<size_t>(8, std::max<size_t>(fit, 1));
+}
+
+}  // namespace mse
+
+using namespace mse;
+
+// validation, count and adoption of a device copy of the array (freed on failure)
+static mse_groups* groups_finish(uint32_t* dev, size_t n_rows, int device) {
+    DevBuf scratch;
+    unsigned long long stats[3] = {0, 0, 0};
+    const size_t n_words = (n_rows + 31) / 32;
+    bool ok = scratch.ensure(24 + std::max<size_t>(n_words, 1) * 4) == 0;
+    if (ok && hipMemsetAsync(scratch.p, 0, 24 + n_words * 4, nullptr) != hipSuccess) { ok = false; fail("groups: clearing the scratch failed"); }
+    unsigned long long* stats_dev = scratch.as<unsigned long long>();
+    uint32_t* present = reinterpret_cast<uint32_t*>(scratch.as<char>() + 24);
+    ok = ok && launch_groups_validate(dev, n_rows, present, stats_dev, nullptr) == 0 && launch_groups_popcount(present, n_words, stats_dev, nullptr) == 0;
+    if (ok && hipMemcpy(stats, stats_dev, 24, hipMemcpyDeviceToHost) != hipSuccess) { ok = false; fail("groups: the validation pass failed"); }
+    if (ok && stats[0] > n_rows) {
+        ok = false;
+        fail("groups: group id " + std::to_string(stats[0] - 1) + " is not below n_rows " + std::to_string(n_rows) + " (and is not the no-group id)");
+    }
+    mse_groups* g = ok ? new (std::nothrow) mse_groups() : nullptr;
+    if (ok && !g) fail("out of host memory");
+    if (!g) { (void)hipFree(dev); return nullptr; }
+    g->device = device; g->n_rows = n_rows; g->group_of = dev;
+    g->count = (size_t)(stats[1] + stats[2]);
+    return g;
+}
+
+static uint32_t* groups_alloc(size_t n_rows, int* device) {
+    if (n_rows > 0xFFFFFFFEull) { fail("row ids are u32: too many rows"); return nullptr; }
+    if (hipGetDevice(device) != hipSuccess) { (void)hipGetLastError(); fail("groups: no HIP device"); return nullptr; }
+    uint32_t* dev = nullptr;
+    if (hipMalloc((void**)&dev, std::max<size_t>(n_rows, 1) * 4) != hipSuccess) { (void)hipGetLastError(); fail("hipMalloc failed for the grouping"); return nullptr; }
+    return dev;
+}
+
+extern "C" {
+
+mse_groups* mse_groups_from_host(const uint32_t* group_of, size_t n_rows) {
+    if (!group_of && n_rows) { fail("groups: null array"); return nullptr; }
+    int device = 0;
+    uint32_t* dev = groups_alloc(n_rows, &device);
+    if (!dev) return nullptr;
+    if (n_rows && hipMemcpy(dev, group_of, n_rows * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(dev); fail("groups: the upload failed"); return nullptr;
+    }
+    return groups_finish(dev, n_rows, device);
+}
+
+mse_groups* mse_groups_from_dev(const void* group_of_dev, size_t n_rows) {
+    if (!group_of_dev && n_rows) { fail("groups: null array"); return nullptr; }
+    if (n_rows) {   // the grouping belongs to the device the array lives on
+        hipPointerAttribute_t at{};
+        if (hipPointerGetAttributes(&at, group_of_dev) != hipSuccess || at.type != hipMemoryTypeDevice) {
+            (void)hipGetLastError();
+            fail("groups_from_dev: not device memory"); return nullptr;
+        }
+        if (hipSetDevice(at.device) != hipSuccess) { fail("groups_from_dev: hipSetDevice failed"); return nullptr; }
+    }
+    int device = 0;
+    uint32_t* dev = groups_alloc(n_rows, &device);
+    if (!dev) return nullptr;
+    if (n_rows && hipMemcpy(dev, group_of_dev, n_rows * 4, hipMemcpyDeviceToDevice) != hipSuccess) {
+        (void)hipFree(dev); fail("groups: the device copy failed"); return nullptr;
+    }
+    return groups_finish(dev, n_rows, device);
+}
+
+void mse_groups_free(mse_groups* g) {
+    if (!g) return;
+    if (g->group_of) (void)hipFree(g->group_of);
+    delete g;
+}
+size_t mse_groups_len(const mse_groups* g) { return g ? g->n_rows : 0; }
+size_t mse_groups_count(const mse_groups* g) { return g ? g->count : 0; }
+
+int mse_searcher_grouped_stats(const mse_searcher* s, uint32_t out[3]) {
+    if (!s || !out) return fail("null argument");
+    for (int i = 0; i < 3; i++) out[i] = s->last_grouped[i];
+    return 0;
+}
+
+int mse_searcher_grouped_timing(mse_searcher* s, int enable, double out[4]) {
+    if (!s) return fail("null searcher");
+    for (int i = 0; out && i < 4; i++) out[i] = s->grp_ms[i];
+    for (int i = 0; enable && i < 4; i++)
+        if (!s->grp_ev[i]) MSE_HIP_TRY(hipEventCreate(&s->grp_ev[i]));
+    if (enable == 2)
+        for (int i = 0; i < 4; i++) s->grp_ms[i] = 0.0;
+    s->grp_timing = enable != 0;
+    return 0;
+}
+
+// test hook: the collapse kernel alone over ranked id lists the caller supplies (tests/test_gpu_grouped.py)
+int mse_debug_collapse_topk(mse_searcher* s, const mse_groups* g, const uint32_t* ids, size_t n_list, size_t nq, size_t k, uint32_t* kept_pos,
+                            uint32_t* n_reps) {
+    if (!s) return fail("null searcher");
+    if (!g) return fail("null grouping");
+    if (!ids || !kept_pos || !n_reps) return fail("collapse_topk: null array");
+    if (n_list == 0 || n_list > 2048) return fail("collapse_topk: 1..2048 entries per list");
+    if (k == 0 || k > 2048) return fail("collapse_topk: k must be 1..2048");
+    if (nq == 0 || nq > 65536) return fail("collapse_topk: 1..65536 queries");
+    if (s->grp_ids.ensure(nq * n_list * 4) || s->grp_pos.ensure(nq * k * 4) || s->grp_reps.ensure(nq * 4)) return -1;
+    MSE_HIP_TRY(hipMemcpyAsync(s->grp_ids.p, ids, nq * n_list * 4, hipMemcpyHostToDevice, s->stream));
+    if (launch_collapse(s->grp_ids.as<uint32_t>(), n_list, n_list, g->group_of, g->n_rows, (int)k, (int)nq, s->grp_pos.as<uint32_t>(),
+                        s->grp_reps.as<uint32_t>(), s->stream)) return -1;
+    MSE_HIP_TRY(hipMemcpyAsync(kept_pos, s->grp_pos.p, nq * k * 4, hipMemcpyDeviceToHost, s->stream));
+    MSE_HIP_TRY(hipMemcpyAsync(n_reps, s->grp_reps.p, nq * 4, hipMemcpyDeviceToHost, s->stream));
+    MSE_HIP_TRY(hipStreamSynchronize(s->stream));
+    return 0;
+}
+
+}  // extern "C"

@@ -193,6 +193,36 @@ int launch_filter_and_flags(const uint32_t* words, size_t n_words, const uint8_t
 int launch_list_bias(const uint32_t* ids, size_t n, const uint8_t* desc, int n_desc, const float* scales, int nq, int64_t* scores, size_t stride,
                      hipStream_t stream);
 
+// ---- group.hip: row groupings of the grouped search (include/mse.h mse_groups) ---------------------------------------------------
+// stats (three zeroed u64): [0] = largest non-NONE id + 1 (0: none), [1] = NONE rows; present (zeroed, (n_rows + 31) / 32 words): the bit
+// of every id below n_rows.  An id at or past n_rows sets no bit
+int launch_groups_validate(const uint32_t* group_of, size_t n_rows, uint32_t* present, unsigned long long* stats, hipStream_t stream);
+// stats[2] += set bits of present
+int launch_groups_popcount(const uint32_t* present, size_t n_words, unsigned long long* stats, hipStream_t stream);
+// Collapse of ranked id lists, one workgroup per query: ids [nq][ids_stride], best first, ID_NONE padding at the tail only, the first
+// n_list <= 2048 entries read; groups by LOCAL row id (a row at or past g_len, or of group NONE, is a group of its own).
+// kept_pos [nq][k]: list positions of the first k representatives (ID_NONE padded); n_reps [nq]: representatives in the whole list
+int launch_collapse(const uint32_t* ids, size_t ids_stride, size_t n_list, const uint32_t* group_of, size_t g_len, int k, int nq,
+                    uint32_t* kept_pos, uint32_t* n_reps, hipStream_t stream);
+// the entries at kept_pos with their payload (key_bytes 8: i64, padding INT64_MIN; 4: f32, padding -FLT_MAX; ids + id_offset, padding
+// ID_NONE) into row dst_rows[q] (null: q) of the outputs, for the queries with take[q] != 0 (null: all)
+int launch_collapse_gather(const uint32_t* kept_pos, int k, const uint32_t* ids, size_t ids_stride, const void* keys, size_t keys_stride,
+                           int key_bytes, int nq, uint64_t id_offset, const uint32_t* dst_rows, const uint8_t* take, void* out_keys,
+                           uint32_t* out_ids, size_t out_stride, hipStream_t stream);
+// Dense path over level 0 (scores [nq][stride], one key per list position p < n; row = list[p], or p without a list): the best row of
+// every group by (key desc, row asc) through integer atomics into best [nq][g_len] u64 (+ best_id [nq][g_len] u32 for i64 keys; unused
+// for f32), then every grouped row that is not its group's best drops to the lowest key (INT64_MIN / the all-ones f32 pattern) IN PLACE.
+// n_sat [nq] (i64 only): representatives and ungrouped rows whose own score is INT64_MIN.  ev_mid (optional): recorded between the
+// atomics and the demotion
+int launch_dense_group_best(bool f32, void* scores, size_t stride, size_t n, const uint32_t* list, const uint32_t* group_of, size_t g_len, int nq,
+                            unsigned long long* best, uint32_t* best_id, uint32_t* n_sat, hipStream_t stream, hipEvent_t ev_mid = nullptr);
+// i64, after the selection over the demoted level 0 (sel_keys [nq][k]), its collapse (kept_pos [nq][k], n_reps) and the gather into the
+// outputs: a query with fewer than k representatives and n_sat > 0 gets its saturated representatives, in id order, behind the others
+int launch_dense_complete(const int64_t* scores, size_t stride, size_t n, const uint32_t* list, const uint32_t* group_of, size_t g_len,
+                          const uint32_t* best_id, const uint32_t* n_sat, const uint32_t* kept_pos, const uint32_t* n_reps, const int64_t* sel_keys,
+                          int k, int nq, uint64_t id_offset, const uint32_t* dst_rows, int64_t* out_scores, uint32_t* out_ids, size_t out_stride,
+                          hipStream_t stream);
+
 // ---- graph_build.hip: what graph_delete.hip shares with the build ---------------------------------------------------------------
 // robust_prune (lib.rs:227-285), one workgroup per candidate list: list k is (ci, cs)[k * stride ..][0 .. counts[k]) in HBM, its point
 // points[k]; the new list (at most r ids) goes to out_ids[k * r ..], its length to out_len[k].  eps_fix: prune_mfma_eps (runtime.h)

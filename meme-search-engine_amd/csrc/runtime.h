@@ -3,6 +3,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "dispatch.h"
+#include <functional>
 #include <mutex>
 #include <vector>
 
@@ -93,6 +94,14 @@ struct mse_filter {
     uint32_t* ids = nullptr;     // device: the allowed rows, ascending (count of them)
 };
 
+// row grouping of the grouped search (group.hip, group_api.hip; immutable once made)
+struct mse_groups {
+    int device = 0;                // HIP ordinal the array lives on
+    size_t n_rows = 0;             // rows it speaks for; rows at or past it are groups of their own
+    size_t count = 0;              // distinct ids + MSE_GROUP_NONE rows
+    uint32_t* group_of = nullptr;  // device [n_rows]: group id (< n_rows) or MSE_GROUP_NONE
+};
+
 struct mse_searcher {
     const mse_base* base = nullptr;
     hipStream_t stream = nullptr;
@@ -121,6 +130,17 @@ struct mse_searcher {
     mse::DevBuf ins_scratch[8];    // scratch of mse_graph_insert_rows (graph_insert.hip): slots, staging slabs, codes, flags
     mse::BuildScratch ins_build;   // ... and of its link step
     uint32_t last_widened = 0, last_max_groups = 0;
+    // grouped search (bruteforce.hip grouped_topk_dev, api_pq.hip): the candidate prefix [nq][k'] (ids | keys), the collapse's positions
+    // and counts, the compact set of the queries that go on, the dense path's group table (best keys | best ids)
+    mse::DevBuf grp_ids, grp_keys, grp_pos, grp_reps, grp_q, grp_q2, grp_idx, grp_best;
+    mse::PinBuf grp_pin;      // representative counts and list tails on their way to the host
+    uint32_t last_grouped[3] = {0, 0, 0};   // of the last grouped call: queries answered from the first prefix, a widened one, the dense path
+    // optional measurement of the grouped search (mse_searcher_grouped_timing, for scripts/grouped_search_probe.py): HIP-event
+    // milliseconds of [0] the collapse kernel of the prefix rounds, and of the dense passes [1] the score pass, [2] the group atomics and
+    // the demotion, [3] the selection with its collapse and gather
+    bool grp_timing = false;
+    hipEvent_t grp_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    double grp_ms[4] = {0.0, 0.0, 0.0, 0.0};
     // thresholded group maxima of the 320-query pass (bruteforce.hip mfma_pass; mse_searcher_set_sparse_maxima): mode 0 auto, 1 off, 2 forced;
     // every sparse_stride-th 256-row tile is the sample (stride - 1 a power of two); sparse_cap survivors per query at most
     int sparse_mode = 0;
@@ -204,6 +224,20 @@ int bruteforce_topk_dev(mse_searcher* s, const mse_filter* f, const void* querie
 struct ListBias { const uint8_t* desc; int n_desc; const float* scales_dev; };   // scales_dev: [nq_pass][n_desc] on the device
 int exact_pass_list(mse_searcher* s, int nq_pass, int k, uint64_t id_offset, int64_t* out_scores, uint32_t* out_ids, size_t out_stride,
                     const uint32_t* ids, size_t n, const ListBias* bias);
+// a grouping may be used on base b: same device, no longer than the rows (group_api.hip); 0, or -1 with the error set
+int check_groups(const mse_base* b, const mse_groups* g);
+// the dense path's scratch is bounded: queries one dense pass may take (1 .. 8) with a group table of g_len entries of `bytes` bytes each
+int dense_pass_queries(size_t g_len, size_t bytes);
+// the collapse half of a round of the grouped search's prefix path (bruteforce.hip), shared with the flat index
+int grouped_collapse_round(mse_searcher* s, const mse_groups* g, int key_bytes, size_t nq, size_t kp, int k, uint64_t id_offset,
+                           const std::vector<uint32_t>* dst, void* out_keys, uint32_t* out_ids, size_t out_stride, std::vector<uint32_t>* open_out,
+                           std::vector<uint32_t>* open_reps);
+// the rounds of the prefix path over the nq queries at q (rows of row_bytes), shared by the brute force and the flat index (bruteforce.hip):
+// round(queries, count, k', output rows or null, &open, &open_reps) runs one search + grouped_collapse_round; dense(queries, count,
+// output rows) answers what the rounds left.  Counts the queries per path into s->last_grouped
+using GroupedRound = std::function<int(const void*, size_t, size_t, const std::vector<uint32_t>*, std::vector<uint32_t>*, std::vector<uint32_t>*)>;
+using GroupedDense = std::function<int(const void*, size_t, const std::vector<uint32_t>&)>;
+int grouped_prefix_drive(mse_searcher* s, const void* q, size_t row_bytes, size_t nq, size_t k, const GroupedRound& round, const GroupedDense& dense);
 // largest row norm of the base (x 1.0001), computed once and kept on the device as float bits (b->norm_bits_dev)
 int ensure_base_norm(const mse_base* b, hipStream_t st);
 // error bound of the matrix-core products robust_prune may decide by (graph_build.hip): *eps_fix = 0 means exact dots only

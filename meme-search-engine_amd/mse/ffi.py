@@ -63,6 +63,16 @@ SIGNATURES = {
     "mse_filter_count": (sz, [vp]),
     "mse_bruteforce_topk_filtered_f16": (C.c_int, [vp, vp, u16p, sz, sz, C.c_int, i64p, u32p]),
     "mse_bruteforce_topk_filtered_f16_dev": (C.c_int, [vp, vp, vp, sz, sz, C.c_int, C.c_uint64, vp, vp]),
+    "mse_groups_from_host": (vp, [u32p, sz]),
+    "mse_groups_from_dev": (vp, [vp, sz]),
+    "mse_groups_free": (None, [vp]),
+    "mse_groups_len": (sz, [vp]),
+    "mse_groups_count": (sz, [vp]),
+    "mse_bruteforce_topk_grouped_f16": (C.c_int, [vp, vp, vp, u16p, sz, sz, C.c_int, i64p, u32p]),
+    "mse_bruteforce_topk_grouped_f16_dev": (C.c_int, [vp, vp, vp, vp, sz, sz, C.c_int, C.c_uint64, vp, vp]),
+    "mse_searcher_grouped_stats": (C.c_int, [vp, u32p]),
+    "mse_searcher_grouped_timing": (C.c_int, [vp, C.c_int, C.POINTER(C.c_double)]),
+    "mse_debug_collapse_topk": (C.c_int, [vp, vp, u32p, sz, sz, sz, u32p, u32p]),
     "mse_bruteforce_ranks_f16": (C.c_int, [vp, u16p, u32p, sz, u32p]),
     "mse_score_rows_f16": (C.c_int, [vp, u32p, sz, u16p, i64p]),
     "mse_merge_topk_dev": (C.c_int, [vp, vp, vp, sz, sz, sz, vp, vp]),
@@ -104,6 +114,7 @@ SIGNATURES = {
     "mse_index_ntotal": (sz, [vp]),
     "mse_index_search": (C.c_int, [vp, f32p, sz, sz, f32p, i64p]),
     "mse_index_search_filtered": (C.c_int, [vp, vp, f32p, sz, sz, f32p, i64p]),
+    "mse_index_search_grouped": (C.c_int, [vp, vp, vp, f32p, sz, sz, f32p, i64p]),
     "mse_index_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
     "mse_dispatcher_new": (vp, [vp, sz, C.c_uint32]),
     "mse_dispatcher_free": (None, [vp]),

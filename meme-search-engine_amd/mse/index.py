@@ -7,7 +7,7 @@ import numpy as np
 
 from . import ffi
 from .ffi import check, check_ptr
-from .vector import RowFilter, _p
+from .vector import RowFilter, RowGroups, _p
 
 
 class SearchResult:
@@ -27,24 +27,34 @@ class ScalarQuantizerIndex:
     def ntotal(self):
         return int(ffi.lib().mse_index_ntotal(self._h))
 
-    def search(self, query, k, allow=None):
+    def search(self, query, k, allow=None, groups=None):
         """labels == -1 marks an empty slot (main.rs:908: `id.get()?`).  allow: a RowFilter or a boolean row mask -- the search
-        over those rows only (rows added after the filter was made are excluded)."""
+        over those rows only (rows added after the filter was made are excluded).  groups: a RowGroups or an integer array of group
+        ids -- one result per group, its best (allowed) row (main.rs:902-917; rows added after the grouping was made are groups of
+        their own)."""
         q = np.ascontiguousarray(query, np.float32).reshape(-1, self.d)
         nq = q.shape[0]
         dist = np.empty((nq, k), np.float32)
         lab = np.empty((nq, k), np.int64)
-        if allow is None:
+        if allow is None and groups is None:
             check(ffi.lib().mse_index_search(self._h, _p(q, C.c_float), nq, k, _p(dist, C.c_float), _p(lab, C.c_int64)),
                   "index.search")
             return SearchResult(dist, lab)
-        f, owned = RowFilter.wrap(allow)
+        f, owned = RowFilter.wrap(allow) if allow is not None else (None, False)
+        g, g_owned = None, False
         try:
-            check(ffi.lib().mse_index_search_filtered(self._h, f._h, _p(q, C.c_float), nq, k, _p(dist, C.c_float), _p(lab, C.c_int64)),
-                  "index.search")
+            if groups is None:
+                check(ffi.lib().mse_index_search_filtered(self._h, f._h, _p(q, C.c_float), nq, k, _p(dist, C.c_float), _p(lab, C.c_int64)),
+                      "index.search")
+            else:
+                g, g_owned = RowGroups.wrap(groups)
+                check(ffi.lib().mse_index_search_grouped(self._h, g._h, f._h if f else None, _p(q, C.c_float), nq, k, _p(dist, C.c_float),
+                                                         _p(lab, C.c_int64)), "index.search")
         finally:
             if owned:
                 f.close()
+            if g_owned:
+                g.close()
         return SearchResult(dist, lab)
 
     def stats(self):

@@ -13,6 +13,7 @@ from .ffi import MseError, check, check_ptr
 
 SCALE = 4294967296.0  # vector.rs:46
 ID_NONE = 0xFFFFFFFF
+GROUP_NONE = 0xFFFFFFFF   # RowGroups: the row is a group of its own
 
 MODE_AUTO, MODE_EXACT, MODE_MFMA = 0, 1, 2
 SPARSE_AUTO, SPARSE_OFF, SPARSE_FORCED = 0, 1, 2   # Searcher.set_sparse_maxima
@@ -275,6 +276,60 @@ class RowFilter:
             pass
 
 
+class RowGroups:
+    """Row grouping of the grouped search (mse_groups): `group_of` is an integer array with one group id per row -- GROUP_NONE (or -1)
+    for a row that is a group of its own, any other id below the number of rows.  A grouped search returns one row per group: the
+    group's best eligible row in the search's own order (the `seen_videos` walk of src/main.rs:902-917).  The array lives on the current
+    device and is immutable.  len() is the number of rows; .count the distinct ids plus the ungrouped rows: the most results a search
+    can return.  A grouping may be shorter than what it is used on (later rows are groups of their own), not longer."""
+
+    def __init__(self, group_of):
+        self._h = None
+        a = np.asarray(group_of)
+        if not np.issubdtype(a.dtype, np.integer):
+            raise TypeError("group_of must be an integer array: one group id per row")
+        if a.ndim != 1:
+            raise ValueError("group_of must be one-dimensional: one group id per row")
+        if a.size and (a.min() < -1 or a.max() > 0xFFFFFFFF):
+            raise ValueError("group ids must be in 0 .. 2**32 - 1 (or -1 for GROUP_NONE)")
+        if a.dtype != np.uint32:
+            a = np.where(a < 0, GROUP_NONE, a).astype(np.uint32)
+        a = np.ascontiguousarray(a)
+        self._h = check_ptr(ffi.lib().mse_groups_from_host(_p(a, C.c_uint32), a.size), "mse_groups_from_host")
+
+    @classmethod
+    def from_device(cls, ptr, n_rows):
+        """mse_groups_from_dev: n_rows u32 group ids that are already in device memory (copied)."""
+        g = cls.__new__(cls)
+        g._h = check_ptr(ffi.lib().mse_groups_from_dev(ptr, int(n_rows)), "mse_groups_from_dev")
+        return g
+
+    @classmethod
+    def wrap(cls, groups):
+        """(grouping, owned): a RowGroups as it is, anything else made into one (and owned by the caller, to close)."""
+        if isinstance(groups, RowGroups):
+            return groups, False
+        return cls(groups), True
+
+    def __len__(self):
+        return int(ffi.lib().mse_groups_len(self._h))
+
+    @property
+    def count(self):
+        return int(ffi.lib().mse_groups_count(self._h))
+
+    def close(self):
+        if self._h:
+            ffi.lib().mse_groups_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Searcher:
     """Per-thread scratch + stream (reference `Scratch`: lib.rs:157-175, query_disk_index.rs:116-123)."""
 
@@ -307,41 +362,72 @@ class Searcher:
         check(ffi.lib().mse_searcher_compact_timing(self._h, int(enable), C.byref(ms)), "compact_timing")
         return float(ms.value)
 
-    def bruteforce_topk(self, queries, k, mode=MODE_AUTO, allow=None):
+    def bruteforce_topk(self, queries, k, mode=MODE_AUTO, allow=None, groups=None):
         """Brute-force scan + ranking of `evaluate` (query_disk_index.rs:262-273) for a query batch.
-        Returns (scores int64 [nq,k], ids uint32 [nq,k]).  allow: a RowFilter or a boolean row mask -- top-k over those rows only."""
+        Returns (scores int64 [nq,k], ids uint32 [nq,k]).  allow: a RowFilter or a boolean row mask -- top-k over those rows only.
+        groups: a RowGroups or an integer array of group ids -- one result per group, the best (allowed) row of each."""
         d = self.vecs.d_emb
         q = _bits(queries).reshape(-1, d)
         nq = q.shape[0]
         scores = np.empty((nq, k), np.int64)
         ids = np.empty((nq, k), np.uint32)
-        if allow is None:
+        if allow is None and groups is None:
             check(ffi.lib().mse_bruteforce_topk_f16(self._h, _p(q, C.c_uint16), nq, k, mode, _p(scores, C.c_int64),
                                                     _p(ids, C.c_uint32)), "bruteforce_topk")
             return scores, ids
-        f, owned = RowFilter.wrap(allow)
+        f, owned = RowFilter.wrap(allow) if allow is not None else (None, False)
+        g, g_owned = None, False
         try:
-            check(ffi.lib().mse_bruteforce_topk_filtered_f16(self._h, f._h, _p(q, C.c_uint16), nq, k, mode, _p(scores, C.c_int64),
-                                                             _p(ids, C.c_uint32)), "bruteforce_topk")
+            if groups is None:
+                check(ffi.lib().mse_bruteforce_topk_filtered_f16(self._h, f._h, _p(q, C.c_uint16), nq, k, mode, _p(scores, C.c_int64),
+                                                                 _p(ids, C.c_uint32)), "bruteforce_topk")
+            else:
+                g, g_owned = RowGroups.wrap(groups)
+                check(ffi.lib().mse_bruteforce_topk_grouped_f16(self._h, g._h, f._h if f else None, _p(q, C.c_uint16), nq, k, mode,
+                                                                _p(scores, C.c_int64), _p(ids, C.c_uint32)), "bruteforce_topk")
         finally:
             if owned:
                 f.close()
+            if g_owned:
+                g.close()
         return scores, ids
 
-    def bruteforce_topk_dev(self, queries_dev, nq, k, scores_dev, ids_dev, mode=MODE_AUTO, id_offset=0, allow=None):
-        if allow is None:
+    def bruteforce_topk_dev(self, queries_dev, nq, k, scores_dev, ids_dev, mode=MODE_AUTO, id_offset=0, allow=None, groups=None):
+        if allow is None and groups is None:
             check(ffi.lib().mse_bruteforce_topk_f16_dev(self._h, queries_dev, nq, k, mode, id_offset, scores_dev, ids_dev),
                   "bruteforce_topk_dev")
             return
-        f, owned = RowFilter.wrap(allow)
+        f, owned = RowFilter.wrap(allow) if allow is not None else (None, False)
+        g, g_owned = None, False
         try:
-            check(ffi.lib().mse_bruteforce_topk_filtered_f16_dev(self._h, f._h, queries_dev, nq, k, mode, id_offset, scores_dev,
-                                                                 ids_dev), "bruteforce_topk_dev")
-            if owned:   # the call is asynchronous on the searcher's stream: the filter must outlive it
+            if groups is None:
+                check(ffi.lib().mse_bruteforce_topk_filtered_f16_dev(self._h, f._h, queries_dev, nq, k, mode, id_offset, scores_dev,
+                                                                     ids_dev), "bruteforce_topk_dev")
+            else:
+                g, g_owned = RowGroups.wrap(groups)
+                check(ffi.lib().mse_bruteforce_topk_grouped_f16_dev(self._h, g._h, f._h if f else None, queries_dev, nq, k, mode, id_offset,
+                                                                    scores_dev, ids_dev), "bruteforce_topk_dev")
+            if owned or g_owned:   # the call is asynchronous on the searcher's stream: the filter / grouping must outlive it
                 check(ffi.lib().mse_device_synchronize(), "bruteforce_topk_dev")
         finally:
             if owned:
                 f.close()
+            if g_owned:
+                g.close()
+
+    def grouped_stats(self):
+        """Of the last grouped call on this searcher (mse_searcher_grouped_stats): queries answered from the first candidate prefix,
+        from the widened prefix, by the dense path."""
+        out = (C.c_uint32 * 3)()
+        check(ffi.lib().mse_searcher_grouped_stats(self._h, out), "grouped_stats")
+        return tuple(int(v) for v in out)
+
+    def grouped_timing(self, enable):
+        """Measurement hook (mse_searcher_grouped_timing): HIP-event milliseconds accumulated so far -- collapse kernel, and of the dense
+        passes the score pass, the group atomics, the selection -- then sets the switch (0 off, 1 on, 2 on and reset)."""
+        out = (C.c_double * 4)()
+        check(ffi.lib().mse_searcher_grouped_timing(self._h, int(enable), out), "grouped_timing")
+        return {"collapse_ms": out[0], "dense_score_ms": out[1], "dense_atomics_ms": out[2], "dense_select_ms": out[3]}
 
     def merge_topk_dev(self, gathered_scores_dev, gathered_ids_dev, n_shards, nq, k, out_scores_dev, out_ids_dev):
         """k-way merge of all-gathered [n_shards][nq][k] shard results (device pointers)."""
