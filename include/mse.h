@@ -672,6 +672,55 @@ int mse_disk_query_submit_filtered_f32(mse_searcher* s, mse_pq* pq, const mse_co
                                        const float* queries_f32, const float* scales, size_t nq, int disable_pq, size_t beamwidth, size_t search_list,
                                        size_t k, uint32_t* ids, int64_t* scores, uint32_t* n_visited, uint32_t* cmps, uint32_t* pq_cmps, void* user,
                                        mse_completion_queue* cq, mse_ticket** ticket_out);
+/* ---- grouped graph search: one result per group on the request path (the `seen_videos` walk of the reference's query_index over
+ * what the large-scale handler, src/query_disk_index.rs:436-540, visited) ----
+ * Contract, met bit for bit by every path.  A grouped request-path call returns, per query, the visited records the ungrouped call would
+ * rank -- those that survive the de-duplication when mse_graph_set_dedup is on -- in the same total order (exact score + bias descending,
+ * id ascending); a record is kept only if no earlier record in that order has its group; the first k kept records are returned with their
+ * own scores, padded with MSE_ID_NONE / INT64_MIN.  In numpy: sort the visited list by (score desc, id asc), keep the first record of
+ * every group, take the first k.  Order of steps: de-duplication (visit order, as the reference has it before its sort), then the group
+ * step, then the selection.
+ * Grouping rules are those of mse_groups: a row of group MSE_GROUP_NONE, or at or past mse_groups_len, is a group of its own; a grouping
+ * longer than the graph, or on another device than the vectors, is an error.  A grouping is BY ROW ID: after mse_graph_compact the caller
+ * remaps it through old_to_new.  A non-representative is never returned, not even to fill a short list; with every row MSE_GROUP_NONE the
+ * answer is the ungrouped answer bit for bit.  n_visited, cmps and pq_cmps are those of the ungrouped call (n_visited counts every visited
+ * record): the traversal does not change.
+ * This is an APPROXIMATE search: the answer is the collapse of what this search visited at this search_list, not the k best groups of the
+ * index.  When one group's rows crowd the visited list fewer than k groups come back, which shows as padding; the caller may ask again
+ * with a longer search_list (nothing is widened automatically).
+ * With a row filter (f not NULL; f NULL: the unfiltered traversal, regime is ignored):
+ *   MSE_FILTERED_GRAPH  the visited list is already filtered and the group step runs over it as above: a group whose best row is
+ *                       disallowed is represented by its best allowed VISITED row.
+ *   MSE_FILTERED_LIST   the grouped exact answer over the eligible rows {allowed AND has_url}: scores fast_dot + descriptor product (with
+ *                       scales and descriptors), order (score desc, id asc), one row per group, counters as LIST.  Scratch: the grouped
+ *                       brute force's dense pass (12 bytes per query per row of the grouping, fewer than 8 queries per pass past 1.1e7
+ *                       rows).  Still an error while de-duplication is on.
+ *   MSE_FILTERED_AUTO   mse_filtered_plan decides as for the filtered call, and the call equals the explicit call at its answer.
+ * Validation order: the filtered or unfiltered call's own checks, then "null grouping" (an error of its own), then the grouping's fit;
+ * argument errors write nothing.  The grouping must outlive the call / the ticket.  Coalesced calls and tickets share a submission only
+ * with requests of the same grouping object (and filter, regime, search_list), never with ungrouped ones; k may differ between sharers.
+ * How: one workgroup per query removes every non-best record of a group from the device-resident visited list in place
+ * (integer atomics on a hash table in LDS, in global memory for lists past 4096 records) between the de-duplication and the selection:
+ * no host decision, no extra synchronisation, no second copy.  The shard's block form has no grouped twin. */
+int mse_disk_query_topk_grouped(mse_searcher* s, mse_pq* pq, const mse_codes* c, const mse_graph* g, const mse_groups* groups, const mse_filter* f,
+                                int regime, const uint32_t* starts, const uint16_t* queries, const float* luts, const float* scales, size_t nq,
+                                int disable_pq, size_t beamwidth, size_t search_list, size_t k, uint32_t* ids, int64_t* scores, uint32_t* n_visited,
+                                uint32_t* cmps, uint32_t* pq_cmps);
+int mse_disk_query_topk_grouped_f32(mse_searcher* s, mse_pq* pq, const mse_codes* c, const mse_graph* g, const mse_groups* groups, const mse_filter* f,
+                                    int regime, const uint32_t* starts, const float* queries_f32, const float* scales, size_t nq, int disable_pq,
+                                    size_t beamwidth, size_t search_list, size_t k, uint32_t* ids, int64_t* scores, uint32_t* n_visited,
+                                    uint32_t* cmps, uint32_t* pq_cmps);
+/* the ticket form: mse_disk_query_submit_filtered_f32 with a grouping (f may be NULL) */
+int mse_disk_query_submit_grouped_f32(mse_searcher* s, mse_pq* pq, const mse_codes* c, const mse_graph* g, const mse_groups* groups, const mse_filter* f,
+                                      int regime, const float* queries_f32, const float* scales, size_t nq, int disable_pq, size_t beamwidth,
+                                      size_t search_list, size_t k, uint32_t* ids, int64_t* scores, uint32_t* n_visited, uint32_t* cmps,
+                                      uint32_t* pq_cmps, void* user, mse_completion_queue* cq, mse_ticket** ticket_out);
+/* Test hook, like mse_debug_collapse_topk: the group step alone over caller-supplied UNRANKED lists.  ids / scores [nq][cap] host arrays
+ * (holes (MSE_ID_NONE, INT64_MIN) allowed anywhere), n_visited [nq] (clamped to cap); of every group the best live record by (score desc,
+ * id asc) stays, every other record of the group becomes a hole, everything else is written back unchanged.  cap 1..65536; the table is
+ * in LDS up to cap 4096 and in global memory beyond, exactly as on the request path.  Synchronous. */
+int mse_debug_visited_collapse(mse_searcher* s, const mse_groups* groups, uint32_t* ids, int64_t* scores, size_t cap, const uint32_t* n_visited,
+                               size_t nq);
 /* A shard's form of the call (multi-GPU, below): the [nq][k] results stay on the device as a packed block -- [nq*k] i64 scores, then
  * [nq*k] u32 ids + id_offset (mse_topk_block_bytes(nq, k) bytes at block_dev) -- ready for the exchange; never coalesced. */
 int mse_disk_query_topk_block(mse_searcher* s, mse_pq* pq, const mse_codes* c, const mse_graph* g, const uint32_t* starts, const uint16_t* queries,

@@ -777,6 +777,9 @@ struct SearchIn {
     // filtered search: the allowed-row set (null: none) and the regime the call runs in -- MSE_FILTERED_GRAPH or _LIST; AUTO has been
     // resolved by then (filtered_resolve), and search_list is the effective one
     const mse_filter* filter = nullptr; int regime = MSE_FILTERED_GRAPH;
+    // grouped search (include/mse.h "grouped graph search"): one result per group of `groups` (null: ungrouped).  grouped: the call came
+    // in through a grouped entry point, whose grouping is checked -- null included -- after the call's own arguments (check_grouping)
+    const mse_groups* groups = nullptr; bool grouped = false;
     SearchIn piece(size_t q0, size_t m) const {   // queries q0 .. q0 + m - 1
         const size_t d = s->base->d;
         SearchIn p = *this;
@@ -786,9 +789,9 @@ struct SearchIn {
         return p;
     }
     // what calls need in common to run as one launch: the same vectors, codec, codes, graph and search parameters, the same kinds of inputs,
-    // the same filter object (or none) and regime
+    // the same filter object (or none) and regime, the same grouping object (or none) -- k may differ: the group step does not depend on it
     bool shares_with(const SearchIn& o) const {
-        return filter == o.filter && regime == o.regime && s->base == o.s->base && pq == o.pq && c == o.c && g == o.g && disable_pq == o.disable_pq && beamwidth == o.beamwidth &&
+        return filter == o.filter && regime == o.regime && groups == o.groups && s->base == o.s->base && pq == o.pq && c == o.c && g == o.g && disable_pq == o.disable_pq && beamwidth == o.beamwidth &&
                search_list == o.search_list && (queries != nullptr) == (o.queries != nullptr) && (luts != nullptr) == (o.luts != nullptr) &&
                (scales != nullptr) == (o.scales != nullptr);
     }
@@ -859,6 +862,15 @@ int check_queued(const SearchIn& in) {
     return 0;
 }
 
+// a grouped entry point's grouping, after the call's own checks: "null grouping" is an error of its own, then the grouping's fit
+int check_grouping(const SearchIn& in) {
+    if (!in.grouped) return 0;
+    if (!in.groups) return fail("null grouping");
+    if (check_groups(in.s->base, in.groups)) return -1;
+    if (in.groups->n_rows > in.g->n) return fail("disk_query_topk_grouped: grouping is longer than the graph");
+    return 0;
+}
+
 // beam_search_kernel<THREADS, ADC> with one workgroup per query; ADC (scoring through the query's distance table) unless disable_pq
 template <int THREADS>
 int launch_beam(const BeamArgs& a, size_t nq, size_t lds, hipStream_t st) {
@@ -913,6 +925,7 @@ int search_check(const SearchRun& r) {
     if (!in.disable_pq && (in.pq->n_chunks != 64 || in.pq->n_centroids != 256 || c->code_size != 64)) return fail("disk_search_batch: needs the 64 x 256 codec");
     if (check_params(in)) return -1;
     if (in.filter && check_filter(r.b, in.filter)) return -1;
+    if (in.groups && check_groups(r.b, in.groups)) return -1;
     if (in.g->max_deg > BS_DEG_MAX) return fail("disk_search_batch: at most 128 neighbours per node");
     if (c->n_desc > BS_DESC_MAX) return fail("disk_search_batch: at most 8 descriptors");
     if (r.d % 32 || r.d > 4096) return fail("disk_search_batch: vector width must be a multiple of 32");
@@ -1103,6 +1116,16 @@ int read_back_fused(const SearchRun& r) {
         DevBuf& db = s->pool[15];
         if (db.ensure(dedup_batch_scratch_bytes(nq, vc))) return -1;
         if (launch_dedup_batch(r.b->dev, (int)r.d, r.vi.as<uint32_t>(), r.vs.as<long long>(), vc, r.cnt_dev, nq, r.in.g->dedup_threshold, db.p, st)) return -1;
+    }
+    if (r.in.groups) {
+        // one result per group: of every group the best visited record stays in the list, the others leave it the way the
+        // de-duplication's do -- after it, before the selection, on the same stream.  Lists past 4096 records (fused_run's repeats)
+        // take the table in global memory: the de-duplication's scratch, which no such list uses
+        DevBuf& gt = s->pool[15];
+        const size_t table_bytes = visited_group_scratch_bytes(nq, vc);
+        if (table_bytes && gt.ensure(table_bytes)) return -1;
+        if (launch_visited_group(r.vi.as<uint32_t>(), r.vs.as<long long>(), vc, r.cnt_dev, nq, r.in.groups->group_of, r.in.groups->n_rows, gt.p, st))
+            return -1;
     }
     SelectArgs sa{};
     sa.kind = KEY_I64; sa.list_ids = r.vi.as<uint32_t>(); sa.list_keys = r.vs.p; sa.list_stride = vc; sa.n_list = vc;
@@ -1364,6 +1387,8 @@ int list_run(const SearchIn& in, const FusedQuery& fz) {
     const size_t nq = in.nq, d = b->d, k = fz.k;
     if (!f) return fail("disk_query_topk_filtered: null filter");
     if (check_filter(b, f) || check_list_regime(in) || check_k(k)) return -1;
+    const mse_groups* grp = in.groups;
+    if (grp && check_groups(b, grp)) return -1;
     if (!fz.dev_sc && !fz.dst && (!fz.ids || !fz.scores)) return fail("disk_query_topk: bad k / outputs");
     if (nq == 0) return 0;
     hipStream_t st = s->stream;
@@ -1401,15 +1426,17 @@ int list_run(const SearchIn& in, const FusedQuery& fz) {
             MSE_HIP_TRY(hipMemcpyAsync(dq.p, in.queries, nq * d * 2, hipMemcpyDefault, st));
         }
         if (bias) MSE_HIP_TRY(hipMemcpyAsync(dsc.p, in.scales, nq * n_desc * 4, hipMemcpyHostToDevice, st));
-        for (size_t q0 = 0; q0 < nq; q0 += 8) {
-            const int nqp = (int)std::min<size_t>(8, nq - q0);
+        // with a grouping a pass is the grouped search's dense pass over the eligible rows: its group table bounds the queries of a pass
+        const size_t tile = grp ? (size_t)dense_pass_queries(grp->n_rows, 12) : 8;
+        for (size_t q0 = 0; q0 < nq; q0 += tile) {
+            const int nqp = (int)std::min<size_t>(tile, nq - q0);
             MSE_HIP_TRY(hipMemsetAsync(s->q_stage.p, 0, (size_t)8 * d * 2, st));
             MSE_HIP_TRY(hipMemcpyAsync(s->q_stage.p, dq.as<uint16_t>() + q0 * d, (size_t)nqp * d * 2, hipMemcpyDeviceToDevice, st));
             const ListBias lb{in.c ? in.c->desc : nullptr, (int)n_desc, dsc.as<float>() + q0 * n_desc};
             // a shard's hand-over: straight into the two halves of its packed block, the shard's first row added to the ids
             int64_t* o_sc = fz.dev_sc ? fz.dev_sc + q0 * k : os.as<int64_t>() + q0 * k;
             uint32_t* o_id = fz.dev_sc ? fz.dev_ids + q0 * k : oi.as<uint32_t>() + q0 * k;
-            if (exact_pass_list(s, nqp, (int)k, fz.dev_sc ? fz.id_offset : 0, o_sc, o_id, k, ids, n_el, bias ? &lb : nullptr)) return -1;
+            if (exact_pass_list(s, nqp, (int)k, fz.dev_sc ? fz.id_offset : 0, o_sc, o_id, k, ids, n_el, bias ? &lb : nullptr, grp)) return -1;
         }
         if (!fz.dev_sc) {
             MSE_HIP_TRY(hipMemcpyAsync(h_sc.data(), os.p, nq * k * 8, hipMemcpyDeviceToHost, st));
@@ -1615,6 +1642,7 @@ int query_front(const QueryCall& k) {
     if (in.nq == 0) return 0;
     if (!in.s || !in.s->base) return fail("disk_query_topk: null searcher");
     if (check_k(k.out.k)) return -1;
+    if (in.grouped && (check_params(in) || check_grouping(in))) return -1;
     // f16 queries may be device-resident (embeddings that never left the GPU): such a call cannot be gathered by the host and goes straight
     // to the device.  f32 queries are host memory by contract (the handler's input, :436-477): no runtime call on the request thread.
     if (in.nq > FUSED_COALESCE_MAX || (in.queries && is_device_pointer(in.queries))) return fused_run(in, k.out);
@@ -1795,6 +1823,32 @@ int mse_disk_query_topk_filtered_f32(mse_searcher* s, mse_pq* pq, const mse_code
     return query_front(QueryCall{in, fused_out(k, ids, scores, n_visited, cmps, pq_cmps)});
 }
 
+// ---- grouped graph search (include/mse.h): the calls above with one result per group.  f may be NULL: the unfiltered traversal, and
+// regime is then ignored.  The filtered or unfiltered call's own checks come first, then the grouping's (check_grouping)
+static int grouped_front(SearchIn in, int regime, const mse_groups* groups, const FusedQuery& out) {
+    if (in.filter && filtered_resolve(in, regime)) return -1;
+    in.groups = groups; in.grouped = true;
+    return query_front(QueryCall{in, out});
+}
+
+int mse_disk_query_topk_grouped(mse_searcher* s, mse_pq* pq, const mse_codes* c, const mse_graph* g, const mse_groups* groups, const mse_filter* f,
+                                int regime, const uint32_t* starts, const uint16_t* queries, const float* luts, const float* scales, size_t nq,
+                                int disable_pq, size_t beamwidth, size_t search_list, size_t k, uint32_t* ids, int64_t* scores, uint32_t* n_visited,
+                                uint32_t* cmps, uint32_t* pq_cmps) {
+    if (!queries) return fail("disk_query_topk: null argument");
+    return grouped_front(SearchIn{s, pq, c, g, starts, queries, nullptr, luts, scales, nq, disable_pq, beamwidth, search_list, f}, regime, groups,
+                         fused_out(k, ids, scores, n_visited, cmps, pq_cmps));
+}
+
+int mse_disk_query_topk_grouped_f32(mse_searcher* s, mse_pq* pq, const mse_codes* c, const mse_graph* g, const mse_groups* groups, const mse_filter* f,
+                                    int regime, const uint32_t* starts, const float* queries_f32, const float* scales, size_t nq, int disable_pq,
+                                    size_t beamwidth, size_t search_list, size_t k, uint32_t* ids, int64_t* scores, uint32_t* n_visited,
+                                    uint32_t* cmps, uint32_t* pq_cmps) {
+    if (!queries_f32) return fail("disk_query_topk_f32: null argument");
+    return grouped_front(SearchIn{s, pq, c, g, starts, nullptr, queries_f32, nullptr, scales, nq, disable_pq, beamwidth, search_list, f}, regime, groups,
+                         fused_out(k, ids, scores, n_visited, cmps, pq_cmps));
+}
+
 // ---- the request path without a thread per request (round 5) ----------------------------------------------------------------
 // A ticket owns everything a queued request needs after the submitting call returned: the request record, the call's arguments and
 // a copy of the query (the caller's buffer is free again at once; the OUTPUT arrays stay the caller's and must outlive the ticket's
@@ -1847,7 +1901,7 @@ int submit_f32(bool copy, const QueryCall& call, void* user, mse_completion_queu
     if (!in.queries_f32 || !ticket_out || !in.g || !call.out.ids || !call.out.scores) return fail("disk_query_submit_f32: null argument");
     if (!in.s || !in.s->base) return fail("disk_query_submit_f32: null searcher");
     if (in.nq == 0 || in.nq > FUSED_COALESCE_MAX) return fail("disk_query_submit_f32: 1.." + std::to_string(FUSED_COALESCE_MAX) + " queries per request");
-    if (check_k(call.out.k) || check_queued(in)) return -1;
+    if (check_k(call.out.k) || check_queued(in) || check_grouping(in)) return -1;
     Coalescer* co = graph_coalescer(in.g);
     if (!co) return -1;
     mse_ticket* t = ticket_take();
@@ -1895,6 +1949,16 @@ int mse_disk_query_submit_filtered_f32(mse_searcher* s, mse_pq* pq, const mse_co
                                        mse_completion_queue* cq, mse_ticket** ticket_out) {
     SearchIn in{s, pq, c, g, nullptr, nullptr, queries_f32, nullptr, scales, nq, disable_pq, beamwidth, search_list, f};
     if (filtered_resolve(in, regime)) return -1;
+    return submit_f32(true, QueryCall{in, fused_out(k, ids, scores, n_visited, cmps, pq_cmps)}, user, cq, ticket_out);
+}
+
+int mse_disk_query_submit_grouped_f32(mse_searcher* s, mse_pq* pq, const mse_codes* c, const mse_graph* g, const mse_groups* groups, const mse_filter* f,
+                                      int regime, const float* queries_f32, const float* scales, size_t nq, int disable_pq, size_t beamwidth,
+                                      size_t search_list, size_t k, uint32_t* ids, int64_t* scores, uint32_t* n_visited, uint32_t* cmps,
+                                      uint32_t* pq_cmps, void* user, mse_completion_queue* cq, mse_ticket** ticket_out) {
+    SearchIn in{s, pq, c, g, nullptr, nullptr, queries_f32, nullptr, scales, nq, disable_pq, beamwidth, search_list, f};
+    if (f && filtered_resolve(in, regime)) return -1;
+    in.groups = groups; in.grouped = true;
     return submit_f32(true, QueryCall{in, fused_out(k, ids, scores, n_visited, cmps, pq_cmps)}, user, cq, ticket_out);
 }
 

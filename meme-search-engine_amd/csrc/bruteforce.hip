@@ -19,20 +19,58 @@ int ensure_base_norm(const mse_base* b, hipStream_t st) {
 
 // The pass itself: rows ids[0 .. n) (ascending; null = rows 0 .. n), and -- the filtered graph search's LIST regime -- the descriptor
 // bias of every listed row added to its score BEFORE the selection (bias: descriptors, their count, the pass's scales on the device).
+// With a grouping g (nq_pass <= dense_pass_queries(g->n_rows, 12)) it is the grouped search's dense pass: the scan leaves every eligible
+// row's score in level 0; the group step (group.hip) finds each group's best row and drops every other grouped row to INT64_MIN; the
+// tournament then ranks representatives before everything it has to, and the collapse of its k results removes the demoted rows that
+// filled a short list -- each comes after its own representative, which has the higher score or the lower id.  Level 0 holds list
+// positions when ids are given: the group step maps them through the list.  Representatives whose own score saturates to INT64_MIN tie
+// with the demoted rows and can be crowded off the list: a short list is completed from them afterwards (group.hip
+// dense_complete_kernel).  Grouped results go to row dst_rows[j] (device; null: j) of the outputs.
 int exact_pass_list(mse_searcher* s, int nq_pass, int k, uint64_t id_offset, int64_t* out_scores, uint32_t* out_ids, size_t out_stride,
-                    const uint32_t* ids, size_t n, const ListBias* bias) {
+                    const uint32_t* ids, size_t n, const ListBias* bias, const mse_groups* g, const uint32_t* dst_rows) {
     const mse_base* b = s->base;
+    hipStream_t st = s->stream;
     if (s->scores.ensure((size_t)nq_pass * n * 8)) return -1;
+    const bool tm = g && s->grp_timing;
+    if (tm) MSE_HIP_TRY(hipEventRecord(s->grp_ev[0], st));
     if (launch_scan_exact(b->dev, n, (int)b->d, s->q_stage.p, nq_pass, false, s->scores.as<int64_t>(), n, nullptr,
-                          s->n_cu, s->stream, ids)) return -1;
-    if (bias && launch_list_bias(ids, n, bias->desc, bias->n_desc, bias->scales_dev, nq_pass, s->scores.as<int64_t>(), n, s->stream)) return -1;
+                          s->n_cu, st, ids)) return -1;
+    if (bias && launch_list_bias(ids, n, bias->desc, bias->n_desc, bias->scales_dev, nq_pass, s->scores.as<int64_t>(), n, st)) return -1;
+    if (tm) MSE_HIP_TRY(hipEventRecord(s->grp_ev[1], st));
+    unsigned long long* best = nullptr;
+    uint32_t *best_id = nullptr, *n_sat = nullptr;
+    if (g && g->n_rows) {   // group table: best keys [nq][g_len] u64 | best ids [nq][g_len] u32 | saturated representatives [nq] u32
+        if (s->grp_best.ensure((size_t)nq_pass * g->n_rows * 12 + (size_t)nq_pass * 4)) return -1;
+        best = s->grp_best.as<unsigned long long>();
+        best_id = reinterpret_cast<uint32_t*>(best + (size_t)nq_pass * g->n_rows);
+        n_sat = best_id + (size_t)nq_pass * g->n_rows;
+        if (launch_dense_group_best(false, s->scores.p, n, n, ids, g->group_of, g->n_rows, nq_pass, best, best_id, n_sat, st)) return -1;
+    }
+    if (tm) MSE_HIP_TRY(hipEventRecord(s->grp_ev[2], st));
     if (s->sel_keys.ensure((size_t)nq_pass * k * 8)) return -1;
     uint32_t* sel = nullptr;
     LevelRef l0{KEY_I64, s->scores.p, n, 1, n, false, 0};
     if (descend(s, l0, nq_pass, k, &sel, s->sel_keys.p)) return -1;
-    if (ids && launch_map_positions(sel, (size_t)nq_pass * k, ids, s->stream)) return -1;
-    return launch_finalize(sel, s->sel_keys.as<int64_t>(), k, k, nq_pass, id_offset, out_scores, out_ids, out_stride,
-                           nullptr, 0, 0, 0, nullptr, nullptr, s->stream);
+    if (ids && launch_map_positions(sel, (size_t)nq_pass * k, ids, st)) return -1;
+    if (!g)
+        return launch_finalize(sel, s->sel_keys.as<int64_t>(), k, k, nq_pass, id_offset, out_scores, out_ids, out_stride,
+                               nullptr, 0, 0, 0, nullptr, nullptr, st);
+    if (s->grp_pos.ensure((size_t)nq_pass * k * 4) || s->grp_reps.ensure((size_t)nq_pass * 4)) return -1;
+    uint32_t *kept = s->grp_pos.as<uint32_t>(), *reps = s->grp_reps.as<uint32_t>();
+    if (launch_collapse(sel, (size_t)k, (size_t)k, g->group_of, g->n_rows, k, nq_pass, kept, reps, st)) return -1;
+    if (launch_collapse_gather(kept, k, sel, (size_t)k, s->sel_keys.p, (size_t)k, 8, nq_pass, id_offset, dst_rows, nullptr, out_scores, out_ids,
+                               out_stride, st)) return -1;
+    if (launch_dense_complete(s->scores.as<int64_t>(), n, n, ids, g->group_of, g->n_rows, best_id, n_sat, kept, reps, s->sel_keys.as<int64_t>(), k,
+                              nq_pass, id_offset, dst_rows, out_scores, out_ids, out_stride, st)) return -1;
+    if (tm) {
+        MSE_HIP_TRY(hipEventRecord(s->grp_ev[3], st));
+        MSE_HIP_TRY(hipEventSynchronize(s->grp_ev[3]));
+        for (int i = 0; i < 3; i++) {
+            float ms = 0.0f;
+            if (hipEventElapsedTime(&ms, s->grp_ev[i], s->grp_ev[i + 1]) == hipSuccess) s->grp_ms[i + 1] += ms;
+        }
+    }
+    return 0;
 }
 
 // exact mode, one pass of <= 8 queries: rows pick[0 .. nq_pass) of q_dev (null: its first nq_pass rows) are staged, zero-padded to 8, in
@@ -497,56 +535,14 @@ static int bruteforce_topk_host(mse_searcher* s, const mse_filter* f, const uint
 // a grouped entry point that was handed no grouping: an error of its own, in the grouping's place of the validation order
 static int null_groups(const mse_searcher* s) { return check_searcher(s) ? -1 : fail("null grouping"); }
 
-// The dense path for one pass of <= dense_pass_queries queries (rows pick[..] of q_dev, or its first nq_pass): the exact pass's scan
-// leaves every eligible row's score in level 0; the group step (group.hip) finds each group's best row and drops every other grouped
-// row to INT64_MIN; the tournament then ranks representatives before everything it has to, and the collapse of its k results removes
-// the demoted rows that filled a short list -- each comes after its own representative, which has the higher score or the lower id.
-// Under a filter level 0 holds list positions: the group step maps them through the filter's ids.  Results to row dst_rows[j] (device;
-// null: j) of the outputs.
-// Representatives whose own score saturates to INT64_MIN tie with the demoted rows and can be crowded off the list: a short list is
-// completed from them afterwards (group.hip dense_complete_kernel).
+// The dense path for one pass of <= dense_pass_queries queries (rows pick[..] of q_dev, or its first nq_pass): the queries staged, then
+// the exact pass with the grouping (exact_pass_list, which the filtered graph search's LIST regime shares), over all rows or the
+// filter's id list.  Results to row dst_rows[j] (device; null: j) of the outputs.
 static int grouped_dense_pass(mse_searcher* s, const mse_groups* g, const mse_filter* f, const uint16_t* q_dev, const uint32_t* pick, int nq_pass,
                               int k, uint64_t id_offset, const uint32_t* dst_rows, int64_t* out_scores, uint32_t* out_ids, size_t out_stride) {
-    const mse_base* b = s->base;
-    hipStream_t st = s->stream;
-    const uint32_t* list = f ? f->ids : nullptr;
-    const size_t n = f ? f->count : b->n;
     if (stage_exact_queries(s, q_dev, pick, nq_pass)) return -1;
-    if (s->scores.ensure((size_t)nq_pass * n * 8)) return -1;
-    const bool tm = s->grp_timing;
-    if (tm) MSE_HIP_TRY(hipEventRecord(s->grp_ev[0], st));
-    if (launch_scan_exact(b->dev, n, (int)b->d, s->q_stage.p, nq_pass, false, s->scores.as<int64_t>(), n, nullptr, s->n_cu, st, list)) return -1;
-    if (tm) MSE_HIP_TRY(hipEventRecord(s->grp_ev[1], st));
-    unsigned long long* best = nullptr;
-    uint32_t *best_id = nullptr, *n_sat = nullptr;
-    if (g->n_rows) {   // group table: best keys [nq][g_len] u64 | best ids [nq][g_len] u32 | saturated representatives [nq] u32
-        if (s->grp_best.ensure((size_t)nq_pass * g->n_rows * 12 + (size_t)nq_pass * 4)) return -1;
-        best = s->grp_best.as<unsigned long long>();
-        best_id = reinterpret_cast<uint32_t*>(best + (size_t)nq_pass * g->n_rows);
-        n_sat = best_id + (size_t)nq_pass * g->n_rows;
-        if (launch_dense_group_best(false, s->scores.p, n, n, list, g->group_of, g->n_rows, nq_pass, best, best_id, n_sat, st)) return -1;
-    }
-    if (tm) MSE_HIP_TRY(hipEventRecord(s->grp_ev[2], st));
-    if (s->sel_keys.ensure((size_t)nq_pass * k * 8) || s->grp_pos.ensure((size_t)nq_pass * k * 4) || s->grp_reps.ensure((size_t)nq_pass * 4)) return -1;
-    uint32_t* sel = nullptr;
-    LevelRef l0{KEY_I64, s->scores.p, n, 1, n, false, 0};
-    if (descend(s, l0, nq_pass, k, &sel, s->sel_keys.p)) return -1;
-    if (list && launch_map_positions(sel, (size_t)nq_pass * k, list, st)) return -1;
-    uint32_t *kept = s->grp_pos.as<uint32_t>(), *reps = s->grp_reps.as<uint32_t>();
-    if (launch_collapse(sel, (size_t)k, (size_t)k, g->group_of, g->n_rows, k, nq_pass, kept, reps, st)) return -1;
-    if (launch_collapse_gather(kept, k, sel, (size_t)k, s->sel_keys.p, (size_t)k, 8, nq_pass, id_offset, dst_rows, nullptr, out_scores, out_ids,
-                               out_stride, st)) return -1;
-    if (launch_dense_complete(s->scores.as<int64_t>(), n, n, list, g->group_of, g->n_rows, best_id, n_sat, kept, reps, s->sel_keys.as<int64_t>(), k,
-                              nq_pass, id_offset, dst_rows, out_scores, out_ids, out_stride, st)) return -1;
-    if (tm) {
-        MSE_HIP_TRY(hipEventRecord(s->grp_ev[3], st));
-        MSE_HIP_TRY(hipEventSynchronize(s->grp_ev[3]));
-        for (int i = 0; i < 3; i++) {
-            float ms = 0.0f;
-            if (hipEventElapsedTime(&ms, s->grp_ev[i], s->grp_ev[i + 1]) == hipSuccess) s->grp_ms[i + 1] += ms;
-        }
-    }
-    return 0;
+    return exact_pass_list(s, nq_pass, k, id_offset, out_scores, out_ids, out_stride, f ? f->ids : nullptr, f ? f->count : s->base->n, nullptr, g,
+                           dst_rows);
 }
 
 // the dense path for the nq queries at q_dev, pass by pass; results to rows dst[..] of the outputs (null: in place)

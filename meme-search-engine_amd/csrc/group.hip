@@ -1,4 +1,5 @@
-// Row groupings of the grouped ("collapse") search (include/mse.h mse_groups): one result per group.  Three device pieces:
+// Row groupings of the grouped ("collapse") search (include/mse.h mse_groups): one result per group.  Four device pieces (the fourth,
+// the group step over the graph request path's unranked visited lists, is described where it stands):
 //   1. validation and count of a grouping: the largest non-NONE id, the NONE rows, the distinct ids (presence bitmap + popcount);
 //   2. the order-preserving collapse of a ranked candidate list: one workgroup per query, an LDS open-addressing table keyed by group in
 //      which every entry publishes its rank by atomic min; an entry whose own rank stands is its group's representative; the survivors
@@ -285,7 +286,137 @@ __global__ __launch_bounds__(256) void dense_complete_kernel(const int64_t* __re
     }
 }
 
+// ---- 4. group step over an UNRANKED visited list (graph request path, beam_search.hip read_back_fused) ---------------------------------
+// One workgroup per query over vis_ids / vis_scores [nq][cap], n = min(n_visited[q], cap) records in visit order, holes (ID_NONE,
+// INT64_MIN) where the de-duplication removed a record.  Of every group that has a live record the best one by (score desc, id asc)
+// stays; every other record of the group becomes a hole in place, exactly as dedup_filter_batch_kernel leaves one, so the selection that
+// follows needs no change.  Records of group NONE or past the grouping, holes, and entries at or past n are not touched.
+// Open-addressing table keyed by group (collapse_kernel's multiplicative hash, linear probing), 16 bytes per slot -- best key u64 | group
+// u32 | id u32, three arrays -- of which a query clears and uses only the power of two of at least 2 n slots (64 at least): at most n keys
+// are ever inserted, so a probe always ends at the key or at a free slot.  A slot is claimed by compare-and-swap; the group's best score
+// is an atomic max of the order-preserving key; after a barrier, an atomic min of the id among the records that hold the maximum; after
+// a second barrier a record stays only if its slot holds its id.  Integer max and min do not depend on arrival order: bit-reproducible.
+// GLOBAL = false: the table in dynamic LDS (cap <= 4096).  true: in global memory, slots_cap slots per query of the launch; its words
+// are read and cleared through agent-scope atomics, so that no wave reads a stale cached line after another wave's atomic.
+constexpr int VG_THREADS = 256;
+constexpr size_t VG_LDS_CAP = 4096;                       // longest list whose table (8192 slots, 128 KiB) fits dynamic LDS
+constexpr size_t VG_TABLE_BUDGET = (size_t)32 << 20;      // global tables of one launch (a query chunk), bytes
+
+template <bool GLOBAL, typename T>
+__device__ __forceinline__ T vg_load(const T* p) {
+    if (GLOBAL) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return *p;
+}
+template <bool GLOBAL, typename T>
+__device__ __forceinline__ void vg_store(T* p, T v) {
+    if (GLOBAL) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else *p = v;
+}
+
+template <bool GLOBAL>
+__device__ __forceinline__ void visited_group_body(uint32_t* __restrict__ ids, long long* __restrict__ scores, uint32_t n,
+                                                   const uint32_t* __restrict__ group_of, size_t g_len, uint32_t bits,
+                                                   unsigned long long* t_best, uint32_t* t_key, uint32_t* t_id) {
+    const uint32_t t = threadIdx.x, slots = 1u << bits, mask = slots - 1u;
+    for (uint32_t i = t; i < slots; i += VG_THREADS) {
+        vg_store<GLOBAL>(&t_best[i], 0ull);
+        vg_store<GLOBAL>(&t_key[i], GROUP_NONE);
+        vg_store<GLOBAL>(&t_id[i], 0xFFFFFFFFu);
+    }
+    __syncthreads();
+    auto group = [&](uint32_t id) { return id != ID_NONE && id < g_len ? group_of[id] : GROUP_NONE; };
+    for (uint32_t i = t; i < n; i += VG_THREADS) {   // claim the group's slot, publish the score
+        const uint32_t g = group(ids[i]);
+        if (g == GROUP_NONE) continue;
+        uint32_t h = (g * 2654435761u) >> (32 - bits);
+        for (;;) {
+            const uint32_t prev = atomicCAS(&t_key[h], GROUP_NONE, g);
+            if (prev == GROUP_NONE || prev == g) break;
+            h = (h + 1) & mask;
+        }
+        const unsigned long long v = sortable_i64(scores[i]);
+        if (vg_load<GLOBAL>(&t_best[h]) < v) atomicMax(&t_best[h], v);   // (the slot only grows: a stale, lower read merely costs the atomic)
+    }
+    __syncthreads();
+    for (uint32_t i = t; i < n; i += VG_THREADS) {   // among the records that hold the maximum, the lowest id
+        const uint32_t id = ids[i], g = group(id);
+        if (g == GROUP_NONE) continue;
+        uint32_t h = (g * 2654435761u) >> (32 - bits);
+        while (vg_load<GLOBAL>(&t_key[h]) != g) h = (h + 1) & mask;   // (entered above)
+        if (sortable_i64(scores[i]) == vg_load<GLOBAL>(&t_best[h]) && vg_load<GLOBAL>(&t_id[h]) > id) atomicMin(&t_id[h], id);
+    }
+    __syncthreads();
+    for (uint32_t i = t; i < n; i += VG_THREADS) {   // everything else of the group leaves the list
+        const uint32_t id = ids[i], g = group(id);
+        if (g == GROUP_NONE) continue;
+        uint32_t h = (g * 2654435761u) >> (32 - bits);
+        while (vg_load<GLOBAL>(&t_key[h]) != g) h = (h + 1) & mask;
+        if (vg_load<GLOBAL>(&t_id[h]) != id) { ids[i] = ID_NONE; scores[i] = (long long)INT64_MIN; }
+    }
+}
+
+template <bool GLOBAL>
+__global__ __launch_bounds__(VG_THREADS) void visited_group_kernel(uint32_t* __restrict__ vis_ids, long long* __restrict__ vis_scores, size_t cap,
+                                                                   const uint32_t* __restrict__ n_visited, const uint32_t* __restrict__ group_of,
+                                                                   size_t g_len, unsigned long long* __restrict__ table, uint32_t slots_cap) {
+    extern __shared__ __attribute__((aligned(16))) char vg_smem[];
+    const size_t q = blockIdx.x;
+    const uint32_t n = (uint32_t)min((size_t)n_visited[q], cap);
+    uint32_t bits = 6;
+    while ((1u << bits) < 2u * n) bits++;   // <= slots_cap: n <= cap
+    // best keys | groups | ids of the slots in use, packed at the front of the query's table (two call sites, so that each inlined copy
+    // of the body knows its address space: LDS atomics stay ds_ instructions)
+    if constexpr (GLOBAL) {
+        char* tab = reinterpret_cast<char*>(table) + q * (size_t)slots_cap * 16;
+        visited_group_body<true>(vis_ids + q * cap, vis_scores + q * cap, n, group_of, g_len, bits, reinterpret_cast<unsigned long long*>(tab),
+                                 reinterpret_cast<uint32_t*>(tab + ((size_t)8 << bits)), reinterpret_cast<uint32_t*>(tab + ((size_t)12 << bits)));
+    } else {
+        visited_group_body<false>(vis_ids + q * cap, vis_scores + q * cap, n, group_of, g_len, bits, reinterpret_cast<unsigned long long*>(vg_smem),
+                                  reinterpret_cast<uint32_t*>(vg_smem + ((size_t)8 << bits)), reinterpret_cast<uint32_t*>(vg_smem + ((size_t)12 << bits)));
+    }
+}
+
+// table slots a list of up to `cap` records may need: the power of two of at least 2 cap (64 at least)
+size_t visited_group_slots(size_t cap) {
+    size_t slots = 64;
+    while (slots < 2 * cap) slots *= 2;
+    return slots;
+}
+
 }  // namespace
+
+// queries of one launch: all of them with the table in LDS, else what the fixed table budget holds (the way launch_dedup_batch chunks)
+static size_t visited_group_chunk_queries(size_t nq, size_t cap) {
+    if (cap <= VG_LDS_CAP) return nq;
+    return std::max<size_t>(1, std::min(nq, VG_TABLE_BUDGET / (visited_group_slots(cap) * 16)));
+}
+
+size_t visited_group_scratch_bytes(size_t nq, size_t cap) {
+    return cap <= VG_LDS_CAP ? 0 : visited_group_chunk_queries(nq, cap) * visited_group_slots(cap) * 16;
+}
+
+int launch_visited_group(uint32_t* vis_ids, long long* vis_scores, size_t cap, const uint32_t* n_visited, size_t nq, const uint32_t* group_of,
+                         size_t g_len, void* table, hipStream_t stream) {
+    if (nq == 0 || cap == 0) return 0;
+    if (cap > ((size_t)1 << 30)) return fail("visited_group: list too long");
+    const size_t slots = visited_group_slots(cap);
+    if (cap <= VG_LDS_CAP) {
+        MSE_DYN_LDS(visited_group_kernel<false>, slots * 16);
+        hipLaunchKernelGGL(visited_group_kernel<false>, dim3((unsigned)nq), dim3(VG_THREADS), slots * 16, stream, vis_ids, vis_scores, cap, n_visited,
+                           group_of, g_len, (unsigned long long*)nullptr, (uint32_t)slots);
+        MSE_HIP_TRY(hipGetLastError());
+        return 0;
+    }
+    if (!table) return fail("visited_group: no table");
+    const size_t chunk = visited_group_chunk_queries(nq, cap);
+    for (size_t q0 = 0; q0 < nq; q0 += chunk) {   // chunks run one after the other on the stream: they share the table
+        const size_t m = std::min(chunk, nq - q0);
+        hipLaunchKernelGGL(visited_group_kernel<true>, dim3((unsigned)m), dim3(VG_THREADS), 0, stream, vis_ids + q0 * cap, vis_scores + q0 * cap, cap,
+                           n_visited + q0, group_of, g_len, static_cast<unsigned long long*>(table), (uint32_t)slots);
+        MSE_HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
 
 int launch_groups_validate(const uint32_t* group_of, size_t n_rows, uint32_t* present, unsigned long long* stats, hipStream_t stream) {
     if (n_rows == 0) return 0;

@@ -1,5 +1,5 @@
-// C ABI (include/mse.h): row groupings as objects, and the collapse kernel's test hook.  The kernels are in group.hip; the searches that
-// take a grouping are in bruteforce.hip and api_pq.hip.
+// C ABI (include/mse.h): row groupings as objects, and the test hooks of the collapse kernel and of the graph request path's group step.
+// The kernels are in group.hip; the searches that take a grouping are in bruteforce.hip, api_pq.hip and beam_search.hip.
 #include "../../include/mse.h"
 #include "runtime.h"
 #include <algorithm>
@@ -128,6 +128,27 @@ int mse_debug_collapse_topk(mse_searcher* s, const mse_groups* g, const uint32_t
                         s->grp_reps.as<uint32_t>(), s->stream)) return -1;
     MSE_HIP_TRY(hipMemcpyAsync(kept_pos, s->grp_pos.p, nq * k * 4, hipMemcpyDeviceToHost, s->stream));
     MSE_HIP_TRY(hipMemcpyAsync(n_reps, s->grp_reps.p, nq * 4, hipMemcpyDeviceToHost, s->stream));
+    MSE_HIP_TRY(hipStreamSynchronize(s->stream));
+    return 0;
+}
+
+// test hook: the group step of the graph request path alone (group.hip launch_visited_group) over caller-supplied visited lists, in the
+// buffers the request path keeps them in; the table form -- LDS or global memory -- is chosen by cap exactly as read_back_fused chooses it
+int mse_debug_visited_collapse(mse_searcher* s, const mse_groups* g, uint32_t* ids, int64_t* scores, size_t cap, const uint32_t* n_visited, size_t nq) {
+    if (!s) return fail("null searcher");
+    if (!g) return fail("null grouping");
+    if (!ids || !scores || !n_visited) return fail("visited_collapse: null array");
+    if (cap == 0 || cap > 65536) return fail("visited_collapse: 1..65536 records per list");
+    if (nq == 0 || nq > 65536) return fail("visited_collapse: 1..65536 queries");
+    DevBuf &vi = s->pool[8], &vs = s->pool[9], &cnt = s->pool[10], &gt = s->pool[15];
+    const size_t table_bytes = visited_group_scratch_bytes(nq, cap);
+    if (vi.ensure(nq * cap * 4) || vs.ensure(nq * cap * 8) || cnt.ensure(nq * 4) || (table_bytes && gt.ensure(table_bytes))) return -1;
+    MSE_HIP_TRY(hipMemcpyAsync(vi.p, ids, nq * cap * 4, hipMemcpyHostToDevice, s->stream));
+    MSE_HIP_TRY(hipMemcpyAsync(vs.p, scores, nq * cap * 8, hipMemcpyHostToDevice, s->stream));
+    MSE_HIP_TRY(hipMemcpyAsync(cnt.p, n_visited, nq * 4, hipMemcpyHostToDevice, s->stream));
+    if (launch_visited_group(vi.as<uint32_t>(), vs.as<long long>(), cap, cnt.as<uint32_t>(), nq, g->group_of, g->n_rows, gt.p, s->stream)) return -1;
+    MSE_HIP_TRY(hipMemcpyAsync(ids, vi.p, nq * cap * 4, hipMemcpyDeviceToHost, s->stream));
+    MSE_HIP_TRY(hipMemcpyAsync(scores, vs.p, nq * cap * 8, hipMemcpyDeviceToHost, s->stream));
     MSE_HIP_TRY(hipStreamSynchronize(s->stream));
     return 0;
 }

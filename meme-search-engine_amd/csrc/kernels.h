@@ -222,6 +222,13 @@ int launch_dense_complete(const int64_t* scores, size_t stride, size_t n, const 
                           const uint32_t* best_id, const uint32_t* n_sat, const uint32_t* kept_pos, const uint32_t* n_reps, const int64_t* sel_keys,
                           int k, int nq, uint64_t id_offset, const uint32_t* dst_rows, int64_t* out_scores, uint32_t* out_ids, size_t out_stride,
                           hipStream_t stream);
+// The group step of the graph request path over UNRANKED visited lists (vis_ids / vis_scores [nq][cap], min(n_visited[q], cap) records,
+// holes (ID_NONE, INT64_MIN) allowed anywhere): of every group the best live record by (score desc, id asc) stays, every other record of
+// the group becomes a hole in place; records of group NONE or at / past g_len and entries past the list are not touched.  cap <= 4096: the
+// table lives in LDS and `table` is not read; longer lists: visited_group_scratch_bytes(nq, cap) bytes of scratch, run in query chunks
+size_t visited_group_scratch_bytes(size_t nq, size_t cap);
+int launch_visited_group(uint32_t* vis_ids, long long* vis_scores, size_t cap, const uint32_t* n_visited, size_t nq, const uint32_t* group_of,
+                         size_t g_len, void* table, hipStream_t stream);
 
 // ---- graph_build.hip: what graph_delete.hip shares with the build ---------------------------------------------------------------
 // robust_prune (lib.rs:227-285), one workgroup per candidate list: list k is (ci, cs)[k * stride ..][0 .. counts[k]) in HBM, its point

@@ -221,9 +221,11 @@ int bruteforce_topk_dev(mse_searcher* s, const mse_filter* f, const void* querie
 // One exact pass of <= 8 queries (staged, padded, in s->q_stage) over the rows ids[0 .. n) -- ascending; null: rows 0 .. n -- and the
 // exact top-k of each: i64 scores in the reference order, (score desc, id asc), padding INT64_MIN / ID_NONE; a row that is not listed is
 // absent.  bias (optional, needs ids): the descriptor product of every listed row is added to its score before the selection.
+// g (optional; then nq_pass <= dense_pass_queries(g->n_rows, 12)): one result per group of g, the grouped search's dense pass over these
+// rows and scores, into row dst_rows[j] (device; null: j) of the outputs.
 struct ListBias { const uint8_t* desc; int n_desc; const float* scales_dev; };   // scales_dev: [nq_pass][n_desc] on the device
 int exact_pass_list(mse_searcher* s, int nq_pass, int k, uint64_t id_offset, int64_t* out_scores, uint32_t* out_ids, size_t out_stride,
-                    const uint32_t* ids, size_t n, const ListBias* bias);
+                    const uint32_t* ids, size_t n, const ListBias* bias, const mse_groups* g = nullptr, const uint32_t* dst_rows = nullptr);
 // a grouping may be used on base b: same device, no longer than the rows (group_api.hip); 0, or -1 with the error set
 int check_groups(const mse_base* b, const mse_groups* g);
 // the dense path's scratch is bounded: queries one dense pass may take (1 .. 8) with a group table of g_len entries of `bytes` bytes each

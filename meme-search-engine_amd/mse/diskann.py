@@ -503,7 +503,7 @@ def coalescer_stats(dgraph):
 
 
 def disk_query_topk(searcher: Searcher, quantizer, codes, dgraph, queries, k, starts=None, luts=None, descriptor_scales=None,
-                    disable_pq=False, beamwidth=1, search_list=1000, filter=None, regime="auto"):
+                    disable_pq=False, beamwidth=1, search_list=1000, filter=None, regime="auto", groups=None):
     """The request path of query_disk_index (:436-540) for a batch in one device submission: entry node (by the graph's entry table
     when `starts` is None), greedy_search, the visited records ordered by exact score and cut to the first k.  f16 query rows in
     (a host array, or `(device_pointer, nq)` for rows already on the device),
@@ -511,7 +511,9 @@ def disk_query_topk(searcher: Searcher, quantizer, codes, dgraph, queries, k, st
     same start nodes.  Rows with fewer than k visited records are padded with ID_NONE / INT64_MIN.
     filter (a RowFilter): only rows it allows (and that have a url) are returned.  regime "graph": the same traversal at search_list,
     disallowed nodes walked through but not returned; "list": the exact k best of the eligible rows, no traversal (n_visited = cmps =
-    eligible rows); "auto": whichever filtered_plan(len(graph), filter.count, search_list, dedup on) names, at its search_list."""
+    eligible rows); "auto": whichever filtered_plan(len(graph), filter.count, search_list, dedup on) names, at its search_list.
+    groups (a RowGroups, by row id): one result per group -- of the records this search visited, ranked as above, the first of every
+    group; fewer than k groups among them show as padding (ask again with a longer search_list).  With or without a filter."""
     from_f32 = False
     if isinstance(queries, tuple):      # (device pointer, nq): f16 rows already resident on the searcher's device, contiguous
         q_ptr, nq = C.cast(C.c_void_p(int(queries[0])), C.POINTER(C.c_uint16)), int(queries[1])
@@ -543,7 +545,14 @@ def disk_query_topk(searcher: Searcher, quantizer, codes, dgraph, queries, k, st
     head = (searcher._h, quantizer._h if quantizer is not None else None, codes._h if codes is not None else None, dgraph._h,
             _p(st, C.c_uint32) if st is not None else None, q_ptr)
     scp = _p(sc, C.c_float) if sc is not None else None
-    if filter is not None:
+    if groups is not None:
+        ghead = head[:4] + (groups._h, filter._h if filter is not None else None, _regime(regime)) + head[4:]
+        if from_f32:
+            check(ffi.lib().mse_disk_query_topk_grouped_f32(*ghead, scp, *tail), "disk_query_topk_grouped_f32")
+        else:
+            check(ffi.lib().mse_disk_query_topk_grouped(*ghead, _p(tables, C.c_float) if tables is not None else None, scp, *tail),
+                  "disk_query_topk_grouped")
+    elif filter is not None:
         fhead = head[:4] + (filter._h, _regime(regime)) + head[4:]
         if from_f32:
             check(ffi.lib().mse_disk_query_topk_filtered_f32(*fhead, scp, *tail), "disk_query_topk_filtered_f32")
@@ -567,12 +576,13 @@ class QueryTickets:
     completion queue of its own."""
 
     def __init__(self, searcher: Searcher, quantizer, codes, dgraph, k, disable_pq=False, beamwidth=1, search_list=1000, own_queue=False,
-                 filter=None, regime="auto"):
+                 filter=None, regime="auto", groups=None):
         """own_queue=True: a completion queue of this object's own (mse_completion_queue_*): its requests come back through its
         collect() / fileno() and nowhere else -- one per event loop of a host that runs several.
-        filter / regime: as disk_query_topk; the filter is kept alive by this object (copy=False is for unfiltered requests)."""
+        filter / regime / groups: as disk_query_topk; filter and grouping are kept alive by this object (copy=False is for requests
+        with neither)."""
         import threading
-        self._filter, self._regime = filter, _regime(regime)
+        self._filter, self._regime, self._groups = filter, _regime(regime), groups
         self._s, self._pq, self._codes, self._g = searcher, quantizer, codes, dgraph
         self.k, self.disable_pq, self.beamwidth, self.search_list = int(k), bool(disable_pq), int(beamwidth), int(search_list)
         self._q = None
@@ -621,12 +631,15 @@ class QueryTickets:
             self._reg["out"][tag] = (key if key is not None else tag, ids, scores) + (() if copy else (q, sc))   # before the request can complete
         t = C.c_void_p()
         try:
-            if self._filter is not None and not copy:
-                raise MseError("QueryTickets: copy=False is not available with a filter")
+            if (self._filter is not None or self._groups is not None) and not copy:
+                raise MseError("QueryTickets: copy=False is not available with a filter or a grouping")
             fn = ffi.lib().mse_disk_query_submit_f32 if copy else ffi.lib().mse_disk_query_submit_f32_nocopy
             flt = ()
             if self._filter is not None:
                 fn, flt = ffi.lib().mse_disk_query_submit_filtered_f32, (self._filter._h, self._regime)
+            if self._groups is not None:
+                fn = ffi.lib().mse_disk_query_submit_grouped_f32
+                flt = (self._groups._h, self._filter._h if self._filter is not None else None, self._regime)
             check(fn(self._s._h, self._pq._h if self._pq is not None else None,
                                                       self._codes._h if self._codes is not None else None, self._g._h, *flt, _p(q, C.c_float),
                                                       _p(sc, C.c_float) if sc is not None else None, nq, int(self.disable_pq), self.beamwidth,

@@ -238,6 +238,13 @@ SIGNATURES = {
                                                    u32p, u32p]),
     "mse_disk_query_submit_filtered_f32": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, f32p, f32p, sz, C.c_int, sz, sz, sz, u32p, i64p, u32p, u32p,
                                                      u32p, vp, vp, C.POINTER(vp)]),
+    "mse_disk_query_topk_grouped": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, u32p, u16p, f32p, f32p, sz, C.c_int, sz, sz, sz, u32p, i64p, u32p,
+                                              u32p, u32p]),
+    "mse_disk_query_topk_grouped_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, u32p, f32p, f32p, sz, C.c_int, sz, sz, sz, u32p, i64p, u32p,
+                                                  u32p, u32p]),
+    "mse_disk_query_submit_grouped_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, f32p, f32p, sz, C.c_int, sz, sz, sz, u32p, i64p, u32p, u32p,
+                                                    u32p, vp, vp, C.POINTER(vp)]),
+    "mse_debug_visited_collapse": (C.c_int, [vp, vp, u32p, i64p, sz, u32p, sz]),
     "mse_graph_new": (vp, [sz, sz]),
     "mse_graph_to_host": (C.c_int, [vp, u32p, u32p]),
     "mse_graph_len": (sz, [vp]),
