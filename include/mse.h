@@ -1108,7 +1108,8 @@ int mse_siglip_finalize(mse_siglip* m);                              /* fails if
  * time) and the same image inside a larger batch (index time) agree to bf16 rounding (cosine within 1e-4; both within 1e-3 of
  * the fp32 model), not bit for bit.  A pipeline that needs index/query bit-equality sets MSE_SIGLIP_NOSMALL=1 in the
  * environment before mse_siglip_create (read once, there): calls of every size, one image included, then return the rows of
- * a larger batch bit for bit. */
+ * a larger batch bit for bit -- as long as no attention row raises its running maximum after its first 32 keys (true of Gaussian-regime
+ * weights; with sharper logits calls of 1-2 images differ from larger batches in the last bits: DESIGN.md 3.4, "Open"). */
 int mse_siglip_encode_image(mse_siglip* m, const void* images, int dtype, int on_device, int batch, int normalize,
                             float* out_f32, uint16_t* out_f16);
 /* Same from decoded RGB bytes [batch][H][W][3] (host): the ToTensor / Normalize(0.5, 0.5) / .half() / stack steps of the
@@ -1131,6 +1132,15 @@ int mse_debug_gemm_ms(int M, int N, int K, int ablation, int iters, float* ms_ou
  * elements that differ from the large-batch kernels' result, and those more than two bf16 steps apart (the kernels differ in
  * summation order only: the second word must be 0). */
 int mse_debug_gemm_small(int rows, int N, int K, int epi, int variant, int iters, float* ms_out, uint64_t* n_diff);
+/* test hooks for the towers' attention kernels alone (head width 72), through the launchers the towers call, so the tiling is chosen
+ * from (B, heads, tokens) as in a forward pass.  Self attention: q / k / v host fp32 [B][heads][tokens][72], rounded to bf16 (nearest
+ * even) and laid out as the QKV epilogue leaves them (token stride = tokens rounded up to 32, padding zero); out host fp32
+ * [B][tokens][heads * 72] (the bf16 result widened).  flags bit 0: the padding (K rows, q rows and V columns from `tokens` to the
+ * stride) holds finite garbage of magnitude up to 1e4 instead of zeros -- the result must not change.
+ * Pooling attention (MAP head): qlat host fp32 [heads * 72], k / v host fp32 [B][tokens][heads * 72] (rounded to bf16); out host fp32
+ * [B][heads * 72]. */
+int mse_debug_siglip_attention(const float* q, const float* k, const float* v, int B, int heads, int tokens, int flags, float* out);
+int mse_debug_siglip_pool_attention(const float* qlat, const float* k, const float* v, int B, int heads, int tokens, float* out);
 
 /* ---- SigLIP text tower: `model.encode_text(tokens)` + normalisation + fp16 serialisation
  * (clip_server.py:98-99,128-131,166).  open_clip's TextTransformer is a third-party dependency not vendored in

@@ -446,6 +446,99 @@ int mse_debug_gemm_small(int rows, int N, int K, int epi, int variant, int iters
     return 0;
 }
 
+namespace {
+uint16_t host_bf16(float f) {   // round to nearest even (finite inputs)
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+float host_bf16_to_f32(uint16_t h) {
+    const uint32_t u = (uint32_t)h << 16;
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
+// finite garbage for the padding of the attention operands: bf16 values of magnitude up to 1e4 from a counter hash
+uint16_t poison_bf16(size_t i, uint32_t seed) {
+    uint32_t h = (uint32_t)i * 2654435761u + seed;
+    h ^= h >> 15; h *= 2246822519u; h ^= h >> 13; h *= 3266489917u; h ^= h >> 16;
+    return host_bf16((float)(int32_t)h * (1.0e4f / 2147483648.0f));
+}
+constexpr int DBG_DH = 72, DBG_DH_PAD = 96, DBG_DV_PAD = 80;   // the towers' head geometry (Encoder: dh, dh_pad, dv_pad)
+}  // namespace
+
+// test hook for the self-attention launchers: q / k / v are host fp32 [B][heads][tokens][72], rounded here to bf16 (nearest even) and
+// laid out as the QKV epilogue leaves them (q rows of 96, K rows of attention_k_stride(), Vt [80][n_pad], n_pad = tokens rounded up to
+// 32, everything else zero); launch_vt_ones_row, then launch_attention exactly as run_blocks calls it, so the tiling is chosen from
+// (B, heads, tokens) as in the towers.  out: host fp32 [B][tokens][heads * 72], the bf16 result widened.
+// flags bit 0: fill the padding -- K rows, q rows and Vt columns (rows 0..71) tokens .. n_pad - 1 -- with finite garbage of magnitude
+// up to 1e4 instead of zeros; the row-sum row stays ones.
+// K and Vt carry `heads` further zeroed matrices like the engines' buffers (BH + H): with n_pad % 64 == 32 the kernel's last 64-key
+// stage reads 32 K rows (7 KiB) past every matrix and 64 bytes past every Vt row, the last matrix's included.
+int mse_debug_siglip_attention(const float* q, const float* k, const float* v, int B, int heads, int tokens, int flags, float* out) {
+    if (!q || !k || !v || !out) return fail("debug siglip attention: null argument");
+    if (B <= 0 || heads <= 0 || tokens <= 0 || (flags & ~1) || (size_t)B * heads * tokens > ((size_t)1 << 22))
+        return fail("debug siglip attention: B, heads, tokens > 0, B * heads * tokens <= 2^22, flags 0 / 1");
+    const size_t T = tokens, NP = round_up(T, 32), BH = (size_t)B * heads, KS = attention_k_stride();
+    const size_t D = (size_t)heads * DBG_DH;
+    std::vector<uint16_t> hq(BH * NP * DBG_DH_PAD, 0), hk((BH + heads) * NP * KS, 0), hvt((BH + heads) * DBG_DV_PAD * NP, 0);
+    for (size_t bh = 0; bh < BH; bh++)
+        for (size_t t = 0; t < NP; t++)
+            for (size_t e = 0; e < (size_t)DBG_DH; e++) {
+                const size_t qi = (bh * NP + t) * DBG_DH_PAD + e, ki = (bh * NP + t) * KS + e, vi = (bh * DBG_DV_PAD + e) * NP + t;
+                if (t < T) {
+                    const size_t src = (bh * T + t) * DBG_DH + e;
+                    hq[qi] = host_bf16(q[src]); hk[ki] = host_bf16(k[src]); hvt[vi] = host_bf16(v[src]);
+                } else if (flags & 1) {
+                    hq[qi] = poison_bf16(qi, 0x51u); hk[ki] = poison_bf16(ki, 0x4bu); hvt[vi] = poison_bf16(vi, 0x56u);
+                }
+            }
+    DevBuf dq, dk, dvt, dout;
+    const size_t out_elems = (size_t)B * NP * D;
+    if (dq.ensure(hq.size() * 2) || dk.ensure(hk.size() * 2) || dvt.ensure(hvt.size() * 2) || dout.ensure(out_elems * 2)) return -1;
+    MSE_HIP_TRY(hipMemcpy(dq.p, hq.data(), hq.size() * 2, hipMemcpyHostToDevice));
+    MSE_HIP_TRY(hipMemcpy(dk.p, hk.data(), hk.size() * 2, hipMemcpyHostToDevice));
+    MSE_HIP_TRY(hipMemcpy(dvt.p, hvt.data(), hvt.size() * 2, hipMemcpyHostToDevice));
+    MSE_HIP_TRY(hipMemset(dout.p, 0, out_elems * 2));
+    if (launch_vt_ones_row(dvt.as<uint16_t>(), BH + heads, DBG_DH, DBG_DV_PAD, (int)NP, nullptr)) return -1;
+    if (launch_attention(dq.as<uint16_t>(), dk.as<uint16_t>(), dvt.as<uint16_t>(), B, heads, tokens, (int)NP, DBG_DH, DBG_DH_PAD, DBG_DV_PAD,
+                         dout.as<uint16_t>(), (int)D, (int)NP, nullptr)) return -1;
+    MSE_HIP_TRY(hipDeviceSynchronize());
+    std::vector<uint16_t> ho(out_elems);
+    MSE_HIP_TRY(hipMemcpy(ho.data(), dout.p, out_elems * 2, hipMemcpyDeviceToHost));
+    for (size_t b = 0; b < (size_t)B; b++)
+        for (size_t t = 0; t < T; t++)
+            for (size_t c = 0; c < D; c++) out[(b * T + t) * D + c] = host_bf16_to_f32(ho[(b * NP + t) * D + c]);
+    return 0;
+}
+
+// test hook for the pooling attention (MAP head): qlat host fp32 [heads * 72] (used as it is, the kernel reads it in fp32); k / v host
+// fp32 [B][tokens][heads * 72], rounded to bf16 and interleaved into the kv projection's layout ([B * n_pad][2 * D], k in columns
+// [0, D), v in [D, 2D), padding rows zero); launch_pool_attention as the image tower calls it.  out: host fp32 [B][heads * 72].
+int mse_debug_siglip_pool_attention(const float* qlat, const float* k, const float* v, int B, int heads, int tokens, float* out) {
+    if (!qlat || !k || !v || !out) return fail("debug siglip pool attention: null argument");
+    if (B <= 0 || heads <= 0 || tokens <= 0 || tokens > 8192 || (size_t)B * heads * tokens > ((size_t)1 << 22))
+        return fail("debug siglip pool attention: B, heads > 0, 0 < tokens <= 8192, B * heads * tokens <= 2^22");
+    const size_t T = tokens, NP = round_up(T, 32), D = (size_t)heads * DBG_DH;
+    std::vector<uint16_t> hkv((size_t)B * NP * 2 * D, 0);
+    for (size_t b = 0; b < (size_t)B; b++)
+        for (size_t t = 0; t < T; t++)
+            for (size_t c = 0; c < D; c++) {
+                hkv[(b * NP + t) * 2 * D + c] = host_bf16(k[(b * T + t) * D + c]);
+                hkv[(b * NP + t) * 2 * D + D + c] = host_bf16(v[(b * T + t) * D + c]);
+            }
+    DevBuf dkv, dql, dout;
+    if (dkv.ensure(hkv.size() * 2) || dql.ensure(D * 4) || dout.ensure((size_t)B * D * 4)) return -1;
+    MSE_HIP_TRY(hipMemcpy(dkv.p, hkv.data(), hkv.size() * 2, hipMemcpyHostToDevice));
+    MSE_HIP_TRY(hipMemcpy(dql.p, qlat, D * 4, hipMemcpyHostToDevice));
+    MSE_HIP_TRY(hipMemset(dout.p, 0, (size_t)B * D * 4));
+    if (launch_pool_attention(dkv.as<uint16_t>(), (int)(2 * D), dql.as<float>(), B, heads, DBG_DH, tokens, (int)NP, dout.as<float>(), (int)D,
+                              nullptr)) return -1;
+    MSE_HIP_TRY(hipDeviceSynchronize());
+    MSE_HIP_TRY(hipMemcpy(out, dout.p, (size_t)B * D * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // test hook: the residual stream ([batch*tokens][emb] fp32) as left by the last forward (after the last block)
 int mse_siglip_debug_residual(mse_siglip* m, float* out) {
     if (!m || !m->last_batch) return fail("siglip: no forward has run");

@@ -1820,8 +1820,11 @@ __global__ __launch_bounds__(NW * 64, 2) void attention64_kernel(const uint16_t*
     bf16x8 qf[QT][3];
 #pragma unroll
     for (int qt = 0; qt < QT; qt++) {
+        // lanes past the last token repeat its row: their result is never stored, but their scores take part in the wave's vote on the
+        // running maximum below, so what the padding rows of q hold would otherwise decide WHEN the real rows of the wave refresh theirs
+        // (the last bits of rows 720 .. 728 of 729)
         int qrow = q0 + qt * 16 + i;
-        if (qrow >= n_pad) qrow = n_pad - 1;
+        if (qrow >= tokens) qrow = tokens - 1;
         const uint16_t* qp = q + ((size_t)bh * n_pad + qrow) * dh_pad;
 #pragma unroll
         for (int ks = 0; ks < 3; ks++) qf[qt][ks] = as_bf8(*reinterpret_cast<const u32x4*>(qp + ks * 32 + g * 8));

@@ -286,6 +286,8 @@ SIGNATURES = {
     "mse_siglip_debug_residual": (C.c_int, [vp, f32p]),
     "mse_debug_gemm_ms": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p]),
     "mse_debug_gemm_small": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.POINTER(C.c_uint64)]),
+    "mse_debug_siglip_attention": (C.c_int, [f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, f32p]),
+    "mse_debug_siglip_pool_attention": (C.c_int, [f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, f32p]),
     "mse_siglip_text_create": (vp, [vp]),
     "mse_siglip_text_destroy": (None, [vp]),
     "mse_siglip_text_n_weights": (C.c_int, [vp]),

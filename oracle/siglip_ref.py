@@ -98,8 +98,10 @@ def _mlp(x, sd, prefix, gelu):   # model.py:13-24 (residual added by the caller)
     return h @ sd[prefix + "fc2.weight"].T + sd[prefix + "fc2.bias"]
 
 
-def encode_image(images, sd, cfg=CONFIG, gelu="erf", eps=1e-6, normalize=True, taps=None):
-    """images: [B,3,H,W] float32 (already normalised).  Returns [B, emb_dim] float32."""
+def encode_image(images, sd, cfg=CONFIG, gelu="erf", eps=1e-6, normalize=True, taps=None, qkv_hook=None):
+    """images: [B,3,H,W] float32 (already normalised).  Returns [B, emb_dim] float32.
+    qkv_hook(block, qkv[3, B, heads, n, dh]) -> qkv: sees, and may replace, what a block's self attention consumes (tests record the
+    logits' regime with it, or round q / k / v where the engine rounds them)."""
     d, heads, p = cfg["emb_dim"], cfg["num_heads"], cfg["patch_size"]
     dh = d // heads
     x = images.float()
@@ -116,6 +118,8 @@ def encode_image(images, sd, cfg=CONFIG, gelu="erf", eps=1e-6, normalize=True, t
         h = _ln(x, sd[b + "norm1.weight"], sd[b + "norm1.bias"], eps)
         qkv = h @ sd[b + "attn.qkv.weight"].T + sd[b + "attn.qkv.bias"]          # [B, n, 3d]
         qkv = qkv.reshape(B, n, 3, heads, dh).permute(2, 0, 3, 1, 4)              # [3, B, heads, n, dh]
+        if qkv_hook is not None:
+            qkv = qkv_hook(i, qkv)
         q, k, v = qkv[0], qkv[1], qkv[2]
         att = torch.softmax((q @ k.transpose(-1, -2)) / math.sqrt(dh), dim=-1)
         o = (att @ v).transpose(1, 2).reshape(B, n, d)
@@ -224,7 +228,8 @@ def synthetic_tokens(batch, cfg, seed=0x5EED0007):
     return torch.from_numpy(t)
 
 
-def encode_text(tokens, sd, cfg=TEXT_CONFIG, gelu="erf", eps=1e-6, normalize=True):
+def encode_text(tokens, sd, cfg=TEXT_CONFIG, gelu="erf", eps=1e-6, normalize=True, qkv_hook=None):
+    """qkv_hook: as in encode_image."""
     d, heads = cfg["width"], cfg["heads"]
     dh = d // heads
     B, n = tokens.shape
@@ -233,6 +238,8 @@ def encode_text(tokens, sd, cfg=TEXT_CONFIG, gelu="erf", eps=1e-6, normalize=Tru
         b = f"text.transformer.resblocks.{i}."
         h = _ln(x, sd[b + "ln_1.weight"], sd[b + "ln_1.bias"], eps)
         qkv = (h @ sd[b + "attn.in_proj_weight"].T + sd[b + "attn.in_proj_bias"]).reshape(B, n, 3, heads, dh).permute(2, 0, 3, 1, 4)
+        if qkv_hook is not None:
+            qkv = qkv_hook(i, qkv)
         att = torch.softmax((qkv[0] @ qkv[1].transpose(-1, -2)) / math.sqrt(dh), dim=-1)   # no causal mask
         o = (att @ qkv[2]).transpose(1, 2).reshape(B, n, d)
         x = x + (o @ sd[b + "attn.out_proj.weight"].T + sd[b + "attn.out_proj.bias"])
