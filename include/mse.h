@@ -1141,6 +1141,49 @@ int mse_debug_gemm_small(int rows, int N, int K, int epi, int variant, int iters
  * [B][heads * 72]. */
 int mse_debug_siglip_attention(const float* q, const float* k, const float* v, int B, int heads, int tokens, int flags, float* out);
 int mse_debug_siglip_pool_attention(const float* qlat, const float* k, const float* v, int B, int heads, int tokens, float* out);
+/* test hooks for the towers' GEMM launches alone: ONE launch_gemm call (or the launch_ln_fold / launch_row_stats / launch_gemm_fused /
+ * launch_ln_finalize sequence of the LayerNorm-fused path) filled in as the towers fill it in, so the kernel is chosen from
+ * (epi, rows, N, K, skinny) as in a forward pass.  Operands are host fp32, rounded in the hook (nearest even) to the 16-bit type the
+ * towers hold them in; destinations come back WHOLE -- M = rows rounded up to 256 rows, padding included -- widened to fp32.  Every
+ * destination lies between guard bands and is filled with bytes 0xA5 before the launch (bf16 0xA5A5 = -7.17e-16, fp16 0xA5A5 =
+ * -0.02204, fp32 -2.87e-16): an element that still holds that value was not written, and a changed guard byte fails the call.  What
+ * a launch may do to padding rows is written above the hooks in csrc/siglip_api.hip.  A geometry the launchers do not accept is
+ * refused before anything runs.  A call with every output pointer NULL launches nothing and fills in the sizes. */
+typedef struct mse_debug_siglip_gemm_args {
+    int rows, N, K;          /* rows = m_valid; x has M = rows rounded up to 256 rows */
+    int epi;                 /* 0 BF16, 1 GELU, 2 RESID, 3 PATCH, 4 QKV, 6 PART (K split: raw fp32 slabs) */
+    int skinny;              /* GemmLaunch::skinny: 0 large-batch kernels, 1 by size, 2 / 3 / 4 force K-split skinny / 64 x 64 / 128 x 128 */
+    int gelu_tanh;
+    int flags;               /* 1: finite garbage (|v| <= 1e4) in x rows rows .. M; 2: in w rows n_valid .. N; 4: 128-column remainder on a side stream */
+    int n_valid;             /* flags & 2 */
+    int tokens, heads, dh;   /* PATCH: tokens (rows of pos); QKV: heads, dh = 72, tokens (the row stride is tokens rounded up to 32) */
+    int ksplit;              /* PART */
+    const float *x, *w, *bias;   /* [rows][K], [N][K] (rows < n_valid are read), [N] */
+    const float* resid;      /* RESID: fp32 [rows][N] */
+    const float* pos;        /* PATCH: fp32 [tokens][N] */
+    float* out;              /* BF16 / GELU (bf16), PATCH (fp16), RESID (fp32): [M][N]; PART: [ksplit][slab_rows][N] */
+    float *q, *k, *vt;       /* QKV: [n_seq * heads][n_pad][dh_pad], [n_seq * heads][n_pad][kdh_pad], [n_seq * heads][dv_pad][n_pad] */
+    int M, n_pad, n_seq, dh_pad, kdh_pad, dv_pad, slab_rows, cu_count;   /* filled in by the hook (cu_count only by a call that runs) */
+} mse_debug_siglip_gemm_args;
+int mse_debug_siglip_gemm(mse_debug_siglip_gemm_args* args);
+typedef struct mse_debug_siglip_gemm_fused_args {
+    int rows, N, K;          /* consumers: K = D, the width of the residual stream */
+    int epi;                 /* 4 QKV, 1 GELU (consumers of a LayerNorm); 5 RESID_LN (producer) */
+    int gelu_tanh;
+    int flags;               /* 1: garbage in the padding rows of x (and xres); 2 (producer): in w rows n_valid .. N */
+    int n_valid;             /* producer: real columns; N = n_valid rounded up to 256 */
+    int heads, dh, tokens;   /* QKV */
+    float eps;
+    const float* x;          /* consumers: fp16 residual [rows][K]; producer: bf16 branch input [rows][K] */
+    const float *w, *bias;   /* bf16 [N][K], fp32 [N] */
+    const float *gamma, *beta;   /* consumers: fp32 [K] */
+    const float* xres;       /* producer: fp16 residual [rows][n_valid] */
+    float* out;              /* GELU: bf16 [M][N]; producer: the updated fp16 residual [M][n_valid] */
+    float *q, *k, *vt;       /* QKV, as above */
+    float* stats;            /* (mean, 1/std) [M][2]: row_stats (consumers), ln_finalize of the producer's parts */
+    int M, n_pad, n_seq, dh_pad, kdh_pad, dv_pad;   /* filled in by the hook */
+} mse_debug_siglip_gemm_fused_args;
+int mse_debug_siglip_gemm_fused(mse_debug_siglip_gemm_fused_args* args);
 
 /* ---- SigLIP text tower: `model.encode_text(tokens)` + normalisation + fp16 serialisation
  * (clip_server.py:98-99,128-131,166).  open_clip's TextTransformer is a third-party dependency not vendored in

@@ -539,6 +539,311 @@ int mse_debug_siglip_pool_attention(const float* qlat, const float* k, const flo
     return 0;
 }
 
+}  // extern "C"
+
+namespace {
+uint16_t host_f16(float f) {   // round to nearest even
+    const _Float16 h = (_Float16)f;
+    uint16_t u;
+    memcpy(&u, &h, 2);
+    return u;
+}
+float host_f16_to_f32(uint16_t u) {
+    _Float16 h;
+    memcpy(&h, &u, 2);
+    return (float)h;
+}
+// the same finite garbage as an fp16 value (the residual stream's padding rows)
+uint16_t poison_f16(size_t i, uint32_t seed) { return host_f16(host_bf16_to_f32(poison_bf16(i, seed))); }
+
+constexpr size_t DBG_GUARD = 4096;          // bytes of sentinel on either side of every destination of the GEMM hooks
+constexpr int DBG_SENTINEL = 0xA5;          // bf16 0xA5A5 = -7.17e-16, fp16 0xA5A5 = -0.02204, fp32 0xA5A5A5A5 = -2.87e-16: all finite
+constexpr size_t DBG_GEMM_MAX = (size_t)1 << 26;   // elements of any one operand or destination
+
+// A destination of the GEMM hooks: `bytes` of payload between two guard bands, all of it filled with the sentinel byte.
+struct GuardedBuf {
+    DevBuf buf;
+    size_t bytes = 0;
+    int make(size_t n) {
+        bytes = round_up(n, 256);
+        if (buf.ensure(bytes + 2 * DBG_GUARD)) return -1;
+        MSE_HIP_TRY(hipMemset(buf.p, DBG_SENTINEL, bytes + 2 * DBG_GUARD));
+        return 0;
+    }
+    template <typename T> T* as() const { return reinterpret_cast<T*>(reinterpret_cast<char*>(buf.p) + DBG_GUARD); }
+    int check(const char* what) const {   // the guard bands still hold the sentinel
+        std::vector<uint8_t> g(2 * DBG_GUARD);
+        MSE_HIP_TRY(hipMemcpy(g.data(), buf.p, DBG_GUARD, hipMemcpyDeviceToHost));
+        MSE_HIP_TRY(hipMemcpy(g.data() + DBG_GUARD, reinterpret_cast<char*>(buf.p) + DBG_GUARD + bytes, DBG_GUARD, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < g.size(); i++)
+            if (g[i] != DBG_SENTINEL)
+                return fail(std::string("debug siglip gemm: a launch wrote ") + (i < DBG_GUARD ? "before" : "past") + " its destination (" + what + ")");
+        return 0;
+    }
+    template <typename T, typename F> int read(size_t n, float* out, F widen) const {
+        std::vector<T> h(n);
+        MSE_HIP_TRY(hipMemcpy(h.data(), as<T>(), n * sizeof(T), hipMemcpyDeviceToHost));
+        for (size_t e = 0; e < n; e++) out[e] = widen(h[e]);
+        return 0;
+    }
+};
+
+// [rows_pad][K] 16-bit operand from host fp32 [rows][K]: rounded by `conv`; rows past `rows` zero, or finite garbage when `poison`
+template <typename Conv, typename Poison>
+int upload_rows16(DevBuf& d, const float* src, size_t rows, size_t rows_pad, size_t K, Conv conv, bool poison, Poison garbage) {
+    std::vector<uint16_t> h(rows_pad * K, 0);
+    for (size_t e = 0; e < rows * K; e++) h[e] = conv(src[e]);
+    for (size_t e = rows * K; poison && e < rows_pad * K; e++) h[e] = garbage(e);
+    if (d.ensure(h.size() * 2)) return -1;
+    MSE_HIP_TRY(hipMemcpy(d.p, h.data(), h.size() * 2, hipMemcpyHostToDevice));
+    return 0;
+}
+int upload_f32(DevBuf& d, const float* src, size_t n) {
+    if (d.ensure(n * 4)) return -1;
+    MSE_HIP_TRY(hipMemcpy(d.p, src, n * 4, hipMemcpyHostToDevice));
+    return 0;
+}
+
+// the streams of a hook call: the engines' kind (non-blocking), with the fork / join events of a side-stream remainder launch
+struct DbgStreams {
+    hipStream_t main = nullptr, side = nullptr;
+    hipEvent_t fork = nullptr, join = nullptr;
+    int make(bool with_side) {
+        MSE_HIP_TRY(hipStreamCreateWithFlags(&main, hipStreamNonBlocking));
+        if (!with_side) return 0;
+        MSE_HIP_TRY(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
+        MSE_HIP_TRY(hipEventCreateWithFlags(&fork, hipEventDisableTiming));
+        MSE_HIP_TRY(hipEventCreateWithFlags(&join, hipEventDisableTiming));
+        return 0;
+    }
+    ~DbgStreams() {
+        if (side) { (void)hipStreamSynchronize(side); (void)hipStreamDestroy(side); }
+        if (main) { (void)hipStreamSynchronize(main); (void)hipStreamDestroy(main); }
+        if (fork) (void)hipEventDestroy(fork);
+        if (join) (void)hipEventDestroy(join);
+    }
+};
+
+// attention operands of the QKV scatter for `n_seq` sequences, as the engines allocate them, each a guarded destination
+struct DbgQkv {
+    GuardedBuf q, k, vt;
+    size_t nq = 0, nk = 0, nvt = 0;
+    int make(size_t n_seq, int heads, int n_pad, hipStream_t st) {
+        const size_t mats = n_seq * heads;
+        nq = mats * n_pad * DBG_DH_PAD; nk = mats * n_pad * attention_k_stride(); nvt = mats * DBG_DV_PAD * n_pad;
+        if (q.make(nq * 2) || k.make(nk * 2) || vt.make(nvt * 2)) return -1;
+        MSE_HIP_TRY(hipDeviceSynchronize());
+        return launch_vt_ones_row(vt.as<uint16_t>(), mats, DBG_DH, DBG_DV_PAD, n_pad, st);
+    }
+    void attach(GemmLaunch& g, int heads, int n_pad) const {
+        g.tokens = n_pad; g.q = q.as<uint16_t>(); g.k = k.as<uint16_t>(); g.vt = vt.as<uint16_t>(); g.heads = heads; g.dh = DBG_DH;
+        g.dh_pad = DBG_DH_PAD; g.n_pad = n_pad; g.dv_pad = DBG_DV_PAD; g.kdh_pad = attention_k_stride();
+    }
+    int read(float* oq, float* ok, float* ovt) const {
+        if (q.check("q") || k.check("k") || vt.check("vt")) return -1;
+        return q.read<uint16_t>(nq, oq, host_bf16_to_f32) || k.read<uint16_t>(nk, ok, host_bf16_to_f32) || vt.read<uint16_t>(nvt, ovt, host_bf16_to_f32);
+    }
+};
+// the towers' QKV geometry (launch_vt_ones_row and the scatter epilogues: 8-token / 8-column pieces inside q / k / v tiles)
+bool dbg_qkv_ok(int rows, int N, int heads, int dh, int tokens) {
+    return heads > 0 && dh == DBG_DH && tokens > 0 && tokens <= 8192 && N == 3 * heads * dh && (heads * dh) % 128 == 0 &&
+           round_up((size_t)tokens, 32) >= 64 && rows % 8 == 0;
+}
+}  // namespace
+
+extern "C" {
+
+// Test hook for the towers' plain GEMM launches (mse.h: mse_debug_siglip_gemm_args).  x [rows][K], w [N][K] are host fp32, rounded here
+// to bf16 (nearest even); bias, resid and pos stay fp32.  The operands are laid out as the towers lay them out (M = rows rounded up to
+// 256 rows of x, every leading dimension = N) and ONE launch_gemm call is made with m_valid = rows, exactly as run_blocks and
+// mse_siglip_encode_image fill in GemmLaunch: the kernel is therefore whichever launch_gemm_t picks for (epi, rows, N, K, skinny).
+// Every destination is allocated between two guard bands and filled, guard bands included, with bytes 0xA5 before the launch; the
+// hook fails if a guard byte changed, and returns the destinations WHOLE (padding included), widened to fp32, so that a test sees
+// what a launch left of the sentinel.  A call with every output pointer NULL launches nothing and only fills in the derived sizes.
+// Geometries the launchers (or the engines' buffers) do not accept are refused before anything is allocated.
+//
+// What a launch may do to padding, read from siglip_kernels.hip (rows = m_valid, M = rows rounded up to 256):
+//   BF16 / GELU   skinny, 64 x 64 and 128 x 128 kernels (store_quad, !mok): rows rows .. rows rounded up to the tile height (64, 64,
+//                 128) are ZEROED, rows above keep what they held.  First-generation and non-persistent ping-pong kernels (K < 256,
+//                 or the GELU remainder): rows rows .. M are ZEROED.  Persistent kernel (K >= 256; its 128-column BF16 remainder
+//                 too): stores are unconditional -- rows rows .. M are OVERWRITTEN with bias + x_pad . w, finite when x's padding
+//                 rows are finite.  In every case: rows rows .. M hold zeros, finite values or what they held; nothing above M.
+//   RESID / PATCH every kernel skips rows >= rows (mok / m < m_valid): the padding rows keep what they held.
+//   QKV           a row m goes to sequence m / n_pad, token m % n_pad.  store_quad and the non-persistent kernels skip rows >= rows.
+//                 The persistent kernels (K >= 256) scatter EVERY row below M: the entries of rows rows .. M (tokens of the last
+//                 sequence past rows, and of up to (M - rows) / n_pad + 1 sequences behind it -- the engines allocate that slack)
+//                 are OVERWRITTEN with finite values.  Columns dh .. of a q / K row, Vt's row-sum row dh and the rows above it are
+//                 never written.  Tokens `tokens` .. n_pad of a sequence are rows below m_valid like any other.
+//   PART          every slab is written up to rows rounded up to the tile height (64; 128 above SPLIT_T128_ROWS rows) with the raw
+//                 sums of x's padding rows (finite); slab rows above that keep what they held.
+// flags: 1 = x's padding rows hold finite garbage (poison_bf16, magnitude <= 1e4) instead of zeros; 2 = rows n_valid .. N of w hold the
+// same garbage (columns < n_valid must not change); 4 = the 128-column remainder launch runs on a side stream between fork / join
+// events of the engines' kind.
+int mse_debug_siglip_gemm(mse_debug_siglip_gemm_args* p) {
+    if (!p) return fail("debug siglip gemm: null argument");
+    const int rows = p->rows, N = p->N, K = p->K, epi = p->epi;
+    const bool qkv = epi == GEMM_EPI_QKV, part = epi == GEMM_EPI_PART;
+    if (rows <= 0 || N <= 0 || K <= 0 || N % gemm_bn() || K % gemm_bk() || p->skinny < 0 || p->skinny > 4 || (p->gelu_tanh & ~1) || (p->flags & ~7))
+        return fail("debug siglip gemm: rows, N, K > 0, N % 128 == 0, K % 64 == 0, skinny 0..4, gelu_tanh 0 / 1, flags 0..7");
+    if (epi != GEMM_EPI_BF16 && epi != GEMM_EPI_GELU && epi != GEMM_EPI_RESID && epi != GEMM_EPI_PATCH && !qkv && !part)
+        return fail("debug siglip gemm: epi must be BF16, GELU, RESID, PATCH, QKV or PART");
+    const size_t M = round_up((size_t)rows, 256);
+    if (M * K > DBG_GEMM_MAX || (size_t)N * K > DBG_GEMM_MAX || M * N > DBG_GEMM_MAX) return fail("debug siglip gemm: an operand exceeds 2^26 elements");
+    const int n_valid = (p->flags & 2) ? p->n_valid : N;
+    if (n_valid <= 0 || n_valid > N) return fail("debug siglip gemm: 0 < n_valid <= N");
+    if (epi == GEMM_EPI_PATCH && (p->tokens <= 0 || (size_t)p->tokens * N > DBG_GEMM_MAX)) return fail("debug siglip gemm: PATCH needs tokens > 0");
+    if (qkv && !dbg_qkv_ok(rows, N, p->heads, p->dh, p->tokens))
+        return fail("debug siglip gemm: QKV needs dh == 72, heads % 16 == 0, N == 3 * heads * dh, 32 < tokens <= 8192, rows % 8 == 0");
+    // K split: only what the towers ask for (gemm_small_ksplit: fc2 of one image; gemm_small_ksplit_short: the projection of one text)
+    if (part && (p->ksplit < 2 || (p->ksplit != gemm_small_ksplit(rows, N, K) && p->ksplit != gemm_small_ksplit_short(rows, N, K))))
+        return fail("debug siglip gemm: PART needs the ksplit that gemm_small_ksplit / gemm_small_ksplit_short give for (rows, N, K)");
+    const int n_pad = qkv ? (int)round_up((size_t)p->tokens, 32) : 0;
+    const size_t n_seq = qkv ? (M + n_pad - 1) / n_pad : 0;   // every row below M has a place: the persistent kernels scatter them all
+    const size_t slab_rows = part ? (size_t)gemm_small_ksplit_rows(rows) : 0;
+    if (qkv && n_seq * p->heads * n_pad * attention_k_stride() > DBG_GEMM_MAX) return fail("debug siglip gemm: an operand exceeds 2^26 elements");
+    p->M = (int)M; p->n_pad = n_pad; p->n_seq = (int)n_seq; p->dh_pad = DBG_DH_PAD; p->kdh_pad = attention_k_stride(); p->dv_pad = DBG_DV_PAD;
+    p->slab_rows = (int)slab_rows; p->cu_count = 0;
+    if (!p->out && !p->q && !p->k && !p->vt) return 0;   // sizes only
+    if (!p->x || !p->w || !p->bias || (qkv ? (!p->q || !p->k || !p->vt) : !p->out) || (epi == GEMM_EPI_RESID && !p->resid) ||
+        (epi == GEMM_EPI_PATCH && !p->pos))
+        return fail("debug siglip gemm: null argument");
+    p->cu_count = device_cu_count();
+
+    DevBuf dx, dw, dbias, dpos;
+    if (upload_rows16(dx, p->x, rows, M, K, host_bf16, p->flags & 1, [](size_t e) { return poison_bf16(e, 0x58u); }) ||
+        upload_rows16(dw, p->w, n_valid, N, K, host_bf16, p->flags & 2, [](size_t e) { return poison_bf16(e, 0x57u); }) ||
+        upload_f32(dbias, p->bias, N))
+        return -1;
+    GuardedBuf out;
+    DbgQkv o3;
+    DbgStreams s;   // declared after every buffer: the streams are synchronised and destroyed before a buffer is freed
+    if (s.make(p->flags & 4)) return -1;
+    GemmLaunch g;
+    g.x = dx.as<uint16_t>(); g.w = dw.as<uint16_t>(); g.bias = dbias.as<float>(); g.M = (int)M; g.N = N; g.K = K; g.m_valid = rows;
+    g.skinny = p->skinny; g.gelu_tanh = p->gelu_tanh; g.side = s.side; g.ev_fork = s.fork; g.ev_join = s.join;
+    const size_t out_elems = part ? (size_t)p->ksplit * slab_rows * N : M * N;
+    if (qkv) {
+        if (o3.make(n_seq, p->heads, n_pad, s.main)) return -1;
+        o3.attach(g, p->heads, n_pad);
+    } else if (epi == GEMM_EPI_RESID) {
+        if (out.make(out_elems * 4)) return -1;
+        MSE_HIP_TRY(hipMemcpy(out.as<float>(), p->resid, (size_t)rows * N * 4, hipMemcpyHostToDevice));
+        g.resid = out.as<float>(); g.ldr = N;
+    } else if (epi == GEMM_EPI_PATCH) {
+        if (out.make(out_elems * 2) || upload_f32(dpos, p->pos, (size_t)p->tokens * N)) return -1;
+        g.out_bf16 = out.as<uint16_t>(); g.ldo = N; g.ldr = N; g.pos = dpos.as<float>(); g.tokens = p->tokens;
+    } else if (part) {
+        if (out.make(out_elems * 4)) return -1;
+        g.kpart = out.as<float>(); g.kpart_stride = slab_rows * N; g.ksplit = p->ksplit; g.ldr = N;
+    } else {
+        if (out.make(out_elems * 2)) return -1;
+        g.out_bf16 = out.as<uint16_t>(); g.ldo = N;
+    }
+    MSE_HIP_TRY(hipDeviceSynchronize());   // uploads and fills ran on the null stream, which the hook's streams do not wait for
+    if (launch_gemm(epi, g, s.main)) return -1;
+    MSE_HIP_TRY(hipStreamSynchronize(s.main));
+    MSE_HIP_TRY(hipDeviceSynchronize());
+    if (qkv) return o3.read(p->q, p->k, p->vt);
+    if (out.check("out")) return -1;
+    if (epi == GEMM_EPI_RESID || part) return out.read<float>(out_elems, p->out, [](float v) { return v; });
+    if (epi == GEMM_EPI_PATCH) return out.read<uint16_t>(out_elems, p->out, host_f16_to_f32);
+    return out.read<uint16_t>(out_elems, p->out, host_bf16_to_f32);
+}
+
+// Test hook for the LayerNorm-fused launches of the image tower (mse.h: mse_debug_siglip_gemm_fused_args), with the same guarded,
+// sentinel-filled destinations, whole-buffer outputs and size-only call as mse_debug_siglip_gemm.
+//   consumers (epi QKV / GELU): x is the fp16 residual stream [rows][K] (host fp32, rounded here to fp16), w [N][K] bf16, gamma / beta
+//     [K], bias [N]; launch_ln_fold, launch_row_stats over all M rows, launch_gemm_fused -- the order and arguments of
+//     Encoder::fold_layernorms and run_blocks.  Returns the output and the (mean, 1/std) pairs [M][2].
+//   producer (epi RESID_LN): x is the bf16 branch input [rows][K], w [N][K] with N = n_valid rounded up to 256, bias [N], xres the fp16
+//     residual [rows][n_valid]; launch_gemm_fused with part_rows = M and a zeroed 4 KiB sink as Encoder::alloc_fused makes them, then
+//     launch_ln_finalize.  Returns the updated residual [M][n_valid] and the (mean, 1/std) pairs [M][2].
+// Padding (gemm8pp_kernel stores unconditionally): every row below M is computed and stored like a real one -- GELU output rows,
+// the QKV entries of rows rows .. M (see mse_debug_siglip_gemm), residual rows and statistics rows rows .. M are OVERWRITTEN with
+// finite values when the padding rows of the inputs are finite.  Columns n_valid .. N of the producer go to the sink: the residual has
+// no such columns.  flags: 1 = the padding rows of x (and of xres) hold finite garbage instead of zeros; 2 = producer: rows n_valid .. N
+// of w hold garbage.
+int mse_debug_siglip_gemm_fused(mse_debug_siglip_gemm_fused_args* p) {
+    if (!p) return fail("debug siglip gemm fused: null argument");
+    const int rows = p->rows, N = p->N, K = p->K, epi = p->epi;
+    const bool qkv = epi == GEMM_EPI_QKV, gelu = epi == GEMM_EPI_GELU, prod = epi == GEMM_EPI_RESID_LN;
+    if (rows <= 0 || N <= 0 || K < 256 || N % 128 || K % 64 || (p->gelu_tanh & ~1) || (p->flags & ~3) || !(p->eps > 0.0f) || !(qkv || gelu || prod))
+        return fail("debug siglip gemm fused: rows, N > 0, K >= 256, N % 128 == 0, K % 64 == 0, flags 0..3, eps > 0, epi QKV, GELU or RESID_LN");
+    const size_t M = round_up((size_t)rows, 256);
+    if (M * K > DBG_GEMM_MAX || (size_t)N * K > DBG_GEMM_MAX || M * N > DBG_GEMM_MAX) return fail("debug siglip gemm fused: an operand exceeds 2^26 elements");
+    if (!prod && (K > 2048 || rows % 8)) return fail("debug siglip gemm fused: consumers need K <= 2048 (row statistics) and rows % 8 == 0");
+    if (gelu && N % 256) return fail("debug siglip gemm fused: GELU needs N % 256 == 0");
+    if (qkv && (!dbg_qkv_ok(rows, N, p->heads, p->dh, p->tokens) || p->heads * p->dh != K ||
+                !gemm_fused_ok((int)M, K, 256, p->heads, p->dh, (int)round_up((size_t)p->tokens, 32), (int)round_up((size_t)p->tokens, 32), rows)))
+        return fail("debug siglip gemm fused: QKV needs the towers' geometry (dh 72, heads % 16 == 0, K == heads * dh, N == 3 K, rows % 8 == 0)");
+    const int n_valid = prod ? p->n_valid : N;
+    if (prod && (n_valid <= 0 || n_valid % 64 || N != (int)round_up((size_t)n_valid, 256)))
+        return fail("debug siglip gemm fused: RESID_LN needs n_valid % 64 == 0 and N == n_valid rounded up to 256");
+    const int n_pad = qkv ? (int)round_up((size_t)p->tokens, 32) : 0;
+    const size_t n_seq = qkv ? (M + n_pad - 1) / n_pad : 0;
+    if (qkv && n_seq * p->heads * n_pad * attention_k_stride() > DBG_GEMM_MAX) return fail("debug siglip gemm fused: an operand exceeds 2^26 elements");
+    p->M = (int)M; p->n_pad = n_pad; p->n_seq = (int)n_seq; p->dh_pad = DBG_DH_PAD; p->kdh_pad = attention_k_stride(); p->dv_pad = DBG_DV_PAD;
+    if (!p->out && !p->q && !p->k && !p->vt && !p->stats) return 0;   // sizes only
+    if (!p->x || !p->w || !p->bias || !p->stats || (qkv ? (!p->q || !p->k || !p->vt) : !p->out) || (prod ? !p->xres : (!p->gamma || !p->beta)))
+        return fail("debug siglip gemm fused: null argument");
+
+    DevBuf dx, dw, dbias, sink, dgamma, dbeta, w16, csum, bias2;
+    GuardedBuf stats, xres, ln_part, out;
+    DbgQkv o3;
+    DbgStreams s;   // declared after every buffer: the streams are synchronised and destroyed before a buffer is freed
+    if (s.make(false)) return -1;
+    hipStream_t st = s.main;
+    if (stats.make(M * 8)) return -1;
+    GemmLaunch g;
+    g.M = (int)M; g.N = N; g.K = K; g.m_valid = rows; g.gelu_tanh = p->gelu_tanh;
+    if (upload_rows16(dw, p->w, n_valid, N, K, host_bf16, prod && (p->flags & 2), [](size_t e) { return poison_bf16(e, 0x57u); }) ||
+        upload_f32(dbias, p->bias, N))
+        return -1;
+    if (prod) {
+        if (upload_rows16(dx, p->x, rows, M, K, host_bf16, p->flags & 1, [](size_t e) { return poison_bf16(e, 0x58u); })) return -1;
+        if (xres.make(M * n_valid * 2) || ln_part.make((size_t)(n_valid / 64) * M * 8) || sink.ensure(4096)) return -1;
+        MSE_HIP_TRY(hipMemset(sink.p, 0, 4096));
+        {
+            std::vector<uint16_t> h(M * n_valid, 0);
+            for (size_t e = 0; e < (size_t)rows * n_valid; e++) h[e] = host_f16(p->xres[e]);
+            for (size_t e = (size_t)rows * n_valid; (p->flags & 1) && e < h.size(); e++) h[e] = poison_f16(e, 0x52u);
+            MSE_HIP_TRY(hipMemcpy(xres.as<uint16_t>(), h.data(), h.size() * 2, hipMemcpyHostToDevice));
+        }
+        g.x = dx.as<uint16_t>(); g.w = dw.as<uint16_t>(); g.bias = dbias.as<float>();
+        g.xres = xres.as<uint16_t>(); g.ldr = n_valid; g.part = ln_part.as<float>(); g.part_rows = M; g.n_valid = n_valid; g.sink = sink.p;
+        MSE_HIP_TRY(hipDeviceSynchronize());
+        if (launch_gemm_fused(GEMM_EPI_RESID_LN, g, st)) return -1;
+        if (launch_ln_finalize(ln_part.as<float>(), M, n_valid / 64, M, p->eps, stats.as<float>(), st)) return -1;
+        MSE_HIP_TRY(hipStreamSynchronize(st));
+        if (xres.check("residual") || ln_part.check("statistics parts") || stats.check("statistics")) return -1;
+        return xres.read<uint16_t>(M * n_valid, p->out, host_f16_to_f32) || stats.read<float>(M * 2, p->stats, [](float v) { return v; });
+    }
+    // consumers
+    if (upload_rows16(dx, p->x, rows, M, K, host_f16, p->flags & 1, [](size_t e) { return poison_f16(e, 0x58u); })) return -1;
+    if (upload_f32(dgamma, p->gamma, K) || upload_f32(dbeta, p->beta, K) || w16.ensure((size_t)N * K * 2) || csum.ensure((size_t)N * 4) ||
+        bias2.ensure((size_t)N * 4))
+        return -1;
+    if (qkv) {
+        if (o3.make(n_seq, p->heads, n_pad, st)) return -1;
+        o3.attach(g, p->heads, n_pad);
+    } else {
+        if (out.make(M * N * 2)) return -1;
+        g.out_bf16 = out.as<uint16_t>(); g.ldo = N;
+    }
+    MSE_HIP_TRY(hipDeviceSynchronize());
+    if (launch_ln_fold(dw.as<uint16_t>(), N, K, dgamma.as<float>(), dbeta.as<float>(), dbias.as<float>(), w16.as<uint16_t>(), csum.as<float>(),
+                       bias2.as<float>(), st))
+        return -1;
+    if (launch_row_stats(dx.as<uint16_t>(), K, K, M, p->eps, stats.as<float>(), st)) return -1;
+    g.x = dx.as<uint16_t>(); g.w = w16.as<uint16_t>(); g.bias = bias2.as<float>(); g.csum = csum.as<float>(); g.ln_stats = stats.as<float>();
+    if (launch_gemm_fused(epi, g, st)) return -1;
+    MSE_HIP_TRY(hipStreamSynchronize(st));
+    if (stats.check("statistics") || stats.read<float>(M * 2, p->stats, [](float v) { return v; })) return -1;
+    if (qkv) return o3.read(p->q, p->k, p->vt);
+    if (out.check("out")) return -1;
+    return out.read<uint16_t>(M * N, p->out, host_bf16_to_f32);
+}
+
 // test hook: the residual stream ([batch*tokens][emb] fp32) as left by the last forward (after the last block)
 int mse_siglip_debug_residual(mse_siglip* m, float* out) {
     if (!m || !m->last_batch) return fail("siglip: no forward has run");

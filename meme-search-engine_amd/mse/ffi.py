@@ -288,6 +288,8 @@ SIGNATURES = {
     "mse_debug_gemm_small": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.POINTER(C.c_uint64)]),
     "mse_debug_siglip_attention": (C.c_int, [f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, f32p]),
     "mse_debug_siglip_pool_attention": (C.c_int, [f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, f32p]),
+    "mse_debug_siglip_gemm": (C.c_int, [vp]),
+    "mse_debug_siglip_gemm_fused": (C.c_int, [vp]),
     "mse_siglip_text_create": (vp, [vp]),
     "mse_siglip_text_destroy": (None, [vp]),
     "mse_siglip_text_n_weights": (C.c_int, [vp]),
@@ -313,6 +315,21 @@ class SiglipConfig(C.Structure):
     _fields_ = [("img_size", C.c_int), ("patch_size", C.c_int), ("in_chans", C.c_int), ("emb_dim", C.c_int),
                 ("depth", C.c_int), ("num_heads", C.c_int), ("mlp_dim", C.c_int), ("eps", C.c_float),
                 ("gelu_tanh", C.c_int), ("max_batch", C.c_int)]
+
+
+class DebugSiglipGemmArgs(C.Structure):
+    """mse_debug_siglip_gemm_args (include/mse.h)"""
+    _fields_ = ([(n, C.c_int) for n in ("rows", "N", "K", "epi", "skinny", "gelu_tanh", "flags", "n_valid", "tokens", "heads", "dh", "ksplit")] +
+                [(n, f32p) for n in ("x", "w", "bias", "resid", "pos", "out", "q", "k", "vt")] +
+                [(n, C.c_int) for n in ("M", "n_pad", "n_seq", "dh_pad", "kdh_pad", "dv_pad", "slab_rows", "cu_count")])
+
+
+class DebugSiglipGemmFusedArgs(C.Structure):
+    """mse_debug_siglip_gemm_fused_args (include/mse.h)"""
+    _fields_ = ([(n, C.c_int) for n in ("rows", "N", "K", "epi", "gelu_tanh", "flags", "n_valid", "heads", "dh", "tokens")] +
+                [("eps", C.c_float)] +
+                [(n, f32p) for n in ("x", "w", "bias", "gamma", "beta", "xres", "out", "q", "k", "vt", "stats")] +
+                [(n, C.c_int) for n in ("M", "n_pad", "n_seq", "dh_pad", "kdh_pad", "dv_pad")])
 
 
 def lib():
