@@ -701,7 +701,8 @@ int mse_disk_query_submit_filtered_f32(mse_searcher* s, mse_pq* pq, const mse_co
  * with requests of the same grouping object (and filter, regime, search_list), never with ungrouped ones; k may differ between sharers.
  * How: one workgroup per query removes every non-best record of a group from the device-resident visited list in place
  * (integer atomics on a hash table in LDS, in global memory for lists past 4096 records) between the de-duplication and the selection:
- * no host decision, no extra synchronisation, no second copy.  The shard's block form has no grouped twin. */
+ * no host decision, no extra synchronisation, no second copy.  The shard's block form has no grouped twin HERE: it is
+ * mse_disk_query_topk_block_grouped, declared with the shard group's grouped searches ("grouped search across the shards" below). */
 int mse_disk_query_topk_grouped(mse_searcher* s, mse_pq* pq, const mse_codes* c, const mse_graph* g, const mse_groups* groups, const mse_filter* f,
                                 int regime, const uint32_t* starts, const uint16_t* queries, const float* luts, const float* scales, size_t nq,
                                 int disable_pq, size_t beamwidth, size_t search_list, size_t k, uint32_t* ids, int64_t* scores, uint32_t* n_visited,
@@ -1027,6 +1028,84 @@ int mse_comm_pq_scan_topk_filtered(mse_comm* c, mse_pq* pq, const mse_codes* cod
 int mse_comm_query_topk_filtered(mse_comm* c, mse_searcher* s, mse_pq* pq, const mse_codes* codes, const mse_graph* g, const mse_filter* f,
                                  int regime, const uint16_t* queries, const float* luts, const float* scales, size_t nq, int disable_pq,
                                  size_t beamwidth, size_t search_list, size_t k, uint64_t first_row, void* scores_dev, void* ids_dev);
+/* ---- grouped search across the shards: one result per group, collapsed again where the shards' answers meet --------
+ * A group's rows straddle shard boundaries, so (a) a shard needs the global grouping cut to ITS rows and relabelled to local ids, and
+ * (b) the per-shard grouped answers must be collapsed once more by the GLOBAL grouping before the k best are taken.  k records per shard
+ * and query are enough for (b): take the union of the shards' records in (score desc, id asc) order and keep the first record of every
+ * group; a record x of group g on shard s among the first k kept is g's representative on s, and every group ranked ahead of g on s has
+ * a record ahead of x in the union, so fewer than k groups precede g on s and x is in that shard's grouped top-k.  Hence
+ *   collapse(merge of the per-shard grouped top-k) = collapse(merge of everything the shards ranked), cut to k,
+ * and the exchange keeps its size: shards x nq x k x 12 bytes.
+ *   mse_groups_slice   a fresh mse_groups over LOCAL rows [0, n_rows) that induces the partition src induces on rows [first_row, first_row
+ *                      + n_rows).  Labels are canonical: a grouped row's local label is the local id of the FIRST row of its group inside
+ *                      the slice; MSE_GROUP_NONE stays.  Rows at or past mse_groups_len(src) are groups of their own: the result is as
+ *                      long as the part of the slice inside src, and a slice wholly past src is the empty grouping (length 0, count 0),
+ *                      under which every row is a group of its own.  count as mse_groups_count defines it.  device: where the result
+ *                      lives, -1 = src's device; for another device the labels of the slice go over by ONE peer copy and are relabelled
+ *                      there.  Transient scratch: 4 bytes x mse_groups_len(src) on the result's device, freed before return.  n_rows =
+ *                      0, a null grouping and a device ordinal out of range are errors.  Deterministic (an atomic min of the local id
+ *                      per label, then a lookup).
+ *   mse_groups_read    the label array, mse_groups_len(g) u32, to the host.
+ * mse_shard_groups: the grouping of a shard group's GLOBAL rows, cut for its shards -- what the grouped searches of the group take.
+ *   mse_shard_group_groups   mse_groups_slice of `global` at each shard's first row and length, on the shard's device, plus a copy of the
+ *                            global label array on the root device (the device of shard 0), which the merge looks up by global row id.
+ *                            A grouping shorter than the group leaves the rows past it groups of their own; one longer than max(first
+ *                            row + rows) over the shards is an error.
+ *   mse_shard_groups_part    shard g's local grouping, BORROWED (it lives as long as the object); NULL without an error for a shard that
+ *                            lies wholly past the grouping -- such a shard runs its ungrouped call, which by contract answers the same --
+ *                            and NULL with the error set for a shard index out of range.
+ *   mse_shard_groups_n_shards its parts
+ * It carries the group's layout stamp exactly as mse_shard_filter does: one made for another group, or from before a re-fill
+ * (mse_shard_group_generate, _load_host, _set_shard_device), is refused by every call that takes one.  It is immutable, holds no reference
+ * to the group or to `global`, and must outlive the calls it is passed to.
+ * The grouped merge: one workgroup per query over the gathered packed blocks IN PLACE -- of every group (group_of[global id]; a record of
+ * group MSE_GROUP_NONE or with an id at or past the grouping is a group of its own) the best record by (score desc, id asc) stays, every
+ * other record of the group becomes the hole (INT64_MIN, MSE_ID_NONE); holes and padding already in the blocks are skipped; the
+ * unchanged selection of mse_merge_topk_packed_dev then takes the k best.  Integer atomics only: bit-reproducible.  The table lives in
+ * LDS up to n_shards x k_in = 4096 records per query and in global memory (scratch of the searcher) beyond, up to 8 x 1984 and more.
+ *   mse_merge_topk_packed_grouped_dev  mse_merge_topk_packed_dev with that step first; k_in records per shard and query in the blocks
+ *                                      (0: k_in = k), the k best representatives out.  groups_global must live on the searcher's
+ *                                      device.  The blocks are CHANGED in place (non-representatives become holes).  Asynchronous on
+ *                                      the searcher's stream.  What a process-per-GPU caller runs after its own all-gather.
+ * The three searches take sg (non-null) and an optional shard filter sf.  Lock discipline and validation order of the _filtered sibling
+ * (whose checks apply only when sf is given); then "null shard groups", an error of its own; then the fit of sg.
+ *   mse_shard_group_search_grouped(_dev)   local step mse_bruteforce_topk_grouped_f16_dev(part g, filter part or NULL, id_offset = first
+ *                                          row), exchange, grouped merge.  Equals mse_bruteforce_topk_grouped_f16 over one base of all
+ *                                          rows with the global grouping (and filter), bit for bit, in every mode.
+ *   mse_shard_group_query_topk_grouped     every shard runs mse_disk_query_topk_block_grouped on its graph and part (regime as in the
+ *                                          filtered call when sf is given), then the grouped merge: the collapse of the merge of what
+ *                                          the shards visited.  An approximate search; a short answer shows as padding, as on one GPU.
+ *   mse_shard_group_pq_scan_topk_grouped   phases A and B of mse_shard_group_pq_scan_topk (A filtered when sf is given); phase B's final
+ *                                          merge is the grouped merge: the collapse of the exactly re-ranked global top-r, k of it,
+ *                                          padded when the r candidates hold fewer than k groups.
+ * mse_shard_group_last_timing keeps its meaning; [2] includes the group step.
+ * Not covered: mse_comm_*_grouped (every rank would need the global labels; mse_merge_topk_packed_grouped_dev is the building block),
+ * an unsharded grouped PQ scan, groupings over mutated graphs after mse_graph_compact (by row id, as on one GPU), bench.py. */
+mse_groups* mse_groups_slice(const mse_groups* src, uint64_t first_row, size_t n_rows, int device);
+int mse_groups_read(const mse_groups* g, uint32_t* out);
+typedef struct mse_shard_groups mse_shard_groups;
+mse_shard_groups* mse_shard_group_groups(mse_shard_group* g, const mse_groups* global);
+const mse_groups* mse_shard_groups_part(const mse_shard_groups* sg, size_t shard);
+size_t mse_shard_groups_n_shards(const mse_shard_groups* sg);
+void mse_shard_groups_free(mse_shard_groups* sg);
+int mse_merge_topk_packed_grouped_dev(mse_searcher* s, const mse_groups* groups_global, void* gathered_blocks_dev, size_t n_shards, size_t nq,
+                                      size_t k_in, size_t k, void* out_scores_dev, void* out_ids_dev);
+int mse_shard_group_search_grouped(mse_shard_group* g, const mse_shard_groups* sg, const mse_shard_filter* sf, const uint16_t* queries, size_t nq,
+                                   size_t k, int mode, int64_t* scores, uint32_t* ids);
+int mse_shard_group_search_grouped_dev(mse_shard_group* g, const mse_shard_groups* sg, const mse_shard_filter* sf, const void* queries_dev,
+                                       size_t nq, size_t k, int mode, void* scores_dev, void* ids_dev);
+int mse_shard_group_pq_scan_topk_grouped(mse_shard_group* g, const mse_shard_groups* sg, const mse_shard_filter* sf, const float* queries_f32,
+                                         const float* scales, size_t nq, size_t r, size_t k, int mode, int64_t* scores, uint32_t* ids);
+int mse_shard_group_query_topk_grouped(mse_shard_group* g, const mse_shard_groups* sg, const mse_shard_filter* sf, const uint16_t* queries,
+                                       const float* luts, const float* scales, size_t nq, int disable_pq, size_t beamwidth, size_t search_list,
+                                       size_t k, int regime, int64_t* scores, uint32_t* ids);
+/* mse_disk_query_topk_block with one result per group of `groups` (non-null; LOCAL row ids) over has_url AND f (f may be NULL: the
+ * unfiltered traversal, regime ignored): the grouped request path (mse_disk_query_topk_grouped) with the results left on the device as a
+ * packed block, ids + id_offset; never coalesced. */
+int mse_disk_query_topk_block_grouped(mse_searcher* s, mse_pq* pq, const mse_codes* c, const mse_graph* g, const mse_groups* groups,
+                                      const mse_filter* f, int regime, const uint32_t* starts, const uint16_t* queries, const float* luts,
+                                      const float* scales, size_t nq, int disable_pq, size_t beamwidth, size_t search_list, size_t k,
+                                      uint64_t id_offset, void* block_dev, uint32_t* n_visited, uint32_t* cmps, uint32_t* pq_cmps);
 /* measurement hook of the row-gather kernel of mse_graph_compact (for scripts/graph_compact_probe.py): *last_gather_ms (or null)
  * receives the HIP-event time of that kernel in the last mse_graph_compact made on s while the switch was on (0: none), then the
  * switch is set (0 off, 1 on, 2 on and reset).  The kernel reads n_live and writes capacity rows of 2 d + code_size + n_desc bytes. */

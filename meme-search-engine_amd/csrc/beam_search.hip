@@ -2048,6 +2048,27 @@ int mse_disk_query_topk_block_filtered(mse_searcher* s, mse_pq* pq, const mse_co
     return fused_run(in, fz);
 }
 
+// The grouped request path (mse_disk_query_topk_grouped: f may be NULL, regime is then ignored) with the shard's hand-over; never
+// coalesced.  The call's own checks first, then the grouping's (check_grouping), as in every grouped entry point.
+int mse_disk_query_topk_block_grouped(mse_searcher* s, mse_pq* pq, const mse_codes* c, const mse_graph* g, const mse_groups* groups,
+                                      const mse_filter* f, int regime, const uint32_t* starts, const uint16_t* queries, const float* luts,
+                                      const float* scales, size_t nq, int disable_pq, size_t beamwidth, size_t search_list, size_t k,
+                                      uint64_t id_offset, void* block_dev, uint32_t* n_visited, uint32_t* cmps, uint32_t* pq_cmps) {
+    if (!g || !queries || !block_dev) return fail("disk_query_topk_block: null argument");
+    SearchIn in{s, pq, c, g, starts, queries, nullptr, luts, scales, nq, disable_pq, beamwidth, search_list, f};
+    if (f && filtered_resolve(in, regime)) return -1;
+    if (nq == 0) return 0;
+    if (!s || !s->base) return fail("disk_query_topk_block: null searcher");
+    if (check_k(k)) return -1;
+    in.groups = groups; in.grouped = true;
+    if (check_grouping(in)) return -1;
+    FusedQuery fz = fused_out(k, nullptr, nullptr, n_visited, cmps, pq_cmps);
+    fz.dev_sc = reinterpret_cast<int64_t*>(block_dev);
+    fz.dev_ids = reinterpret_cast<uint32_t*>(static_cast<char*>(block_dev) + nq * k * 8);
+    fz.id_offset = id_offset;
+    return fused_run(in, fz);
+}
+
 int mse_graph_set_dedup(mse_graph* g, float threshold) {
     if (!g) return fail("null graph");
     if (!(threshold >= 0.0f)) return fail("graph_set_dedup: threshold must be >= 0 (0 = off)");

@@ -290,17 +290,6 @@ int mse_filter_read_ids(const mse_filter* f, size_t first, size_t n, uint32_t* o
 }
 
 // ---- a filter over GLOBAL rows cut into filters over LOCAL rows, and back (filter.hip slice_words_kernel / place_words_kernel) ----------
-// the thread's current device for the length of a call that must build on another one
-struct DeviceScope {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceScope(int device) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = hipSetDevice(device) == hipSuccess;
-    }
-    ~DeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
 static int resolve_filter_device(int device, int own, const char* who) {
     if (device < 0) return own;
     int n_dev = 0;

@@ -1,5 +1,6 @@
-// Row groupings of the grouped ("collapse") search (include/mse.h mse_groups): one result per group.  Four device pieces (the fourth,
-// the group step over the graph request path's unranked visited lists, is described where it stands):
+// Row groupings of the grouped ("collapse") search (include/mse.h mse_groups): one result per group.  Six device pieces (the fourth, the
+// group step over the graph request path's unranked visited lists, its twin over the gathered blocks of a sharded search -- the grouped
+// merge -- and the relabelling of a grouping cut to a shard's rows are described where they stand):
 //   1. validation and count of a grouping: the largest non-NONE id, the NONE rows, the distinct ids (presence bitmap + popcount);
 //   2. the order-preserving collapse of a ranked candidate list: one workgroup per query, an LDS open-addressing table keyed by group in
 //      which every entry publishes its rank by atomic min; an entry whose own rank stands is its group's representative; the survivors
@@ -313,9 +314,22 @@ __device__ __forceinline__ void vg_store(T* p, T v) {
     else *p = v;
 }
 
-template <bool GLOBAL>
-__device__ __forceinline__ void visited_group_body(uint32_t* __restrict__ ids, long long* __restrict__ scores, uint32_t n,
-                                                   const uint32_t* __restrict__ group_of, size_t g_len, uint32_t bits,
+// Where the records of one query's list live.  Flat: one contiguous list, the request path's visited list.  Blocks: the gathered
+// packed blocks of a sharded search (shard_group.hip merge_packed's addressing) -- record i is record i % k_in of shard i / k_in, a
+// shard's ids / scores of the query id_stride / sc_stride elements after the previous shard's.
+struct VgFlat {
+    uint32_t* ids; long long* scores;
+    __device__ __forceinline__ uint32_t* id_at(uint32_t i) const { return ids + i; }
+    __device__ __forceinline__ long long* score_at(uint32_t i) const { return scores + i; }
+};
+struct VgBlocks {
+    uint32_t* ids; long long* scores; uint32_t k_in; size_t id_stride, sc_stride;
+    __device__ __forceinline__ uint32_t* id_at(uint32_t i) const { return ids + (size_t)(i / k_in) * id_stride + i % k_in; }
+    __device__ __forceinline__ long long* score_at(uint32_t i) const { return scores + (size_t)(i / k_in) * sc_stride + i % k_in; }
+};
+
+template <bool GLOBAL, typename Rec>
+__device__ __forceinline__ void visited_group_body(const Rec rec, uint32_t n, const uint32_t* __restrict__ group_of, size_t g_len, uint32_t bits,
                                                    unsigned long long* t_best, uint32_t* t_key, uint32_t* t_id) {
     const uint32_t t = threadIdx.x, slots = 1u << bits, mask = slots - 1u;
     for (uint32_t i = t; i < slots; i += VG_THREADS) {
@@ -326,7 +340,7 @@ __device__ __forceinline__ void visited_group_body(uint32_t* __restrict__ ids, l
     __syncthreads();
     auto group = [&](uint32_t id) { return id != ID_NONE && id < g_len ? group_of[id] : GROUP_NONE; };
     for (uint32_t i = t; i < n; i += VG_THREADS) {   // claim the group's slot, publish the score
-        const uint32_t g = group(ids[i]);
+        const uint32_t g = group(*rec.id_at(i));
         if (g == GROUP_NONE) continue;
         uint32_t h = (g * 2654435761u) >> (32 - bits);
         for (;;) {
@@ -334,24 +348,41 @@ __device__ __forceinline__ void visited_group_body(uint32_t* __restrict__ ids, l
             if (prev == GROUP_NONE || prev == g) break;
             h = (h + 1) & mask;
         }
-        const unsigned long long v = sortable_i64(scores[i]);
+        const unsigned long long v = sortable_i64(*rec.score_at(i));
         if (vg_load<GLOBAL>(&t_best[h]) < v) atomicMax(&t_best[h], v);   // (the slot only grows: a stale, lower read merely costs the atomic)
     }
     __syncthreads();
     for (uint32_t i = t; i < n; i += VG_THREADS) {   // among the records that hold the maximum, the lowest id
-        const uint32_t id = ids[i], g = group(id);
+        const uint32_t id = *rec.id_at(i), g = group(id);
         if (g == GROUP_NONE) continue;
         uint32_t h = (g * 2654435761u) >> (32 - bits);
         while (vg_load<GLOBAL>(&t_key[h]) != g) h = (h + 1) & mask;   // (entered above)
-        if (sortable_i64(scores[i]) == vg_load<GLOBAL>(&t_best[h]) && vg_load<GLOBAL>(&t_id[h]) > id) atomicMin(&t_id[h], id);
+        if (sortable_i64(*rec.score_at(i)) == vg_load<GLOBAL>(&t_best[h]) && vg_load<GLOBAL>(&t_id[h]) > id) atomicMin(&t_id[h], id);
     }
     __syncthreads();
     for (uint32_t i = t; i < n; i += VG_THREADS) {   // everything else of the group leaves the list
-        const uint32_t id = ids[i], g = group(id);
+        const uint32_t id = *rec.id_at(i), g = group(id);
         if (g == GROUP_NONE) continue;
         uint32_t h = (g * 2654435761u) >> (32 - bits);
         while (vg_load<GLOBAL>(&t_key[h]) != g) h = (h + 1) & mask;
-        if (vg_load<GLOBAL>(&t_id[h]) != id) { ids[i] = ID_NONE; scores[i] = (long long)INT64_MIN; }
+        if (vg_load<GLOBAL>(&t_id[h]) != id) { *rec.id_at(i) = ID_NONE; *rec.score_at(i) = (long long)INT64_MIN; }
+    }
+}
+
+// the query's table: best keys | groups | ids of the slots in use, packed at its front (two call sites, so that each inlined copy of the
+// body knows its address space: LDS atomics stay ds_ instructions)
+template <bool GLOBAL, typename Rec>
+__device__ __forceinline__ void visited_group_run(const Rec rec, uint32_t n, const uint32_t* __restrict__ group_of, size_t g_len, char* smem,
+                                                  unsigned long long* table, size_t q, uint32_t slots_cap) {
+    uint32_t bits = 6;
+    while ((1u << bits) < 2u * n) bits++;   // <= slots_cap: n <= cap
+    if constexpr (GLOBAL) {
+        char* tab = reinterpret_cast<char*>(table) + q * (size_t)slots_cap * 16;
+        visited_group_body<true>(rec, n, group_of, g_len, bits, reinterpret_cast<unsigned long long*>(tab),
+                                 reinterpret_cast<uint32_t*>(tab + ((size_t)8 << bits)), reinterpret_cast<uint32_t*>(tab + ((size_t)12 << bits)));
+    } else {
+        visited_group_body<false>(rec, n, group_of, g_len, bits, reinterpret_cast<unsigned long long*>(smem),
+                                  reinterpret_cast<uint32_t*>(smem + ((size_t)8 << bits)), reinterpret_cast<uint32_t*>(smem + ((size_t)12 << bits)));
     }
 }
 
@@ -362,18 +393,48 @@ __global__ __launch_bounds__(VG_THREADS) void visited_group_kernel(uint32_t* __r
     extern __shared__ __attribute__((aligned(16))) char vg_smem[];
     const size_t q = blockIdx.x;
     const uint32_t n = (uint32_t)min((size_t)n_visited[q], cap);
-    uint32_t bits = 6;
-    while ((1u << bits) < 2u * n) bits++;   // <= slots_cap: n <= cap
-    // best keys | groups | ids of the slots in use, packed at the front of the query's table (two call sites, so that each inlined copy
-    // of the body knows its address space: LDS atomics stay ds_ instructions)
-    if constexpr (GLOBAL) {
-        char* tab = reinterpret_cast<char*>(table) + q * (size_t)slots_cap * 16;
-        visited_group_body<true>(vis_ids + q * cap, vis_scores + q * cap, n, group_of, g_len, bits, reinterpret_cast<unsigned long long*>(tab),
-                                 reinterpret_cast<uint32_t*>(tab + ((size_t)8 << bits)), reinterpret_cast<uint32_t*>(tab + ((size_t)12 << bits)));
-    } else {
-        visited_group_body<false>(vis_ids + q * cap, vis_scores + q * cap, n, group_of, g_len, bits, reinterpret_cast<unsigned long long*>(vg_smem),
-                                  reinterpret_cast<uint32_t*>(vg_smem + ((size_t)8 << bits)), reinterpret_cast<uint32_t*>(vg_smem + ((size_t)12 << bits)));
-    }
+    visited_group_run<GLOBAL>(VgFlat{vis_ids + q * cap, vis_scores + q * cap}, n, group_of, g_len, vg_smem, table, q, slots_cap);
+}
+
+// ---- 5. the grouped merge of a sharded search (shard_group.hip) -------------------------------------------------------------------------
+// The same step over the gathered packed blocks, in place: n_shards blocks of {[nq][k_in] i64 scores, [nq][k_in] u32 GLOBAL ids},
+// block_bytes apart; query q0 + blockIdx.x (a launch takes a chunk of queries when the table is in global memory: its row of the table
+// is blockIdx.x).  group_of is the GLOBAL grouping.  Every record of the n_shards * k_in of a query is looked at: holes and padding
+// (ID_NONE) anywhere are skipped by the body.
+template <bool GLOBAL>
+__global__ __launch_bounds__(VG_THREADS) void merge_group_kernel(char* __restrict__ blocks, size_t block_bytes, uint32_t n_shards, size_t nq, size_t q0,
+                                                                 uint32_t k_in, const uint32_t* __restrict__ group_of, size_t g_len,
+                                                                 unsigned long long* __restrict__ table, uint32_t slots_cap) {
+    extern __shared__ __attribute__((aligned(16))) char vg_smem[];
+    const size_t q = q0 + blockIdx.x;
+    const VgBlocks rec{reinterpret_cast<uint32_t*>(blocks + nq * k_in * 8) + q * k_in, reinterpret_cast<long long*>(blocks) + q * k_in, k_in,
+                       block_bytes / 4, block_bytes / 8};
+    visited_group_run<GLOBAL>(rec, n_shards * k_in, group_of, g_len, vg_smem, table, blockIdx.x, slots_cap);
+}
+
+// ---- 6. a grouping cut to a row range and relabelled (mse_groups_slice) -----------------------------------------------------------------
+// labels [m]: the source's labels of the slice's rows (each below src_len, or NONE); table [src_len] u32, uninitialised.  Three launches
+// on one stream: the entries the slice touches are set to all ones, every row publishes its local id under its label by atomic min, and a
+// row's new label is what stands under its old one -- the local id of the first row of its group inside the slice.  Order-independent.
+__global__ __launch_bounds__(256) void groups_slice_clear_kernel(const uint32_t* __restrict__ labels, size_t m, uint32_t* __restrict__ table) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const uint32_t g = labels[i];
+    if (g != GROUP_NONE) table[g] = 0xFFFFFFFFu;
+}
+__global__ __launch_bounds__(256) void groups_slice_min_kernel(const uint32_t* __restrict__ labels, size_t m, uint32_t* __restrict__ table) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const uint32_t g = labels[i];
+    if (g == GROUP_NONE) return;   // (the entry only falls: a stale, higher read merely costs the atomic)
+    if (__hip_atomic_load(&table[g], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > (uint32_t)i) atomicMin(&table[g], (uint32_t)i);
+}
+__global__ __launch_bounds__(256) void groups_slice_lookup_kernel(const uint32_t* __restrict__ labels, size_t m, const uint32_t* __restrict__ table,
+                                                                 uint32_t* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const uint32_t g = labels[i];
+    out[i] = g == GROUP_NONE ? GROUP_NONE : table[g];
 }
 
 // table slots a list of up to `cap` records may need: the power of two of at least 2 cap (64 at least)
@@ -415,6 +476,45 @@ int launch_visited_group(uint32_t* vis_ids, long long* vis_scores, size_t cap, c
                            n_visited + q0, group_of, g_len, static_cast<unsigned long long*>(table), (uint32_t)slots);
         MSE_HIP_TRY(hipGetLastError());
     }
+    return 0;
+}
+
+size_t merge_group_scratch_bytes(size_t nq, size_t n_records) { return visited_group_scratch_bytes(nq, n_records); }
+
+int launch_merge_group(void* blocks, size_t block_bytes, size_t n_shards, size_t nq, size_t k_in, const uint32_t* group_of, size_t g_len, void* table,
+                       hipStream_t stream) {
+    const size_t n = n_shards * k_in;
+    if (nq == 0 || n == 0) return 0;
+    if (n > ((size_t)1 << 30) || k_in > 0xFFFFFFFFull) return fail("merge_group: too many records per query");
+    if (block_bytes % 8 || block_bytes < nq * k_in * 12) return fail("merge_group: bad block stride");
+    const size_t slots = visited_group_slots(n);
+    if (n <= VG_LDS_CAP) {
+        MSE_DYN_LDS(merge_group_kernel<false>, slots * 16);
+        hipLaunchKernelGGL(merge_group_kernel<false>, dim3((unsigned)nq), dim3(VG_THREADS), slots * 16, stream, static_cast<char*>(blocks), block_bytes,
+                           (uint32_t)n_shards, nq, (size_t)0, (uint32_t)k_in, group_of, g_len, (unsigned long long*)nullptr, (uint32_t)slots);
+        MSE_HIP_TRY(hipGetLastError());
+        return 0;
+    }
+    if (!table) return fail("merge_group: no table");
+    const size_t chunk = visited_group_chunk_queries(nq, n);
+    for (size_t q0 = 0; q0 < nq; q0 += chunk) {   // chunks run one after the other on the stream: they share the table
+        const size_t m = std::min(chunk, nq - q0);
+        hipLaunchKernelGGL(merge_group_kernel<true>, dim3((unsigned)m), dim3(VG_THREADS), 0, stream, static_cast<char*>(blocks), block_bytes,
+                           (uint32_t)n_shards, nq, q0, (uint32_t)k_in, group_of, g_len, static_cast<unsigned long long*>(table), (uint32_t)slots);
+        MSE_HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+int launch_groups_slice(const uint32_t* labels, size_t m, uint32_t* table, uint32_t* out, hipStream_t stream) {
+    if (m == 0) return 0;
+    const dim3 grid((unsigned)((m + 255) / 256)), block(256);
+    hipLaunchKernelGGL(groups_slice_clear_kernel, grid, block, 0, stream, labels, m, table);
+    MSE_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(groups_slice_min_kernel, grid, block, 0, stream, labels, m, table);
+    MSE_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(groups_slice_lookup_kernel, grid, block, 0, stream, labels, m, (const uint32_t*)table, out);
+    MSE_HIP_TRY(hipGetLastError());
     return 0;
 }
 

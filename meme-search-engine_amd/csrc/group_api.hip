@@ -96,6 +96,48 @@ void mse_groups_free(mse_groups* g) {
 size_t mse_groups_len(const mse_groups* g) { return g ? g->n_rows : 0; }
 size_t mse_groups_count(const mse_groups* g) { return g ? g->count : 0; }
 
+int mse_groups_read(const mse_groups* g, uint32_t* out) {
+    if (!g) return fail("groups_read: null grouping");
+    if (g->n_rows == 0) return 0;
+    if (!out) return fail("groups_read: null buffer");
+    if (hipMemcpy(out, g->group_of, g->n_rows * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail("groups_read: the read-back failed");
+    return 0;
+}
+
+// The partition src induces on rows [first_row, first_row + n_rows), over local ids and canonically labelled (group.hip
+// launch_groups_slice); validated and counted like any other grouping.  The scratch table goes when the call returns: groups_finish blocks
+mse_groups* mse_groups_slice(const mse_groups* src, uint64_t first_row, size_t n_rows, int device) {
+    if (!src) { fail("groups_slice: null grouping"); return nullptr; }
+    if (n_rows == 0) { fail("groups_slice: n_rows must be positive"); return nullptr; }
+    if (first_row > 0xFFFFFFFEull) { fail("groups_slice: row ids are u32: first_row is too large"); return nullptr; }
+    int dev = src->device;
+    if (device >= 0) {
+        int n_dev = 0;
+        if (hipGetDeviceCount(&n_dev) != hipSuccess || device >= n_dev) { fail("groups_slice: device ordinal out of range"); return nullptr; }
+        dev = device;
+    }
+    DeviceScope scope(dev);
+    if (!scope.ok) { fail("groups_slice: hipSetDevice failed"); return nullptr; }
+    const size_t m = first_row < src->n_rows ? std::min<size_t>(n_rows, src->n_rows - (size_t)first_row) : 0;   // the part inside src
+    int made_on = 0;
+    uint32_t* out = groups_alloc(m, &made_on);
+    if (!out) return nullptr;
+    DevBuf range, table;
+    if (m) {
+        const uint32_t* labels = src->group_of + first_row;
+        if (dev != src->device) {   // another device: the slice's labels come over by ONE peer copy and are relabelled here
+            if (range.ensure(m * 4)) { (void)hipFree(out); return nullptr; }
+            if (hipMemcpyPeer(range.p, dev, labels, src->device, m * 4) != hipSuccess) {
+                (void)hipGetLastError();
+                (void)hipFree(out); fail("groups_slice: the peer copy failed"); return nullptr;
+            }
+            labels = range.as<uint32_t>();
+        }
+        if (table.ensure(src->n_rows * 4) || launch_groups_slice(labels, m, table.as<uint32_t>(), out, nullptr)) { (void)hipFree(out); return nullptr; }
+    }
+    return groups_finish(out, m, dev);
+}
+
 int mse_searcher_grouped_stats(const mse_searcher* s, uint32_t out[3]) {
     if (!s || !out) return fail("null argument");
     for (int i = 0; i < 3; i++) out[i] = s->last_grouped[i];

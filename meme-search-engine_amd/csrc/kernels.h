@@ -229,6 +229,15 @@ int launch_dense_complete(const int64_t* scores, size_t stride, size_t n, const 
 size_t visited_group_scratch_bytes(size_t nq, size_t cap);
 int launch_visited_group(uint32_t* vis_ids, long long* vis_scores, size_t cap, const uint32_t* n_visited, size_t nq, const uint32_t* group_of,
                          size_t g_len, void* table, hipStream_t stream);
+// The same step over the gathered packed blocks of a sharded search, in place (the grouped merge, include/mse.h): n_shards blocks of
+// {[nq][k_in] i64 scores, [nq][k_in] u32 GLOBAL ids}, block_bytes apart; group_of / g_len: the GLOBAL grouping, on the blocks' device.
+// n_shards * k_in <= 4096 records per query: the table lives in LDS; more: merge_group_scratch_bytes(nq, n_shards * k_in) bytes of `table`
+size_t merge_group_scratch_bytes(size_t nq, size_t n_records);
+int launch_merge_group(void* blocks, size_t block_bytes, size_t n_shards, size_t nq, size_t k_in, const uint32_t* group_of, size_t g_len, void* table,
+                       hipStream_t stream);
+// mse_groups_slice's relabelling: labels [m] (each below the source's length, or NONE) -> out [m], the lowest i with the same label (NONE
+// stays); table: scratch of the source's length in u32, uninitialised
+int launch_groups_slice(const uint32_t* labels, size_t m, uint32_t* table, uint32_t* out, hipStream_t stream);
 
 // ---- graph_build.hip: what graph_delete.hip shares with the build ---------------------------------------------------------------
 // robust_prune (lib.rs:227-285), one workgroup per candidate list: list k is (ci, cs)[k * stride ..][0 .. counts[k]) in HBM, its point

@@ -19,6 +19,17 @@ struct DevBuf {
     template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
+// the thread's current device for the length of a call that must build on another one (filter_api.hip, group_api.hip)
+struct DeviceScope {
+    int prev = -1;
+    bool ok = false;
+    explicit DeviceScope(int device) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        ok = hipSetDevice(device) == hipSuccess;
+    }
+    ~DeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
 // growable pinned host staging: grows to max(2 x bytes, floor) by hipHostMalloc + free (contents are NOT preserved).  Move-only: it
 // lives in objects that are moved (a vector of worker contexts), never copied
 struct PinBuf {
@@ -218,6 +229,9 @@ int bruteforce_auto_mode(const mse_base* b, const mse_filter* f, size_t nq, bool
 // the body of mse_bruteforce_topk_f16_dev (f = null) and mse_bruteforce_topk_filtered_f16_dev, validation included (bruteforce.hip)
 int bruteforce_topk_dev(mse_searcher* s, const mse_filter* f, const void* queries_dev, size_t nq, size_t k, int mode, uint64_t id_offset,
                         void* scores_dev, void* ids_dev);
+// the body of mse_bruteforce_topk_grouped_f16_dev (g non-null, f may be null), validation included (bruteforce.hip)
+int grouped_topk_dev(mse_searcher* s, const mse_groups* g, const mse_filter* f, const void* queries_dev, size_t nq, size_t k, int mode,
+                     uint64_t id_offset, void* scores_dev, void* ids_dev);
 // One exact pass of <= 8 queries (staged, padded, in s->q_stage) over the rows ids[0 .. n) -- ascending; null: rows 0 .. n -- and the
 // exact top-k of each: i64 scores in the reference order, (score desc, id asc), padding INT64_MIN / ID_NONE; a row that is not listed is
 // absent.  bias (optional, needs ids): the descriptor product of every listed row is added to its score before the selection.

@@ -14,7 +14,9 @@
 //   mse_comm          one process per GPU (torchrun's shape): ONE ncclAllGather of the packed 12-byte-per-record block on the
 //                     searcher's stream through librccl.so (dlopen'ed here; the unique id travels through the host's own
 //                     rendezvous), then the same merge on every rank.
-// The merge is the radix select of topk.hip over the G*k candidates of a query (unique composite key, so deterministic).
+// The merge is the radix select of topk.hip over the G*k candidates of a query (unique composite key, so deterministic).  The grouped
+// searches (one result per group; mse_shard_groups) collapse the gathered records by the GLOBAL grouping first, in place
+// (merge_packed_grouped: group.hip's group step over the block addresses), because a group's rows straddle shard boundaries.
 #include "../../include/mse.h"
 #include "runtime.h"
 #include <dlfcn.h>
@@ -58,6 +60,20 @@ int merge_packed(mse_searcher* s, const char* gathered, size_t n_shards, size_t 
     return launch_finalize(s->misc.as<uint32_t>(), s->sel_keys.as<int64_t>(), k, (int)k, (int)nq, 0,
                            reinterpret_cast<int64_t*>(out_scores_dev), reinterpret_cast<uint32_t*>(out_ids_dev), k, nullptr, 0,
                            0, 0, nullptr, nullptr, s->stream);
+}
+
+// the grouped merge (include/mse.h): of every group of the GLOBAL grouping the best record over all blocks stays, the others become holes IN
+// PLACE; then merge_packed as it is.  labels / g_len on the searcher's device; the table past 4096 records per query is the searcher's
+// pool[15], as on the request path
+int merge_packed_grouped(mse_searcher* s, char* gathered, size_t n_shards, size_t nq, size_t k, size_t k_in, const uint32_t* labels, size_t g_len,
+                         void* out_scores_dev, void* out_ids_dev) {
+    if (k_in == 0) k_in = k;
+    if (k > (size_t)TOPK_KMAX || k_in > (size_t)TOPK_KMAX) return fail("k too large");
+    DevBuf& gt = s->pool[15];
+    const size_t table_bytes = merge_group_scratch_bytes(nq, n_shards * k_in);
+    if (table_bytes && gt.ensure(table_bytes)) return -1;
+    if (launch_merge_group(gathered, block_bytes(nq, k_in), n_shards, nq, k_in, labels, g_len, gt.p, s->stream)) return -1;
+    return merge_packed(s, gathered, n_shards, nq, k, out_scores_dev, out_ids_dev, k_in);
 }
 
 // rows of the global top-r that live on this shard: local id = global id - first_row, ID_NONE for everybody else's
@@ -207,6 +223,16 @@ struct mse_shard_filter {
     std::vector<uint64_t> first_rows;     // global id of each part's row 0
 };
 
+// the grouping of a group's global rows, cut for its shards (include/mse.h)
+struct mse_shard_groups {
+    uint64_t layout = 0;                  // the group's stamp when it was made
+    std::vector<mse_groups*> parts;       // owned; part g speaks the LOCAL ids of shard g; null: the shard lies wholly past the grouping
+    std::vector<uint64_t> first_rows;     // global id of each part's row 0
+    int root_device = 0;
+    uint32_t* labels = nullptr;           // owned, on the root device: the global label array, looked up by global row id in the merge
+    size_t len = 0;                       // its length
+};
+
 // contiguous split, remainder spread over the first shards (the same rule as the host mirror's shard_range)
 static void shard_range(size_t n, size_t g, size_t G, size_t* lo, size_t* hi) {
     const size_t base = n / G, rem = n % G;
@@ -222,6 +248,19 @@ int mse_merge_topk_packed_dev(mse_searcher* s, const void* gathered_blocks_dev, 
     if (!s) return fail("null searcher");
     if (nq == 0 || k == 0 || n_shards == 0) return 0;
     return merge_packed(s, reinterpret_cast<const char*>(gathered_blocks_dev), n_shards, nq, k, out_scores_dev, out_ids_dev);
+}
+// the same with the grouped merge's step first, IN PLACE: the caller's blocks lose every non-representative record
+int mse_merge_topk_packed_grouped_dev(mse_searcher* s, const mse_groups* groups_global, void* gathered_blocks_dev, size_t n_shards, size_t nq,
+                                      size_t k_in, size_t k, void* out_scores_dev, void* out_ids_dev) {
+    if (!s) return fail("null searcher");
+    if (!groups_global) return fail("null grouping");
+    if (nq == 0 || k == 0 || n_shards == 0) return 0;
+    if (!gathered_blocks_dev || !out_scores_dev || !out_ids_dev) return fail("merge_topk_packed_grouped: null argument");
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || groups_global->device != (s->base ? s->base->device : dev))
+        return fail("merge_topk_packed_grouped: the grouping was made on another device than the searcher's");
+    return merge_packed_grouped(s, static_cast<char*>(gathered_blocks_dev), n_shards, nq, k, k_in, groups_global->group_of, groups_global->n_rows,
+                                out_scores_dev, out_ids_dev);
 }
 
 mse_shard_group* mse_shard_group_new(const int* devices, size_t n_shards, size_t d) {
@@ -373,8 +412,9 @@ int mse_shard_group_set_shard_device(mse_shard_group* G, size_t shard, const voi
 using LocalFn = std::function<int(Shard& sh, const void* q, char* blk)>;
 
 // One sharded search: every shard's local step, ONE exchange of the packed blocks, the k best of all shards' k_in records per query.
+// mg: the grouping whose global labels collapse the gathered records before the selection (the grouped merge); null: the plain merge.
 static int search_dev_locked(mse_shard_group* G, const void* queries_dev, size_t qbytes, size_t nq, size_t k_in, size_t k, const LocalFn& local,
-                             void* scores_dev, void* ids_dev) {
+                             void* scores_dev, void* ids_dev, const mse_shard_groups* mg = nullptr) {
     for (const Shard& s : G->shards) if (!s.searcher) return fail("shard group: a shard holds no rows yet");
     const auto wall0 = std::chrono::steady_clock::now();
     const size_t n_shards = G->shards.size();
@@ -384,7 +424,7 @@ static int search_dev_locked(mse_shard_group* G, const void* queries_dev, size_t
     (void)hipGetDevice(&prev);
     MSE_HIP_TRY(hipSetDevice(G->root_device));
     int rc = use_rccl ? 0 : G->gathered.ensure(B * n_shards);
-    const char* merged_from = nullptr;
+    char* merged_from = nullptr;
     if (!rc) {
         char* const gathered = G->gathered.as<char>();
         rc = G->run([=](size_t g) -> int {
@@ -460,7 +500,7 @@ static int search_dev_locked(mse_shard_group* G, const void* queries_dev, size_t
                 G->exchange = MSE_EXCHANGE_PEER;
                 G->rccl_ranks = 0;
                 (void)hipSetDevice(prev);
-                const int rc2 = search_dev_locked(G, queries_dev, qbytes, nq, k_in, k, local, scores_dev, ids_dev);   // over the peer-store exchange
+                const int rc2 = search_dev_locked(G, queries_dev, qbytes, nq, k_in, k, local, scores_dev, ids_dev, mg);   // over the peer-store exchange
                 if (rc2) return rc2;
                 set_error("RCCL exchange failed and was shut down (" + why + "); the search was answered over the peer-store exchange");
                 return 0;
@@ -470,7 +510,8 @@ static int search_dev_locked(mse_shard_group* G, const void* queries_dev, size_t
         hipStream_t rs = G->root->stream;
         if (!rc) for (hipEvent_t& e : G->ev_merge) if (!e && hipEventCreate(&e) != hipSuccess) rc = fail("shard group: event");
         if (!rc && hipEventRecord(G->ev_merge[0], rs) != hipSuccess) rc = fail("shard group: event");
-        if (!rc) rc = merge_packed(G->root, merged_from, n_shards, nq, k, scores_dev, ids_dev, k_in);
+        if (!rc) rc = mg ? merge_packed_grouped(G->root, merged_from, n_shards, nq, k, k_in, mg->labels, mg->len, scores_dev, ids_dev)
+                         : merge_packed(G->root, merged_from, n_shards, nq, k, scores_dev, ids_dev, k_in);
         if (!rc && hipEventRecord(G->ev_merge[1], rs) != hipSuccess) rc = fail("shard group: event");
         if (!rc && hipStreamSynchronize(rs) != hipSuccess) rc = fail("shard group: merge failed");
         if (!rc) {
@@ -518,9 +559,12 @@ static int bring_up_rccl(mse_shard_group* G) {
 
 // the brute-force local step: exact top-k of the shard's rows -- of those its slice of sf allows (null: all; the slice speaks local ids) --
 // with global ids (the shard's first row added)
-static LocalFn bruteforce_local(const mse_shard_group* G, const mse_shard_filter* sf, size_t nq, size_t k, int mode) {
+// sg (null: ungrouped): one record per group of the shard's part; a shard wholly past the grouping has no part and runs the ungrouped call
+static LocalFn bruteforce_local(const mse_shard_group* G, const mse_shard_filter* sf, const mse_shard_groups* sg, size_t nq, size_t k, int mode) {
     return [=](Shard& sh, const void* q, char* blk) -> int {
-        const mse_filter* f = sf ? sf->parts[(size_t)(&sh - G->shards.data())] : nullptr;
+        const size_t g = (size_t)(&sh - G->shards.data());
+        const mse_filter* f = sf ? sf->parts[g] : nullptr;
+        if (sg && sg->parts[g]) return grouped_topk_dev(sh.searcher, sg->parts[g], f, q, nq, k, mode, sh.first_row, blk, blk + nq * k * 8);
         return bruteforce_topk_dev(sh.searcher, f, q, nq, k, mode, sh.first_row, blk, blk + nq * k * 8);
     };
 }
@@ -540,6 +584,20 @@ static int check_shard_filter(const mse_shard_group* G, const mse_shard_filter* 
     return 0;
 }
 
+// The same for shard groups; "null shard groups" is an error of its own
+static int check_shard_groups(const mse_shard_group* G, const mse_shard_groups* sg) {
+    if (!sg) return fail("shard group: null shard groups");
+    if (sg->layout != G->layout || sg->parts.size() != G->shards.size())
+        return fail("shard group: the shard groups were made for another group, or before the group's rows were replaced");
+    for (size_t g = 0; g < G->shards.size(); g++) {
+        const Shard& sh = G->shards[g];
+        const mse_groups* p = sg->parts[g];
+        if (!sh.base || (p && (p->n_rows > sh.base->n || p->device != sh.device)) || sg->first_rows[g] != sh.first_row || sg->root_device != G->root_device)
+            return fail("shard group: the shard groups do not fit shard " + std::to_string(g));
+    }
+    return 0;
+}
+
 static bool known_mode(int mode) { return mode == MSE_MODE_AUTO || mode == MSE_MODE_EXACT || mode == MSE_MODE_MFMA; }
 
 // The brute-force entry points, sf = null being the unfiltered search.  One order of checks for all four: the group, the mode and k before
@@ -551,9 +609,11 @@ static int check_search(const mse_shard_group* G, int mode, size_t k) {
     return 0;
 }
 // the caller holds G->call_mu: -1 with the error set, 0 = nothing to do, 1 = go on
-static int check_search_locked(const mse_shard_group* G, const mse_shard_filter* sf, const void* queries, size_t nq, size_t k, const void* scores,
-                               const void* ids) {
+// grouped: the call takes shard groups, checked -- null included -- after the filter
+static int check_search_locked(const mse_shard_group* G, const mse_shard_filter* sf, bool grouped, const mse_shard_groups* sg, const void* queries,
+                               size_t nq, size_t k, const void* scores, const void* ids) {
     if (sf && check_shard_filter(G, sf)) return -1;
+    if (grouped && check_shard_groups(G, sg)) return -1;
     if (nq == 0 || k == 0) return 0;
     if (!queries || !scores || !ids) return fail("shard group: null argument");
     return 1;
@@ -561,29 +621,29 @@ static int check_search_locked(const mse_shard_group* G, const mse_shard_filter*
 
 // queries_dev: [nq][d] f16 on the ROOT device (device of shard 0), complete before the call; outputs [nq][k] on the root device.
 // Returns when the merged result is complete.
-static int search_dev_impl(mse_shard_group* G, const mse_shard_filter* sf, const void* queries_dev, size_t nq, size_t k, int mode,
-                           void* scores_dev, void* ids_dev) {
+static int search_dev_impl(mse_shard_group* G, const mse_shard_filter* sf, bool grouped, const mse_shard_groups* sg, const void* queries_dev, size_t nq,
+                           size_t k, int mode, void* scores_dev, void* ids_dev) {
     if (check_search(G, mode, k)) return -1;
     std::lock_guard<std::mutex> call(G->call_mu);
-    if (const int go = check_search_locked(G, sf, queries_dev, nq, k, scores_dev, ids_dev); go <= 0) return go;
-    return search_dev_locked(G, queries_dev, nq * G->d * 2, nq, k, k, bruteforce_local(G, sf, nq, k, mode), scores_dev, ids_dev);
+    if (const int go = check_search_locked(G, sf, grouped, sg, queries_dev, nq, k, scores_dev, ids_dev); go <= 0) return go;
+    return search_dev_locked(G, queries_dev, nq * G->d * 2, nq, k, k, bruteforce_local(G, sf, sg, nq, k, mode), scores_dev, ids_dev, sg);
 }
 
 // the host form.  ONE lock across the check, upload, search and download: two host threads on the same group must not see each other's
 // queries in q_root or each other's answers in out_s / out_i
-static int search_impl(mse_shard_group* G, const mse_shard_filter* sf, const uint16_t* queries, size_t nq, size_t k, int mode, int64_t* scores,
-                       uint32_t* ids) {
+static int search_impl(mse_shard_group* G, const mse_shard_filter* sf, bool grouped, const mse_shard_groups* sg, const uint16_t* queries, size_t nq,
+                       size_t k, int mode, int64_t* scores, uint32_t* ids) {
     if (check_search(G, mode, k)) return -1;
     int prev = 0;
     (void)hipGetDevice(&prev);
     int rc = 0;
     {
         std::lock_guard<std::mutex> call(G->call_mu);
-        if (const int go = check_search_locked(G, sf, queries, nq, k, scores, ids); go <= 0) return go;
+        if (const int go = check_search_locked(G, sf, grouped, sg, queries, nq, k, scores, ids); go <= 0) return go;
         MSE_HIP_TRY(hipSetDevice(G->root_device));
         rc = G->q_root.ensure(nq * G->d * 2) || G->out_s.ensure(nq * k * 8) || G->out_i.ensure(nq * k * 4);
         if (!rc && hipMemcpy(G->q_root.p, queries, nq * G->d * 2, hipMemcpyHostToDevice) != hipSuccess) rc = fail("query upload failed");
-        if (!rc) rc = search_dev_locked(G, G->q_root.p, nq * G->d * 2, nq, k, k, bruteforce_local(G, sf, nq, k, mode), G->out_s.p, G->out_i.p);
+        if (!rc) rc = search_dev_locked(G, G->q_root.p, nq * G->d * 2, nq, k, k, bruteforce_local(G, sf, sg, nq, k, mode), G->out_s.p, G->out_i.p, sg);
         if (!rc && (hipMemcpy(scores, G->out_s.p, nq * k * 8, hipMemcpyDeviceToHost) != hipSuccess ||
                     hipMemcpy(ids, G->out_i.p, nq * k * 4, hipMemcpyDeviceToHost) != hipSuccess)) rc = fail("result download failed");
     }
@@ -595,24 +655,35 @@ extern "C" {
 
 int mse_shard_group_search_dev(mse_shard_group* G, const void* queries_dev, size_t nq, size_t k, int mode,
                                void* scores_dev, void* ids_dev) {
-    return search_dev_impl(G, nullptr, queries_dev, nq, k, mode, scores_dev, ids_dev);
+    return search_dev_impl(G, nullptr, false, nullptr, queries_dev, nq, k, mode, scores_dev, ids_dev);
 }
 
 int mse_shard_group_search_filtered_dev(mse_shard_group* G, const mse_shard_filter* sf, const void* queries_dev, size_t nq, size_t k, int mode,
                                         void* scores_dev, void* ids_dev) {
     if (G && !sf) return fail("shard group: null shard filter");
-    return search_dev_impl(G, sf, queries_dev, nq, k, mode, scores_dev, ids_dev);
+    return search_dev_impl(G, sf, false, nullptr, queries_dev, nq, k, mode, scores_dev, ids_dev);
 }
 
 int mse_shard_group_search_filtered(mse_shard_group* G, const mse_shard_filter* sf, const uint16_t* queries, size_t nq, size_t k, int mode,
                                     int64_t* scores, uint32_t* ids) {
     if (G && !sf) return fail("shard group: null shard filter");
-    return search_impl(G, sf, queries, nq, k, mode, scores, ids);
+    return search_impl(G, sf, false, nullptr, queries, nq, k, mode, scores, ids);
 }
 
 int mse_shard_group_search(mse_shard_group* G, const uint16_t* queries, size_t nq, size_t k, int mode, int64_t* scores,
                            uint32_t* ids) {
-    return search_impl(G, nullptr, queries, nq, k, mode, scores, ids);
+    return search_impl(G, nullptr, false, nullptr, queries, nq, k, mode, scores, ids);
+}
+
+// one result per group of sg (non-null; checked under the lock, after the filter), over the rows sf allows (null: all)
+int mse_shard_group_search_grouped(mse_shard_group* G, const mse_shard_groups* sg, const mse_shard_filter* sf, const uint16_t* queries, size_t nq,
+                                   size_t k, int mode, int64_t* scores, uint32_t* ids) {
+    return search_impl(G, sf, true, sg, queries, nq, k, mode, scores, ids);
+}
+
+int mse_shard_group_search_grouped_dev(mse_shard_group* G, const mse_shard_groups* sg, const mse_shard_filter* sf, const void* queries_dev,
+                                       size_t nq, size_t k, int mode, void* scores_dev, void* ids_dev) {
+    return search_dev_impl(G, sf, true, sg, queries_dev, nq, k, mode, scores_dev, ids_dev);
 }
 
 // ---- the approximate-search paths over the same shards (round 5; SURVEY 8(e): "rows (and their PQ codes / descriptors)") ---------
@@ -671,8 +742,9 @@ static int pq_rescore_members(const mse_base* b, const mse_codes* codes, uint64_
 // Records exchanged: 2 x shards x nq x r x 12 bytes (r = 200, 32 queries, 8 shards: 1.2 MB in all).
 // sf: the allowed rows (null: all; then `mode` is unused) -- phase A becomes mse_pq_scan_topk_block_filtered over the shard's slice, and
 // phase B stays as it is: every member of the merged top-r is allowed by construction
+// sg (null: ungrouped): phase B's final merge is the grouped merge -- one result per group of the exactly re-ranked global top-r
 static int pq_scan_topk_impl(mse_shard_group* G, const mse_shard_filter* sf, int mode, const float* queries_f32, const float* scales, size_t nq,
-                             size_t r, size_t k, int64_t* scores, uint32_t* ids) {
+                             size_t r, size_t k, int64_t* scores, uint32_t* ids, const mse_shard_groups* sg = nullptr) {
     if (!G || !queries_f32 || !scores || !ids) return fail("shard group pq scan: null argument");
     if (nq == 0 || k == 0) return 0;
     if (r < k) r = k;
@@ -686,7 +758,7 @@ static int pq_scan_topk_impl(mse_shard_group* G, const mse_shard_filter* sf, int
     int rc = 0;
     {
         std::lock_guard<std::mutex> call(G->call_mu);
-        if (sf && check_shard_filter(G, sf)) { (void)hipSetDevice(prev); return -1; }
+        if ((sf && check_shard_filter(G, sf)) || (sg && check_shard_groups(G, sg))) { (void)hipSetDevice(prev); return -1; }
         // root staging: [f16 queries nq x d][merged top-r ids nq x r][scales n_desc f32] -- phase B's payload, one buffer so that a shard
         // that cannot map the root's memory gets it in one peer copy
         const size_t off_ids = (nq * d * 2 + 255) & ~(size_t)255, off_sc = (off_ids + nq * r * 4 + 255) & ~(size_t)255;
@@ -716,7 +788,7 @@ static int pq_scan_topk_impl(mse_shard_group* G, const mse_shard_filter* sf, int
                 const char* p = static_cast<const char*>(q);
                 return pq_rescore_members(sh.base, sh.codes, sh.first_row, p, reinterpret_cast<const uint32_t*>(p + off_ids),
                                           bias ? reinterpret_cast<const float*>(p + off_sc) : nullptr, nq, r, sh.ann_a, sh.ann_b, blk, sh.searcher->stream);
-            }, G->out_s.p, G->out_i.p);
+            }, G->out_s.p, G->out_i.p, sg);
         if (!rc) for (int i = 0; i < 4; i++) G->last_ms[i] += tA[i];   // both phases
         if (!rc && (hipMemcpy(scores, G->out_s.p, nq * k * 8, hipMemcpyDeviceToHost) != hipSuccess ||
                     hipMemcpy(ids, G->out_i.p, nq * k * 4, hipMemcpyDeviceToHost) != hipSuccess)) rc = fail("result download failed");
@@ -742,14 +814,30 @@ int mse_shard_group_pq_scan_topk_filtered(mse_shard_group* G, const mse_shard_fi
     return pq_scan_topk_impl(G, sf, mode, queries_f32, scales, nq, r, k, scores, ids);
 }
 
+// the checks of the filtered call where sf is given, then the shard groups' (a stale object is refused even by a call that has nothing to do)
+int mse_shard_group_pq_scan_topk_grouped(mse_shard_group* G, const mse_shard_groups* sg, const mse_shard_filter* sf, const float* queries_f32,
+                                         const float* scales, size_t nq, size_t r, size_t k, int mode, int64_t* scores, uint32_t* ids) {
+    if (!G) return fail("shard group pq scan: null argument");
+    if (sf && mode != MSE_PQ_FILTER_AUTO && mode != MSE_PQ_FILTER_SCAN && mode != MSE_PQ_FILTER_LIST) return fail("unknown mode");
+    {
+        std::lock_guard<std::mutex> call(G->call_mu);
+        if (sf && check_shard_filter(G, sf)) return -1;
+        if (check_shard_groups(G, sg)) return -1;
+    }
+    return pq_scan_topk_impl(G, sf, mode, queries_f32, scales, nq, r, k, scores, ids, sg);
+}
+
 // The graph index sharded: ONE Vamana graph per shard over its own rows (the reference's shards are exactly that:
 // src/generate_index_shard.rs builds a shard's graph over the shard's vectors).  Every shard answers the whole query batch from ITS
 // graph -- entry by its own entry table, query_disk_index::greedy_search, the k best visited records (mse_disk_query_topk_block) --
 // and the blocks meet in the one exchange: the merged result is the merge of the per-shard searches.  queries: f16 [nq][d] host rows;
 // neighbours scored exactly (disable_pq = 1) or by ADC through the shard's codec and codes with tables from `luts` ([nq][64*256] f32).
 // sf: the allowed rows (null: all; then `regime` is unused) -- every shard runs mse_disk_query_topk_block_filtered over its slice
+// sg (null: ungrouped): every shard runs mse_disk_query_topk_block_grouped over its part (a shard wholly past the grouping has none and runs
+// the ungrouped form), and the merge is the grouped merge
 static int query_topk_impl(mse_shard_group* G, const mse_shard_filter* sf, int regime, const uint16_t* queries, const float* luts, const float* scales,
-                           size_t nq, int disable_pq, size_t beamwidth, size_t search_list, size_t k, int64_t* scores, uint32_t* ids) {
+                           size_t nq, int disable_pq, size_t beamwidth, size_t search_list, size_t k, int64_t* scores, uint32_t* ids,
+                           const mse_shard_groups* sg = nullptr) {
     if (!G || !queries || !scores || !ids) return fail("shard group query: null argument");
     if (nq == 0 || k == 0) return 0;
     if (k > (size_t)TOPK_KMAX - 64) return fail("k too large (max 1984)");
@@ -763,18 +851,23 @@ static int query_topk_impl(mse_shard_group* G, const mse_shard_filter* sf, int r
     int rc = 0;
     {
         std::lock_guard<std::mutex> call(G->call_mu);
-        if (sf && check_shard_filter(G, sf)) { (void)hipSetDevice(prev); return -1; }
+        if ((sf && check_shard_filter(G, sf)) || (sg && check_shard_groups(G, sg))) { (void)hipSetDevice(prev); return -1; }
         rc = G->q_root.ensure(nq * G->d * 2) || G->out_s.ensure(nq * k * 8) || G->out_i.ensure(nq * k * 4);
         if (!rc && hipMemcpy(G->q_root.p, queries, nq * G->d * 2, hipMemcpyHostToDevice) != hipSuccess) rc = fail("query upload failed");
         if (!rc)
             rc = search_dev_locked(G, G->q_root.p, nq * G->d * 2, nq, k, k, [=](Shard& sh, const void* q, char* blk) -> int {
+                const size_t g = (size_t)(&sh - G->shards.data());
+                if (sg && sg->parts[g])
+                    return mse_disk_query_topk_block_grouped(sh.searcher, sh.pq, sh.codes, sh.graph, sg->parts[g], sf ? sf->parts[g] : nullptr, regime, nullptr,
+                                                             static_cast<const uint16_t*>(q), luts, scales, nq, disable_pq, beamwidth, search_list, k,
+                                                             sh.first_row, blk, nullptr, nullptr, nullptr);
                 if (sf)   // (AUTO: each shard's plan from its own rows and count)
-                    return mse_disk_query_topk_block_filtered(sh.searcher, sh.pq, sh.codes, sh.graph, sf->parts[(size_t)(&sh - G->shards.data())], regime,
+                    return mse_disk_query_topk_block_filtered(sh.searcher, sh.pq, sh.codes, sh.graph, sf->parts[g], regime,
                                                               nullptr, static_cast<const uint16_t*>(q), luts, scales, nq, disable_pq, beamwidth,
                                                               search_list, k, sh.first_row, blk, nullptr, nullptr, nullptr);
                 return mse_disk_query_topk_block(sh.searcher, sh.pq, sh.codes, sh.graph, nullptr, static_cast<const uint16_t*>(q), luts, scales, nq, disable_pq,
                                                  beamwidth, search_list, k, sh.first_row, blk, nullptr, nullptr, nullptr);
-            }, G->out_s.p, G->out_i.p);
+            }, G->out_s.p, G->out_i.p, sg);
         if (!rc && (hipMemcpy(scores, G->out_s.p, nq * k * 8, hipMemcpyDeviceToHost) != hipSuccess ||
                     hipMemcpy(ids, G->out_i.p, nq * k * 4, hipMemcpyDeviceToHost) != hipSuccess)) rc = fail("result download failed");
     }
@@ -798,6 +891,19 @@ int mse_shard_group_query_topk_filtered(mse_shard_group* G, const mse_shard_filt
         if (check_shard_filter(G, sf)) return -1;
     }
     return query_topk_impl(G, sf, regime, queries, luts, scales, nq, disable_pq, beamwidth, search_list, k, scores, ids);
+}
+
+int mse_shard_group_query_topk_grouped(mse_shard_group* G, const mse_shard_groups* sg, const mse_shard_filter* sf, const uint16_t* queries,
+                                       const float* luts, const float* scales, size_t nq, int disable_pq, size_t beamwidth, size_t search_list,
+                                       size_t k, int regime, int64_t* scores, uint32_t* ids) {
+    if (!G) return fail("shard group query: null argument");
+    if (sf && regime != MSE_FILTERED_AUTO && regime != MSE_FILTERED_GRAPH && regime != MSE_FILTERED_LIST) return fail("shard group query: unknown regime");
+    {
+        std::lock_guard<std::mutex> call(G->call_mu);
+        if (sf && check_shard_filter(G, sf)) return -1;
+        if (check_shard_groups(G, sg)) return -1;
+    }
+    return query_topk_impl(G, sf, regime, queries, luts, scales, nq, disable_pq, beamwidth, search_list, k, scores, ids, sg);
 }
 
 // ---- shard filters: a row filter per shard, each on its shard's device (include/mse.h) ------------------------------------------------
@@ -891,6 +997,72 @@ mse_filter* mse_shard_filter_global(const mse_shard_filter* sf, int device) {
     uint64_t end = 0;
     for (size_t g = 0; g < sf->parts.size(); g++) end = std::max<uint64_t>(end, sf->first_rows[g] + sf->parts[g]->n_rows);
     return mse_filter_concat(sf->parts.data(), sf->first_rows.data(), sf->parts.size(), (size_t)end, device);
+}
+
+// ---- shard groups: the global grouping cut for the shards, plus its label array on the root device for the merge (include/mse.h) --------
+void mse_shard_groups_free(mse_shard_groups* sg) {
+    if (!sg) return;
+    for (mse_groups* p : sg->parts) mse_groups_free(p);
+    if (sg->labels) {
+        DeviceScope scope(sg->root_device);
+        (void)hipFree(sg->labels);
+    }
+    delete sg;
+}
+
+mse_shard_groups* mse_shard_group_groups(mse_shard_group* G, const mse_groups* global) {
+    if (!G || !global) { fail("shard group groups: null argument"); return nullptr; }
+    std::lock_guard<std::mutex> call(G->call_mu);
+    uint64_t end = 0;
+    for (const Shard& sh : G->shards) {
+        if (!sh.base) { fail("shard group: a shard holds no rows yet"); return nullptr; }
+        end = std::max<uint64_t>(end, sh.first_row + sh.base->n);
+    }
+    if (global->n_rows > end) {
+        fail("shard group: the grouping is longer than the group (" + std::to_string(global->n_rows) + " > " + std::to_string(end) + " rows)");
+        return nullptr;
+    }
+    mse_shard_groups* sg = new (std::nothrow) mse_shard_groups();
+    if (!sg) { fail("out of host memory"); return nullptr; }
+    try {
+        sg->parts.assign(G->shards.size(), nullptr);
+        sg->first_rows.assign(G->shards.size(), 0);
+    } catch (const std::bad_alloc&) {
+        delete sg; fail("out of host memory"); return nullptr;
+    }
+    sg->layout = G->layout;
+    sg->root_device = G->root_device;
+    sg->len = global->n_rows;
+    int rc = 0;
+    {   // the global labels, on the root device
+        DeviceScope scope(G->root_device);
+        if (!scope.ok || hipMalloc((void**)&sg->labels, std::max<size_t>(sg->len, 1) * 4) != hipSuccess) {
+            (void)hipGetLastError();
+            sg->labels = nullptr;
+            rc = fail("shard group groups: hipMalloc failed for the global labels");
+        } else if (sg->len && (global->device == G->root_device
+                                   ? hipMemcpy(sg->labels, global->group_of, sg->len * 4, hipMemcpyDeviceToDevice)
+                                   : hipMemcpyPeer(sg->labels, G->root_device, global->group_of, global->device, sg->len * 4)) != hipSuccess) {
+            (void)hipGetLastError();
+            rc = fail("shard group groups: the copy of the global labels failed");
+        }
+    }
+    if (!rc)
+        rc = G->run([&](size_t g) -> int {   // each part on its shard's own thread (and device)
+            Shard& sh = G->shards[g];
+            sg->first_rows[g] = sh.first_row;
+            if (sh.base->n == 0 || sh.first_row >= global->n_rows) return 0;   // nothing to say: the shard runs its ungrouped call
+            return (sg->parts[g] = mse_groups_slice(global, sh.first_row, sh.base->n, sh.device)) ? 0 : -1;
+        });
+    if (rc) { const std::string why = mse_last_error(); mse_shard_groups_free(sg); set_error(why); return nullptr; }
+    return sg;
+}
+
+size_t mse_shard_groups_n_shards(const mse_shard_groups* sg) { return sg ? sg->parts.size() : 0; }
+const mse_groups* mse_shard_groups_part(const mse_shard_groups* sg, size_t shard) {
+    if (!sg || shard >= sg->parts.size()) { fail("shard groups: shard index out of range"); return nullptr; }
+    set_error("");
+    return sg->parts[shard];
 }
 
 int mse_shard_group_set_exchange(mse_shard_group* G, int kind) {

@@ -176,6 +176,19 @@ SIGNATURES = {
     "mse_comm_search_filtered_dev": (C.c_int, [vp, vp, vp, vp, sz, sz, C.c_int, C.c_uint64, vp, vp]),
     "mse_comm_pq_scan_topk_filtered": (C.c_int, [vp, vp, vp, vp, vp, f32p, f32p, sz, sz, sz, C.c_int, C.c_uint64, vp, vp]),
     "mse_comm_query_topk_filtered": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, u16p, f32p, f32p, sz, C.c_int, sz, sz, sz, C.c_uint64, vp, vp]),
+    "mse_groups_slice": (vp, [vp, C.c_uint64, sz, C.c_int]),
+    "mse_groups_read": (C.c_int, [vp, u32p]),
+    "mse_shard_group_groups": (vp, [vp, vp]),
+    "mse_shard_groups_part": (vp, [vp, sz]),
+    "mse_shard_groups_n_shards": (sz, [vp]),
+    "mse_shard_groups_free": (None, [vp]),
+    "mse_merge_topk_packed_grouped_dev": (C.c_int, [vp, vp, vp, sz, sz, sz, sz, vp, vp]),
+    "mse_shard_group_search_grouped": (C.c_int, [vp, vp, vp, u16p, sz, sz, C.c_int, i64p, u32p]),
+    "mse_shard_group_search_grouped_dev": (C.c_int, [vp, vp, vp, vp, sz, sz, C.c_int, vp, vp]),
+    "mse_shard_group_pq_scan_topk_grouped": (C.c_int, [vp, vp, vp, f32p, f32p, sz, sz, sz, C.c_int, i64p, u32p]),
+    "mse_shard_group_query_topk_grouped": (C.c_int, [vp, vp, vp, u16p, f32p, f32p, sz, C.c_int, sz, sz, sz, C.c_int, i64p, u32p]),
+    "mse_disk_query_topk_block_grouped": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, u32p, u16p, f32p, f32p, sz, C.c_int, sz, sz, sz, C.c_uint64, vp,
+                                                    u32p, u32p, u32p]),
     "mse_descriptor_product": (C.c_int64, [f32p, sz, u8p, C.c_uint32]),
     "mse_nb_new": (vp, [sz]),
     "mse_nb_free": (None, [vp]),

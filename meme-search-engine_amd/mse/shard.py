@@ -22,7 +22,7 @@ import numpy as np
 from . import ffi
 from .ffi import check, check_ptr
 from .diskann import REGIMES
-from .vector import MODE_AUTO, PQ_FILTER_MODES, RowFilter, Searcher, _bits, _p
+from .vector import MODE_AUTO, PQ_FILTER_MODES, RowFilter, RowGroups, Searcher, _bits, _p
 
 
 class _BorrowedSearcher(Searcher):
@@ -109,6 +109,61 @@ def _shard_filter_handle(sf):
     if not isinstance(sf, ShardFilter):
         raise TypeError("the filtered searches of a ShardGroup take a ShardFilter (ShardGroup.filter / .filter_from_local / .live_filter)")
     return sf._h
+
+
+class _BorrowedGroups(RowGroups):
+    """A shard's local grouping, owned by its ShardGroups (which it keeps alive)."""
+
+    def __init__(self, handle, owner):   # noqa: D401 -- no creator call: the shard groups made it
+        self._h = handle
+        self._owner = owner
+
+    def close(self):
+        self._h = None
+        self._owner = None
+
+
+class ShardGroups:
+    """The grouping of a ShardGroup's GLOBAL rows cut for its shards (mse_shard_groups): one local RowGroups per shard on its shard's
+    device (RowGroups.slice) and the global labels on the root device for the merge.  Made by ShardGroup.groups, taken by the group's
+    *_grouped searches.  It belongs to the layout of the group it was made for: after generate / load_host / set_shard_device the group
+    refuses it.  It does not depend on the RowGroups it was made from."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @property
+    def n_shards(self):
+        return int(ffi.lib().mse_shard_groups_n_shards(self._h))
+
+    def shard(self, g):
+        """Shard g's grouping over its LOCAL rows (borrowed: valid while this ShardGroups is open); None for a shard that lies wholly
+        past the grouping -- it runs its ungrouped search, which answers the same."""
+        if not 0 <= int(g) < self.n_shards:
+            raise IndexError("shard index out of range")
+        h = ffi.lib().mse_shard_groups_part(self._h, int(g))
+        return _BorrowedGroups(h, self) if h else None
+
+    def close(self):
+        if self._h:
+            ffi.lib().mse_shard_groups_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _shard_groups_handle(sg):
+    if sg is not None and not isinstance(sg, ShardGroups):
+        raise TypeError("the grouped searches of a ShardGroup take a ShardGroups (ShardGroup.groups)")
+    return sg._h if sg is not None else None   # (None reaches the library, which names the error)
+
+
+def _optional_shard_filter(sf):
+    return None if sf is None else _shard_filter_handle(sf)
 
 
 class ShardGroup:
@@ -229,6 +284,63 @@ class ShardGroup:
                                                             _p(sc, C.c_float) if sc is not None else None, nq, int(bool(disable_pq)), int(beamwidth),
                                                             int(search_list), int(k), REGIMES[regime], _p(scores, C.c_int64), _p(ids, C.c_uint32)),
               "mse_shard_group_query_topk_filtered")
+        return scores, ids
+
+    # ---- grouped search across the shards: one result per group of a grouping over GLOBAL rows ----
+    def groups(self, row_groups):
+        """A RowGroups over GLOBAL rows cut for the shards, on the devices (mse_shard_group_groups).  Shorter than the group: the rows past
+        it are groups of their own; longer: an error."""
+        if not isinstance(row_groups, RowGroups):
+            raise TypeError("row_groups must be a RowGroups")
+        return ShardGroups(check_ptr(ffi.lib().mse_shard_group_groups(self._h, row_groups._h), "mse_shard_group_groups"))
+
+    def bruteforce_topk_grouped(self, shard_groups, queries, k, shard_filter=None, mode=MODE_AUTO):
+        """bruteforce_topk with one result per group; equals Searcher.bruteforce_topk(groups=the global grouping, allow=the global
+        filter) over all rows."""
+        sg, sf = _shard_groups_handle(shard_groups), _optional_shard_filter(shard_filter)
+        q = _bits(queries).reshape(-1, self.d)
+        nq = q.shape[0]
+        scores = np.empty((nq, k), np.int64)
+        ids = np.empty((nq, k), np.uint32)
+        check(ffi.lib().mse_shard_group_search_grouped(self._h, sg, sf, _p(q, C.c_uint16), nq, k, mode, _p(scores, C.c_int64), _p(ids, C.c_uint32)),
+              "mse_shard_group_search_grouped")
+        return scores, ids
+
+    def bruteforce_topk_grouped_dev(self, shard_groups, queries_dev, nq, k, scores_dev, ids_dev, shard_filter=None, mode=MODE_AUTO):
+        check(ffi.lib().mse_shard_group_search_grouped_dev(self._h, _shard_groups_handle(shard_groups), _optional_shard_filter(shard_filter),
+                                                           queries_dev, nq, k, mode, scores_dev, ids_dev), "mse_shard_group_search_grouped_dev")
+
+    def pq_scan_topk_grouped(self, shard_groups, queries_f32, r, k, scales=None, shard_filter=None, mode="auto"):
+        """pq_scan_topk (pq_scan_topk_filtered with a shard_filter) with one result per group: the collapse of the exactly re-ranked
+        global top-r, k of it, padded when the r candidates hold fewer than k groups."""
+        sg, sf = _shard_groups_handle(shard_groups), _optional_shard_filter(shard_filter)
+        q = np.ascontiguousarray(queries_f32, np.float32).reshape(-1, self.d)
+        nq = q.shape[0]
+        sc = None if scales is None else np.ascontiguousarray(scales, np.float32).reshape(-1)
+        scores, ids = np.empty((nq, k), np.int64), np.empty((nq, k), np.uint32)
+        check(ffi.lib().mse_shard_group_pq_scan_topk_grouped(self._h, sg, sf, _p(q, C.c_float), _p(sc, C.c_float) if sc is not None else None, nq,
+                                                             int(r), int(k), PQ_FILTER_MODES[mode], _p(scores, C.c_int64), _p(ids, C.c_uint32)),
+              "mse_shard_group_pq_scan_topk_grouped")
+        return scores, ids
+
+    def query_topk_grouped(self, shard_groups, queries, k, luts=None, scales=None, disable_pq=True, beamwidth=4, search_list=64, shard_filter=None,
+                           regime="auto"):
+        """query_topk (query_topk_filtered with a shard_filter) with one result per group: the collapse of the merge of what the shards
+        visited.  An approximate search: a short answer shows as padding."""
+        sg, sf = _shard_groups_handle(shard_groups), _optional_shard_filter(shard_filter)
+        q = _bits(queries).reshape(-1, self.d)
+        nq = q.shape[0]
+        tables = None if luts is None else np.ascontiguousarray(luts, np.float32).reshape(nq, -1)
+        sc = None
+        if scales is not None:
+            sc = np.ascontiguousarray(scales, np.float32)
+            if sc.ndim == 1:
+                sc = np.ascontiguousarray(np.broadcast_to(sc, (nq, sc.size)))
+        scores, ids = np.empty((nq, k), np.int64), np.empty((nq, k), np.uint32)
+        check(ffi.lib().mse_shard_group_query_topk_grouped(self._h, sg, sf, _p(q, C.c_uint16), _p(tables, C.c_float) if tables is not None else None,
+                                                           _p(sc, C.c_float) if sc is not None else None, nq, int(bool(disable_pq)), int(beamwidth),
+                                                           int(search_list), int(k), REGIMES[regime], _p(scores, C.c_int64), _p(ids, C.c_uint32)),
+              "mse_shard_group_query_topk_grouped")
         return scores, ids
 
     # ---- the approximate-search paths over the same shards ----

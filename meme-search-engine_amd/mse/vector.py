@@ -318,6 +318,20 @@ class RowGroups:
     def count(self):
         return int(ffi.lib().mse_groups_count(self._h))
 
+    def slice(self, first, n_rows, device=None):
+        """mse_groups_slice: a fresh RowGroups over LOCAL rows 0 .. n_rows - 1 with the partition this one has on rows first .. first +
+        n_rows - 1, labelled canonically (a grouped row's label is the local id of the first row of its group inside the slice); as long as
+        the part of the slice inside this grouping (a slice wholly past it is empty).  device: where it lives (None: this one's)."""
+        g = RowGroups.__new__(RowGroups)
+        g._h = check_ptr(ffi.lib().mse_groups_slice(self._h, int(first), int(n_rows), -1 if device is None else int(device)), "mse_groups_slice")
+        return g
+
+    def to_host(self):
+        """The label array as uint32 (GROUP_NONE for ungrouped rows)."""
+        out = np.empty(len(self), np.uint32)
+        check(ffi.lib().mse_groups_read(self._h, _p(out, C.c_uint32)), "mse_groups_read")
+        return out
+
     def close(self):
         if self._h:
             ffi.lib().mse_groups_free(self._h)
