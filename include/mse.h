@@ -647,8 +647,10 @@ int mse_disk_query_topk_f32(mse_searcher* s, mse_pq* pq, const mse_codes* c, con
  *                       what AUTO will do; AUTO then equals the explicit call at its answer.
  * Rows at or past mse_filter_len(f) are excluded; a filter longer than the graph, or on another device than the vectors, is an error, as
  * is a null filter or an unknown regime; argument errors write nothing.  The filter must outlive the call / the ticket.  Everything else
- * -- arguments, limits, outputs, coalescing of small calls -- is that of the unfiltered call each one extends; coalesced calls and
- * tickets share a submission only with requests of the same filter object, regime and effective search_list, and never with unfiltered ones.
+ * -- arguments, limits, outputs, coalescing of small calls -- is that of the unfiltered call each one extends.  Sharing: coalesced calls
+ * and tickets whose regime resolves to GRAPH share a submission with every request of equal effective search_list, whatever its filter
+ * object, unfiltered requests (traversals at their own search_list) included: the launch reads a filter per query ("a filter per query"
+ * below).  LIST requests share only with requests of the same filter object.
  *   mse_disk_search_batch_filtered       extends mse_disk_search_batch (:144-212 with :172 filtered): GRAPH, list form
  *   mse_disk_query_topk_filtered / _f32  extend mse_disk_query_topk / _f32 (:436-540)
  *   mse_disk_query_submit_filtered_f32   extends mse_disk_query_submit_f32 (:640-655,716-732: tickets) */
@@ -698,7 +700,8 @@ int mse_disk_query_submit_filtered_f32(mse_searcher* s, mse_pq* pq, const mse_co
  *   MSE_FILTERED_AUTO   mse_filtered_plan decides as for the filtered call, and the call equals the explicit call at its answer.
  * Validation order: the filtered or unfiltered call's own checks, then "null grouping" (an error of its own), then the grouping's fit;
  * argument errors write nothing.  The grouping must outlive the call / the ticket.  Coalesced calls and tickets share a submission only
- * with requests of the same grouping object (and filter, regime, search_list), never with ungrouped ones; k may differ between sharers.
+ * with requests of the same grouping object (and regime and search_list; filters as for the filtered calls: any in GRAPH, the same object
+ * in LIST), never with ungrouped ones; k may differ between sharers.
  * How: one workgroup per query removes every non-best record of a group from the device-resident visited list in place
  * (integer atomics on a hash table in LDS, in global memory for lists past 4096 records) between the de-duplication and the selection:
  * no host decision, no extra synchronisation, no second copy.  The shard's block form has no grouped twin HERE: it is
@@ -716,6 +719,42 @@ int mse_disk_query_submit_grouped_f32(mse_searcher* s, mse_pq* pq, const mse_cod
                                       int regime, const float* queries_f32, const float* scales, size_t nq, int disable_pq, size_t beamwidth,
                                       size_t search_list, size_t k, uint32_t* ids, int64_t* scores, uint32_t* n_visited, uint32_t* cmps,
                                       uint32_t* pq_cmps, void* user, mse_completion_queue* cq, mse_ticket** ticket_out);
+/* ---- a filter per query: the filtered request path for a batch whose queries each bring their own allowed-row set ----
+ * A filter is a property of the request (this user's sources, "not what I have seen"), a launch serves many requests.  Each call below is
+ * the twin of a single-filter call with `filters` ([nq] host array of filter handles; an entry may be NULL: that query is unfiltered)
+ * where `f` stands, and the two top-k forms take an optional grouping (NULL: ungrouped; one grouping for the call -- it is a property of
+ * the index).
+ * Contract: for every query i the ids, scores, n_visited, cmps and pq_cmps equal, bit for bit, those of the single-filter call made with
+ * query i alone, filters[i], the same regime argument and the same other arguments -- the unfiltered (or grouped unfiltered) call where
+ * filters[i] is NULL.
+ * `regime` is one argument, resolved per query: under MSE_FILTERED_AUTO each query asks mse_filtered_plan with its own
+ * mse_filter_count, so the queries of one call may run in different regimes and at different effective search lists.  The call splits
+ * its queries, keeping their order, into classes -- GRAPH queries by effective search_list (unfiltered ones at the caller's), LIST
+ * queries by filter object, and the LIST queries whose filter allows nothing (padding, nothing launched) -- and runs each class as ONE
+ * launch (the kernel reads query q's bitmap and row bound from a device table) or one list pass; results land at the caller's positions.
+ * A call whose queries form one class is one submission over the caller's arrays and, with nq <= 16, is coalesced like its twin; a call
+ * of several classes runs them one after the other on `s` (inputs gathered into staging that `s` keeps until mse_searcher_free), and
+ * then `s` must not be in use by another thread.  Explicit MSE_FILTERED_GRAPH with a filter that allows nothing still traverses (its
+ * twin does, and reports its counters).
+ * Validation covers all nq entries before anything is written: a null `filters` array, an unknown regime, and per entry what the
+ * single-filter call rejects -- a filter longer than the graph or on another device than the vectors, LIST while mse_graph_set_dedup is
+ * on (unless that filter allows nothing) -- with the twin's message followed by " (query i)".  On error the outputs are untouched.
+ * The filters must outlive the call.  The answer does not depend on the calls made before it on the same handle.
+ *   mse_disk_query_topk_filtered_each / _f32   twins of mse_disk_query_topk_filtered / _f32 (of _grouped / _grouped_f32 with groups)
+ *   mse_disk_search_batch_filtered_each        twin of mse_disk_search_batch_filtered: GRAPH, list form, always one launch */
+int mse_disk_query_topk_filtered_each(mse_searcher* s, mse_pq* pq, const mse_codes* c, const mse_graph* g, const mse_filter* const* filters,
+                                      int regime, const mse_groups* groups, const uint32_t* starts, const uint16_t* queries, const float* luts,
+                                      const float* scales, size_t nq, int disable_pq, size_t beamwidth, size_t search_list, size_t k, uint32_t* ids,
+                                      int64_t* scores, uint32_t* n_visited, uint32_t* cmps, uint32_t* pq_cmps);
+int mse_disk_query_topk_filtered_each_f32(mse_searcher* s, mse_pq* pq, const mse_codes* c, const mse_graph* g, const mse_filter* const* filters,
+                                          int regime, const mse_groups* groups, const uint32_t* starts, const float* queries_f32,
+                                          const float* scales, size_t nq, int disable_pq, size_t beamwidth, size_t search_list, size_t k,
+                                          uint32_t* ids, int64_t* scores, uint32_t* n_visited, uint32_t* cmps, uint32_t* pq_cmps);
+int mse_disk_search_batch_filtered_each(mse_searcher* s, mse_pq* pq, const mse_codes* c, const mse_graph* g, const mse_filter* const* filters,
+                                        const uint32_t* starts, const uint16_t* queries, const float* luts, const float* scales, size_t nq,
+                                        int disable_pq, size_t beamwidth, size_t search_list, uint32_t* buf_ids, int64_t* buf_scores,
+                                        uint32_t* buf_len, uint32_t* visited_ids, int64_t* visited_scores, size_t visited_cap, uint32_t* n_visited,
+                                        uint32_t* cmps, uint32_t* pq_cmps);
 /* Test hook, like mse_debug_collapse_topk: the group step alone over caller-supplied UNRANKED lists.  ids / scores [nq][cap] host arrays
  * (holes (MSE_ID_NONE, INT64_MIN) allowed anywhere), n_visited [nq] (clamped to cap); of every group the best live record by (score desc,
  * id asc) stays, every other record of the group becomes a hole, everything else is written back unchanged.  cap 1..65536; the table is
@@ -742,6 +781,10 @@ int mse_searcher_beam_timing(mse_searcher* s, int enable, uint64_t out[8]);
 int mse_graph_set_dedup(mse_graph* g, float threshold);
 int mse_graph_set_coalescer(mse_graph* g, size_t max_queries_per_pass, uint32_t max_wait_us, int workers);
 int mse_graph_coalescer_stats(const mse_graph* g, uint64_t out[6]);
+/* What the sharing rule decided, since the graph was made: the workers gather waiting requests into batches (the "submissions" counted
+ * above) and split every batch into GROUPS of requests that can share a launch; each group runs as one entry step + one search launch +
+ * one select (or one list pass).  out = {groups run, requests in them}: groups == requests means nothing shared a launch. */
+int mse_graph_coalescer_groups(const mse_graph* g, uint64_t out[2]);
 /* everything `producer_stream` (a hipStream_t) holds at the time of the call completes before anything this searcher's stream is
  * given afterwards starts: an event recorded there, waited for here; no host synchronisation */
 int mse_searcher_wait_stream(mse_searcher* s, void* producer_stream);

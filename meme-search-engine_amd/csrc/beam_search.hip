@@ -22,7 +22,10 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <new>
+#include <string>
+#include <tuple>
 #include <vector>
 
 using namespace mse;
@@ -36,6 +39,11 @@ constexpr int BS_LMAX = 1024;
 constexpr int BS_BEAM_MAX = 8;
 constexpr int BS_DEG_MAX = 128;   // merged indexes: up to SHARD_SPILL x R neighbours per node
 constexpr int BS_DESC_MAX = 8;
+
+// one query's filter as the kernel reads it: the bitmap (null: every row allowed) and the rows it speaks for
+struct BeamFilter {
+    const uint32_t* words; size_t rows;
+};
 
 struct BeamArgs {
     const uint16_t* base; size_t n; int d;
@@ -56,6 +64,10 @@ struct BeamArgs {
     // filtered search (mse_filter): one bit per row, rows at or past flt_rows excluded; null = every row allowed.  A fetched node is
     // expanded whatever its bit says; the bit only decides, with has_url, whether it enters the visited list
     const uint32_t* flt_words; size_t flt_rows;
+    // a filter per query of the launch (mse_disk_query_topk_filtered_each): entry q is query q's bitmap and row bound, null words =
+    // that query is unfiltered.  Null table: flt_words / flt_rows serve every query, as before.  A launch whose queries all have the
+    // same filter (or none) never carries a table (search_launch), so those launches run the instructions they always ran
+    const BeamFilter* flt_each;
 };
 
 // beam_search_kernel's dynamic LDS, byte offsets in carving order: distance table (ADC scoring) | query (exact scoring) | list scores |
@@ -89,7 +101,11 @@ __host__ __device__ inline BeamLds beam_lds(bool adc, uint32_t d, uint32_t L, ui
 // ADC: neighbours scored through the query's distance table (the reference's default); false: exactly (disable_pq).  Two kernels, so
 // that each keeps only its own scoring code and its own register budget (the ADC form runs two workgroups per CU whatever it uses:
 // its fetched rows' exact scores take all 36 loads of a row in flight at once -- one round trip instead of three, round 6).
-template <int THREADS, bool ADC>
+// TABLE: the launch carries a filter per query (BeamArgs::flt_each); its workgroup reads its entry once, before the search loop.  A
+// kernel of its own, so that every launch without a table -- unfiltered, or one filter for all queries -- runs the code it always ran:
+// the kernels have no scalar register to spare (all 106 in use, the rest spilt into vector lanes), and the pair kept across the loop
+// moves the allocation.
+template <int THREADS, bool ADC, bool TABLE = false>
 __global__ __launch_bounds__(THREADS, THREADS == 64 ? 4 : 1) void beam_search_kernel(BeamArgs a) {
     constexpr bool EXACT = !ADC;   // the call's disable_pq
     constexpr int BS_THREADS = THREADS;
@@ -129,6 +145,10 @@ __global__ __launch_bounds__(THREADS, THREADS == 64 ? 4 : 1) void beam_search_ke
     uint32_t* bm_adj = a.bm_adj + qi * a.bm_words;
     uint32_t* bm_vis = a.bm_vis + qi * a.bm_words;
     const bool use_bias = a.scales && a.desc && a.n_desc > 0;
+    // TABLE: this query's filter, read once -- one workgroup serves one query, so the entry is uniform
+    [[maybe_unused]] const uint32_t* flt_words = nullptr;
+    [[maybe_unused]] size_t flt_rows = 0;
+    if constexpr (TABLE) { flt_words = a.flt_each[qi].words; flt_rows = a.flt_each[qi].rows; }
 
     if (!EXACT)
         for (int e = tid; e < 64 * 256 / 4; e += BS_THREADS)
@@ -262,7 +282,11 @@ __global__ __launch_bounds__(THREADS, THREADS == 64 ? 4 : 1) void beam_search_ke
             bool first = true;
             for (int i = 0; i < tid; i++) first &= s_pts[i] != pt;
             bool url = !a.has_url || a.has_url[pt];
-            if (a.flt_words) url = url && pt < a.flt_rows && ((a.flt_words[pt >> 5] >> (pt & 31)) & 1u);
+            if constexpr (TABLE) {
+                if (flt_words) url = url && pt < flt_rows && ((flt_words[pt >> 5] >> (pt & 31)) & 1u);
+            } else {
+                if (a.flt_words) url = url && pt < a.flt_rows && ((a.flt_words[pt >> 5] >> (pt & 31)) & 1u);
+            }
             s_visok[tid] = (first && visited_insert(bm_vis, a.hash_bits, pt) && url) ? 1 : 0;
         }
         if (wave == 0 && (!EXACT || n_iter == 0)) {   // (exactly scored searches: s_ptsc was taken from the list above)
@@ -780,18 +804,26 @@ struct SearchIn {
     // grouped search (include/mse.h "grouped graph search"): one result per group of `groups` (null: ungrouped).  grouped: the call came
     // in through a grouped entry point, whose grouping is checked -- null included -- after the call's own arguments (check_grouping)
     const mse_groups* groups = nullptr; bool grouped = false;
+    // a filter per query ([nq] host array, entries may be null: that query is unfiltered), GRAPH regime only; `filter` is null then.
+    // The launch reads them through a device table -- or through the uniform fields when they are all one object (search_launch)
+    const mse_filter* const* filters_each = nullptr;
+    const mse_filter* filter_of(size_t q) const { return filters_each ? filters_each[q] : filter; }
     SearchIn piece(size_t q0, size_t m) const {   // queries q0 .. q0 + m - 1
         const size_t d = s->base->d;
         SearchIn p = *this;
         p.starts = shifted(starts, q0); p.queries = shifted(queries, q0 * d); p.queries_f32 = shifted(queries_f32, q0 * d);
         p.luts = shifted(luts, q0 * 16384); p.scales = scales ? scales + q0 * c->n_desc : nullptr;
+        p.filters_each = shifted(filters_each, q0);
         p.nq = m;
         return p;
     }
     // what calls need in common to run as one launch: the same vectors, codec, codes, graph and search parameters, the same kinds of inputs,
-    // the same filter object (or none) and regime, the same grouping object (or none) -- k may differ: the group step does not depend on it
+    // the same regime, the same grouping object (or none) -- k may differ: the group step does not depend on it.  The filter: a traversal
+    // (GRAPH; an unfiltered call is one, at its own search_list) takes a filter per query, so any filters share; a list pass serves one
+    // filter object
     bool shares_with(const SearchIn& o) const {
-        return filter == o.filter && regime == o.regime && groups == o.groups && s->base == o.s->base && pq == o.pq && c == o.c && g == o.g && disable_pq == o.disable_pq && beamwidth == o.beamwidth &&
+        return (regime == MSE_FILTERED_GRAPH || (filter == o.filter && !filters_each && !o.filters_each)) && regime == o.regime && groups == o.groups &&
+               s->base == o.s->base && pq == o.pq && c == o.c && g == o.g && disable_pq == o.disable_pq && beamwidth == o.beamwidth &&
                search_list == o.search_list && (queries != nullptr) == (o.queries != nullptr) && (luts != nullptr) == (o.luts != nullptr) &&
                (scales != nullptr) == (o.scales != nullptr);
     }
@@ -871,19 +903,24 @@ int check_grouping(const SearchIn& in) {
     return 0;
 }
 
-// beam_search_kernel<THREADS, ADC> with one workgroup per query; ADC (scoring through the query's distance table) unless disable_pq
-template <int THREADS>
-int launch_beam(const BeamArgs& a, size_t nq, size_t lds, hipStream_t st) {
+// beam_search_kernel<THREADS, ADC, TABLE> with one workgroup per query; ADC (scoring through the query's distance table) unless disable_pq
+template <int THREADS, bool TABLE>
+int launch_beam_as(const BeamArgs& a, size_t nq, size_t lds, hipStream_t st) {
     if constexpr (THREADS == 64) {   // one wave per query: exact scoring only, within the default LDS (no opt-in)
-        hipLaunchKernelGGL((beam_search_kernel<64, false>), dim3((unsigned)nq), dim3(64), lds, st, a);
+        hipLaunchKernelGGL((beam_search_kernel<64, false, TABLE>), dim3((unsigned)nq), dim3(64), lds, st, a);
     } else if (a.disable_pq) {
-        MSE_DYN_LDS((beam_search_kernel<THREADS, false>), 160 * 1024 - 1024);
-        hipLaunchKernelGGL((beam_search_kernel<THREADS, false>), dim3((unsigned)nq), dim3(THREADS), lds, st, a);
+        MSE_DYN_LDS((beam_search_kernel<THREADS, false, TABLE>), 160 * 1024 - 1024);
+        hipLaunchKernelGGL((beam_search_kernel<THREADS, false, TABLE>), dim3((unsigned)nq), dim3(THREADS), lds, st, a);
     } else {
-        MSE_DYN_LDS((beam_search_kernel<THREADS, true>), 160 * 1024 - 1024);
-        hipLaunchKernelGGL((beam_search_kernel<THREADS, true>), dim3((unsigned)nq), dim3(THREADS), lds, st, a);
+        MSE_DYN_LDS((beam_search_kernel<THREADS, true, TABLE>), 160 * 1024 - 1024);
+        hipLaunchKernelGGL((beam_search_kernel<THREADS, true, TABLE>), dim3((unsigned)nq), dim3(THREADS), lds, st, a);
     }
     return 0;
+}
+// the table instantiation only for a launch that carries a table: every other launch runs the kernel it always ran
+template <int THREADS>
+int launch_beam(const BeamArgs& a, size_t nq, size_t lds, hipStream_t st) {
+    return a.flt_each ? launch_beam_as<THREADS, true>(a, nq, lds, st) : launch_beam_as<THREADS, false>(a, nq, lds, st);
 }
 
 // ---- one batched search, in steps: checks, buffers, upload and entry step, launch, read-back (list form or fused form)
@@ -925,6 +962,11 @@ int search_check(const SearchRun& r) {
     if (!in.disable_pq && (in.pq->n_chunks != 64 || in.pq->n_centroids != 256 || c->code_size != 64)) return fail("disk_search_batch: needs the 64 x 256 codec");
     if (check_params(in)) return -1;
     if (in.filter && check_filter(r.b, in.filter)) return -1;
+    for (size_t q = 0; in.filters_each && q < r.nq; q++) {   // (the kernel trusts an entry's row bound to lie inside its bitmap and the graph)
+        const mse_filter* f = in.filters_each[q];
+        if (f && check_filter(r.b, f)) return -1;
+    }
+    if (in.filter && in.filters_each) return fail("disk_search_batch: one filter or a filter per query, not both");
     if (in.groups && check_groups(r.b, in.groups)) return -1;
     if (in.g->max_deg > BS_DEG_MAX) return fail("disk_search_batch: at most 128 neighbours per node");
     if (c->n_desc > BS_DESC_MAX) return fail("disk_search_batch: at most 8 descriptors");
@@ -1041,6 +1083,28 @@ int search_launch(SearchRun& r) {
     a.err = r.cnt_dev + 3 * nq;
     a.fill_vis = r.fz ? 1 : 0;
     a.flt_words = in.filter ? in.filter->words : nullptr; a.flt_rows = in.filter ? in.filter->n_rows : 0;
+    a.flt_each = nullptr;
+    if (in.filters_each) {
+        // one object (or none) for every query: the uniform fields, and the launch is the single-filter launch.  Otherwise the table,
+        // rewritten by every launch that reads it (the host copy lives on the searcher, next to the device one; a run that fails drains the stream before it returns, so no copy
+        // of an earlier table is in flight here)
+        bool uniform = true;
+        for (size_t q = 1; q < nq && uniform; q++) uniform = in.filters_each[q] == in.filters_each[0];
+        if (uniform) {
+            const mse_filter* f = in.filters_each[0];
+            a.flt_words = f ? f->words : nullptr; a.flt_rows = f ? f->n_rows : 0;
+        } else {
+            s->flt_host.resize(nq * sizeof(BeamFilter));
+            BeamFilter* host = reinterpret_cast<BeamFilter*>(s->flt_host.data());
+            for (size_t q = 0; q < nq; q++) {
+                const mse_filter* f = in.filters_each[q];
+                host[q] = BeamFilter{f ? f->words : nullptr, f ? f->n_rows : 0};
+            }
+            if (s->flt_tab.ensure(nq * sizeof(BeamFilter))) return -1;
+            MSE_HIP_TRY(hipMemcpyAsync(s->flt_tab.p, host, nq * sizeof(BeamFilter), hipMemcpyHostToDevice, st));
+            a.flt_each = s->flt_tab.as<BeamFilter>();
+        }
+    }
     a.entry_nq = (int)nq;
     size_t hash_slots = 64;
     while (hash_slots < 2 * p_cap) hash_slots *= 2;
@@ -1196,6 +1260,11 @@ int disk_search_batch_impl(int visited_mode, const SearchIn& in_arg, const ListO
         return 0;
     }
     SearchRun r(in, out, fz, use_hash, table_bits, set_words);
+    // (a failure past the first enqueue drains the stream: the copies of this run read host memory that the next call rewrites)
+    struct Drain {
+        hipStream_t st; bool on = true;
+        ~Drain() { if (on && hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError(); }
+    } drain{in.s->stream};
     if (search_check(r) || search_buffers(r) || search_upload(r) || search_launch(r)) return -1;
     struct BeamTimed {   // read once the stream has been waited for (every read-back does before it returns)
         mse_searcher* s; bool on; size_t nq;
@@ -1209,6 +1278,7 @@ int disk_search_batch_impl(int visited_mode, const SearchIn& in_arg, const ListO
         }
     } beam_timed{in.s, r.timed, r.nq};
     const int rc = fz ? read_back_fused(r) : read_back_list(r);
+    drain.on = rc != 0;   // (every successful read-back has waited for the stream)
     // a search outgrew its table: the bit maps have room for everything
     return rc == REPEAT_WITH_BITMAPS ? disk_search_batch_impl(0, in, out, fz) : rc;
 }
@@ -1305,9 +1375,11 @@ int beam_run_requests(DispatchReq* const* reqs, size_t n) {
     std::vector<int64_t> sc(n * L), vsc(lead.out.visited_scores ? n * vc : 0);
     std::vector<uint16_t> q16(lead.in.queries ? n * d : 0);
     std::vector<float> q32(lead.in.queries_f32 ? n * d : 0), luts(lead.in.luts ? n * 16384 : 0), scl(n_desc ? n * n_desc : 0);
+    std::vector<const mse_filter*> flt(n);   // every sharer keeps its own filter (or none)
     for (size_t j = 0; j < n; j++) {
         const SearchIn& k = static_cast<const BeamCall*>(reqs[j]->aux0)->in;
         starts[j] = k.starts[0];
+        flt[j] = k.filter_of(0);
         if (k.queries) memcpy(q16.data() + j * d, k.queries, d * 2);
         if (k.queries_f32) memcpy(q32.data() + j * d, k.queries_f32, d * 4);
         if (k.luts) memcpy(luts.data() + j * 16384, k.luts, 16384 * 4);
@@ -1316,6 +1388,7 @@ int beam_run_requests(DispatchReq* const* reqs, size_t n) {
     SearchIn in = lead.in;
     in.starts = starts.data(); in.queries = lead.in.queries ? q16.data() : nullptr; in.queries_f32 = lead.in.queries_f32 ? q32.data() : nullptr;
     in.luts = lead.in.luts ? luts.data() : nullptr; in.scales = n_desc ? scl.data() : lead.in.scales; in.nq = n;
+    in.filter = nullptr; in.filters_each = flt.data();
     const ListOut out{ids.data(), sc.data(), len.data(), lead.out.visited_ids ? vids.data() : nullptr, lead.out.visited_scores ? vsc.data() : nullptr,
                       vc, nv.data(), cm.data(), pc.data()};
     if (const int rc = beam_impl_shared(in, out)) return rc;
@@ -1533,6 +1606,14 @@ int query_run_requests(mse_graph::WorkerCtx& ctx, DispatchReq* const* reqs, size
     if (ctx.pin.ensure(off_lut + lut_bytes + 64, (size_t)1 << 16)) return -1;
     char* p = ctx.pin.as<char>();
     ctx.dsts.resize(total);
+    // a traversal's sharers keep their own filters (a list pass's sharers have one object between them)
+    bool any_filter = false;
+    for (size_t i = 0; i < n && !any_filter; i++) {
+        const SearchIn& k = static_cast<const QueryCall*>(reqs[i]->aux0)->in;
+        any_filter = k.filter || k.filters_each;
+    }
+    const bool per_query = lead.regime == MSE_FILTERED_GRAPH && any_filter;
+    if (per_query) ctx.filters.resize(total);
     size_t row = 0;
     for (size_t i = 0; i < n; i++) {
         const SearchIn& k = static_cast<const QueryCall*>(reqs[i]->aux0)->in;
@@ -1542,8 +1623,10 @@ int query_run_requests(mse_graph::WorkerCtx& ctx, DispatchReq* const* reqs, size
         if (n_desc) memcpy(p + off_sc + row * n_desc * 4, k.scales, k.nq * n_desc * 4);
         if (k.starts) memcpy(p + off_st + row * 4, k.starts, k.nq * 4);
         if (k.luts) memcpy(p + off_lut + row * 65536, k.luts, k.nq * 65536);
-        for (size_t q = 0; q < k.nq; q++, row++)
+        for (size_t q = 0; q < k.nq; q++, row++) {
             ctx.dsts[row] = QueryDst{o.ids + q * o.k, o.scores + q * o.k, shifted(o.n_visited, q), shifted(o.cmps, q), shifted(o.pq_cmps, q), o.k};
+            if (per_query) ctx.filters[row] = k.filter_of(q);
+        }
     }
     SearchIn in = lead;
     in.s = ctx.s;
@@ -1553,6 +1636,7 @@ int query_run_requests(mse_graph::WorkerCtx& ctx, DispatchReq* const* reqs, size
     in.luts = lead.luts ? reinterpret_cast<const float*>(p + off_lut) : nullptr;
     in.scales = n_desc ? reinterpret_cast<const float*>(p + off_sc) : lead.scales;
     in.nq = total;
+    if (per_query) { in.filter = nullptr; in.filters_each = ctx.filters.data(); }
     FusedQuery fz;
     fz.k = kmax; fz.dst = ctx.dsts.data();
     return fused_run(in, fz);
@@ -1585,6 +1669,9 @@ bool same_call(const DispatchReq& a, const DispatchReq& b) {
 
 void graph_run_batch(std::vector<DispatchReq*>& batch) {
     for_each_shared_group(batch, same_call, [](std::vector<DispatchReq*>& grp) {
+        const mse_graph* g = grp[0]->aux_n == REQ_BEAM ? static_cast<const BeamCall*>(grp[0]->aux0)->in.g : static_cast<const QueryCall*>(grp[0]->aux0)->in.g;
+        g->co_groups.fetch_add(1, std::memory_order_relaxed);
+        g->co_group_requests.fetch_add(grp.size(), std::memory_order_relaxed);
         if (grp[0]->aux_n == REQ_BEAM) beam_run_group(grp);
         else query_run_group(grp);
     });
@@ -1655,6 +1742,134 @@ int query_front(const QueryCall& k) {
     r.aux0 = &k;
     r.aux_n = REQ_QUERY;
     return co->submit(r);
+}
+
+// ---- a filter per query within one call (include/mse.h "a filter per query") -------------------------------------
+// what one query of such a call runs as: the regime and effective search_list filtered_resolve gives its filter (null: the unfiltered
+// traversal at the caller's search_list)
+struct EachPlan {
+    int regime; size_t search_list; const mse_filter* f;
+};
+
+// The front of every _each call: all nq entries are checked, and resolved, before anything runs or is written.  An entry's error is the
+// single-filter call's own message with the query's position behind it.
+int each_resolve(const SearchIn& in, const mse_filter* const* filters, int regime, std::vector<EachPlan>& plan) {
+    if (!filters) return fail("disk_query_topk_filtered_each: null filters array");
+    if (regime != MSE_FILTERED_AUTO && regime != MSE_FILTERED_GRAPH && regime != MSE_FILTERED_LIST) return fail("disk_query_topk_filtered: unknown regime");
+    if (!in.g) return fail("disk_query_topk_filtered: null argument");
+    if (!in.s || !in.s->base) return fail("disk_query_topk_filtered: null searcher");
+    if (check_params(in)) return -1;
+    try {
+        plan.resize(in.nq);
+    } catch (const std::bad_alloc&) {
+        return fail("out of host memory");
+    }
+    for (size_t q = 0; q < in.nq; q++) {
+        plan[q] = EachPlan{MSE_FILTERED_GRAPH, in.search_list, nullptr};
+        if (!filters[q]) continue;
+        SearchIn one = in;
+        one.filter = filters[q];
+        if (filtered_resolve(one, regime)) return fail(std::string(mse_last_error()) + " (query " + std::to_string(q) + ")");
+        plan[q] = EachPlan{one.regime, one.search_list, filters[q]};
+    }
+    return 0;
+}
+
+// The top-k forms.  The queries are split, stably, into classes that one submission can serve: traversals by effective search_list (any
+// filters: the launch reads them per query), list passes by filter object, and one class for the filters that allow nothing (a list pass
+// over no rows: padding, nothing launched).  A call of one class is that submission over the caller's own arrays; otherwise each class's
+// inputs are gathered into the searcher's staging and its results go straight to the caller's positions (QueryDst).
+int each_topk(SearchIn in, const mse_filter* const* filters, int regime, const mse_groups* groups, const FusedQuery& out) {
+    std::vector<EachPlan> plan;
+    if (each_resolve(in, filters, regime, plan)) return -1;
+    if (!out.ids || !out.scores || (!in.queries && !in.queries_f32)) return fail("disk_query_topk: null argument");
+    if (in.nq == 0) return 0;
+    if (check_k(out.k)) return -1;
+    if (groups) { in.groups = groups; in.grouped = true; }
+    if (check_grouping(in)) return -1;
+    mse_searcher* s = in.s;
+    const size_t nq = in.nq, d = s->base->d, k = out.k;
+    struct Class {
+        int regime; size_t search_list; const mse_filter* f; std::vector<uint32_t> qs;
+    };
+    std::vector<Class> classes;
+    try {
+        std::map<std::tuple<int, size_t, const mse_filter*>, size_t> at;
+        for (size_t q = 0; q < nq; q++) {
+            const EachPlan& p = plan[q];
+            const bool list = p.regime == MSE_FILTERED_LIST;
+            const auto key = std::make_tuple(p.regime, list ? (size_t)0 : p.search_list, list && p.f->count ? p.f : nullptr);
+            const auto it = at.find(key);
+            size_t ci = it == at.end() ? classes.size() : it->second;
+            if (it == at.end()) {
+                at.emplace(key, ci);
+                classes.push_back(Class{p.regime, p.search_list, list ? p.f : nullptr, {}});
+            }
+            classes[ci].qs.push_back((uint32_t)q);
+        }
+    } catch (const std::bad_alloc&) {
+        return fail("out of host memory");
+    }
+    if (classes.size() == 1) {
+        const Class& c = classes[0];
+        in.regime = c.regime; in.search_list = c.search_list;
+        if (c.regime == MSE_FILTERED_LIST) in.filter = c.f;
+        else in.filters_each = filters;
+        return query_front(QueryCall{in, out});
+    }
+    // what belongs to the caller's arguments is found for EVERY class before the first one runs and writes: argument errors write nothing
+    for (const Class& c : classes) {
+        SearchIn probe = in;
+        probe.regime = c.regime; probe.search_list = c.search_list; probe.starts = nullptr;
+        if (check_queued(probe)) return -1;
+        for (size_t j = 0; c.regime != MSE_FILTERED_LIST && in.starts && j < c.qs.size(); j++)
+            if (in.starts[c.qs[j]] >= in.g->n) return fail("disk_search_batch: start node out of range");
+    }
+    const bool on_device = in.queries && is_device_pointer(in.queries);
+    const size_t n_desc = (in.scales && in.c) ? in.c->n_desc : 0;
+    // pinned staging, sized once for the largest class: [a host copy of device-resident queries, fetched in ONE copy | a class's inputs]
+    const size_t q_row = d * (in.queries ? 2 : 4), lut_row = in.luts ? 65536 : 0, sc_row = n_desc * 4, st_row = in.starts ? 4 : 0;
+    const size_t all_q = on_device ? (nq * q_row + 63) & ~(size_t)63 : 0;
+    if (s->each_stage.ensure(all_q + nq * (q_row + lut_row + sc_row + st_row) + 256, (size_t)1 << 16)) return -1;
+    const unsigned char* q_src = in.queries ? reinterpret_cast<const unsigned char*>(in.queries) : reinterpret_cast<const unsigned char*>(in.queries_f32);
+    if (on_device) {
+        MSE_HIP_TRY(hipMemcpy(s->each_stage.p, in.queries, nq * q_row, hipMemcpyDeviceToHost));
+        q_src = s->each_stage.as<unsigned char>();
+    }
+    for (const Class& c : classes) {
+        const size_t m = c.qs.size();
+        const size_t off_lut = (m * q_row + 63) & ~(size_t)63, off_sc = off_lut + m * lut_row, off_st = (off_sc + m * sc_row + 63) & ~(size_t)63;
+        try {
+            s->each_filters.resize(m);
+            s->each_dsts.resize(m);
+        } catch (const std::bad_alloc&) {
+            return fail("out of host memory");
+        }
+        unsigned char* p = s->each_stage.as<unsigned char>() + all_q;
+        for (size_t j = 0; j < m; j++) {
+            const size_t q = c.qs[j];
+            memcpy(p + j * q_row, q_src + q * q_row, q_row);
+            if (lut_row) memcpy(p + off_lut + j * lut_row, in.luts + q * 16384, lut_row);
+            if (sc_row) memcpy(p + off_sc + j * sc_row, in.scales + q * n_desc, sc_row);
+            if (st_row) memcpy(p + off_st + j * 4, in.starts + q, 4);
+            s->each_filters[j] = plan[q].f;
+            s->each_dsts[j] = QueryDst{out.ids + q * k, out.scores + q * k, shifted(out.n_visited, q), shifted(out.cmps, q), shifted(out.pq_cmps, q), k};
+        }
+        SearchIn ci = in;
+        ci.nq = m; ci.regime = c.regime; ci.search_list = c.search_list;
+        ci.queries = in.queries ? reinterpret_cast<const uint16_t*>(p) : nullptr;
+        ci.queries_f32 = in.queries ? nullptr : reinterpret_cast<const float*>(p);
+        ci.luts = lut_row ? reinterpret_cast<const float*>(p + off_lut) : nullptr;
+        ci.scales = sc_row ? reinterpret_cast<const float*>(p + off_sc) : in.scales;
+        ci.starts = st_row ? reinterpret_cast<const uint32_t*>(p + off_st) : nullptr;
+        if (c.regime == MSE_FILTERED_LIST) ci.filter = c.f;
+        else ci.filters_each = s->each_filters.data();
+        if (check_queued(ci)) return -1;
+        FusedQuery fz;
+        fz.k = k; fz.dst = s->each_dsts.data();
+        if (const int rc = fused_run(ci, fz)) return rc;
+    }
+    return 0;
 }
 }  // namespace
 
@@ -1847,6 +2062,37 @@ int mse_disk_query_topk_grouped_f32(mse_searcher* s, mse_pq* pq, const mse_codes
     if (!queries_f32) return fail("disk_query_topk_f32: null argument");
     return grouped_front(SearchIn{s, pq, c, g, starts, nullptr, queries_f32, nullptr, scales, nq, disable_pq, beamwidth, search_list, f}, regime, groups,
                          fused_out(k, ids, scores, n_visited, cmps, pq_cmps));
+}
+
+// ---- a filter per query (include/mse.h): the filtered calls with filters[q] in f's place, one launch per class of queries (each_topk)
+int mse_disk_query_topk_filtered_each(mse_searcher* s, mse_pq* pq, const mse_codes* c, const mse_graph* g, const mse_filter* const* filters,
+                                      int regime, const mse_groups* groups, const uint32_t* starts, const uint16_t* queries, const float* luts,
+                                      const float* scales, size_t nq, int disable_pq, size_t beamwidth, size_t search_list, size_t k, uint32_t* ids,
+                                      int64_t* scores, uint32_t* n_visited, uint32_t* cmps, uint32_t* pq_cmps) {
+    return each_topk(SearchIn{s, pq, c, g, starts, queries, nullptr, luts, scales, nq, disable_pq, beamwidth, search_list}, filters, regime, groups,
+                     fused_out(k, ids, scores, n_visited, cmps, pq_cmps));
+}
+
+int mse_disk_query_topk_filtered_each_f32(mse_searcher* s, mse_pq* pq, const mse_codes* c, const mse_graph* g, const mse_filter* const* filters,
+                                          int regime, const mse_groups* groups, const uint32_t* starts, const float* queries_f32,
+                                          const float* scales, size_t nq, int disable_pq, size_t beamwidth, size_t search_list, size_t k,
+                                          uint32_t* ids, int64_t* scores, uint32_t* n_visited, uint32_t* cmps, uint32_t* pq_cmps) {
+    return each_topk(SearchIn{s, pq, c, g, starts, nullptr, queries_f32, nullptr, scales, nq, disable_pq, beamwidth, search_list}, filters, regime,
+                     groups, fused_out(k, ids, scores, n_visited, cmps, pq_cmps));
+}
+
+// the list form: GRAPH at the caller's search_list for every query, so always one launch
+int mse_disk_search_batch_filtered_each(mse_searcher* s, mse_pq* pq, const mse_codes* c, const mse_graph* g, const mse_filter* const* filters,
+                                        const uint32_t* starts, const uint16_t* queries, const float* luts, const float* scales, size_t nq,
+                                        int disable_pq, size_t beamwidth, size_t search_list, uint32_t* buf_ids, int64_t* buf_scores,
+                                        uint32_t* buf_len, uint32_t* visited_ids, int64_t* visited_scores, size_t visited_cap, uint32_t* n_visited,
+                                        uint32_t* cmps, uint32_t* pq_cmps) {
+    SearchIn in{s, pq, c, g, starts, queries, nullptr, luts, scales, nq, disable_pq, beamwidth, search_list};
+    std::vector<EachPlan> plan;
+    if (each_resolve(in, filters, MSE_FILTERED_GRAPH, plan)) return -1;
+    if (!queries) return fail("disk_search_batch: null argument");
+    in.filters_each = filters;
+    return disk_search_batch(BeamCall{in, ListOut{buf_ids, buf_scores, buf_len, visited_ids, visited_scores, visited_cap, n_visited, cmps, pq_cmps}});
 }
 
 // ---- the request path without a thread per request (round 5) ----------------------------------------------------------------
@@ -2137,6 +2383,12 @@ int mse_graph_coalescer_stats(const mse_graph* g, uint64_t out[6]) {
         if (g->co) st = g->co->stats();
     }
     out[0] = st.queries; out[1] = st.requests; out[2] = st.passes; out[3] = st.max_pass_queries; out[4] = st.deadline_fires; out[5] = st.run_us;
+    return 0;
+}
+
+int mse_graph_coalescer_groups(const mse_graph* g, uint64_t out[2]) {
+    if (!g || !out) return fail("null argument");
+    out[0] = g->co_groups.load(std::memory_order_relaxed); out[1] = g->co_group_requests.load(std::memory_order_relaxed);
     return 0;
 }
 

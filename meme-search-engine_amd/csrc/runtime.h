@@ -113,6 +113,13 @@ struct mse_groups {
     uint32_t* group_of = nullptr;  // device [n_rows]: group id (< n_rows) or MSE_GROUP_NONE
 };
 
+namespace mse {
+// one query's outputs of the fused request path (any of the counter pointers may be null)
+struct QueryDst {
+    uint32_t* ids; int64_t* scores; uint32_t *n_visited, *cmps, *pq_cmps; size_t k;
+};
+}  // namespace mse
+
 struct mse_searcher {
     const mse_base* base = nullptr;
     hipStream_t stream = nullptr;
@@ -137,6 +144,13 @@ struct mse_searcher {
     // which is all a floor needs (api_pq.hip); tests/test_gpu_topk_select.py pins `<= k-th key`, not equality.
     const unsigned long long* last_kth = nullptr;
     mse::DevBuf pool[16];     // scratch of the batched graph searches (kept between calls: no hipMalloc on the query path)
+    // a filter per query (beam_search.hip, mse_disk_query_topk_filtered_each): the launch's table [nq] of (bitmap, rows), and the host
+    // staging of a call that splits into classes -- gathered inputs, the classes' filter pointers and output destinations
+    mse::DevBuf flt_tab;
+    std::vector<unsigned char> flt_host;   // the table on its way to the device: lives as long as the copy may be in flight
+    mse::PinBuf each_stage;
+    std::vector<const mse_filter*> each_filters;
+    std::vector<mse::QueryDst> each_dsts;
     mse::DevBuf del_scratch[10];   // scratch of mse_graph_delete_rows (graph_delete.hip), kept between calls for the same reason
     mse::DevBuf ins_scratch[8];    // scratch of mse_graph_insert_rows (graph_insert.hip): slots, staging slabs, codes, flags
     mse::BuildScratch ins_build;   // ... and of its link step
@@ -270,13 +284,6 @@ int build_graph_on_device(mse_searcher* s, ::mse_graph* g, const uint32_t* order
 size_t visited_budget_bytes();
 }  // namespace mse
 
-namespace mse {
-// one query's outputs of the fused request path (any of the counter pointers may be null)
-struct QueryDst {
-    uint32_t* ids; int64_t* scores; uint32_t *n_visited, *cmps, *pq_cmps; size_t k;
-};
-}  // namespace mse
-
 struct mse_graph {
     uint32_t* adj = nullptr;   // device [n][max_deg]
     uint32_t* deg = nullptr;   // device [n]
@@ -295,8 +302,12 @@ struct mse_graph {
         mse_searcher* s = nullptr;   // made on first use over the callers' base
         mse::PinBuf pin;             // gathered inputs (queries, scales, starts, tables)
         std::vector<mse::QueryDst> dsts;   // where each gathered query's results go
+        std::vector<const mse_filter*> filters;   // each gathered query's filter, when the sharers' filters differ
     };
     mutable std::vector<WorkerCtx> co_ctx;
+    // what the sharing rule decides (mse_graph_coalescer_groups): groups of requests that ran as ONE submission each -- a gathered
+    // batch is split into them by shares_with -- and the requests in them
+    mutable std::atomic<uint64_t> co_groups{0}, co_group_requests{0};
     size_t co_max_queries = 0;       // mse_graph_set_coalescer: 0 = defaults (1024 queries per pass, 200 us, two workers)
     uint32_t co_max_wait_us = 0;
     int co_workers = 0;

@@ -9,7 +9,7 @@ from .vector import (SCALE, ID_NONE, GROUP_NONE, MODE_AUTO, MODE_EXACT, MODE_MFM
 from .diskann import (NeighbourBuffer, IndexGraph, greedy_search, disk_greedy_search, DiskSearchResult, medioid,  # noqa: F401
                       select_shard, dedup_visited, DUPLICATES_THRESHOLD, DeviceGraph, disk_search_batch, IndexBuildConfig,
                       BuildGraph, robust_prune, topk_of_visited, set_entries, disk_query_topk, QueryTickets, set_entry_centroids,
-                      set_coalescer, coalescer_stats, set_dedup, filtered_plan, DELETE_STATS, INSERT_STATS, COMPACT_STATS)
+                      set_coalescer, coalescer_stats, coalescer_groups, set_dedup, filtered_plan, DELETE_STATS, INSERT_STATS, COMPACT_STATS)
 from .index import ScalarQuantizerIndex  # noqa: F401
 from .common import decode_fp16_buffer, chunk_fp16_buffer, get_total_embedding  # noqa: F401
 from .index_pack import ScoreModel, descriptor_buckets  # noqa: F401

@@ -392,6 +392,23 @@ def _regime(regime):
         raise ValueError(f"regime must be one of {sorted(REGIMES)}") from None
 
 
+def _filter_array(filter, nq):
+    """A filter per query: `filter` as the [nq] handle array of the *_filtered_each calls (None entries: unfiltered), or None when it
+    is a single RowFilter.  The array holds the RowFilter objects (._keep), so they live as long as it does, whatever kind of iterable
+    they came from: the caller keeps the array until the call has returned."""
+    if filter is None or isinstance(filter, RowFilter):
+        return None
+    fs = list(filter)
+    if len(fs) != nq:
+        raise MseError(f"a filter per query: {len(fs)} filters for {nq} queries")
+    for f in fs:
+        if f is not None and not isinstance(f, RowFilter):
+            raise TypeError("filter must be a RowFilter, or a sequence of RowFilter / None with one entry per query")
+    arr = (C.c_void_p * nq)(*[f._h if f is not None else None for f in fs])
+    arr._keep = fs
+    return arr
+
+
 def filtered_plan(n_rows, allowed, search_list, dedup_on=False):
     """What regime="auto" does for a filter of `allowed` rows on a graph of `n_rows` (mse_filtered_plan): (regime name, effective
     search_list).  No allowed row: "list" (all padding).  L' = ceil(search_list * n_rows / allowed) <= 1024: "graph" at max(search_list,
@@ -406,7 +423,8 @@ def disk_search_batch(searcher: Searcher, quantizer, codes, dgraph: DeviceGraph,
                       disable_pq=False, beamwidth=1, search_list=1000, visited_cap=4096, as_arrays=False, filter=None):
     """query_disk_index::greedy_search for a batch of queries, entirely on the device (one workgroup per query).
     filter (a RowFilter, f16 queries only): the same traversal, but a fetched node enters the visited list only if the filter allows
-    it (and it has a url) -- the search over an index whose has_url is has_url AND allowed.
+    it (and it has a url) -- the search over an index whose has_url is has_url AND allowed.  A sequence of nq RowFilter / None gives
+    every query its own filter (None: unfiltered) in the same single launch (mse_disk_search_batch_filtered_each).
     as_arrays=True returns the padded output arrays themselves (dict: buf_ids, buf_scores, buf_len, visited_ids,
     visited_scores, n_visited, cmps, pq_cmps) instead of one tuple per query.
     queries: f16 rows with `luts` (QueryLUTs / [nq][64*256] f32; not needed with disable_pq), or f32 rows with luts=None --
@@ -436,7 +454,15 @@ def disk_search_batch(searcher: Searcher, quantizer, codes, dgraph: DeviceGraph,
     tail = (nq, int(bool(disable_pq)), int(beamwidth), int(search_list), _p(bi, C.c_uint32), _p(bs, C.c_int64), _p(bl, C.c_uint32),
             _p(vi, C.c_uint32), _p(vs, C.c_int64), visited_cap, _p(nv, C.c_uint32), _p(cm, C.c_uint32), _p(pc, C.c_uint32))
     scp = _p(sc, C.c_float) if sc is not None else None
-    if filter is not None:
+    each = _filter_array(filter, nq)
+    if each is not None:
+        if from_f32:
+            raise MseError("disk_search_batch: a filtered search takes f16 queries (with luts, or disable_pq)")
+        check(ffi.lib().mse_disk_search_batch_filtered_each(searcher._h, quantizer._h if quantizer is not None else None,
+                                                            codes._h if codes is not None else None, dgraph._h, each, _p(st, C.c_uint32),
+                                                            _p(q, C.c_uint16), _p(tables, C.c_float) if tables is not None else None, scp, *tail),
+              "disk_search_batch_filtered_each")
+    elif filter is not None:
         if from_f32:
             raise MseError("disk_search_batch: a filtered search takes f16 queries (with luts, or disable_pq)")
         check(ffi.lib().mse_disk_search_batch_filtered(searcher._h, quantizer._h if quantizer is not None else None,
@@ -502,6 +528,14 @@ def coalescer_stats(dgraph):
             "deadline_fires": int(out[4]), "run_us": int(out[5])}
 
 
+def coalescer_groups(dgraph):
+    """What shared a launch (mse_graph_coalescer_groups): the groups of coalesced requests that ran as one launch each, and the requests
+    in them.  groups == requests: nothing shared."""
+    out = (C.c_uint64 * 2)()
+    check(ffi.lib().mse_graph_coalescer_groups(dgraph._h, out), "graph_coalescer_groups")
+    return {"groups": int(out[0]), "requests": int(out[1])}
+
+
 def disk_query_topk(searcher: Searcher, quantizer, codes, dgraph, queries, k, starts=None, luts=None, descriptor_scales=None,
                     disable_pq=False, beamwidth=1, search_list=1000, filter=None, regime="auto", groups=None):
     """The request path of query_disk_index (:436-540) for a batch in one device submission: entry node (by the graph's entry table
@@ -512,6 +546,8 @@ def disk_query_topk(searcher: Searcher, quantizer, codes, dgraph, queries, k, st
     filter (a RowFilter): only rows it allows (and that have a url) are returned.  regime "graph": the same traversal at search_list,
     disallowed nodes walked through but not returned; "list": the exact k best of the eligible rows, no traversal (n_visited = cmps =
     eligible rows); "auto": whichever filtered_plan(len(graph), filter.count, search_list, dedup on) names, at its search_list.
+    A sequence of nq RowFilter / None gives every query its own filter (None: unfiltered; mse_disk_query_topk_filtered_each): row i is
+    the answer of the one-query call with filter[i], the regime resolved per query, and queries that can share a launch do.
     groups (a RowGroups, by row id): one result per group -- of the records this search visited, ranked as above, the first of every
     group; fewer than k groups among them show as padding (ask again with a longer search_list).  With or without a filter."""
     from_f32 = False
@@ -545,7 +581,15 @@ def disk_query_topk(searcher: Searcher, quantizer, codes, dgraph, queries, k, st
     head = (searcher._h, quantizer._h if quantizer is not None else None, codes._h if codes is not None else None, dgraph._h,
             _p(st, C.c_uint32) if st is not None else None, q_ptr)
     scp = _p(sc, C.c_float) if sc is not None else None
-    if groups is not None:
+    each = _filter_array(filter, nq)
+    if each is not None:
+        ehead = head[:4] + (each, _regime(regime), groups._h if groups is not None else None) + head[4:]
+        if from_f32:
+            check(ffi.lib().mse_disk_query_topk_filtered_each_f32(*ehead, scp, *tail), "disk_query_topk_filtered_each_f32")
+        else:
+            check(ffi.lib().mse_disk_query_topk_filtered_each(*ehead, _p(tables, C.c_float) if tables is not None else None, scp, *tail),
+                  "disk_query_topk_filtered_each")
+    elif groups is not None:
         ghead = head[:4] + (groups._h, filter._h if filter is not None else None, _regime(regime)) + head[4:]
         if from_f32:
             check(ffi.lib().mse_disk_query_topk_grouped_f32(*ghead, scp, *tail), "disk_query_topk_grouped_f32")
@@ -564,6 +608,9 @@ def disk_query_topk(searcher: Searcher, quantizer, codes, dgraph, queries, k, st
     else:
         check(ffi.lib().mse_disk_query_topk(*head, _p(tables, C.c_float) if tables is not None else None, scp, *tail), "disk_query_topk")
     return ids, scores, {"n_visited": nv, "cmps": cm, "pq_cmps": pc}
+
+
+_OWN_FILTER = object()   # QueryTickets.submit: "the filter this object was made with"
 
 
 class QueryTickets:
@@ -615,9 +662,15 @@ class QueryTickets:
         """Requests of the whole graph submitted and not yet collected."""
         return len(self._reg["out"])
 
-    def submit(self, query_f32, descriptor_scales=None, key=None, copy=True):
+    def submit(self, query_f32, descriptor_scales=None, key=None, copy=True, filter=_OWN_FILTER):
         """copy=False: the library reads the query where it lies (mse_disk_query_submit_f32_nocopy); this object keeps the array alive
-        until the request has been collected."""
+        until the request has been collected.
+        filter: a RowFilter for THIS request in place of the object's own (None: this request is unfiltered); it is kept alive until
+        the request has been collected.  Requests with different filters still share a launch when they resolve to the graph regime
+        at the same search_list."""
+        flt_obj = self._filter if filter is _OWN_FILTER else filter
+        if flt_obj is not None and not isinstance(flt_obj, RowFilter):
+            raise TypeError("filter must be a RowFilter or None")
         q = np.ascontiguousarray(np.asarray(query_f32, np.float32).reshape(-1, np.asarray(query_f32).shape[-1]))
         nq = q.shape[0]
         sc = None
@@ -628,18 +681,18 @@ class QueryTickets:
         with self._reg["lock"]:
             tag = self._reg["next"]
             self._reg["next"] += 1
-            self._reg["out"][tag] = (key if key is not None else tag, ids, scores) + (() if copy else (q, sc))   # before the request can complete
+            self._reg["out"][tag] = (key if key is not None else tag, ids, scores, flt_obj) + (() if copy else (q, sc))   # before the request can complete
         t = C.c_void_p()
         try:
-            if (self._filter is not None or self._groups is not None) and not copy:
+            if (flt_obj is not None or self._groups is not None) and not copy:
                 raise MseError("QueryTickets: copy=False is not available with a filter or a grouping")
             fn = ffi.lib().mse_disk_query_submit_f32 if copy else ffi.lib().mse_disk_query_submit_f32_nocopy
             flt = ()
-            if self._filter is not None:
-                fn, flt = ffi.lib().mse_disk_query_submit_filtered_f32, (self._filter._h, self._regime)
+            if flt_obj is not None:
+                fn, flt = ffi.lib().mse_disk_query_submit_filtered_f32, (flt_obj._h, self._regime)
             if self._groups is not None:
                 fn = ffi.lib().mse_disk_query_submit_grouped_f32
-                flt = (self._groups._h, self._filter._h if self._filter is not None else None, self._regime)
+                flt = (self._groups._h, flt_obj._h if flt_obj is not None else None, self._regime)
             check(fn(self._s._h, self._pq._h if self._pq is not None else None,
                                                       self._codes._h if self._codes is not None else None, self._g._h, *flt, _p(q, C.c_float),
                                                       _p(sc, C.c_float) if sc is not None else None, nq, int(self.disable_pq), self.beamwidth,

@@ -237,6 +237,7 @@ SIGNATURES = {
     "mse_graph_set_dedup": (C.c_int, [vp, C.c_float]),
     "mse_graph_set_coalescer": (C.c_int, [vp, sz, C.c_uint32, C.c_int]),
     "mse_graph_coalescer_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+    "mse_graph_coalescer_groups": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
     "mse_searcher_wait_stream": (C.c_int, [vp, vp]),
     "mse_searcher_beam_timing": (C.c_int, [vp, C.c_int, C.POINTER(C.c_uint64)]),
     "mse_debug_coalescer_selftest_workers": (C.c_int, [C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
@@ -257,6 +258,13 @@ SIGNATURES = {
                                                   u32p, u32p]),
     "mse_disk_query_submit_grouped_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, f32p, f32p, sz, C.c_int, sz, sz, sz, u32p, i64p, u32p, u32p,
                                                     u32p, vp, vp, C.POINTER(vp)]),
+    # a filter per query: [nq] filter handles (NULL entries: unfiltered) where the single-filter calls take one handle
+    "mse_disk_query_topk_filtered_each": (C.c_int, [vp, vp, vp, vp, C.POINTER(vp), C.c_int, vp, u32p, u16p, f32p, f32p, sz, C.c_int, sz, sz, sz,
+                                                    u32p, i64p, u32p, u32p, u32p]),
+    "mse_disk_query_topk_filtered_each_f32": (C.c_int, [vp, vp, vp, vp, C.POINTER(vp), C.c_int, vp, u32p, f32p, f32p, sz, C.c_int, sz, sz, sz,
+                                                        u32p, i64p, u32p, u32p, u32p]),
+    "mse_disk_search_batch_filtered_each": (C.c_int, [vp, vp, vp, vp, C.POINTER(vp), u32p, u16p, f32p, f32p, sz, C.c_int, sz, sz, u32p, i64p,
+                                                      u32p, u32p, i64p, sz, u32p, u32p, u32p]),
     "mse_debug_visited_collapse": (C.c_int, [vp, vp, u32p, i64p, sz, u32p, sz]),
     "mse_graph_new": (vp, [sz, sz]),
     "mse_graph_to_host": (C.c_int, [vp, u32p, u32p]),
