@@ -401,6 +401,61 @@ int mse_pq_quantize_batch(mse_pq* pq, const float* x, size_t n, uint8_t* codes);
 int mse_pq_preprocess_query(mse_pq* pq, const float* query, float* lut);               /* :367-384, lut[n_chunks*n_centroids] */
 int mse_pq_adc(mse_pq* pq, const float* lut, const uint8_t* codes, size_t n, int64_t* out); /* :387-405 */
 
+/* ---- codec training: diskann/aopq_train.py on the device ----------------------------------------------------------
+ * Trains the arrays of opq.msgpack (aopq_train.py:87-93): centroids [n_centroids][n_dims] f32, transform [n_dims][n_dims] f32.  The
+ * algorithm is the script's (:33-85) with the expectation over queries taken exactly through their second moment: start from a rotation and
+ * per-sub-space max-inner-product k-means; rounds of { Adam steps on the centroids against L = (1/n) sum_x r^T C r, r = x' - y(x'),
+ * C = T C0 T^T; one non-parametric OPQ rotation update }.  Adam's moments and step count live in the handle and persist across calls, as
+ * the script's one optimiser does (:75).  Rotation and assignment are mse_pq_apply_transform's and mse_pq_quantize_batch's arithmetic.
+ * Every sum over rows is an ORDER-FREE SUM: with vmax = max |v| = f 2^ex, f in [0.5, 1) (ex = 0 at vmax = 0) and
+ * E = 61 - ceil(log2 n) - ex, each term is llrint((double)v 2^E) (round-half-even), summed in int64 by integer atomics; its value is
+ * (double)S 2^-E.  A non-finite term is an error.  Results are the same bits run to run.
+ * THE ROTATION SOLVE BELONGS TO THE CALLER: mse_pq_trainer_cross returns M = X'^T Y; the caller computes U S V^T = svd(M) (float64) and
+ * passes T_new = (U V^T)^T T_old to mse_pq_trainer_set_transform (:79-85).  This library links no solver.
+ * A handle belongs to the device that was current when it was made; calls on one handle must not overlap. */
+typedef struct mse_pq_trainer mse_pq_trainer;
+/* Shape rules of mse_pq_load; refused before anything is allocated. */
+mse_pq_trainer* mse_pq_trainer_new(size_t n_dims, size_t n_dims_per_code, size_t n_centroids);
+void mse_pq_trainer_free(mse_pq_trainer* tr);
+/* The sample (aopq_train.py:14,70): n host rows, or rows ids[0 .. n) of a resident base, gathered and kept as f16, widened on the device.
+ * n < n_centroids and an id at or past the base's rows are errors.  The unrotated sample is kept: every set_transform rotates it afresh. */
+int mse_pq_trainer_set_sample_f32(mse_pq_trainer* tr, const float* x, size_t n);
+int mse_pq_trainer_set_sample_base(mse_pq_trainer* tr, const mse_base* b, const uint32_t* ids, size_t n);
+/* T [n_dims][n_dims] (:69,85): X' = rows of the sample through T, and C = T C0 T^T when a moment is set. */
+int mse_pq_trainer_set_transform(mse_pq_trainer* tr, const float* T);
+int mse_pq_trainer_set_centroids(mse_pq_trainer* tr, const float* centroids);          /* [n_centroids][n_dims] (:73) */
+/* C0 = Q^T Q / m of the UNROTATED queries, [n_dims][n_dims] (:43,51-53 with the mean over queries taken exactly). */
+int mse_pq_trainer_set_query_moment(mse_pq_trainer* tr, const float* C0);
+/* iters k-means steps: assign; order-free sums of the members' sub-vectors (one vmax over X'); c = (float)(((double)S / (double)count) 2^-E).
+ * A cell without members keeps its centroid; *empty_cells (may be NULL) = such cells in the last step, over all sub-spaces. */
+int mse_pq_trainer_kmeans(mse_pq_trainer* tr, size_t iters, uint64_t* empty_cells);
+/* steps Adam steps (:33-58, torch.optim.Adam's arithmetic in f32): assign; G = R C on the f32-input matrix cores, rows in chunks of 262144;
+ * gradient = (float)(sum over chunks of (double)S_c 2^-E_c, times -2 / n) from the order-free sums of G's column blocks by code; update.
+ * loss[s] = L at the centroids BEFORE step s's update.  An error without a query moment. */
+int mse_pq_trainer_refine(mse_pq_trainer* tr, size_t steps, float lr, float beta1, float beta2, float eps, double* loss);
+int mse_pq_trainer_loss(mse_pq_trainer* tr, double* loss);                             /* L now; changes no state */
+/* M [n_dims][n_dims] f64 = X'^T Y in the current rotated coordinates (:82-84), through full-width order-free sums of X' by code. */
+int mse_pq_trainer_cross(mse_pq_trainer* tr, double* M);
+int mse_pq_trainer_read(mse_pq_trainer* tr, float* centroids, float* transform);      /* either may be NULL */
+int mse_pq_trainer_codes(mse_pq_trainer* tr, uint8_t* codes);                          /* [n][n_chunks]: the sample under the current state */
+/* out [m][n_dims] = rows rows[0 .. m) of X' (the start of :72-73 takes its centroids from sample rows); a row at or past n is an error. */
+int mse_pq_trainer_rotated_rows(mse_pq_trainer* tr, const uint32_t* rows, size_t m, float* out);
+/* Adam's state out and in (m, v: [n_centroids][n_dims]; t: steps taken), for resuming.  Outputs may be NULL. */
+int mse_pq_trainer_adam_state(mse_pq_trainer* tr, float* m, float* v, uint64_t* t);
+int mse_pq_trainer_set_adam_state(mse_pq_trainer* tr, const float* m, const float* v, uint64_t t);
+/* The gradient the last refine step applied, [n_centroids][n_dims] (zero for cells without members); an error before the first step. */
+int mse_pq_trainer_gradient(mse_pq_trainer* tr, float* grad);
+/* A loaded quantiser from the current arrays (:87-93); the trainer stays usable. */
+mse_pq* mse_pq_trainer_finish(mse_pq_trainer* tr);
+/* HIP-event milliseconds of the last step of the last refine call: assignment, residual GEMM, order-free sums of G, Adam. */
+int mse_pq_trainer_timing(mse_pq_trainer* tr, float ms[4]);
+/* test hooks: the order-free sum alone (host arrays; sums [n_cells][w], *E as defined above); the residual GEMM alone (G [n][n_dims] and
+ * l_row [n] = r . G_row for given X', codes [n][n_chunks], centroids and C); the trainer's rows per GEMM pass (default 262144). */
+int mse_debug_accumulate_by_code(const float* v, size_t n, size_t w, const uint8_t* code, size_t n_cells, int64_t* sums, int* E);
+int mse_debug_residual_gemm(const float* xr, const uint8_t* codes, const float* centroids, const float* C, size_t n, size_t n_dims,
+                            size_t n_dims_per_code, size_t n_centroids, float* G, float* lrow);
+int mse_debug_pq_trainer_chunk_rows(mse_pq_trainer* tr, size_t rows);
+
 /* PQ codes (+ optional descriptor bytes) resident in HBM: the mmap'd index.pq-codes.bin /
  * index.descriptor-codes.bin of src/query_disk_index.rs:686-709. */
 typedef struct mse_codes mse_codes;

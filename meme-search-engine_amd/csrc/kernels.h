@@ -144,6 +144,45 @@ int rank_max_targets();
 int launch_rank(const int64_t* scores, size_t n, const uint32_t* targets, int m, unsigned long long* counts, int n_cu,
                 hipStream_t stream);
 
+// ---- pq_train.hip: codec training (include/mse.h mse_pq_trainer) ----------------------------------------------------
+// *max_bits = bit pattern of max |v| over count floats (zeroed here first); inf / NaN patterns win the maximum
+int launch_abs_max(const float* v, size_t count, uint32_t* max_bits, hipStream_t stream);
+// *E = 61 - ceil(log2 n) - ex for vmax = f 2^ex, f in [0.5, 1) (ex = 0 at vmax = 0); a non-finite maximum sets bit 0 of *err instead
+int launch_fixed_exponent(const uint32_t* max_bits, size_t n, int* E, uint32_t* err, hipStream_t stream);
+// The order-free sum: slice z < n_slices adds llrint((double)v[row][z * v_step + c] * 2^E) for c < w into sums[z * sums_step + cell * w + c],
+// cell = code[row * code_stride + z * code_step] (a code at or past n_cells is skipped), as int64 through integer atomics.  sums (and
+// counts, optional: members per cell, [n_slices][n_cells]) are zeroed by the caller.  The result does not depend on rows_per_block (0: 4096)
+struct AccumulateArgs {
+    const float* v = nullptr; size_t n = 0; int w = 0; size_t v_stride = 0; int v_step = 0;
+    const uint8_t* code = nullptr; size_t code_stride = 1; int code_step = 0;
+    int n_cells = 0, n_slices = 1; const int* E = nullptr;
+    long long* sums = nullptr; size_t sums_step = 0;
+    unsigned long long* counts = nullptr;
+    unsigned rows_per_block = 0;
+};
+int launch_accumulate_by_code(const AccumulateArgs& a, hipStream_t stream);
+// centroids[k][s * dpc + u] = (float)(((double)sums[s][k][u] / (double)counts[s][k]) * 2^-E); a cell with count 0 is left alone and adds 1 to *empty
+int launch_kmeans_update(const long long* sums, const unsigned long long* counts, const int* E, int n_chunks, int n_cells, int dpc, int d,
+                         float* centroids, unsigned long long* empty, hipStream_t stream);
+// G [n][d] = R Cm with R = xr - (the centroids the codes name), formed while the operand is loaded; G may be null (loss only).
+// lrow [n] = r . G_row; lpart: scratch of n * residual_gemm_parts(d) floats.  Every output is one k-ascending fma chain
+int residual_gemm_parts(int d);
+int launch_residual_gemm(const float* xr, const uint8_t* codes, const float* centroids, const float* Cm, size_t n, int d, int dpc, float* G,
+                         float* lpart, float* lrow, hipStream_t stream);
+int launch_loss_finish(const long long* S, const int* E, size_t n, double* out, hipStream_t stream);   // *out = ((double)S 2^-E) / n
+// gradient from the chunk sums (sums + c * slot_stride with exponent E[c], c < n_slots, layout [n_chunks][n_cells][dpc]) and one Adam step
+struct AdamArgs {
+    const long long* sums; size_t slot_stride; const int* E; int n_slots; size_t n;
+    int n_chunks, n_cells, dpc, d;
+    float *centroids, *m, *v, *grad;   // grad [n_cells][d]: the step's gradient, kept for mse_pq_trainer_gradient
+    float beta1, beta2, step_size, bc2_sqrt, eps;
+};
+int launch_adam_step(const AdamArgs& a, hipStream_t stream);
+// M [d][d] f64 from the full-width sums sigma [n_chunks][n_cells][d] of X' by each sub-space's codes
+int launch_cross_matrix(const long long* sigma, const int* E, const float* centroids, int n_cells, int dpc, int d, double* M, hipStream_t stream);
+int launch_transpose_f32(const float* in, int d, float* out, hipStream_t stream);
+int launch_gather_rows_f16(const uint16_t* base, const uint32_t* ids, size_t n, int d, uint16_t* out, hipStream_t stream);
+
 // ---- disk_search.hip: the runtime de-duplication of the request path for a batch, on the device ------------------------------------
 // per query q: similarity bits over its visited records (vis_ids [nq][cap], n_visited[q] of them, visit order), greedy keep-first
 // filter; a dropped record becomes (ID_NONE, INT64_MIN) in place.  bits: dedup_batch_scratch_bytes(nq, cap) bytes of scratch.

@@ -130,6 +130,28 @@ SIGNATURES = {
     "mse_pq_quantize_batch": (C.c_int, [vp, f32p, sz, u8p]),
     "mse_pq_preprocess_query": (C.c_int, [vp, f32p, f32p]),
     "mse_pq_adc": (C.c_int, [vp, f32p, u8p, sz, i64p]),
+    "mse_pq_trainer_new": (vp, [sz, sz, sz]),
+    "mse_pq_trainer_free": (None, [vp]),
+    "mse_pq_trainer_set_sample_f32": (C.c_int, [vp, f32p, sz]),
+    "mse_pq_trainer_set_sample_base": (C.c_int, [vp, vp, u32p, sz]),
+    "mse_pq_trainer_set_transform": (C.c_int, [vp, f32p]),
+    "mse_pq_trainer_set_centroids": (C.c_int, [vp, f32p]),
+    "mse_pq_trainer_set_query_moment": (C.c_int, [vp, f32p]),
+    "mse_pq_trainer_kmeans": (C.c_int, [vp, sz, C.POINTER(C.c_uint64)]),
+    "mse_pq_trainer_refine": (C.c_int, [vp, sz, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_double)]),
+    "mse_pq_trainer_loss": (C.c_int, [vp, C.POINTER(C.c_double)]),
+    "mse_pq_trainer_cross": (C.c_int, [vp, C.POINTER(C.c_double)]),
+    "mse_pq_trainer_read": (C.c_int, [vp, f32p, f32p]),
+    "mse_pq_trainer_codes": (C.c_int, [vp, u8p]),
+    "mse_pq_trainer_rotated_rows": (C.c_int, [vp, u32p, sz, f32p]),
+    "mse_pq_trainer_adam_state": (C.c_int, [vp, f32p, f32p, C.POINTER(C.c_uint64)]),
+    "mse_pq_trainer_set_adam_state": (C.c_int, [vp, f32p, f32p, C.c_uint64]),
+    "mse_pq_trainer_gradient": (C.c_int, [vp, f32p]),
+    "mse_pq_trainer_finish": (vp, [vp]),
+    "mse_pq_trainer_timing": (C.c_int, [vp, f32p]),
+    "mse_debug_accumulate_by_code": (C.c_int, [f32p, sz, sz, u8p, sz, i64p, C.POINTER(C.c_int)]),
+    "mse_debug_residual_gemm": (C.c_int, [f32p, u8p, f32p, f32p, sz, sz, sz, sz, f32p, f32p]),
+    "mse_debug_pq_trainer_chunk_rows": (C.c_int, [vp, sz]),
     "mse_codes_from_host": (vp, [u8p, sz, sz, u8p, sz]),
     "mse_codes_free": (None, [vp]),
     "mse_codes_quantize_base": (vp, [vp, vp, u8p, sz]),

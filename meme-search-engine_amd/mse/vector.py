@@ -752,6 +752,39 @@ class ProductQuantizer:
                                                _p(o1, C.c_int64) if o1 is not None else None), "debug_pq_group_max")
         return (o0, o1) if l1 is not None else o0
 
+    @classmethod
+    def _adopt(cls, handle, n_dims, n_dims_per_code, n_centroids):
+        self = cls.__new__(cls)
+        self.n_dims, self.n_dims_per_code, self.n_centroids = n_dims, n_dims_per_code, n_centroids
+        self.n_chunks = n_dims // n_dims_per_code
+        self._h = handle
+        return self
+
+    @classmethod
+    def train(cls, sample, queries, *, rounds=3, steps=300, lr=5e-4, kmeans_iters=3, seed=4, n_dims_per_code=18, n_centroids=256):
+        """The codec as diskann/aopq_train.py:33-85 trains it, on the device (CodecTrainer): a seeded random rotation and k-means, then
+        `rounds` x { `steps` Adam steps on the centroids against the query-aware loss; one rotation update }.  sample [n, d] / queries
+        [m, d]: float32 host arrays.  -> (ProductQuantizer, info); info carries the first and last loss of every round."""
+        sample = np.ascontiguousarray(sample, np.float32)
+        tr = CodecTrainer(sample.shape[1], n_dims_per_code, n_centroids)
+        try:
+            tr.set_sample(sample)
+            tr.init(seed)
+            tr.set_queries(queries)
+            empty = tr.kmeans(kmeans_iters)
+            hist = []
+            for _ in range(rounds):
+                losses = tr.refine(steps, lr=lr)
+                if losses:
+                    hist += [losses[0], losses[-1]]
+                tr.update_rotation()
+            info = {"rounds": rounds, "adam_steps_per_round": steps, "lr": lr, "rows": int(sample.shape[0]),
+                    "queries": int(np.asarray(queries).shape[0]), "empty_cells_after_kmeans": empty,
+                    "query_aware_loss_first_last_per_round": hist}
+            return tr.quantizer(), info
+        finally:
+            tr.close()
+
     def close(self):
         if self._h:
             ffi.lib().mse_pq_free(self._h)
@@ -815,6 +848,151 @@ class Codes:
     def close(self):
         if self._h:
             ffi.lib().mse_codes_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def opq_msgpack(centroids, transform, n_dims_per_code, n_dims):
+    """The bytes of opq.msgpack (diskann/aopq_train.py:87-93): the four keys with flattened float lists, as ProductQuantizer.from_msgpack
+    and the reference's loader read them.  A pure host function."""
+    import msgpack
+    c = np.ascontiguousarray(centroids, np.float32).reshape(-1)
+    t = np.ascontiguousarray(transform, np.float32).reshape(-1)
+    if t.size != n_dims * n_dims or c.size % n_dims != 0 or n_dims % n_dims_per_code != 0:
+        raise MseError("opq_msgpack: array shapes do not match n_dims / n_dims_per_code")
+    return msgpack.packb({"centroids": c.tolist(), "transform": t.tolist(), "n_dims_per_code": int(n_dims_per_code), "n_dims": int(n_dims)})
+
+
+class CodecTrainer:
+    """mse_pq_trainer (include/mse.h): diskann/aopq_train.py:33-85 on the device.  The host keeps the plumbing: seeded choices, the
+    random orthonormal start, the queries' second moment and the SVD of the rotation update."""
+
+    def __init__(self, n_dims=1152, n_dims_per_code=18, n_centroids=256):
+        self.n_dims, self.n_dims_per_code, self.n_centroids = int(n_dims), int(n_dims_per_code), int(n_centroids)
+        self._h = check_ptr(ffi.lib().mse_pq_trainer_new(self.n_dims, self.n_dims_per_code, self.n_centroids), "mse_pq_trainer_new")
+        self.n_chunks = self.n_dims // self.n_dims_per_code
+        self.n = 0
+
+    def set_sample(self, x_f32):
+        x = np.ascontiguousarray(x_f32, np.float32).reshape(-1, self.n_dims)
+        check(ffi.lib().mse_pq_trainer_set_sample_f32(self._h, _p(x, C.c_float), x.shape[0]), "pq_trainer_set_sample_f32")
+        self.n = x.shape[0]
+
+    def set_sample_rows(self, vector_list_or_searcher, ids):
+        """Rows `ids` of a resident index as the sample: gathered and widened on the device, nothing crosses PCIe but the ids."""
+        vecs = getattr(vector_list_or_searcher, "vecs", vector_list_or_searcher)
+        ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        check(ffi.lib().mse_pq_trainer_set_sample_base(self._h, vecs._h, _p(ids, C.c_uint32), ids.size), "pq_trainer_set_sample_base")
+        self.n = ids.size      # (the rows are copied: the index need not outlive the call)
+
+    def set_transform(self, T):
+        T = np.ascontiguousarray(T, np.float32).reshape(self.n_dims, self.n_dims)
+        check(ffi.lib().mse_pq_trainer_set_transform(self._h, _p(T, C.c_float)), "pq_trainer_set_transform")
+
+    def set_centroids(self, centroids):
+        c = np.ascontiguousarray(centroids, np.float32).reshape(self.n_centroids, self.n_dims)
+        check(ffi.lib().mse_pq_trainer_set_centroids(self._h, _p(c, C.c_float)), "pq_trainer_set_centroids")
+
+    def set_query_moment(self, C0):
+        m = np.ascontiguousarray(C0, np.float32).reshape(self.n_dims, self.n_dims)
+        check(ffi.lib().mse_pq_trainer_set_query_moment(self._h, _p(m, C.c_float)), "pq_trainer_set_query_moment")
+
+    def init(self, seed):
+        """aopq_train.py:62-73: a random orthonormal transform (numpy QR), centroids = the rotated rows at n_centroids seeded distinct ids."""
+        if not self.n:
+            raise MseError("CodecTrainer.init: set a sample first")
+        rng = np.random.default_rng(seed)
+        T = np.linalg.qr(rng.standard_normal((self.n_dims, self.n_dims)))[0].astype(np.float32)
+        rows = np.sort(rng.choice(self.n, self.n_centroids, replace=False))
+        self.set_transform(T)
+        self.set_centroids(self.rotated_rows(rows))
+        return rows
+
+    def rotated_rows(self, rows):
+        """X'[rows]: the listed sample rows under the current transform."""
+        rows = np.ascontiguousarray(rows, np.uint32).reshape(-1)
+        out = np.empty((rows.size, self.n_dims), np.float32)
+        check(ffi.lib().mse_pq_trainer_rotated_rows(self._h, _p(rows, C.c_uint32), rows.size, _p(out, C.c_float)), "pq_trainer_rotated_rows")
+        return out
+
+    def set_queries(self, q_f32):
+        """C0 = Q^T Q / m of the unrotated queries, in float64 on the host, handed over as f32."""
+        q = np.ascontiguousarray(q_f32, np.float64).reshape(-1, self.n_dims)
+        self.set_query_moment((q.T @ q / q.shape[0]).astype(np.float32))
+
+    def kmeans(self, iters):
+        empty = C.c_uint64(0)
+        check(ffi.lib().mse_pq_trainer_kmeans(self._h, int(iters), C.byref(empty)), "pq_trainer_kmeans")
+        return int(empty.value)
+
+    def refine(self, steps, lr=5e-4, betas=(0.9, 0.999), eps=1e-8):
+        loss = np.zeros(max(int(steps), 1), np.float64)
+        check(ffi.lib().mse_pq_trainer_refine(self._h, int(steps), lr, betas[0], betas[1], eps, _p(loss, C.c_double)), "pq_trainer_refine")
+        return [float(v) for v in loss[:int(steps)]]
+
+    def loss(self):
+        out = C.c_double(0.0)
+        check(ffi.lib().mse_pq_trainer_loss(self._h, C.byref(out)), "pq_trainer_loss")
+        return float(out.value)
+
+    def cross(self):
+        M = np.empty((self.n_dims, self.n_dims), np.float64)
+        check(ffi.lib().mse_pq_trainer_cross(self._h, _p(M, C.c_double)), "pq_trainer_cross")
+        return M
+
+    def update_rotation(self):
+        """aopq_train.py:79-85: U S V^T = svd(X'^T Y) in float64, T_new = (U V^T)^T T_old.  The centroids are not refitted."""
+        u, _, vt = np.linalg.svd(self.cross())
+        T_old = self.arrays()[1].astype(np.float64)
+        self.set_transform(((u @ vt).T @ T_old).astype(np.float32))
+
+    def arrays(self):
+        c = np.empty((self.n_centroids, self.n_dims), np.float32)
+        T = np.empty((self.n_dims, self.n_dims), np.float32)
+        check(ffi.lib().mse_pq_trainer_read(self._h, _p(c, C.c_float), _p(T, C.c_float)), "pq_trainer_read")
+        return c, T
+
+    def codes(self):
+        out = np.empty((self.n, self.n_chunks), np.uint8)
+        check(ffi.lib().mse_pq_trainer_codes(self._h, _p(out, C.c_uint8)), "pq_trainer_codes")
+        return out
+
+    def adam_state(self):
+        m = np.empty((self.n_centroids, self.n_dims), np.float32)
+        v = np.empty_like(m)
+        t = C.c_uint64(0)
+        check(ffi.lib().mse_pq_trainer_adam_state(self._h, _p(m, C.c_float), _p(v, C.c_float), C.byref(t)), "pq_trainer_adam_state")
+        return m, v, int(t.value)
+
+    def set_adam_state(self, m, v, t):
+        m = np.ascontiguousarray(m, np.float32).reshape(self.n_centroids, self.n_dims)
+        v = np.ascontiguousarray(v, np.float32).reshape(self.n_centroids, self.n_dims)
+        check(ffi.lib().mse_pq_trainer_set_adam_state(self._h, _p(m, C.c_float), _p(v, C.c_float), int(t)), "pq_trainer_set_adam_state")
+
+    def gradient(self):
+        """The gradient the last refine step applied, [n_centroids, n_dims]."""
+        g = np.empty((self.n_centroids, self.n_dims), np.float32)
+        check(ffi.lib().mse_pq_trainer_gradient(self._h, _p(g, C.c_float)), "pq_trainer_gradient")
+        return g
+
+    def timing(self):
+        """HIP-event milliseconds of the last refine step: {assign, gemm, accumulate, adam}."""
+        ms = np.zeros(4, np.float32)
+        check(ffi.lib().mse_pq_trainer_timing(self._h, _p(ms, C.c_float)), "pq_trainer_timing")
+        return dict(zip(("assign", "gemm", "accumulate", "adam"), (float(x) for x in ms)))
+
+    def quantizer(self):
+        h = check_ptr(ffi.lib().mse_pq_trainer_finish(self._h), "mse_pq_trainer_finish")
+        return ProductQuantizer._adopt(h, self.n_dims, self.n_dims_per_code, self.n_centroids)
+
+    def close(self):
+        if self._h:
+            ffi.lib().mse_pq_trainer_free(self._h)
             self._h = None
 
     def __del__(self):
