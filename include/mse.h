@@ -456,6 +456,85 @@ int mse_debug_residual_gemm(const float* xr, const uint8_t* codes, const float* 
                             size_t n_dims_per_code, size_t n_centroids, float* G, float* lrow);
 int mse_debug_pq_trainer_chunk_rows(mse_pq_trainer* tr, size_t rows);
 
+/* ---- shard partition: kmeans.py and the spill-2 assignment of src/dump_processor.rs on the device --------------------
+ * Produces what mse_graph_set_entry_centroids, mse_select_shard and the shard files consume: balanced shard centroids (kmeans.py:73-127),
+ * the two shards of every row (src/dump_processor.rs:438-461) and, with mse_medioid_ids, each shard's medioid.
+ * THE SCORE, defined once: score(x, c) = sum_k (double)x_k (double)c_k, k ascending, one f64 accumulator; x an f16 row widened exactly,
+ * c an f32 centroid.  Every product is exact in f64, so a fused and an unfused accumulation give the same bits.  It is the order
+ * mse_select_shard states.  Everything below is defined on these f64 values and is the same bits run to run.
+ * THE NOISE is the library's generator, not torch.randn (which cannot be reproduced): z(key)[j] = (float)ints(seed, key)[j] * K with ints
+ * the integers of mse_base_generate's row `key` and K = (float)(sqrt(3) / 65536): unit variance, bounded at +-3.47 -- not a Gaussian.
+ * Keys: initial centroid s: s; the candidate of iteration t >= 1: t S + s; a reroll at iteration t: 2^40 + t S + s.
+ * NORMALISATION (torch.nn.functional.normalize, :80,127): ss = sum_k (double)c_k^2, k ascending; norm = 48 Newton steps y = (y + ss / y) / 2
+ * from y = 1; c^_k = (float)((double)c_k / norm); a zero row stays zero.
+ * FITNESS in integers: sizes[rank][s] = rows whose best (rank 0) / second best (rank 1) normalised centroid is s -- score descending,
+ * lowest index on ties -- and F = max over rank, s of |S sizes[rank][s] - n| (S times the script's value, :92-94); worst[rank] = the
+ * first s that attains the maximum of that rank.
+ * ONE ITERATION t >= 1, temperature T in f32, every operation rounded on its own (:103-122): cand = c + z T; F_new, worst of cand;
+ * if F_new < last { c = cand; T *= accept_decay; last = F_new; li = 0 } else { T *= reject_decay; li += 1 };
+ * if li > reroll_after { rows worst[0], worst[1] of c = fresh noise; li = 0; T *= reroll_heat; last = F_new }  (the script's quirk, kept);
+ * if last 10^6 < n round(stop_fraction 10^6) stop (before the cap; a stop_fraction of 0 never stops); else T = min(temperature_cap, T).
+ * Iteration 0 evaluates the initial centroids (:100).  The decision is a one-thread device step; a call enqueues its iterations without
+ * a host round trip and polls the stopped flag every 256; once it is set the remaining launches do nothing.
+ * A handle is made without touching a device and belongs to the device current at its first device call; calls on one handle must not
+ * overlap.  Limits, refused before anything is allocated: 2 <= n_shards <= 64, d % 8 == 0, d <= 4096, n >= n_shards. */
+typedef struct mse_partitioner mse_partitioner;
+typedef struct mse_partition_config {
+    float temperature0, accept_decay, reject_decay, reroll_heat, temperature_cap;   /* 1.0, 0.999, 0.9995, 1.1, 1.5 (:98,108,112,118,122) */
+    uint32_t reroll_after;                                                          /* 100 (:114) */
+    uint32_t seed;
+    double stop_fraction;                                                           /* 0.1 (:120), taken to six decimals */
+} mse_partition_config;
+typedef struct mse_partition_status {
+    uint64_t t;                 /* iterations decided (the initial evaluation not counted) */
+    uint64_t last_fitness;      /* F units: S times the script's last_fitness */
+    uint64_t last_improvement;
+    float temperature;
+    uint32_t stopped;
+} mse_partition_status;
+void mse_partition_config_default(mse_partition_config* cfg);                          /* the script's values, seed 0 */
+mse_partitioner* mse_partition_new(size_t n_shards, size_t d, const mse_partition_config* cfg);   /* cfg may be NULL: the defaults */
+void mse_partition_free(mse_partitioner* p);
+/* The sample (kmeans.py:9): n host rows [n][d] f16, or rows ids[0 .. n) of a resident base gathered on the device.  Resets the annealing. */
+int mse_partition_set_sample_f16(mse_partitioner* p, const uint16_t* rows, size_t n);
+int mse_partition_set_sample_base(mse_partitioner* p, const mse_base* b, const uint32_t* ids, size_t n);
+/* iters more iterations of kmeans.py:102-125 (the first call runs iteration 0 before them); returns early once stopped.  Afterwards the
+ * result of :127 and :153 is ready, and the assignment's centroids are that f16 result widened. */
+int mse_partition_anneal(mse_partitioner* p, size_t iters);
+int mse_partition_state(mse_partitioner* p, mse_partition_status* out);
+/* Entry j of the trace belongs to iteration j + 1: F[j] = F_new, code[j] = 0 rejected, 1 accepted, 2 rejected and rerolled. */
+int mse_partition_trace(mse_partitioner* p, size_t first, size_t n, uint64_t* F, uint8_t* code);
+/* [n_shards][d] each, any may be NULL: the raw centroids, their normalisation (:127), its f16 rounding (RNE: the bytes of centroids.bin). */
+int mse_partition_centroids(mse_partitioner* p, float* raw, float* normalised, uint16_t* f16);
+/* The assignment's centroids [n_shards][d] f32, used as given: for the reference's result pass the f16 file widened (dump_processor.rs:150-159). */
+int mse_partition_set_centroids(mse_partitioner* p, const float* centroids);
+/* The two forms of the score pass over the sample against centroids [n_shards][d] given by the caller (they replace nothing in the handle):
+ * counting (kmeans.py:82-90) -- sizes [2][n_shards] and, optionally, every row's (best, second) as top2 [n][2] -- and scores out,
+ * scores [n][n_shards] f64 (dump_processor.rs:442). */
+int mse_partition_count(mse_partitioner* p, const float* centroids, uint64_t* sizes, uint8_t* top2);
+int mse_partition_scores(mse_partitioner* p, const float* centroids, double* scores);
+/* src/dump_processor.rs:438-461 with --balance-fudge `fudge` (default 0.2, :64): for each row in order and each shard s,
+ * key_s = -scale_dot_result_f64(score(x, c_s) - fudge ((double)count_s / (double)bal)); the row goes to the two smallest keys; both
+ * counts and bal (which starts at 1) are incremented.  ONE DEVIATION: equal keys go to the lowest shard index (the reference's order then
+ * depends on the history of its sort).  Rows are appended to the assignment; counts and bal carry on across calls, so a stream of calls
+ * equals one call.  Rows are n host rows, or rows first .. first + n of a resident base.  An error before centroids exist. */
+int mse_partition_assign_f16(mse_partitioner* p, const uint16_t* rows, size_t n, double fudge);
+int mse_partition_assign_base(mse_partitioner* p, const mse_base* b, size_t first, size_t n, double fudge);
+int mse_partition_assign_reset(mse_partitioner* p);                                    /* forget the assignment, counts and bal */
+int mse_partition_assignment(mse_partitioner* p, size_t first, size_t n, uint8_t* out);   /* out [n][2]: first choice, second choice */
+int mse_partition_counts(mse_partitioner* p, uint64_t* counts, uint64_t* n_assigned);  /* counts [n_shards]; either may be NULL */
+/* The assigned rows that belong to shard s, as a filter over rows 0 .. n_assigned, built on the device (mse_filter_from_bits_dev).
+ * mse_filter_read_ids gives the shard's member list, ascending: the order dump_processor.rs:452-455 appends them to the shard file. */
+mse_filter* mse_partition_shard_filter(mse_partitioner* p, size_t s);
+/* HIP-event milliseconds of the last iteration of the last anneal call: candidate + normalisation, counting pass, decision. */
+int mse_partition_timing(mse_partitioner* p, float ms[3]);
+/* mse_medioid (diskann/src/lib.rs:52-68) over rows[ids] in list order; *id_out = the POSITION in the list (ids may repeat). */
+int mse_medioid_ids(const mse_base* b, const uint32_t* ids, size_t n_ids, uint32_t* id_out);
+/* test hooks: z(key) (d floats); the normalisation of n_rows rows of d floats (f16_out may be NULL); rows per scores-out pass (65536). */
+int mse_debug_partition_noise(uint32_t seed, uint64_t key, size_t d, float* out);
+int mse_debug_partition_normalise(const float* c, size_t n_rows, size_t d, float* out, uint16_t* f16_out);
+int mse_debug_partition_chunk_rows(mse_partitioner* p, size_t rows);
+
 /* PQ codes (+ optional descriptor bytes) resident in HBM: the mmap'd index.pq-codes.bin /
  * index.descriptor-codes.bin of src/query_disk_index.rs:686-709. */
 typedef struct mse_codes mse_codes;

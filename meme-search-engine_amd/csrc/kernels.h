@@ -183,6 +183,45 @@ int launch_cross_matrix(const long long* sigma, const int* E, const float* centr
 int launch_transpose_f32(const float* in, int d, float* out, hipStream_t stream);
 int launch_gather_rows_f16(const uint16_t* base, const uint32_t* ids, size_t n, int d, uint16_t* out, hipStream_t stream);
 
+// ---- partition.hip: the shard partition (include/mse.h mse_partitioner) ----------------------------------------------
+// One pass rows x centroids: score(x, c) = the k-ascending f64 chain over exact products.  Row r < n is rows[ids ? ids[r] : r].  Whatever of
+// sizes ([2][S], added to; rank 0 = best centroid of a row, rank 1 = second; f64 score descending, lowest index on ties), top2 ([n][2]) and
+// scores ([n][S]) is not null is written.  stopped (optional): a non-zero word makes the launch a no-op
+struct PartitionScoreArgs {
+    const uint16_t* rows = nullptr; const uint32_t* ids = nullptr; size_t n = 0; int d = 0, S = 0;
+    const float* cen = nullptr;
+    unsigned long long* sizes = nullptr; uint8_t* top2 = nullptr; double* scores = nullptr;
+    const uint32_t* stopped = nullptr;
+};
+int launch_partition_score(const PartitionScoreArgs& a, hipStream_t stream);
+// the annealing state on the device: mse_partition_status (include/mse.h) and, after it, which of the two centroid buffers is current
+struct PartitionDevState {
+    unsigned long long t, last, li;
+    float T; uint32_t stopped;
+    uint32_t cur, pad;
+};
+struct PartitionAnnealArgs {
+    PartitionDevState* st; float* c[2]; float* nrm;        // raw centroids (two buffers [S][d]), the normalised candidate
+    unsigned long long* sizes;                             // [2][S]: read by the decision, zeroed by it for the next count
+    unsigned long long* trace_F; uint8_t* trace_code; size_t trace_cap;   // entry t - 1 belongs to iteration t >= 1
+    int S, d; size_t n;
+    uint32_t seed, reroll_after;
+    float accept_decay, reject_decay, reroll_heat, cap;
+    unsigned long long stop_num, stop_den;                 // stop when last * stop_den < n * stop_num
+};
+// candidate of iteration st->t into c[cur ^ 1] (t = 0: the initial noise; else c[cur] + z T) and its normalisation into nrm
+int launch_partition_candidate(const PartitionAnnealArgs& a, hipStream_t stream);
+// the decision of iteration st->t from sizes (include/mse.h); the rerolled rows are rewritten by the same launch
+int launch_partition_decide(const PartitionAnnealArgs& a, hipStream_t stream);
+// out = the rows of c normalised; f16_out (RNE of out) and wide_out (f16_out widened) may be null
+int launch_partition_normalise(const float* c, int S, int d, float* out, uint16_t* f16_out, float* wide_out, hipStream_t stream);
+int launch_partition_noise(uint32_t seed, uint64_t key, int d, float* out, hipStream_t stream);   // z(key), d floats
+// dump_processor.rs:438-461 over `rows` rows of scores [rows][S]: one wave, lane = shard; counts [S] and *bal carry on from call to call
+int launch_partition_walk(const double* scores, size_t rows, int S, double fudge, unsigned long long* counts, unsigned long long* bal,
+                          uint8_t* assignment, hipStream_t stream);
+// bit r of bits = row r of assignment [n][2] names shard s; bits holds whole 64-row words
+int launch_partition_shard_bits(const uint8_t* assignment, size_t n, int s, uint32_t* bits, hipStream_t stream);
+
 // ---- disk_search.hip: the runtime de-duplication of the request path for a batch, on the device ------------------------------------
 // per query q: similarity bits over its visited records (vis_ids [nq][cap], n_visited[q] of them, visit order), greedy keep-first
 // filter; a dropped record becomes (ID_NONE, INT64_MIN) in place.  bits: dedup_batch_scratch_bytes(nq, cap) bytes of scratch.

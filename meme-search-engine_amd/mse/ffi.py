@@ -152,6 +152,29 @@ SIGNATURES = {
     "mse_debug_accumulate_by_code": (C.c_int, [f32p, sz, sz, u8p, sz, i64p, C.POINTER(C.c_int)]),
     "mse_debug_residual_gemm": (C.c_int, [f32p, u8p, f32p, f32p, sz, sz, sz, sz, f32p, f32p]),
     "mse_debug_pq_trainer_chunk_rows": (C.c_int, [vp, sz]),
+    "mse_partition_config_default": (None, [vp]),
+    "mse_partition_new": (vp, [sz, sz, vp]),
+    "mse_partition_free": (None, [vp]),
+    "mse_partition_set_sample_f16": (C.c_int, [vp, u16p, sz]),
+    "mse_partition_set_sample_base": (C.c_int, [vp, vp, u32p, sz]),
+    "mse_partition_anneal": (C.c_int, [vp, sz]),
+    "mse_partition_state": (C.c_int, [vp, vp]),
+    "mse_partition_trace": (C.c_int, [vp, sz, sz, C.POINTER(C.c_uint64), u8p]),
+    "mse_partition_centroids": (C.c_int, [vp, f32p, f32p, u16p]),
+    "mse_partition_set_centroids": (C.c_int, [vp, f32p]),
+    "mse_partition_count": (C.c_int, [vp, f32p, C.POINTER(C.c_uint64), u8p]),
+    "mse_partition_scores": (C.c_int, [vp, f32p, C.POINTER(C.c_double)]),
+    "mse_partition_assign_f16": (C.c_int, [vp, u16p, sz, C.c_double]),
+    "mse_partition_assign_base": (C.c_int, [vp, vp, sz, sz, C.c_double]),
+    "mse_partition_assign_reset": (C.c_int, [vp]),
+    "mse_partition_assignment": (C.c_int, [vp, sz, sz, u8p]),
+    "mse_partition_counts": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "mse_partition_shard_filter": (vp, [vp, sz]),
+    "mse_partition_timing": (C.c_int, [vp, f32p]),
+    "mse_medioid_ids": (C.c_int, [vp, u32p, sz, u32p]),
+    "mse_debug_partition_noise": (C.c_int, [C.c_uint32, C.c_uint64, sz, f32p]),
+    "mse_debug_partition_normalise": (C.c_int, [f32p, sz, sz, f32p, u16p]),
+    "mse_debug_partition_chunk_rows": (C.c_int, [vp, sz]),
     "mse_codes_from_host": (vp, [u8p, sz, sz, u8p, sz]),
     "mse_codes_free": (None, [vp]),
     "mse_codes_quantize_base": (vp, [vp, vp, u8p, sz]),
@@ -344,6 +367,18 @@ SIGNATURES = {
     "mse_siglip_text_output_device": (vp, [vp, C.c_int]),
     "mse_siglip_text_stream": (vp, [vp]),
 }
+
+
+class PartitionConfig(C.Structure):
+    """mse_partition_config (include/mse.h)"""
+    _fields_ = [("temperature0", C.c_float), ("accept_decay", C.c_float), ("reject_decay", C.c_float), ("reroll_heat", C.c_float),
+                ("temperature_cap", C.c_float), ("reroll_after", C.c_uint32), ("seed", C.c_uint32), ("stop_fraction", C.c_double)]
+
+
+class PartitionState(C.Structure):
+    """mse_partition_status (include/mse.h)"""
+    _fields_ = [("t", C.c_uint64), ("last_fitness", C.c_uint64), ("last_improvement", C.c_uint64), ("temperature", C.c_float),
+                ("stopped", C.c_uint32)]
 
 
 class SiglipTextConfig(C.Structure):
