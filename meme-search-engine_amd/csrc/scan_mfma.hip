@@ -76,6 +76,8 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 constexpr int KB = 64;            // contraction elements per K block
 constexpr int W = 8;              // waves per workgroup
 constexpr int TILE_ROWS = 32 * W;
+constexpr int TAU_SLOTS = 384;    // floats of LDS for the thresholds of the 320-query tile-subset kernel: lane (i, g) of query half qh
+                                  // reads slots qh * 160 + (g + 4 j) * 16 + i, j = 0 .. 2 (at most 351)
 
 // packed[kb][q][slot ^ ((q>>1)&7)] = 16-byte slot `slot` of K block kb of query q   (bn queries per tile)
 // Query rows at or past n_rows (counted over all passes of the launch) are the padding of the last pass: they are packed as zeros, so
@@ -342,12 +344,33 @@ __global__ __launch_bounds__(W * 64) void scan_mfma_kernel(const uint16_t* __res
 // with everything due inside one iteration, what is issued late is waited for.
 // Code object: register and scratch figures at launch_scan_mfma's 320-query branch.  The masked form (filtered search) spills two
 // registers with this order and keeps the every-other-group one.
+//
+// The turn-over between two row tiles of the search kernel (BN = 320, GR = 64: TURN; plain, masked and tile-subset form).  Between
+// the last barrier of a tile and the first K block of the next all eight waves are in the same phase and no MFMA issues; the cycle
+// stamps (PROF = 1, MSE_SCAN_ABL=33, profiles/scan_turnover_prof.txt) put that stretch at 8.3 % (dense) and 9.1 % (thresholded) of a
+// tile's cycles with the epilogue this one replaced (a balanced fmaxf tree per column tile, two dependent ds_bpermute round trips per
+// column tile, ten gated stores or append blocks, thresholds re-loaded from global memory, next-tile row pointers by a 64-bit multiply
+// and a clamp per lane and piece, accumulators zeroed twice).  Now:
+//   - a lane's maximum over its 16 rows of a column tile is one fmaxf chain (v_max3_f32);
+//   - the maximum over the four 16-lane rows g is formed in registers and TRANSPOSED: v_permlane16_swap on the pairs of column
+//     tiles (2 j, 2 j + 1) + one max: ten registers -> five; v_permlane32_swap on pairs of those + one max: five -> three.  No LDS,
+//     no waits.  Afterwards lane (i, g) holds in register j the finished maximum of column i of column tile 4 j + g of its query half
+//     (j = 0 .. 2; j = 2: g < 2 only; rows 2, 3 hold copies there and stay silent);
+//   - dense: three stores per tile, each 16-lane row one whole 64-byte segment; thresholded: three compare-and-append blocks with
+//     all 64 lanes eligible, thresholds read from a copy in LDS made once per workgroup (TAU_SLOTS).  The lists hold the same
+//     (group, maximum) pairs and the arrays the same values as before; only who writes them changed;
+//   - the next tile's row pointers are this tile's plus a distance the scalar unit works out, unless one of the two tiles is ragged;
+//   - the K loop is entered without a test, so the accumulators are zeroed once.  (Not taken: the first k step on a constant-zero C
+//     operand.  It needs a second copy of the first two K blocks, and hipcc spills 32 to 36 registers in that copy.)
 typedef float float16v __attribute__((ext_vector_type(16)));
 
 #ifdef MSE_DEV_KERNELS
 // developer profile of the 2-D kernel (PROF = 1): shader cycles a wave spends [0] issuing a K block (barrier release -> closing wait),
-// [1] in the closing vmcnt wait, [2] at the barrier; [3] = K blocks counted.  s_memtime stamps sit where lgkmcnt is drained anyway.
-__device__ unsigned long long g_scan_prof[4];
+// [1] in the closing vmcnt wait, [2] at the barrier; [3] = K blocks counted; [4] in the turn-over between the K loops of two row tiles
+// (a tile's prologue, up to its first K block, and its epilogue, from its last closing barrier on), [5] = tiles counted.  s_memtime
+// stamps sit where lgkmcnt is drained anyway.  MSE_SCAN_2D=161: the 256-query kernel; MSE_SCAN_ABL=33: the 320-query search kernel
+// (64 rows per maximum), plain and tile-subset form.
+__device__ unsigned long long g_scan_prof[6];
 __device__ __forceinline__ uint32_t memtime() { return (uint32_t)__builtin_amdgcn_s_memtime(); }   // deltas fit 32 bits
 #endif
 
@@ -365,7 +388,8 @@ __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __r
                                                              Mask... mask) {
     constexpr bool SPF = is_tile_subset<Mask...>::value;
     constexpr bool MASKED = sizeof...(Mask) != 0 && !SPF;
-    static_assert(sizeof...(Mask) == 0 || (MF == 16 && PROF == 0), "the masked form is the product kernel's");
+    static_assert(sizeof...(Mask) == 0 || (MF == 16 && (PROF == 0 || (PROF == 1 && is_tile_subset<Mask...>::value))),
+                  "the masked form is the product kernel's");
     static_assert(!SPF || (BN == 320 && GR == 64), "a tile subset: the 320-query search pass only");
     static_assert(BN == 256 || (BN == 320 && MF == 16 && S == 2), "320 queries: 16x16x32 tiles on the two-stage ring only");
     static_assert(GR == 32 || (GR == 64 && MF == 16), "rows per written maximum: 32, or the wave's 64");
@@ -376,10 +400,11 @@ __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __r
                                              // PROF = 5: rows first, one piece in front of every other MFMA group as in the S = 3 form
     constexpr int CLOSE = S == 2 ? 0 : 4;    // DMAs that may still fly at the closing barrier
     constexpr int RG_BYTES = 64 * 128;       // one K block of a row group
+    constexpr bool TURN = BN == 320 && GR == 64;   // the search kernel's short turn-over between two row tiles (header comment)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
-    // (the tile-subset form has no register to spare for its epilogue's addressing: it keeps the wave index in a scalar)
-    const int lane = tid & 63, wave = is_tile_subset<Mask...>::value ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
+    // (the search kernel has no register to spare for its epilogue's addressing: it keeps the wave index in a scalar)
+    const int lane = tid & 63, wave = TURN ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
     const int rg = wave >> 1, qh = wave & 1;
     const int nkb = d / KB;
     const size_t row_bytes = (size_t)d * 2;
@@ -418,6 +443,13 @@ __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __r
 #pragma unroll
             for (int u = 0; u < 4; u++) dma16(rp[u] + (size_t)(j % nkb) * 128, xbase + j * RG_BYTES + (qh * 4 + u) * 1024);
     }
+    // tile-subset form, thresholded: the pass's thresholds, once per workgroup, behind the query tiles and the row rings (TAU_SLOTS
+    // floats, launch_scan_mfma_tiles sizes the LDS); past the BN columns +inf, which no maximum exceeds
+    float* const tau_lds = reinterpret_cast<float*>(smem + 2 * QT_BYTES + 4 * S * RG_BYTES);
+    if constexpr (SPF) {
+        if (sp.tau && tid < TAU_SLOTS) tau_lds[tid] = tid < BN ? sp.tau[tid] : __builtin_inff();
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // written before the barrier below lets anyone read it
+    }
     vm_wait<0>();
     __builtin_amdgcn_s_barrier();
 
@@ -433,7 +465,7 @@ __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __r
 
     int buf = 0;
 #ifdef MSE_DEV_KERNELS
-    uint32_t pt_issue = 0, pt_wait = 0, pt_bar = 0, pt_n = 0, pt_last = 0;
+    uint32_t pt_issue = 0, pt_wait = 0, pt_bar = 0, pt_n = 0, pt_last = 0, pt_turn = 0, pt_tiles = 0;
     if constexpr (PROF == 1) pt_last = memtime();
 #endif
     while (true) {
@@ -448,10 +480,33 @@ __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __r
         const size_t next_vt = vt + gridDim.x;
         const size_t next_tile = tile_of(next_vt);
         const bool has_next_tile = next_vt < n_vt;
+        // TURN: both tiles whole (a uniform test; only the base's last tile can be ragged): the next tile's rows lie a wave-uniform
+        // distance from this tile's, which the scalar unit works out -- no 64-bit multiply and no row clamp per lane and piece
+        if (TURN && has_next_tile && (tile + 1) * TILE_ROWS <= n_rows && (next_tile + 1) * TILE_ROWS <= n_rows) {
+            const size_t ahead = (next_tile - tile) * TILE_ROWS * row_bytes;
 #pragma unroll
-        for (int u = 0; u < 4; u++) rn[u] = has_next_tile ? src_ptr(next_tile, u) : rp[u];
+            for (int u = 0; u < 4; u++) rn[u] = rp[u] + ahead;
+        } else {
+#pragma unroll
+            for (int u = 0; u < 4; u++) rn[u] = has_next_tile ? src_ptr(next_tile, u) : rp[u];
+        }
 
-        for (int kb0 = 0; kb0 < nkb; kb0 += S) {
+#ifdef MSE_DEV_KERNELS
+        if constexpr (PROF == 1) {   // the prologue ends here: charged to the turn-over, not to the first K block
+            // (the zeroed accumulators are made to exist here: left alone, hipcc zeroes them behind the stamp)
+#pragma unroll
+            for (int rt = 0; rt < NRT; rt++)
+#pragma unroll
+                for (int ct = 0; ct < NCTW; ct++) asm volatile("" : "+v"(acc[rt][ct]));
+            __builtin_amdgcn_sched_barrier(0);
+            const uint32_t t = memtime();
+            pt_turn += t - pt_last; pt_last = t;
+            __builtin_amdgcn_sched_barrier(0);
+        }
+#endif
+        // TURN: the loop is entered without a test (nkb >= S always: the launchers want a positive multiple).  With the test hipcc
+        // zeroes the 160 accumulators twice per tile, once for the path around the loop and once for the loop
+        for (int kb0 = 0; kb0 < nkb || (TURN && kb0 == 0); kb0 += S) {
 #pragma unroll
             for (int j = 0; j < S; j++) {
                 const int kb = kb0 + j;
@@ -562,50 +617,70 @@ __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __r
                 if constexpr (MASKED) return (allowed >> (4 * rt + r)) & 1u ? acc[rt][ct][r] : MASKED_OUT;
                 else return acc[rt][ct][r];
             };
-            // tile-subset form, thresholded: this lane's thresholds, columns (g + 4 j) * 16 + i of the wave's half (1280 B per pass: cache hits)
-            float tq[3] = {0.0f, 0.0f, 0.0f};
+            static_assert(NCTW == 10, "the transposed reduction below is laid out for the ten column tiles of the 320-query kernel");
             uint32_t cbase = (uint32_t)(qh * HALF + i);   // this lane's column of column tile 0
-            if constexpr (SPF) {
-                // opaque: everything addressed from it is worked out here, in the epilogue -- hoisted out of the tile loop, ten list
-                // offsets per lane would have to live through the main loop, which has no register to spare
-                asm volatile("" : "+v"(cbase));
-                if (sp.tau) {
-#pragma unroll
-                    for (int j = 0; j < 3; j++) tq[j] = g + 4 * j < NCTW ? sp.tau[cbase + (g + 4 * j) * MF] : __builtin_inff();
-                }
-            }
+            // opaque: everything addressed from it is worked out here, in the epilogue -- hoisted out of the tile loop, the list and
+            // array offsets of a lane would have to live through the main loop, which has no register to spare
+            asm volatile("" : "+v"(cbase));
+            // this lane's maximum over its 16 rows of each column tile: one chain per tile, which hipcc folds into v_max3_f32 (the
+            // balanced tree of fmaxf it replaced cost a canonicalising v_max per accumulator on top of its eleven)
+            float m[NCTW];
 #pragma unroll
             for (int ct = 0; ct < NCTW; ct++) {
-                float m = fmaxf(fmaxf(av(0, ct, 0), av(0, ct, 1)), fmaxf(av(0, ct, 2), av(0, ct, 3)));
+                float x = av(0, ct, 0);
 #pragma unroll
-                for (int rt = 1; rt < 4; rt++)
-                    m = fmaxf(m, fmaxf(fmaxf(av(rt, ct, 0), av(rt, ct, 1)), fmaxf(av(rt, ct, 2), av(rt, ct, 3))));
-                m = fmaxf(m, __shfl_xor(m, 16));
-                m = fmaxf(m, __shfl_xor(m, 32));
+                for (int e = 1; e + 1 < 16; e += 2) x = fmaxf(fmaxf(x, av(e >> 2, ct, e & 3)), av((e + 1) >> 2, ct, (e + 1) & 3));
+                m[ct] = fmaxf(x, av(3, ct, 3));
+            }
+            // Across the four 16-lane rows g, in registers and transposed.  v_permlane16_swap a, b exchanges rows 1, 3 of a with rows
+            // 0, 2 of b, so max(a', b') holds in rows 0, 2 a's maximum over rows {0, 1}, {2, 3} and in rows 1, 3 b's: ten registers
+            // become five.  v_permlane32_swap a, b exchanges rows 2, 3 of a with rows 0, 1 of b, so max(a', b') holds in rows 0, 1 the
+            // finished maxima of a's two column tiles and in rows 2, 3 those of b's: five become three (the fifth pairs with itself).
+            // Afterwards lane (i, g) holds in q[j] the maximum over the wave's 64 rows of column i of column tile 4 j + g (q[2]: g < 2).
+            auto swap_max = [](float a, float b, auto half) {
+                uint32_t ua = __builtin_bit_cast(uint32_t, a), ub = __builtin_bit_cast(uint32_t, b);
+                uint32_t r0, r1;
+                if constexpr (decltype(half)::value) {
+                    const auto r = __builtin_amdgcn_permlane32_swap(ua, ub, false, false);
+                    r0 = r[0]; r1 = r[1];
+                } else {
+                    const auto r = __builtin_amdgcn_permlane16_swap(ua, ub, false, false);
+                    r0 = r[0]; r1 = r[1];
+                }
+                return fmaxf(__builtin_bit_cast(float, r0), __builtin_bit_cast(float, r1));
+            };
+            float p[5], q[3];
+#pragma unroll
+            for (int j = 0; j < 5; j++) p[j] = swap_max(m[2 * j], m[2 * j + 1], std::false_type{});
+            q[0] = swap_max(p[0], p[1], std::true_type{});
+            q[1] = swap_max(p[2], p[3], std::true_type{});
+            q[2] = swap_max(p[4], p[4], std::true_type{});
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                const uint32_t col = cbase + (4 * j + g) * MF;   // the column q[j] belongs to
+                const bool mine = (j < 2 || g < 2) && group < n_groups;
 #ifdef MSE_DEV_KERNELS
-                if constexpr (PROF == 6) { asm volatile("" ::"v"(m)); continue; }   // timing ablation: the maxima are formed and not stored
+                if constexpr (PROF == 6) { asm volatile("" ::"v"(q[j])); continue; }   // timing ablation: the maxima are formed and not stored
 #endif
                 if constexpr (SPF) {
                     if (sp.tau) {
-                        // thresholded: the few maxima above the column's threshold go to the column's list, nothing else is written.
-                        // Every lane of a column holds m: lane group ct & 3 speaks for column tile ct (its thresholds are in tq)
-                        const uint32_t col = cbase + ct * MF;
-                        if (g == (ct & 3) && group < n_groups && m > tq[ct >> 2]) {
+                        // thresholded: the few maxima above the column's threshold (read from the workgroup's copy in LDS) go to the
+                        // column's list, nothing else is written.  All 64 lanes speak, each for its own column tiles
+                        if (mine && q[j] > tau_lds[col]) {
                             uint32_t one;
                             asm volatile("v_mov_b32 %0, 1" : "=v"(one));   // made here, not kept in a register through the main loop
                             const uint32_t pos = atomicAdd(&sp.counts[col], one);
                             if (pos < sp.cap) {
                                 sp.ids[col * sp.cap + pos] = (uint32_t)group;
-                                sp.keys[col * sp.cap + pos] = m;
+                                sp.keys[col * sp.cap + pos] = q[j];
                             }
                         }
-                    } else if (g == 0 && group < n_groups) {
-                        gmax[(vt * 4 + rg) * (size_t)nq_pad + cbase + ct * MF] = m;   // the launch's own groups: a small dense array
+                    } else if (mine) {
+                        gmax[(vt * 4 + rg) * (size_t)nq_pad + col] = q[j];   // the launch's own groups: a small dense array
                     }
-                    __builtin_amdgcn_sched_barrier(0);   // one column tile at a time: the accumulators free their registers as they go
-                    continue;
+                } else if (mine) {
+                    gmax[group * (size_t)nq_pad + col] = q[j];   // four whole 64-byte segments per store, one per 16-lane row
                 }
-                if (g == 0 && group < n_groups) gmax[group * (size_t)nq_pad + qh * HALF + ct * MF + i] = m;
             }
         } else {
 #pragma unroll
@@ -630,14 +705,19 @@ __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __r
             }
         }
 
+#ifdef MSE_DEV_KERNELS
+        if constexpr (PROF == 1) {   // the epilogue is charged to the turn-over, not to the next K block
+            __builtin_amdgcn_sched_barrier(0);
+            const uint32_t t = memtime();
+            pt_turn += t - pt_last; pt_last = t; pt_tiles++;
+            __builtin_amdgcn_sched_barrier(0);
+        }
+#endif
         if (!has_next_tile) break;
         vt = next_vt;
         tile = next_tile;
 #pragma unroll
         for (int u = 0; u < 4; u++) rp[u] = rn[u];
-#ifdef MSE_DEV_KERNELS
-        if constexpr (PROF == 1) pt_last = memtime();   // the epilogue is not charged to the next K block
-#endif
     }
     vm_wait<0>();
 #ifdef MSE_DEV_KERNELS
@@ -645,6 +725,7 @@ __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __r
         if (lane == 0) {
             atomicAdd(&g_scan_prof[0], (unsigned long long)pt_issue); atomicAdd(&g_scan_prof[1], (unsigned long long)pt_wait);
             atomicAdd(&g_scan_prof[2], (unsigned long long)pt_bar); atomicAdd(&g_scan_prof[3], (unsigned long long)pt_n);
+            atomicAdd(&g_scan_prof[4], (unsigned long long)pt_turn); atomicAdd(&g_scan_prof[5], (unsigned long long)pt_tiles);
         }
     }
 #endif
@@ -871,8 +952,8 @@ size_t mfma_packed_bytes(int d) { return (size_t)(d / KB) * 320 * 128; }
 #endif
 int mfma_group_rows(int nq_pad) {
 #ifdef MSE_DEV_KERNELS
-    // MSE_SCAN_ABL=32 is the ablation of the 64-row form itself (no stores of group maxima) and keeps its groups
-    if (getenv("MSE_SCAN_2D") || (getenv("MSE_SCAN_ABL") && atoi(getenv("MSE_SCAN_ABL")) != 32)) return 32;
+    // MSE_SCAN_ABL=32 is the ablation of the 64-row form itself (no stores of group maxima), 33 its cycle profile: they keep its groups
+    if (getenv("MSE_SCAN_2D") || (getenv("MSE_SCAN_ABL") && atoi(getenv("MSE_SCAN_ABL")) != 32 && atoi(getenv("MSE_SCAN_ABL")) != 33)) return 32;
 #endif
     return nq_pad == 320 ? MSE_GROUP_ROWS_320 : 32;
 }
@@ -942,6 +1023,9 @@ int launch_scan_mfma(const uint16_t* base, size_t n_rows, int d, const uint16_t*
     // of maxima costs the scan (profiles/sparse_maxima_ab.txt); the array keeps whatever an earlier, unablated step left in it
     if (!mask && group_rows == 64 && nq_pad == 320 && getenv("MSE_SCAN_ABL") && atoi(getenv("MSE_SCAN_ABL")) == 32)
         rc = launch_2d<2, 16, 6, 320, 64>(grid, stream, base, n_rows, d, packed, group_max, gs);
+    // MSE_SCAN_ABL=33: the same kernel with the cycle stamps of PROF = 1 (mse_dev_scan_prof); its results are the product kernel's
+    if (!mask && group_rows == 64 && nq_pad == 320 && getenv("MSE_SCAN_ABL") && atoi(getenv("MSE_SCAN_ABL")) == 33)
+        rc = launch_2d<2, 16, 1, 320, 64>(grid, stream, base, n_rows, d, packed, group_max, gs);
     if (rc != -2) {
         if (rc) return rc;
         if (ev_end) MSE_HIP_TRY(hipEventRecord(ev_end, stream));
@@ -956,10 +1040,11 @@ int launch_scan_mfma(const uint16_t* base, size_t n_rows, int d, const uint16_t*
         // Code object (hipcc --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage): unmasked 255 VGPRs, masked 256; both 0
         // spilled, 0 scratch, 2 waves per SIMD.  The 1-D <2,20> kernel this replaced is kept in the developer library (MSE_SCAN_2D=0).
         // group_rows = 64 (the search passes): one maximum per wave's 64 rows instead of two per 32 -- half the array of group maxima,
-        // half the 64-byte partial stores, half of what the tournament's first level reads back.  Code object of that form: 255 VGPRs
-        // unmasked and masked (the mask is applied by selection in the epilogue), 0 spilled, 0 scratch.
+        // half the 64-byte partial stores, half of what the tournament's first level reads back.  Code object of that form (with the
+        // short turn-over of the kernel's header comment): 248 VGPRs unmasked, 250 masked (the mask is applied by selection in the
+        // epilogue), 0 spilled, 0 scratch, 2 waves per SIMD.
         // The tile-subset form of that kernel (launch_scan_mfma_tiles, the sparse maxima of api.hip mfma_pass): scan_mfma2d_kernel<2, 16,
-        // 0, 320, 64, ScanSparse>: VGPRs: 252, ScratchSize [bytes/lane]: 0, Occupancy [waves/SIMD]: 2, SGPRs Spill: 0, VGPRs Spill: 0.
+        // 0, 320, 64, ScanSparse>: VGPRs: 250, ScratchSize [bytes/lane]: 0, Occupancy [waves/SIMD]: 2, SGPRs Spill: 0, VGPRs Spill: 0.
         if (group_rows == 64) rc = run([&](auto... m) { return launch_2d<2, 16, 0, 320, 64>(grid, stream, base, n_rows, d, packed, group_max, gs, m...); });
         else rc = run([&](auto... m) { return launch_2d<2, 16, 0, 320>(grid, stream, base, n_rows, d, packed, group_max, gs, m...); });
     } else if (nq_pad == 192) {
@@ -990,11 +1075,14 @@ int launch_scan_mfma_tiles(const uint16_t* base, size_t n_rows, int d, const uin
     if (pack) hipLaunchKernelGGL(pack_queries_kernel, dim3(64, 1), dim3(256), 0, stream, queries_dev, d, BN, nq_rows, packed);
     if (ev_begin) MSE_HIP_TRY(hipEventRecord(ev_begin, stream));
     if (sp.n_tiles) {
-        // Code object of this form (hipcc --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage): 252 VGPRs, 92 SGPRs, 0 spilled,
+        // Code object of this form (hipcc --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage): 250 VGPRs, 0 spilled,
         // 0 scratch, 2 waves per SIMD (with the wave index in a vector register and the list offsets hoisted out of the tile loop it
         // spilled 2 to 46 registers: see the kernel's epilogue)
         auto kernel = scan_mfma2d_kernel<2, 16, 0, BN, 64, ScanSparse>;
-        const size_t lds = 2 * (size_t)(BN * 128) + (size_t)4 * 2 * 8192;
+#ifdef MSE_DEV_KERNELS
+        if (getenv("MSE_SCAN_ABL") && atoi(getenv("MSE_SCAN_ABL")) == 33) kernel = scan_mfma2d_kernel<2, 16, 1, BN, 64, ScanSparse>;   // cycle stamps
+#endif
+        const size_t lds = 2 * (size_t)(BN * 128) + (size_t)4 * 2 * 8192 + TAU_SLOTS * sizeof(float);   // 144 KiB + the thresholds' 1.5 KiB
         const size_t n_tiles = (n_rows + TILE_ROWS - 1) / TILE_ROWS;
         const size_t grid = std::min<size_t>((size_t)n_cu, sp.n_tiles);
         MSE_DYN_LDS(kernel, lds);
@@ -1009,9 +1097,9 @@ int launch_scan_mfma_tiles(const uint16_t* base, size_t n_rows, int d, const uin
 }  // namespace mse
 
 #ifdef MSE_DEV_KERNELS
-// developer library only (not in include/mse.h): read and clear the counters of the profiled 2-D scan (MSE_SCAN_2D=161)
-extern "C" __attribute__((visibility("default"))) int mse_dev_scan_prof(unsigned long long out[4]) {
-    unsigned long long z[4] = {0, 0, 0, 0};
+// developer library only (not in include/mse.h): read and clear the counters of the profiled 2-D scan (MSE_SCAN_2D=161, MSE_SCAN_ABL=33)
+extern "C" __attribute__((visibility("default"))) int mse_dev_scan_prof(unsigned long long out[6]) {
+    unsigned long long z[6] = {0, 0, 0, 0, 0, 0};
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(mse::g_scan_prof), sizeof(z)) != hipSuccess) return -1;
     if (hipMemcpyToSymbol(HIP_SYMBOL(mse::g_scan_prof), z, sizeof(z)) != hipSuccess) return -1;
     return 0;

@@ -21,6 +21,8 @@ else:
     vl = mse.VectorList.generate(0x5EED0001, 0, n)
 qs = mse.VectorList.generate(0x5EED0002, 0, nq)
 s = mse.Searcher(vl)
+if os.environ.get("SPARSE"):   # the 320-query pass: thresholded group maxima off | auto | forced (Searcher.set_sparse_maxima)
+    s.set_sparse_maxima(os.environ["SPARSE"], int(os.environ.get("SPARSE_STRIDE", 0)))
 out_s = torch.empty((nq, 10), dtype=torch.int64, device="cuda")
 out_i = torch.empty((nq, 10), dtype=torch.int32, device="cuda")
 for _ in range(2):
@@ -42,15 +44,18 @@ if os.environ.get("CHECK") and os.environ.get("MSE_SCAN_2D") != "162":   # the v
     s.bruteforce_topk_dev(qs.device_ptr, 8, 10, chk_s.data_ptr(), chk_i.data_ptr(), mse.MODE_EXACT)
     torch.cuda.synchronize()
     print("answers equal the exact-order kernel:", bool(torch.equal(chk_s, out_s[:8]) and torch.equal(chk_i, out_i[:8])), s.last_stats())
-if os.environ.get("MSE_SCAN_2D") == "161":   # developer library: where a wave's cycles go (scan_mfma.hip, PROF)
+if os.environ.get("MSE_SCAN_2D") == "161" or os.environ.get("MSE_SCAN_ABL") == "33":   # developer library: where a wave's cycles go (scan_mfma.hip, PROF)
     import ctypes
     from mse import ffi
-    out = (ctypes.c_ulonglong * 4)()
+    out = (ctypes.c_ulonglong * 6)()
     ffi.lib().mse_dev_scan_prof(out)          # clear what the warm-up and the timed loop left
     s.bruteforce_topk_dev(qs.device_ptr, nq, 10, out_s.data_ptr(), out_i.data_ptr(), mse.MODE_MFMA)
     torch.cuda.synchronize()
     ffi.lib().mse_dev_scan_prof(out)
-    issue, wait, bar, nkb = [int(x) for x in out]
+    issue, wait, bar, nkb, turn, tiles = [int(x) for x in out]
     tot = issue + wait + bar
     print(f"profiled 2-D scan: per K block and wave {tot / nkb:.0f} cycles = issue {issue / nkb:.0f} + vmcnt wait {wait / nkb:.0f} + barrier {bar / nkb:.0f}"
           f" ({nkb} wave-K-blocks)")
+    if tiles:   # per row tile and wave: its K loop against the turn-over (epilogue + prologue) around it
+        print(f"per tile and wave: K loop {tot / tiles:.0f} cycles ({nkb / tiles:.1f} K blocks) + turn-over {turn / tiles:.0f} cycles = "
+              f"{turn / (tot + turn) * 100:.2f} % of the tile ({tiles} wave-tiles, sparse maxima {os.environ.get('SPARSE', 'auto')})")
