@@ -526,7 +526,8 @@ int mse_pq_adc(mse_pq* pq, const float* lut, const uint8_t* codes, size_t n, int
     if (n == 0) return 0;
     std::lock_guard<std::mutex> g(pq->mu);
     const size_t lut_bytes = pq->n_chunks * pq->n_centroids * 4;
-    if (pq->a.ensure(lut_bytes) || pq->b.ensure(n * pq->n_chunks) || pq->c.ensure(n * 8)) return -1;
+    // + 4 KiB of slack: the full-scan kernel fetches whole groups of 64 vectors (pq.hip)
+    if (pq->a.ensure(lut_bytes) || pq->b.ensure(n * pq->n_chunks + 4096) || pq->c.ensure(n * 8)) return -1;
     MSE_HIP_TRY(hipMemcpy(pq->a.p, lut, lut_bytes, hipMemcpyHostToDevice));
     MSE_HIP_TRY(hipMemcpy(pq->b.p, codes, n * pq->n_chunks, hipMemcpyHostToDevice));
     if (launch_pq_adc(pq->a.as<float>(), (int)pq->n_chunks, (int)pq->n_centroids, pq->b.as<uint8_t>(), n, nullptr, n,
