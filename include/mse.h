@@ -1332,6 +1332,49 @@ int mse_score_model_score_batch(mse_score_model* m, const float* input, size_t b
  * (meme-rater/compute_cdf.py: 255 quantiles, 255 = above the last). */
 int mse_descriptor_buckets(const float* cdfs, size_t n_desc, size_t cdf_len, const float* scores, size_t n, uint8_t* out);
 
+/* ---- Descriptors of a resident index: scores, CDFs and descriptor bytes without the rows or the activations crossing PCIe ----
+ * mse_scores: a device-resident score table, [n][channels] f32 plus an optional u32 timestamp channel (channel index `channels`).
+ *   mse_scores_from_base   ScoreModel::score_batch (src/score_model.rs:13-32) over decode_fp16_buffer of the base's rows (the widening is
+ *                          exact), fused on the f32 matrix cores: rows ids[i], i < n (any order, repeats allowed; each < mse_base_len), or
+ *                          first .. first + n when ids is NULL.  The model's d_emb must equal the base's d and it has at most 8 output
+ *                          channels.  The summation orders are fixed (csrc/describe.hip) and name neither the row's place in the call nor
+ *                          the call's size: a row's score bits are the same however it is asked for.  timestamps: host [n] or NULL, each in
+ *                          [0, 2^32) (the extra channel of meme-rater/compute_cdf.py:61-62).
+ *   mse_scores_from_f16    the same kernel over f16 rows the caller holds on the host, [n_rows][d] of ANY width d >= 1 (a base's is a
+ *                          multiple of 64), uploaded for the call to the current device: rows that are in no base yet.
+ *   mse_scores_from_host   the same table from scores the caller has already (on the current device).
+ * Errors leave the model, the base and the codes as they were. */
+typedef struct mse_scores mse_scores;
+mse_scores* mse_scores_from_base(mse_score_model* m, const mse_base* b, const uint32_t* ids_or_null, size_t first, size_t n,
+                                 const int64_t* timestamps_or_null);
+mse_scores* mse_scores_from_f16(mse_score_model* m, const uint16_t* rows_f16, size_t n_rows, size_t d, const uint32_t* ids_or_null, size_t first,
+                                size_t n, const int64_t* timestamps_or_null);
+mse_scores* mse_scores_from_host(const float* scores, size_t n, size_t n_channels, const int64_t* timestamps_or_null);
+void mse_scores_free(mse_scores* s);
+size_t mse_scores_len(const mse_scores* s);
+size_t mse_scores_channels(const mse_scores* s);       /* the f32 channels; the timestamps are one more */
+int mse_scores_has_timestamps(const mse_scores* s);
+int mse_scores_read(const mse_scores* s, float* out /* [n][channels] */, uint32_t* ts_out_or_null /* [n] */);
+/* out[i] = the value at rank ranks[i] (0-based, < n) of the channel's ascending order -- numpy.sort(x)[ranks], which is what
+ * numpy.quantile partitions for (meme-rater/compute_cdf.py:69) -- exactly, without sorting: a three-pass radix select (11 / 11 / 10 bits)
+ * over keys that order f32 with -0.0 == +0.0 (the timestamps: plain u32), in scratch of fixed size, integer atomics only.  Any number of
+ * ranks (512 per select).  A NaN among the keys fails the call with their count (the reference's partial_cmp().unwrap() panics,
+ * src/dump_processor.rs:483-491); +-inf are ordinary keys.  n < 2^32. */
+int mse_scores_order_statistics(const mse_scores* s, size_t channel, const uint64_t* ranks, size_t n_ranks, double* out);
+/* cdfs_out [channels (+ 1 with timestamps)][cdf_len] = numpy.quantile(channel, numpy.linspace(0, 1, cdf_len)) narrowed to f32
+ * (meme-rater/compute_cdf.py:64-71; IndexHeader.descriptor_cdfs): order statistics from the device, numpy's interpolation in float64
+ * on the host.  1 <= cdf_len <= 255. */
+int mse_scores_fit_cdfs(const mse_scores* s, size_t cdf_len, float* cdfs_out);
+/* desc[row][j] = mse_descriptor_buckets' byte of value_j in cdfs[j] for row = ids[i] (distinct; or first + i), i < mse_scores_len(s):
+ * value_j = scores[i][j], and (float)timestamp[i] for the last channel (src/dump_processor.rs:481-491), written in place into the codes'
+ * descriptor bytes; other rows keep theirs.  The codes must carry channels (+ 1 with timestamps) descriptor bytes per row.  With a
+ * graph, the write happens under the graph's exclusive lock, as mse_graph_insert_rows does. */
+int mse_codes_describe(mse_codes* c, mse_graph* graph_or_null, const mse_scores* s, const uint32_t* ids_or_null, size_t first, const float* cdfs,
+                       size_t cdf_len);
+/* measurement hook (scripts/describe_probe.py): HIP-event milliseconds of the score kernel of the last mse_scores_from_base and of the
+ * three counting passes of the last select made while the switch was on; then the switch is set (0 off, 1 on, 2 on and reset). */
+int mse_describe_timing(int enable, double* mlp_ms_or_null, double* select_pass_ms_or_null /* [3] */);
+
 /* ---- SigLIP ViT image tower: the in-process seam of clip_server.py, `fast_image_fns[batch](images NCHW
  * fp16 on device) -> [batch, 1152]` (clip_server.py:31,66-82,105-112), plus the normalisation and fp16
  * serialisation of do_inference / run_inference (clip_server.py:115,166).  Graph: aitemplate/model.py:13-123;

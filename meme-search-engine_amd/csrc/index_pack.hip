@@ -9,17 +9,10 @@
 // silu(x) = x / (1 + exp(-x)) with the device's expf, so oracle <-> HIP parity is to tolerance (1e-5 relative), not bit exact.  The bucket search is integer
 // logic and is bit exact: it replays core::slice::binary_search_by (Rust 1.7x: halve `size`, keep `base`).
 #include "../../include/mse.h"
-#include "runtime.h"
+#include "index_pack.h"
 #include <new>
 
 using namespace mse;
-
-struct mse_score_model {
-    float *up = nullptr, *bias = nullptr, *down = nullptr;  // device
-    size_t d_emb = 0, d_hidden = 0, out_ch = 0;
-    DevBuf x, h, y;
-    std::mutex mu;
-};
 
 namespace {
 
@@ -52,18 +45,7 @@ __global__ void descriptor_buckets_kernel(const float* __restrict__ cdfs, int n_
     if (idx >= n * (size_t)n_desc) return;
     const int j = (int)(idx % n_desc);
     const float* cdf = cdfs + (size_t)j * cdf_len;
-    const float s = scores[idx];
-    // core::slice::binary_search_by with cmp(x) = x.partial_cmp(&s)
-    size_t size = (size_t)cdf_len, base = 0;
-    if (size == 0) { out[idx] = 0; return; }
-    while (size > 1) {
-        const size_t half = size / 2, mid = base + half;
-        base = (cdf[mid] > s) ? base : mid;
-        size -= half;
-    }
-    const float c = cdf[base];
-    const size_t r = (c == s) ? base : base + (c < s ? 1 : 0);
-    out[idx] = (uint8_t)r;
+    out[idx] = descriptor_bucket(cdf, cdf_len, scores[idx]);   // index_pack.h
 }
 
 }  // namespace

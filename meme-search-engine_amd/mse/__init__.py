@@ -12,6 +12,6 @@ from .diskann import (NeighbourBuffer, IndexGraph, greedy_search, disk_greedy_se
                       set_coalescer, coalescer_stats, coalescer_groups, set_dedup, filtered_plan, DELETE_STATS, INSERT_STATS, COMPACT_STATS)
 from .index import ScalarQuantizerIndex  # noqa: F401
 from .common import decode_fp16_buffer, chunk_fp16_buffer, get_total_embedding  # noqa: F401
-from .index_pack import ScoreModel, descriptor_buckets  # noqa: F401
+from .index_pack import ScoreModel, RowScores, descriptor_buckets  # noqa: F401
 from .partition import ShardPartitioner, medioid_ids  # noqa: F401
 from .shard import ShardGroup, ShardFilter, ShardGroups, Comm, shard_range  # noqa: F401

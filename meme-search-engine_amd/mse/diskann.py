@@ -369,6 +369,11 @@ class DeviceGraph(_RowDeletes):
                                                           graph.adj.shape[1], _p(hu, C.c_uint8) if hu is not None else None),
                             "mse_graph_from_host")
 
+    def describe(self, codes: Codes, scores, cdfs, ids=None, first=0):
+        """Codes.describe on the live index's codes under this graph's exclusive lock (as insert_rows): request-path calls see the rows'
+        descriptor bytes wholly before or wholly after.  ids: the rows scores' entries belong to, e.g. the slots just inserted."""
+        codes.describe(scores, cdfs, ids, first, _graph=self._graph_handle())
+
     def close(self):
         if getattr(self, "_h", None):
             ffi.lib().mse_graph_free(self._h)

@@ -337,6 +337,18 @@ SIGNATURES = {
     "mse_score_model_output_channels": (sz, [vp]),
     "mse_score_model_score_batch": (C.c_int, [vp, f32p, sz, f32p]),
     "mse_descriptor_buckets": (C.c_int, [f32p, sz, sz, f32p, sz, u8p]),
+    "mse_scores_from_base": (vp, [vp, vp, u32p, sz, sz, i64p]),
+    "mse_scores_from_f16": (vp, [vp, u16p, sz, sz, u32p, sz, sz, i64p]),
+    "mse_scores_from_host": (vp, [f32p, sz, sz, i64p]),
+    "mse_scores_free": (None, [vp]),
+    "mse_scores_len": (sz, [vp]),
+    "mse_scores_channels": (sz, [vp]),
+    "mse_scores_has_timestamps": (C.c_int, [vp]),
+    "mse_scores_read": (C.c_int, [vp, f32p, u32p]),
+    "mse_scores_order_statistics": (C.c_int, [vp, sz, C.POINTER(C.c_uint64), sz, C.POINTER(C.c_double)]),
+    "mse_scores_fit_cdfs": (C.c_int, [vp, sz, f32p]),
+    "mse_codes_describe": (C.c_int, [vp, vp, vp, u32p, sz, f32p, sz]),
+    "mse_describe_timing": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "mse_siglip_create": (vp, [vp]),
     "mse_siglip_destroy": (None, [vp]),
     "mse_siglip_n_weights": (C.c_int, [vp]),

@@ -845,6 +845,31 @@ class Codes:
               "codes_read_rows")
         return (codes, desc) if descriptors else codes
 
+    def describe(self, scores, cdfs, ids=None, first=0, _graph=None):
+        """Write the descriptor bytes of scores' rows in place (mse_codes_describe; src/dump_processor.rs:481-491): entry i of `scores`
+        (a RowScores) describes row ids[i] (distinct integer ids, one per entry) or row first + i; byte j is the bucket of channel j in
+        cdfs[j] (float32 [n_desc, cdf_len], e.g. RowScores.fit_cdfs()), the timestamp channel last.  Other rows keep their bytes.  The
+        codes must carry one descriptor byte per channel.  On a live index use DeviceGraph.describe, which takes the graph's lock."""
+        c = np.ascontiguousarray(cdfs, np.float32)
+        if c.ndim != 2:
+            raise MseError("cdfs must be [n_desc, cdf_len]")
+        if c.shape[0] != self.n_desc or c.shape[0] != scores.n_desc:
+            raise MseError(f"describe: the codes carry {self.n_desc} descriptor bytes per row, the scores have {scores.n_desc} channels "
+                           f"and {c.shape[0]} CDFs were given")
+        ip = None
+        if ids is not None:
+            i = np.asarray(ids)
+            if i.size and not np.issubdtype(i.dtype, np.integer):
+                raise TypeError("ids must be an integer array")
+            i = i.reshape(-1)
+            if i.size != len(scores):
+                raise ValueError(f"ids must name one row per entry of the scores: {i.size} ids for {len(scores)} entries")
+            if i.size and (i.min() < 0 or i.max() > 0xFFFFFFFF):
+                raise ValueError("ids must be in 0 .. 2**32 - 1")
+            i = np.ascontiguousarray(i, np.uint32)
+            ip = _p(i, C.c_uint32)
+        check(ffi.lib().mse_codes_describe(self._h, _graph, scores._h, ip, int(first), _p(c, C.c_float), c.shape[1]), "codes_describe")
+
     def close(self):
         if self._h:
             ffi.lib().mse_codes_free(self._h)
