@@ -1144,6 +1144,64 @@ int mse_filter_kernel_timing(int enable, double* last_ms);
  *                      part on another device comes over by one peer copy of its words. */
 mse_filter* mse_filter_slice(const mse_filter* f, uint64_t first_row, size_t n_rows, int device);
 mse_filter* mse_filter_concat(const mse_filter* const* parts, const uint64_t* first_rows, size_t n_parts, size_t n_rows, int device);
+
+/* ---- near-duplicate join: exact pairs of a resident base, keep-first groups ------------------------------------------------------------
+ * The reference meets its near-duplicates twice.  At ingest, -D (src/dump_processor.rs:375-392) hashes a 64-bit binarisation of each
+ * embedding into a ring of the last 2^21 records ("distance thresholding is too costly to do over a long range so just do it badly").
+ * At query time the handler multiplies the visited vectors against themselves and retains a record only if no already retained one
+ * lies above DUPLICATES_THRESHOLD (src/query_disk_index.rs:99,513-527) -- mse_graph_set_dedup / mse_dedup_visited here.  The join below
+ * is the ingest half done exactly: the pairs are found by a Gram matrix on the matrix cores and confirmed in reference order.
+ *
+ * mse_join_self returns ALL pairs (lo, hi) of rows of the searcher's base with lo < hi, hi - lo <= window (window 0: no limit), both rows
+ * allowed by within_or_null when one is given, and fast_dot(row lo, row hi) >= threshold -- the reference-order i64 score, the number
+ * mse_bruteforce_scores_f16 returns with one of the rows as the query (fast_dot is symmetric; saturation and NaN as there).  The test is
+ * >=, as in mse_filter_from_scores; the handler's test is > on f32 sums, so a caller who wants strictness passes threshold + 1.  Each
+ * pair carries its exact score.  Canonical order: hi ascending, then lo ascending.  The list lives on the base's device and is
+ * immutable; its bytes do not depend on the run, the mode, the size of the internal candidate buffer or the calls made before on the
+ * same searcher.
+ * Modes (MSE_MODE_*): EXACT scores every pair of the schedule on the vector ALU in reference order.  MFMA runs 128 x 128 Gram tiles of
+ * the lower triangle that meet the window band on the f16 matrix cores (tiles whose rows `within` excludes altogether do no work), an
+ * accumulator nominates a pair when it is >= threshold - bound (bound: 2.8e-4 x the largest row norm squared plus the subnormal term,
+ * the brute-force certificate's allowance), and every nominated pair is re-scored in reference order; when no bound can be stated (a
+ * width that is no multiple of 64, a non-finite row) the exact path runs.  AUTO is MFMA.  A full candidate buffer makes the strip of
+ * tiles run again in windows of its nominations; the answer is the same.
+ * The call runs on the searcher's stream, uses the searcher's scratch (one call per searcher at a time) and blocks until the list is
+ * complete.  More than max_pairs pairs: an error that makes nothing; mse_join_stats then holds the true count in [3].
+ * Errors, in this order: a null searcher; a `within` longer than the base or made on another device (the messages of the filtered
+ * searches); an unknown mode.  A base of 0 rows gives an empty list.  A graph's base: pass mse_graph_live_filter(g, 0) as `within` --
+ * deleted slots hold stale rows -- and keep deletes, inserts and restores on that graph out while the call runs, as for any brute-force
+ * scan over a graph's base (the lock notes of mse_graph_delete_rows / mse_graph_insert_rows).
+ *   mse_pairs_rows / _count   rows of the base the list was made over | pairs
+ *   mse_pairs_read            pairs first .. first + n of the canonical order (any output may be null); past the count is an error
+ *   mse_join_stats            of the last mse_join_self on s: [0] tiles that did work, [1] pairs nominated, [2] pairs re-scored,
+ *                             [3] pairs kept (or the count that did not fit), [4] strip launches repeated for a full buffer,
+ *                             [5] rounds of the last keep-first resolution of a list made by s
+ *   mse_join_timing           measurement hook (scripts/near_duplicate_probe.py): out (or null) receives the HIP-event milliseconds of the
+ *                             last mse_join_self on s -- [0] tile launches, [1] re-score launches, [2] building the list in canonical
+ *                             order -- then the switch is set; while it is on the call waits once more per launch
+ *   mse_debug_join_candidate_capacity   test hook: nominated pairs one launch may store (0: the default, 2^20)
+ * Keep-first over the list (the handler's retain loop applied in row order to the whole base): row i is KEPT iff no kept row j < i forms
+ * a pair with it -- the lexicographically first maximal independent set of the pair graph; rep[i] = i for a kept row, the lowest kept
+ * earlier neighbour for a dropped one.  Rows `within` excluded are in no pair: kept and ungrouped.  Resolved on the device in rounds
+ * over integer state (dropped as soon as one earlier neighbour is kept, kept once all are dropped; a chain of m pairs takes about m
+ * rounds), once per list, on the null stream; the result is bit-reproducible.
+ *   mse_pairs_duplicates        the dropped rows as a fresh filter, ready for mse_graph_delete_rows
+ *   mse_pairs_groups            a fresh grouping: label rep[i] for every row of a group of two or more (the representative included),
+ *                               MSE_GROUP_NONE for every other row; every member scores >= threshold against its representative
+ *   mse_pairs_representatives   rep, mse_pairs_rows(p) entries, to the host
+ * Not covered: connected-component grouping, a join between two bases or of a query batch against the rows, the shard group. */
+typedef struct mse_pairs mse_pairs;
+mse_pairs* mse_join_self(mse_searcher* s, int64_t threshold, uint64_t window, const mse_filter* within_or_null, int mode, uint64_t max_pairs);
+void mse_pairs_free(mse_pairs* p);
+size_t mse_pairs_rows(const mse_pairs* p);
+size_t mse_pairs_count(const mse_pairs* p);
+int mse_pairs_read(const mse_pairs* p, size_t first, size_t n, uint32_t* lo, uint32_t* hi, int64_t* scores);
+int mse_join_stats(const mse_searcher* s, uint64_t out[6]);
+int mse_join_timing(mse_searcher* s, int enable, double out[3]);
+int mse_debug_join_candidate_capacity(mse_searcher* s, uint64_t n);
+mse_filter* mse_pairs_duplicates(const mse_pairs* p);
+mse_groups* mse_pairs_groups(const mse_pairs* p);
+int mse_pairs_representatives(const mse_pairs* p, uint32_t* rep);
 /* mse_shard_filter: one LOCAL filter per shard of a group, each on its shard's device -- what the filtered searches of the group take.
  *   mse_shard_group_filter             mse_filter_slice of `global` at each shard's first row and length.  A filter shorter than the group
  *                                      excludes the rows past it; one longer than max(first row + rows) over the shards is an error.

@@ -291,6 +291,8 @@ void mse_searcher_free(mse_searcher* s) {
     if (s->own_stream && s->stream) { (void)hipStreamSynchronize(s->stream); (void)hipStreamDestroy(s->stream); }
     if (s->ev0) (void)hipEventDestroy(s->ev0);
     if (s->ev1) (void)hipEventDestroy(s->ev1);
+    for (hipEvent_t e : s->join.ev)
+        if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : s->ev_pool) (void)hipEventDestroy(e);
     if (s->ev_wait) (void)hipEventDestroy(s->ev_wait);
     for (hipEvent_t e : s->grp_ev)

@@ -1209,11 +1209,28 @@ int check_graph(const mse_graph* g, hipStream_t st, const char* who) {
     return 0;
 }
 
-// Bound, in the fixed-point scale, on |MFMA f16 sum - fast_dot| for two base rows: 2.8e-4 * (largest row norm)^2, the
-// allowance the scan's certificate uses (DESIGN 3.1).  *eps_fix = 0 when no bound can be stated (the exact kernels run).
+// mfma_pair_bound under the build's limits on alpha: *eps_fix = 0 when no bound can be stated (the exact kernels run).
 int mfma_bound(const mse_base* b, const mse_build_config* cfg, hipStream_t st, long long* eps_fix) {
     *eps_fix = 0;
-    if (b->d % 64 || cfg->alpha <= 0 || cfg->alpha > (1 << 20) || cfg->query_alpha <= 0 || cfg->query_alpha > (1 << 20)) return 0;
+    if (cfg->alpha <= 0 || cfg->alpha > (1 << 20) || cfg->query_alpha <= 0 || cfg->query_alpha > (1 << 20)) return 0;
+    return mfma_pair_bound(b, st, eps_fix);
+}
+
+template <typename K> int set_lds(K kernel) {
+    MSE_DYN_LDS(kernel, 96 * 1024);
+    return 0;
+}
+
+}  // namespace
+
+// ---- robust_prune over candidate lists in HBM and the write-back of the new lists, for graph_delete.hip (kernels.h) ----------------
+namespace mse {
+
+// Bound, in the fixed-point scale, on |MFMA f16 sum - fast_dot| for two base rows: 2.8e-4 * (largest row norm)^2, the
+// allowance the scan's certificate uses (DESIGN 3.1).  *eps_fix = 0 when no bound can be stated (the exact kernels run).
+int mfma_pair_bound(const mse_base* b, hipStream_t st, long long* eps_fix) {
+    *eps_fix = 0;
+    if (b->d % 64) return 0;
     if (ensure_base_norm(b, st)) return -1;
     uint32_t bits[3] = {0, 0, 0};
     MSE_HIP_TRY(hipMemcpy(bits, b->norm_bits_dev, 12, hipMemcpyDeviceToHost));
@@ -1226,16 +1243,6 @@ int mfma_bound(const mse_base* b, const mse_build_config* cfg, hipStream_t st, l
     *eps_fix = (long long)ceil(bound * 4294967296.0) + 1;
     return 0;
 }
-
-template <typename K> int set_lds(K kernel) {
-    MSE_DYN_LDS(kernel, 96 * 1024);
-    return 0;
-}
-
-}  // namespace
-
-// ---- robust_prune over candidate lists in HBM and the write-back of the new lists, for graph_delete.hip (kernels.h) ----------------
-namespace mse {
 
 int prune_mfma_eps(const mse_base* b, const mse_build_config* cfg, hipStream_t st, long long* eps_fix) {
     *eps_fix = 0;

@@ -351,6 +351,45 @@ int launch_delete_finish(uint32_t* deg, uint8_t* has_url, uint32_t* deleted, con
 // restore: bit cleared in `deleted`, has_url = 1
 int launch_delete_restore(uint8_t* has_url, uint32_t* deleted, const uint32_t* ids, size_t n_ids, hipStream_t stream);
 
+// ---- join.hip: the near-duplicate self-join (include/mse.h mse_join_self) -------------------------------------------
+constexpr int JOIN_TILE = 128;   // rows per side of a Gram tile
+struct JoinPair { uint32_t lo, hi; int64_t score; };
+// One launch over a strip of the tile schedule: hi tiles h0 .. h0 + n_hi, tile t = (hi tile - h0) * span + x with lo tile = hi tile - x
+// (x < span; tiles outside the triangle or the window band do not exist).  tile_base == null: the strip's FIRST launch -- every tile writes
+// its nomination count to tile_count[t], reserves room at *cursor (zeroed by the caller) and stores its pairs if they end within cap;
+// *tiles_run += tiles that did work.  tile_base != null (the exclusive prefix of tile_count): a WINDOW launch -- the nominations numbered
+// win_lo .. win_lo + cap in tile order are stored at cand[number - win_lo]; tiles without one leave at once
+struct JoinStrip {
+    uint32_t h0 = 0, n_hi = 0, span = 0;
+    uint64_t window = 0;                                  // hi - lo <= window (0: no limit)
+    const uint32_t* within = nullptr; size_t within_words = 0;   // bitmap words of an mse_filter (null: every row)
+    uint32_t* tile_count = nullptr;
+    const unsigned long long* tile_base = nullptr;
+    unsigned long long win_lo = 0;
+    unsigned long long* cursor = nullptr;
+    unsigned long long* tiles_run = nullptr;
+    uint2* cand = nullptr; unsigned long long cap = 0;     // nominated (lo, hi) pairs
+};
+size_t join_tile_lds_bytes();
+// exact: every pair of the tile scored in reference order and nominated by score >= threshold; else the matrix-core tile, nominating by
+// accumulator * 2^32 >= thr_lo (the caller's threshold - bound, rounded down to a double); d % 64 == 0 there
+int launch_join_tiles(bool exact, const uint16_t* base, size_t n, int d, const JoinStrip& sp, int64_t threshold, double thr_lo, hipStream_t stream);
+int launch_join_scan_tiles(const uint32_t* counts, size_t n_tiles, unsigned long long* out, hipStream_t stream);
+// a lane quad per nominated pair: *kept += pairs with fast_dot >= threshold; those numbered below store_cap are appended to conf and counted
+// into row_count[hi]
+int launch_join_rescore(const uint16_t* base, int d, const uint2* cand, size_t m, int64_t threshold, unsigned long long* kept, JoinPair* conf,
+                        unsigned long long store_cap, uint32_t* row_count, int n_cu, hipStream_t stream);
+// conf (count pairs, any order; row_count as the re-score left it, consumed) -> offsets [n + 1] over hi, and lo / hi / scores in canonical
+// order: hi ascending, then lo ascending
+int launch_join_csr(const JoinPair* conf, size_t count, size_t n, uint32_t* row_count, unsigned long long* offsets, uint32_t* lo, uint32_t* hi,
+                    int64_t* scores, hipStream_t stream);
+// one round of the keep-first rule: state 0 undecided / 1 kept / 2 dropped, in -> out; *undecided += rows still open
+int launch_join_round(const unsigned long long* offsets, const uint32_t* lo, size_t n, const uint8_t* in, uint8_t* out, unsigned long long* undecided,
+                      hipStream_t stream);
+// rep, the dropped rows' bitmap (dup_words: whole 256-row tiles) and the group labels from the final state; has_member: n zeroed bytes
+int launch_join_finish(const unsigned long long* offsets, const uint32_t* lo, size_t n, const uint8_t* state, uint32_t* rep, uint8_t* has_member,
+                       uint32_t* dup_words, uint32_t* labels, hipStream_t stream);
+
 // ---- scan_mfma.hip ---------------------------------------------------------------------------
 // group_max[q_pad_index][g] layout: [n_groups][nq_pad] floats (group-major), nq_pad multiple of 32
 int launch_scan_mfma(const uint16_t* base, size_t n_rows, int d, const uint16_t* queries_dev, int nq_pad,

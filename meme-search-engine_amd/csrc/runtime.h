@@ -4,6 +4,7 @@
 #include "kernels.h"
 #include "dispatch.h"
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <vector>
 
@@ -120,8 +121,39 @@ struct QueryDst {
 };
 }  // namespace mse
 
+namespace mse {
+// the self-join's state on a searcher (join_api.hip): what mse_join_stats reads -- shared with the pair lists the searcher made, so that a
+// list's keep-first resolution can report its rounds after the call that made it -- the test hook's buffer size and the call scratch
+struct JoinStats { std::atomic<uint64_t> v[6]; JoinStats() { for (auto& x : v) x.store(0); } };
+struct JoinState {
+    std::shared_ptr<JoinStats> stats = std::make_shared<JoinStats>();
+    uint64_t cand_cap = 0;       // nominated pairs one launch may store; 0 = default
+    DevBuf cand, tiles, tile_base, counters, row_count;
+    // optional measurement (mse_join_timing, for scripts/near_duplicate_probe.py): HIP-event milliseconds of the last call's tile
+    // launches, re-score launches and list build; while it is on the call waits once more per launch
+    bool timing = false;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    double ms[3] = {0.0, 0.0, 0.0};
+};
+}  // namespace mse
+
+// result of mse_join_self (join.hip, join_api.hip; the list is immutable, the keep-first resolution is made on first use and kept)
+struct mse_pairs {
+    int device = 0;
+    size_t n_rows = 0, count = 0;
+    unsigned long long* offsets = nullptr;   // device [n_rows + 1]: the CSR over hi
+    uint32_t *lo = nullptr, *hi = nullptr;   // device [count], canonical order
+    int64_t* scores = nullptr;               // device [count]
+    std::shared_ptr<mse::JoinStats> stats;
+    std::mutex mu;                           // guards the resolution below
+    bool resolved = false;
+    uint64_t rounds = 0;
+    uint32_t *rep = nullptr, *labels = nullptr, *dup_words = nullptr;   // device [n_rows] | [n_rows] | whole 256-row tiles of bitmap
+};
+
 struct mse_searcher {
     const mse_base* base = nullptr;
+    mse::JoinState join;
     hipStream_t stream = nullptr;
     bool own_stream = false;
     int n_cu = 256;
@@ -270,6 +302,9 @@ using GroupedDense = std::function<int(const void*, size_t, const std::vector<ui
 int grouped_prefix_drive(mse_searcher* s, const void* q, size_t row_bytes, size_t nq, size_t k, const GroupedRound& round, const GroupedDense& dense);
 // largest row norm of the base (x 1.0001), computed once and kept on the device as float bits (b->norm_bits_dev)
 int ensure_base_norm(const mse_base* b, hipStream_t st);
+// Bound, in the fixed-point scale, on |MFMA f16 sum - fast_dot| for two rows of b (graph_build.hip; the certificate of DESIGN.md 3.2):
+// *eps_fix = 0 when none can be stated (a width that is no multiple of 64, a non-finite row)
+int mfma_pair_bound(const mse_base* b, hipStream_t st, long long* eps_fix);
 // error bound of the matrix-core products robust_prune may decide by (graph_build.hip): *eps_fix = 0 means exact dots only
 int prune_mfma_eps(const mse_base* b, const ::mse_build_config* cfg, hipStream_t st, long long* eps_fix);
 // the limits mse_build_graph sets on the searcher, the graph and the config (graph_build.hip); 0, or -1 with the error set

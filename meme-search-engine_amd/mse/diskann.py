@@ -164,6 +164,26 @@ class _RowDeletes:
         return RowFilter.from_handle(check_ptr(ffi.lib().mse_graph_live_filter(self._graph_handle(), int(bool(and_has_url))),
                                                "graph_live_filter"))
 
+    def near_duplicates(self, searcher: Searcher, threshold, **kw):
+        """Searcher.near_duplicates over the graph's rows within live_filter() (has_url is not consulted): deleted slots hold stale rows and
+        do not pair.  within=... narrows it further.  Like every brute-force scan over a graph's base it takes no part in the graph's
+        lock: the caller keeps delete_rows, insert_rows and restores on this graph out while it runs."""
+        if searcher is None or getattr(searcher, "_h", None) is None:
+            raise MseError("near_duplicates needs the searcher over the graph's rows")
+        live = self.live_filter(False)
+        within = kw.pop("within", None)
+        both = None
+        try:
+            if within is not None:
+                if not isinstance(within, RowFilter):
+                    raise TypeError("within must be a RowFilter")
+                both = live & within
+            return searcher.near_duplicates(threshold, within=both if both is not None else live, **kw)
+        finally:
+            live.close()
+            if both is not None:
+                both.close()
+
     def delete_rows(self, searcher: Searcher, ids_or_filter, config, batch=0):
         """Remove rows from the live graph and repair the lists that pointed at them, on the device (mse_graph_delete_rows).
         ids_or_filter: a RowFilter over the graph's rows whose SET bits name the rows to remove, a boolean mask with one entry per row, or

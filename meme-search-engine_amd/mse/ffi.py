@@ -204,6 +204,17 @@ SIGNATURES = {
     "mse_filter_kernel_timing": (C.c_int, [C.c_int, C.POINTER(C.c_double)]),
     "mse_filter_slice": (vp, [vp, C.c_uint64, sz, C.c_int]),
     "mse_filter_concat": (vp, [C.POINTER(vp), C.POINTER(C.c_uint64), sz, sz, C.c_int]),
+    "mse_join_self": (vp, [vp, C.c_int64, C.c_uint64, vp, C.c_int, C.c_uint64]),
+    "mse_pairs_free": (None, [vp]),
+    "mse_pairs_rows": (sz, [vp]),
+    "mse_pairs_count": (sz, [vp]),
+    "mse_pairs_read": (C.c_int, [vp, sz, sz, u32p, u32p, i64p]),
+    "mse_join_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+    "mse_join_timing": (C.c_int, [vp, C.c_int, C.POINTER(C.c_double)]),
+    "mse_debug_join_candidate_capacity": (C.c_int, [vp, C.c_uint64]),
+    "mse_pairs_duplicates": (vp, [vp]),
+    "mse_pairs_groups": (vp, [vp]),
+    "mse_pairs_representatives": (C.c_int, [vp, u32p]),
     "mse_shard_group_filter": (vp, [vp, vp]),
     "mse_shard_group_filter_from_local": (vp, [vp, C.POINTER(vp)]),
     "mse_shard_group_live_filter": (vp, [vp, C.c_int]),

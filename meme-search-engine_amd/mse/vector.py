@@ -344,6 +344,60 @@ class RowGroups:
             pass
 
 
+class RowPairs:
+    """Result of Searcher.near_duplicates (mse_pairs): every pair (lo, hi), lo < hi, of rows of a base whose reference-order i64 score
+    reaches the threshold, in canonical order (hi ascending, then lo ascending), each with its exact score.  The list lives on the device
+    and is immutable.  len() is the number of rows of the base; .count the pairs.  duplicates(), groups() and representatives() apply the
+    keep-first rule (a row is kept iff no kept earlier row forms a pair with it), resolved on the device once per list."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    def __len__(self):
+        return int(ffi.lib().mse_pairs_rows(self._h))
+
+    @property
+    def count(self):
+        return int(ffi.lib().mse_pairs_count(self._h))
+
+    def read(self, first=0, n=None):
+        """(lo uint32, hi uint32, scores int64): all pairs, or n of them from position `first` of the canonical order."""
+        n = self.count - int(first) if n is None else int(n)
+        if first < 0 or n < 0:
+            raise ValueError("first and n must not be negative")
+        lo, hi, sc = np.empty(n, np.uint32), np.empty(n, np.uint32), np.empty(n, np.int64)
+        check(ffi.lib().mse_pairs_read(self._h, int(first), n, _p(lo, C.c_uint32), _p(hi, C.c_uint32), _p(sc, C.c_int64)), "mse_pairs_read")
+        return lo, hi, sc
+
+    def duplicates(self):
+        """The dropped rows as a RowFilter, ready for delete_rows; its complement within the join's `within` is the deduplicated index."""
+        return RowFilter.from_handle(check_ptr(ffi.lib().mse_pairs_duplicates(self._h), "mse_pairs_duplicates"))
+
+    def groups(self):
+        """A RowGroups: every row of a group of two or more carries its representative's id (the representative included), every other
+        row GROUP_NONE."""
+        g = RowGroups.__new__(RowGroups)
+        g._h = check_ptr(ffi.lib().mse_pairs_groups(self._h), "mse_pairs_groups")
+        return g
+
+    def representatives(self):
+        """rep (uint32, one per row): the row itself when it is kept, its lowest kept earlier neighbour when it is dropped."""
+        out = np.empty(len(self), np.uint32)
+        check(ffi.lib().mse_pairs_representatives(self._h, _p(out, C.c_uint32)), "mse_pairs_representatives")
+        return out
+
+    def close(self):
+        if self._h:
+            ffi.lib().mse_pairs_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Searcher:
     """Per-thread scratch + stream (reference `Scratch`: lib.rs:157-175, query_disk_index.rs:116-123)."""
 
@@ -428,6 +482,38 @@ class Searcher:
                 f.close()
             if g_owned:
                 g.close()
+
+    def near_duplicates(self, threshold, window=0, within=None, mode=MODE_AUTO, max_pairs=1 << 32):
+        """The near-duplicate self-join of the base (mse_join_self) -> RowPairs: all pairs (lo, hi), lo < hi, hi - lo <= window (0: no
+        limit), both rows allowed by `within` (a RowFilter) when given, whose reference-order score is >= threshold.  threshold: an int is
+        the i64 score, a float goes through scale_dot_result.  More than max_pairs pairs is an error; join_stats()["kept"] then holds the
+        count."""
+        if within is not None and not isinstance(within, RowFilter):
+            raise TypeError("within must be a RowFilter")
+        if isinstance(threshold, (float, np.floating)):
+            threshold = scale_dot_result(threshold)
+        if window < 0 or max_pairs < 0:
+            raise ValueError("window and max_pairs must not be negative")
+        return RowPairs(check_ptr(ffi.lib().mse_join_self(self._h, int(threshold), int(window), None if within is None else within._h, int(mode),
+                                                          int(max_pairs)), "mse_join_self"))
+
+    def join_stats(self):
+        """Of the last near_duplicates call on this searcher (mse_join_stats); "rounds" is of the last keep-first resolution of one of
+        its lists."""
+        out = (C.c_uint64 * 6)()
+        check(ffi.lib().mse_join_stats(self._h, out), "join_stats")
+        return dict(zip(("tiles", "nominated", "rescored", "kept", "strips_repeated", "rounds"), (int(v) for v in out)))
+
+    def join_timing(self, enable):
+        """Measurement hook (mse_join_timing): HIP-event milliseconds of the last near_duplicates call made while the switch was on --
+        tile launches, re-score launches, building the list -- then sets the switch."""
+        out = (C.c_double * 3)()
+        check(ffi.lib().mse_join_timing(self._h, int(enable), out), "join_timing")
+        return {"tile_ms": out[0], "rescore_ms": out[1], "list_ms": out[2]}
+
+    def debug_join_candidate_capacity(self, n):
+        """Test hook: nominated pairs one launch of the join may store (0: the default)."""
+        check(ffi.lib().mse_debug_join_candidate_capacity(self._h, int(n)), "debug_join_candidate_capacity")
 
     def grouped_stats(self):
         """Of the last grouped call on this searcher (mse_searcher_grouped_stats): queries answered from the first candidate prefix,
