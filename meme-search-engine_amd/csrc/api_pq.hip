@@ -583,428 +583,522 @@ int mse_pq_adc_gather(mse_pq* pq, const mse_codes* c, const float* lut, const fl
     return 0;
 }
 
-static int prep_table(mse_pq* pq, mse_searcher* s, const float* query_dev, float* t_dev, float* lut_dev) {
-    if (launch_pq_transform_vec(pq->transform_t, (int)pq->d, query_dev, t_dev, s->stream)) return -1;
-    return launch_pq_lut(pq->centroids, (int)pq->n_centroids, (int)pq->d, (int)pq->dpc, t_dev, lut_dev, s->stream);
-}
+}  // extern "C"
 
-// everything after the scan of one query.  gmax: the scan's group maxima [n_groups] (i64), or null when the codec shape has no
-// group-maximum scan (then every vector is scored here).
-// f (or null): the filter of a filtered call.  With gmax (the masked scan's maxima) the disallowed vectors of the nominated groups are
-// dropped at the expansion; without gmax -- the LIST mode, and every other codec shape under a filter -- the ADC scores of the filter's
-// ascending id list are taken by the gather kernel and the tournament runs over list positions, which order as their ids do.
-static int scan_tail_async(mse_pq* pq, const mse_codes* c, mse_searcher* s, const int64_t* gmax, const float* query_dev,
-                           const float* lut_dev, uint16_t* qf16_dev, const float* scales_dev, size_t r, size_t k,
-                           int64_t* out_scores_dev, uint32_t* out_ids_dev, const mse_filter* f = nullptr) {
-    hipStream_t st = s->stream;
-    const size_t d = pq->d;
-    const uint8_t* desc = scales_dev ? c->desc : nullptr;
-    uint32_t* top_ids = nullptr;           // the r best by approximate score
-    const int64_t* top_scores = nullptr;
-    if (s->sel_keys.ensure(r * 8)) return -1;
-    if (gmax) {
-        const size_t n_groups = (c->n + 63) / 64;
-        const size_t rg = std::min(r, n_groups);
-        if (s->gkeys.ensure(rg * 8) || s->cand_ids.ensure(rg * 64 * 4) || s->cand_scores.ensure(rg * 64 * 8) || s->out_ids.ensure(r * 4))
-            return -1;
-        uint32_t* gsel = nullptr;
-        LevelRef l0{KEY_I64, const_cast<int64_t*>(gmax), n_groups, 1, n_groups, false, 0};
-        if (descend(s, l0, 1, (int)rg, &gsel, s->gkeys.p)) return -1;
-        if (f ? launch_expand_groups_masked(gsel, rg, rg, 64, c->n, f->words, f->n_words, s->cand_ids.as<uint32_t>(), rg * 64, 1, st)
-              : launch_expand_groups(gsel, rg, rg, 64, c->n, s->cand_ids.as<uint32_t>(), rg * 64, 1, st)) return -1;
-        // (a dropped vector is ID_NONE: the gather kernel scores it INT64_MIN and the select skips it)
-        if (launch_pq_adc(lut_dev, (int)pq->n_chunks, (int)pq->n_centroids, c->codes, c->n, s->cand_ids.as<uint32_t>(), rg * 64,
-                          desc, (int)c->n_desc, scales_dev, s->cand_scores.as<int64_t>(), s->n_cu, st)) return -1;
-        SelectArgs a{};
-        a.kind = KEY_I64; a.list_ids = s->cand_ids.as<uint32_t>(); a.list_keys = s->cand_scores.p; a.list_stride = rg * 64;
-        a.n_list = rg * 64; a.k = (int)r; a.out_ids = s->out_ids.as<uint32_t>(); a.out_keys = s->sel_keys.p; a.out_stride = r; a.nq = 1;
-        // r group maxima reach the r-th best group's key, so r vectors do: the key is a floor for the select.  This leans on the
-        // scan kernels and pq_adc_kernel producing the SAME i64 for a vector (same adds in the same order, bias added after the
-        // conversion); tests/test_gpu_pq_index_graph.py::test_group_maxima_equal_the_gathered_scores pins exactly that.
-        // Under a filter the maxima are over ALLOWED vectors, so the argument holds as long as the r-th key belongs to a group with an
-        // allowed vector.  When fewer than r groups have one, the r-th key is INT64_MIN, whose sortable form is 0: a floor of 0 cuts
-        // nothing, and padding (ID_NONE) is skipped by the select before the floor is looked at (topk.hip), so it is never admitted.
-        if (rg == r) a.floor_hi = s->last_kth;
-        if (launch_select(a, st)) return -1;
-        top_ids = s->out_ids.as<uint32_t>();
-    } else if (f) {
-        const size_t m = f->count;   // (> 0: the entry points answer an empty filter without a launch)
-        if (s->scores.ensure(m * 8)) return -1;
-        if (launch_pq_adc(lut_dev, (int)pq->n_chunks, (int)pq->n_centroids, c->codes, c->n, f->ids, m, desc, (int)c->n_desc,
-                          scales_dev, s->scores.as<int64_t>(), s->n_cu, st)) return -1;
-        LevelRef l0{KEY_I64, s->scores.p, m, 1, m, false, 0};
-        if (descend(s, l0, 1, (int)r, &top_ids, s->sel_keys.p)) return -1;
-        if (launch_map_positions(top_ids, r, f->ids, st)) return -1;
-    } else {
-        // other codec shapes: every vector's score, then the tournament over them
-        if (s->scores.ensure(c->n * 8)) return -1;
-        if (launch_pq_adc(lut_dev, (int)pq->n_chunks, (int)pq->n_centroids, c->codes, c->n, nullptr, c->n, desc, (int)c->n_desc,
-                          scales_dev, s->scores.as<int64_t>(), s->n_cu, st)) return -1;
-        LevelRef l0{KEY_I64, s->scores.p, c->n, 1, c->n, false, 0};
-        if (descend(s, l0, 1, (int)r, &top_ids, s->sel_keys.p)) return -1;
-    }
-    top_scores = s->sel_keys.as<int64_t>();
-    if (s->base) {
-        // exact re-score: f16(query) . base[id] (+ descriptor bias), query_disk_index.rs:168-170,477
-        const mse_base* b = s->base;
-        if (s->cand_scores.ensure(r * 8) || s->misc.ensure(k * 4) || s->gkeys.ensure(k * 8)) return -1;
-        if (launch_f32_to_f16(query_dev, d, qf16_dev, st)) return -1;
-        if (launch_score_rows(b->dev, b->n, (int)d, qf16_dev, false, top_ids, r, r, s->cand_scores.as<int64_t>(), nullptr, st))
-            return -1;
-        if (launch_add_descriptor(top_ids, r, desc, (int)c->n_desc, c->n, scales_dev, s->cand_scores.as<int64_t>(), st)) return -1;
-        SelectArgs a{};
-        a.kind = KEY_I64; a.list_ids = top_ids; a.list_keys = s->cand_scores.p; a.list_stride = r; a.n_list = r;
-        a.k = (int)k; a.out_ids = s->misc.as<uint32_t>(); a.out_keys = s->gkeys.p; a.out_stride = k; a.nq = 1;
-        if (launch_select(a, st)) return -1;
-        top_ids = s->misc.as<uint32_t>();
-        top_scores = s->gkeys.as<int64_t>();
-    }
-    MSE_HIP_TRY(hipMemcpyAsync(out_ids_dev, top_ids, k * 4, hipMemcpyDeviceToDevice, st));
-    MSE_HIP_TRY(hipMemcpyAsync(out_scores_dev, top_scores, k * 8, hipMemcpyDeviceToDevice, st));
+// ---- the flat ADC scan (mse_pq_scan_topk and its batch, block and filtered forms) ----
+namespace mse {
+
+int check_pq_mode(int mode) {
+    if (mode != MSE_PQ_FILTER_AUTO && mode != MSE_PQ_FILTER_SCAN && mode != MSE_PQ_FILTER_LIST) return fail("unknown mode");
     return 0;
 }
-
-// One query (n_q = 1) or a PAIR of queries (n_q = 2) of the flat ADC scan, entirely on the searcher's stream (no host synchronisation):
-//   table(query) -> scan of all codes keeping one maximum per 64 vectors (a pair shares ONE pass over the codes: pq_scan64x2_kernel)
-//   -> per query: tournament over the maxima -> the r best groups' r x 64 vectors re-scored by the gather kernel (same arithmetic)
-//   -> exact top-r by ADC score (ties: lower id) -> with base vectors: exact fast_dot re-score of those r (+ descriptor bias), top-k
-// t_dev: transformed queries (fp32 [2][d]) scratch, lut_dev: table scratch (2 x 64 KiB), qf16_dev: f16 copy of a query (8 rows)
-// prepared: lut_dev already holds this group's tables (the batch entry point builds all tables of a call in two launches)
-static int scan_topk_async(mse_pq* pq, const mse_codes* c, mse_searcher* s, const float* queries_dev, int n_q, float* t_dev,
-                           float* lut_dev, uint16_t* qf16_dev, const float* scales_dev, size_t r, size_t k,
-                           int64_t* out_scores_dev, uint32_t* out_ids_dev, bool prepared = false, const mse_filter* f = nullptr,
-                           bool list = false /* filtered: skip the scan, score the filter's id list (scan_tail_async) */) {
-    const size_t d = pq->d, lut_floats = pq->n_chunks * pq->n_centroids;
-    const uint8_t* desc = scales_dev ? c->desc : nullptr;
-    const bool gm = !list && pq_scan_gmax_supported((int)pq->n_chunks, (int)pq->n_centroids, desc, (int)c->n_desc, scales_dev);
-    for (int j = 0; j < n_q && !prepared; j++)
-        if (prep_table(pq, s, queries_dev + j * d, t_dev + j * d, lut_dev + j * lut_floats)) return -1;
-    const size_t n_groups = (c->n + 63) / 64;
-    int64_t* g0 = nullptr;
-    int64_t* g1 = nullptr;
-    if (gm) {
-        if (s->scores.ensure(n_groups * 8) || (n_q == 2 && s->gmax.ensure(n_groups * 8))) return -1;
-        g0 = s->scores.as<int64_t>();
-        g1 = s->gmax.as<int64_t>();
-        if (n_q == 2) {
-            if (launch_pq_scan_gmax2(lut_dev, lut_dev + lut_floats, c->codes, c->n, desc, scales_dev, g0, g1, s->n_cu, s->stream,
-                                     f ? f->words : nullptr, f ? f->n_words : 0)) return -1;
-        } else if (launch_pq_scan_gmax(lut_dev, c->codes, c->n, desc, scales_dev, g0, s->n_cu, s->stream, f ? f->words : nullptr,
-                                       f ? f->n_words : 0)) return -1;
-    }
-    for (int j = 0; j < n_q; j++)
-        if (scan_tail_async(pq, c, s, gm ? (j ? g1 : g0) : nullptr, queries_dev + j * d, lut_dev + j * lut_floats, qf16_dev, scales_dev,
-                            r, k, out_scores_dev + j * k, out_ids_dev + j * k, f)) return -1;
+int check_pq_r(size_t r, size_t k) {
+    if (std::max(r, k) > (size_t)TOPK_KMAX - 64) return fail("r too large (max 1984)");
     return 0;
 }
-
-// FOUR (12-bit tables) or EIGHT (8-bit tables) queries in one pass over the codes (pq_scan64x4_kernel: integer nomination under a
-// certificate, pq.hip).  Per query:
-// the n_nom best groups by their integer maximum (+ one more, whose key bounds everything excluded) -> their vectors re-scored in the
-// reference's arithmetic (pq_adc_kernel) -> exact top-r among them -> certificate flag (1 = provably the exact top-r of all
-// vectors) -> with base vectors the same fast_dot re-score as the other paths.  flags_dev[j] = 0 asks the caller to repeat query j
-// through the exact scan.  lut_dev: NQ tables; t_dev: NQ transformed queries.
-// How many groups to nominate: the certificate needs every group whose integer maximum lies within ~2 eps of the r-th exact
-// score.  With 12-bit tables that is a few tens of vectors at 1e8 codes (r + max(64, r / 2) groups); the 8-bit step is 16 times
-// coarser and the band holds ~0.7 r vectors on random codes (simulated at 1e7 codes, r = 200: 339 groups reach it): 2 r + 112.
-static size_t pq_nominated(size_t r, int NQ) { return NQ == 4 ? r + std::max<size_t>(64, r / 2) : 2 * r + 112; }
-static int scan_topk4_async(mse_pq* pq, const mse_codes* c, mse_searcher* s, const float* queries_dev, float* t_dev, float* lut_dev,
-                            uint16_t* qf16_dev, const float* scales_dev, size_t r, size_t k, int64_t* out_scores_dev,
-                            uint32_t* out_ids_dev, int* flags_dev, bool prepared, int NQ, const mse_filter* f = nullptr) {
-    hipStream_t st = s->stream;
-    const size_t d = pq->d, lut_floats = pq->n_chunks * pq->n_centroids;
-    const uint8_t* desc = scales_dev ? c->desc : nullptr;
-    for (int j = 0; j < NQ && !prepared; j++)
-        if (prep_table(pq, s, queries_dev + j * d, t_dev + j * d, lut_dev + j * lut_floats)) return -1;
-    const size_t n_groups = (c->n + 63) / 64;
-    // one more group than nominated is selected, only for its key
-    const size_t n_nom = std::min(n_groups, pq_nominated(r, NQ));
-    const size_t n_sel = std::min(n_groups, n_nom + 1);
-    if (n_sel > (size_t)TOPK_KMAX) return fail("pq scan: r too large for the four-query scan");
-    if (s->pq4.ensure(pq4_table_bytes() + 8 * sizeof(Pq4Params)) || s->gmax.ensure((size_t)NQ * n_groups * 4)) return -1;
-    void* table = s->pq4.p;
-    Pq4Params* params = reinterpret_cast<Pq4Params*>(s->pq4.as<char>() + pq4_table_bytes());
-    if (launch_pq4_table(lut_dev, scales_dev, NQ, table, params, st, NQ)) return -1;
-    hipEvent_t te0 = nullptr, te1 = nullptr;
-    if (pq->timing) {
-        while (s->ev_pool.size() < s->ev_used + 2) {
-            hipEvent_t e = nullptr;
-            MSE_HIP_TRY(hipEventCreate(&e));
-            s->ev_pool.push_back(e);
-        }
-        te0 = s->ev_pool[s->ev_used];
-        te1 = s->ev_pool[s->ev_used + 1];
-        s->ev_used += 2;
-        MSE_HIP_TRY(hipEventRecord(te0, st));
-    }
-    if (launch_pq_scan_gmax4(table, c->codes, c->n, desc, s->gmax.as<uint32_t>(), s->n_cu, st, NQ, f ? f->words : nullptr, f ? f->n_words : 0))
-        return -1;
-    if (te1) MSE_HIP_TRY(hipEventRecord(te1, st));
-    // the NQ tails as ONE chain of launches with a query dimension (their kernels are latency-bound: four chains in a row cost more
-    // than the scan); every buffer at its final size before the first kernel that uses it
-    const size_t n_cand = n_nom * 64;
-    const size_t Q = (size_t)NQ;
-    if (s->gkeys.ensure(Q * std::max(k, n_sel) * 8) || s->cand_ids.ensure(Q * n_cand * 4) || s->cand_scores.ensure(Q * std::max(r, n_cand) * 8) ||
-        s->out_ids.ensure(Q * r * 4) || s->sel_keys.ensure(Q * r * 8) || s->misc.ensure(Q * k * 4) || s->scores.ensure(Q * k * 8)) return -1;
-    uint32_t* gsel = nullptr;
-    LevelRef l0{KEY_U32, s->gmax.p, 1, (size_t)NQ, n_groups, false, 0};   // group-major: element (q, g) at gmax[g * NQ + q]
-#ifdef MSE_DEV_KERNELS
-    // developer library, MSE_PQ_TAIL_SKIP=mask: the scan WITHOUT parts of its tail (answers are garbage, every query is reported
-    // certified): what the tail costs the scans that run beside it.  1 tournament, 2 expand + re-score, 4 exact top-r, 8 certificate
-    static const int tail_skip = getenv("MSE_PQ_TAIL_SKIP") ? atoi(getenv("MSE_PQ_TAIL_SKIP")) : 0;
-    if (tail_skip) {
-        if (!(tail_skip & 1) && descend(s, l0, NQ, (int)n_sel, &gsel, s->gkeys.p)) return -1;
-        if (!(tail_skip & 2) && gsel) {
-            if (launch_expand_groups(gsel, n_sel, n_nom, 64, c->n, s->cand_ids.as<uint32_t>(), n_cand, NQ, st)) return -1;
-            if (launch_pq_adc(lut_dev, (int)pq->n_chunks, (int)pq->n_centroids, c->codes, c->n, s->cand_ids.as<uint32_t>(), n_cand, desc,
-                              (int)c->n_desc, scales_dev, s->cand_scores.as<int64_t>(), s->n_cu, st, NQ, n_cand)) return -1;
-        }
-        if (!(tail_skip & 4)) {
-            SelectArgs a{};
-            a.kind = KEY_I64; a.list_ids = s->cand_ids.as<uint32_t>(); a.list_keys = s->cand_scores.p; a.list_stride = n_cand;
-            a.n_list = n_cand; a.k = (int)r; a.out_ids = s->out_ids.as<uint32_t>(); a.out_keys = s->sel_keys.p; a.out_stride = r; a.nq = NQ;
-            if (launch_select(a, st)) return -1;
-        }
-        MSE_HIP_TRY(hipMemsetAsync(flags_dev, 1, (size_t)NQ * sizeof(int), st));
-        return 0;
-    }
-#endif
-    if (descend(s, l0, NQ, (int)n_sel, &gsel, s->gkeys.p)) return -1;                      // gsel [NQ][n_sel], gkeys u32 [NQ][n_sel]
-    if (f ? launch_expand_groups_masked(gsel, n_sel, n_nom, 64, c->n, f->words, f->n_words, s->cand_ids.as<uint32_t>(), n_cand, NQ, st)
-          : launch_expand_groups(gsel, n_sel, n_nom, 64, c->n, s->cand_ids.as<uint32_t>(), n_cand, NQ, st)) return -1;
-    if (launch_pq_adc(lut_dev, (int)pq->n_chunks, (int)pq->n_centroids, c->codes, c->n, s->cand_ids.as<uint32_t>(), n_cand, desc,
-                      (int)c->n_desc, scales_dev, s->cand_scores.as<int64_t>(), s->n_cu, st, NQ, n_cand)) return -1;
-    {
-        SelectArgs a{};
-        a.kind = KEY_I64; a.list_ids = s->cand_ids.as<uint32_t>(); a.list_keys = s->cand_scores.p; a.list_stride = n_cand;
-        a.n_list = n_cand; a.k = (int)r; a.out_ids = s->out_ids.as<uint32_t>(); a.out_keys = s->sel_keys.p; a.out_stride = r; a.nq = NQ;
-        if (launch_select(a, st)) return -1;
-    }
-    // the vectors that must exist among the nominated: min(r, rows) -- under a filter min(r, allowed rows).  The bound from the best
-    // excluded group stays sound there: its masked maximum bounds every ALLOWED vector outside the nominated groups, and a masked
-    // vector's key (the all-zero sum) is the smallest possible
-    if (launch_pq4_certify(params, s->gkeys.as<uint32_t>(), (int)n_nom, (int)n_sel, s->out_ids.as<uint32_t>(), s->sel_keys.as<int64_t>(), r,
-                           (int)std::min(r, f ? f->count : c->n), NQ, flags_dev, st)) return -1;
-    const uint32_t* top_ids = s->out_ids.as<uint32_t>();      // [NQ][r]
-    const int64_t* top_scores = s->sel_keys.as<int64_t>();
-    size_t top_stride = r;
-    if (s->base) {
-        // exact re-score: f16(query) . base[id] (+ descriptor bias), query_disk_index.rs:168-170,477 -- four queries per launch
-        const mse_base* b = s->base;
-        if (launch_f32_to_f16(queries_dev, Q * d, qf16_dev, st)) return -1;
-        if (launch_score_rows(b->dev, b->n, (int)d, qf16_dev, false, top_ids, Q * r, r, s->cand_scores.as<int64_t>(), nullptr, st)) return -1;
-        if (launch_add_descriptor(top_ids, Q * r, desc, (int)c->n_desc, c->n, scales_dev, s->cand_scores.as<int64_t>(), st)) return -1;
-        SelectArgs b2{};
-        b2.kind = KEY_I64; b2.list_ids = top_ids; b2.list_keys = s->cand_scores.p; b2.list_stride = r; b2.n_list = r;
-        b2.k = (int)k; b2.out_ids = s->misc.as<uint32_t>(); b2.out_keys = s->scores.p; b2.out_stride = k; b2.nq = NQ;
-        if (launch_select(b2, st)) return -1;
-        top_ids = s->misc.as<uint32_t>();
-        top_scores = s->scores.as<int64_t>();
-        top_stride = k;
-    }
-    MSE_HIP_TRY(hipMemcpy2DAsync(out_ids_dev, k * 4, top_ids, top_stride * 4, k * 4, Q, hipMemcpyDeviceToDevice, st));
-    MSE_HIP_TRY(hipMemcpy2DAsync(out_scores_dev, k * 8, top_scores, top_stride * 8, k * 8, Q, hipMemcpyDeviceToDevice, st));
-    return 0;
-}
-
-// (a sharded scan hands its results over as a packed block on the device: launch_block_finish, topk.hip)
-// f (or null) / list: the filtered entry points further down (the unfiltered ones pass null and take exactly the launches they always took)
-static int pq_scan_topk_batch_impl(mse_pq* pq, const mse_codes* c, mse_searcher* s_or_null, const float* queries_f32, size_t nq,
-                                   const float* scales, size_t r, size_t k, int64_t* scores, uint32_t* ids, uint64_t id_offset, void* block_dev,
-                                   const mse_filter* f = nullptr, bool list = false);
-
-int mse_pq_scan_topk_batch(mse_pq* pq, const mse_codes* c, mse_searcher* s_or_null, const float* queries_f32, size_t nq,
-                           const float* scales, size_t r, size_t k, int64_t* scores, uint32_t* ids) {
-    if (!scores || !ids) return fail("null output");
-    return pq_scan_topk_batch_impl(pq, c, s_or_null, queries_f32, nq, scales, r, k, scores, ids, 0, nullptr);
-}
-
-int mse_pq_scan_topk_block(mse_pq* pq, const mse_codes* c, mse_searcher* s_or_null, const float* queries_f32, size_t nq, const float* scales,
-                           size_t r, size_t k, uint64_t id_offset, void* block_dev) {
-    if (!block_dev) return fail("null output block");
-    return pq_scan_topk_batch_impl(pq, c, s_or_null, queries_f32, nq, scales, r, k, nullptr, nullptr, id_offset, block_dev);
-}
-
-static int pq_scan_topk_batch_impl(mse_pq* pq, const mse_codes* c, mse_searcher* s_or_null, const float* queries_f32, size_t nq,
-                                   const float* scales, size_t r, size_t k, int64_t* scores, uint32_t* ids, uint64_t id_offset, void* block_dev,
-                                   const mse_filter* f, bool list) {
-    if (!pq || !c) return fail("null quantiser or codes");
-    if (c->code_size != pq->n_chunks) return fail("code size does not match the quantiser");
-    if (k == 0 || nq == 0) return 0;
-    if (r < k) r = k;
-    if (r > (size_t)TOPK_KMAX - 64) return fail("r too large (max 1984)");
-    if (!block_dev)
-        for (size_t i = 0; i < nq * k; i++) { scores[i] = INT64_MIN; ids[i] = MSE_ID_NONE; }
-    if (c->n == 0 || (f && f->count == 0)) {   // (no allowed row: everything is padding, no scan is launched)
-        if (block_dev) {   // an empty shard still hands over a block: all slots empty
-            if (launch_block_finish(nullptr, nullptr, nq * k, 0, reinterpret_cast<int64_t*>(block_dev), reinterpret_cast<uint32_t*>(static_cast<char*>(block_dev) + nq * k * 8), nullptr)) return -1;
-            MSE_HIP_TRY(hipStreamSynchronize(nullptr));
-        }
-        return 0;
-    }
-    std::lock_guard<std::mutex> g(pq->mu);
-    pq->last_uncertified = 0;
-    mse_searcher* s = s_or_null;
-    if (!s) {
-        if (!pq->scratch && !(pq->scratch = scratch_searcher_new())) return -1;
-        s = pq->scratch;
-    }
-    if (s->base && s->base->n != c->n) return fail("base and codes differ in length");
-    if (s->base && s->base->d != pq->d) return fail("base width differs from the quantiser");
-    hipStream_t st = s->stream;
-    const size_t d = pq->d;
-    int rc = -1;
-    do {
-        // all queries (+ scales) go up in ONE copy from pinned memory; every query then runs on the streams; ONE download at the end
-        const size_t sc_off = (nq * d * 4 + 255) & ~(size_t)255;
-        const size_t sc_bytes = (scales && c->n_desc) ? c->n_desc * 4 : 0;
-        const size_t in_bytes = sc_off + sc_bytes, out_bytes = nq * k * 12 + nq * 4;   // scores, ids, certificate flags
-        // batches of 4 .. 2048 queries: all transformed queries and tables up front, in two launches (the same kernels the codec's
-        // batch entry points use; same arithmetic as the one-vector forms) instead of two small launches per query in front of every scan
-        const size_t lut_floats_b = pq->n_chunks * pq->n_centroids;
-        const bool prep_all = nq >= 4 && nq <= 2048;
-        const size_t n_tab = prep_all ? nq : 8;
-        if (pq->a.ensure(in_bytes + 256) || pq->b.ensure(n_tab * d * 4) || pq->c.ensure(n_tab * lut_floats_b * 4)) break;
-        if (s->q_stage.ensure(8 * d * 2) || s->out_scores.ensure(out_bytes)) break;
-        if (pq->pin.ensure(std::max(in_bytes, out_bytes), (size_t)1 << 16)) break;
-        memcpy(pq->pin.p, queries_f32, nq * d * 4);
-        if (sc_bytes) memcpy(pq->pin.as<char>() + sc_off, scales, sc_bytes);
-        if (hipMemcpyAsync(pq->a.p, pq->pin.p, in_bytes, hipMemcpyHostToDevice, st) != hipSuccess) { fail("H2D failed"); break; }
-        float* scales_dev = sc_bytes ? reinterpret_cast<float*>(pq->a.as<char>() + sc_off) : nullptr;
-        int64_t* const out_scores_dev = s->out_scores.as<int64_t>();
-        uint32_t* const out_ids_dev = reinterpret_cast<uint32_t*>(s->out_scores.as<char>() + nq * k * 8);
-        // Groups of queries alternate between TWO streams (each with its own scratch): the chain of small kernels that follows a
-        // scan (tournament, re-score of the nominated groups, selects, certificate) runs beside the next group's scan, on the CUs
-        // that scan leaves free.  (A third stream -- so that group u + 2 would not queue behind group u's tail -- and 16 / 24 / 32
-        // spare CUs were measured in round 4: 0.194-0.203 ms per query at 32 per call in every combination, two streams and 8 spare
-        // CUs being the best; the code below keeps room for a third lane.)
-        mse_searcher* lanes[3] = {s, nullptr, nullptr};
-        DevBuf &t2 = pq->t2, &lut2 = pq->lut2;
-        DevBuf* qfs[3] = {&s->q_stage, &pq->qf2, &pq->qf3};
-        if (nq >= 4) {
-            mse_searcher** extra[2] = {&pq->lane2, &pq->lane3};
-#ifdef MSE_DEV_KERNELS
-            static const int n_extra = getenv("MSE_PQ_LANES") ? std::min(std::max(atoi(getenv("MSE_PQ_LANES")) - 1, 0), 2) : 1;   // developer library: 1-3 streams
-#else
-            const int n_extra = 1;
-#endif
-            bool lanes_ok = true;
-            for (int e = 0; e < n_extra && lanes_ok; e++) {
-                mse_searcher*& ln = *extra[e];
-                if (ln && ln->base != s->base) { mse_searcher_free(ln); ln = nullptr; }
-                if (!ln) ln = s->base ? mse_searcher_new(s->base) : scratch_searcher_new();
-                lanes[e + 1] = ln;
-                lanes_ok = ln != nullptr && qfs[e + 1]->ensure(8 * d * 2) == 0;
-            }
-            if (!lanes_ok || t2.ensure(8 * d * 4) || lut2.ensure(8 * pq->n_chunks * pq->n_centroids * 4)) break;
-            if (hipStreamSynchronize(st) != hipSuccess) { fail("H2D failed"); break; }   // uploads visible to every stream
-        }
-        const int n_lanes = lanes[2] ? 3 : lanes[1] ? 2 : 1;
-        // queries go through in groups that share one pass over the codes: EIGHTS (8-bit tables) and FOURS (12-bit tables) -- integer
-        // nomination under a certificate, pq_scan64x4_kernel --, then a PAIR (pq_scan64x2_kernel, exact), then a single one; groups
-        // alternate between the streams
-        int* const flags_dev = reinterpret_cast<int*>(s->out_scores.as<char>() + nq * k * 12);
-        if (hipMemsetAsync(flags_dev, 0xff, nq * 4, st) != hipSuccess) { fail("memset failed"); break; }   // non-zero = certified / exact
-        if (prep_all && (launch_pq_transform(pq->transform, (int)d, pq->a.as<float>(), nq, pq->b.as<float>(), st) ||
-                         launch_pq_lut_batch(pq->centroids, (int)pq->n_centroids, (int)d, (int)pq->dpc, pq->b.as<float>(), nq, pq->c.as<float>(), st)))
-            break;
-        if (lanes[1] && hipStreamSynchronize(st) != hipSuccess) { fail("memset failed"); break; }
-        const uint8_t* desc_dev = scales_dev ? c->desc : nullptr;
-        // (a filtered LIST call shares no pass over the codes: its queries go one by one, still alternating between the streams)
-        const bool four_ok = !list && pq_scan_gmax_supported((int)pq->n_chunks, (int)pq->n_centroids, desc_dev, (int)c->n_desc, scales_dev) &&
-                             r + std::max<size_t>(64, r / 2) + 1 <= (size_t)TOPK_KMAX;
-        // eight per pass while the 8-bit certificate holds for this quantiser's data: a batch in which more than an eighth of the
-        // eight-per-pass queries had to be repeated through the exact scan switches the handle back to four per pass for good
-        const bool eight_ok = four_ok && !pq->avoid8 && pq_nominated(r, 8) + 1 <= (size_t)TOPK_KMAX;
-        std::vector<char> in_eight(nq, 0);
-        bool ok = true;
-        size_t q = 0;
-        for (size_t unit = 0; q < nq && ok; unit++) {
-            const int n_q = (eight_ok && nq - q >= 8) ? 8 : (four_ok && nq - q >= 4) ? 4 : (nq - q >= 2 && !list) ? 2 : 1;
-            const int w = (int)(unit % (size_t)n_lanes);
-            float* const tw = prep_all ? pq->b.as<float>() + q * d : w ? t2.as<float>() : pq->b.as<float>();     // (several lanes imply prep_all)
-            float* const lw = prep_all ? pq->c.as<float>() + q * lut_floats_b : w ? lut2.as<float>() : pq->c.as<float>();
-            uint16_t* const qw = qfs[w]->as<uint16_t>();
-            if (n_q >= 4) {
-                ok = scan_topk4_async(pq, c, lanes[w], pq->a.as<float>() + q * d, tw, lw, qw, scales_dev, r, k, out_scores_dev + q * k,
-                                      out_ids_dev + q * k, flags_dev + q, prep_all, n_q, f) == 0;
-                if (n_q == 8) for (int j = 0; j < 8; j++) in_eight[q + j] = 1;
-            }
-            else
-                ok = scan_topk_async(pq, c, lanes[w], pq->a.as<float>() + q * d, n_q, tw, lw, qw, scales_dev, r, k,
-                                     out_scores_dev + q * k, out_ids_dev + q * k, prep_all, f, list) == 0;
-            q += n_q;
-        }
-        for (int w = 1; w < n_lanes; w++)
-            if (hipStreamSynchronize(lanes[w]->stream) != hipSuccess) ok = false;
-        if (!ok) { if (std::string(mse_last_error()).empty()) fail("scan failed"); break; }
-        if (four_ok && nq >= 4) {
-            // a query whose certificate did not hold (rare: the band of +-eps around its r-th score reached past the nominated
-            // groups) is repeated through the exact one-query scan, into the same output rows
-            std::vector<int> flags(nq);
-            if (hipMemcpyAsync(flags.data(), flags_dev, nq * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipStreamSynchronize(st) != hipSuccess) { fail("D2H failed"); break; }
-            pq->last_uncertified = 0;
-            size_t n8 = 0, bad8 = 0;
-            for (size_t j = 0; j < nq; j++) { n8 += in_eight[j]; bad8 += in_eight[j] && !flags[j]; }
-            // filtered batches are left out of this decision: a sparse filter legitimately fails more certificates (fewer than r allowed
-            // vectors among the nominated groups), which says nothing about the quantiser's data
-            if (!f && n8 && bad8 * 8 > n8) pq->avoid8 = true;
-            for (size_t j = 0; j < nq && ok; j++)
-                if (!flags[j]) {
-                    pq->last_uncertified++;
-                    ok = scan_topk_async(pq, c, s, pq->a.as<float>() + j * d, 1, pq->b.as<float>() + (prep_all ? j * d : 0),
-                                         pq->c.as<float>() + (prep_all ? j * lut_floats_b : 0), s->q_stage.as<uint16_t>(), scales_dev, r, k,
-                                         out_scores_dev + j * k, out_ids_dev + j * k, prep_all, f) == 0;
-                }
-            if (!ok) { if (std::string(mse_last_error()).empty()) fail("scan failed"); break; }
-        }
-        if (block_dev) {
-            if (launch_block_finish(out_scores_dev, out_ids_dev, nq * k, id_offset, reinterpret_cast<int64_t*>(block_dev),
-                                    reinterpret_cast<uint32_t*>(static_cast<char*>(block_dev) + nq * k * 8), st) || hipStreamSynchronize(st) != hipSuccess) {
-                fail("block hand-over failed"); break;
-            }
-        } else if (hipMemcpyAsync(pq->pin.p, s->out_scores.p, nq * k * 12, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                   hipStreamSynchronize(st) != hipSuccess) { fail("D2H failed"); break; }
-        {   // sustained rate: from the first scan's start to the last scan's end of this call, over its scans (they run back to back,
-            // alternating between the streams: what a launch costs when the next one is already waiting behind it)
-            size_t scans = 0;
-            float span = 0.0f;
-            for (mse_searcher* ln : lanes)
-                if (ln && ln->ev_used >= 2 && lanes[0]->ev_used >= 2) {
-                    float ms = 0.0f;
-                    if (hipEventElapsedTime(&ms, lanes[0]->ev_pool[0], ln->ev_pool[ln->ev_used - 1]) == hipSuccess) span = std::max(span, ms);
-                    scans += ln->ev_used / 2;
-                }
-            if (scans >= 4 && span > 0.0f) { pq->span_ms_total += span; pq->span_scans += scans; }
-        }
-        for (mse_searcher* ln : lanes)      // both streams are idle here: the scan launches' event pairs can be read
-            if (ln) {
-                for (size_t e = 0; e + 1 < ln->ev_used; e += 2) {
-                    float ms = 0.0f;
-                    if (hipEventElapsedTime(&ms, ln->ev_pool[e], ln->ev_pool[e + 1]) == hipSuccess) { pq->scan_ms_total += ms; pq->scan_launches++; }
-                }
-                ln->ev_used = 0;
-            }
-        if (!block_dev) {
-            memcpy(scores, pq->pin.p, nq * k * 8);
-            memcpy(ids, pq->pin.as<char>() + nq * k * 8, nq * k * 4);
-            for (size_t i = 0; i < nq * k; i++)
-                if (ids[i] == MSE_ID_NONE) scores[i] = INT64_MIN;
-        }
-        rc = 0;
-    } while (0);
-    return rc;
-}
-
-// test hook: the group maxima the flat scan nominates with -- lut1 == null: pq_scan64_kernel<true> for one table; otherwise
-// pq_scan64x2_kernel for the pair.  out0 / out1: [ceil(n / 64)] i64 on the host.
-static int check_pq_filter(const mse_pq* pq, const mse_codes* c, const mse_filter* f) {
+static int check_pq_filter(const mse_pq* pq, const mse_codes* c, const mse_filter* f) {   // (also the debug hooks')
     if (!f) return fail("null filter");
     if (f->n_rows > c->n) return fail("filter is longer than the codes (" + std::to_string(f->n_rows) + " > " + std::to_string(c->n) + " rows)");
     if (f->device != pq->device) return fail("filter was made on another device than the quantiser's");   // no silent copy
     return 0;
 }
+int check_pq_scan(const mse_pq* pq, const mse_codes* c, const mse_searcher* s, size_t nq, size_t r, size_t k, const PqFilterArg* fa) {
+    if (!pq || !c) return fail("null quantiser or codes");
+    if (fa && (check_pq_filter(pq, c, fa->f) || check_pq_mode(fa->mode))) return -1;
+    if (c->code_size != pq->n_chunks) return fail("code size does not match the quantiser");
+    if (!fa && (nq == 0 || k == 0)) return 0;   // an unfiltered call with nothing to do is answered before r and the base are looked at
+    if (check_pq_r(r, k)) return -1;
+    if (s && s->base && s->base->n != c->n) return fail("base and codes differ in length");
+    if (s && s->base && s->base->d != pq->d) return fail("base width differs from the quantiser");
+    return 0;
+}
+
+int exact_rescore(const mse_base* b, const mse_codes* c, const float* scales_dev, const void* q16, const uint32_t* ids, size_t n, size_t per_query,
+                  int64_t* out, hipStream_t st) {
+    if (launch_score_rows(b->dev, b->n, (int)b->d, q16, false, ids, n, per_query, out, nullptr, st)) return -1;
+    if (scales_dev && c->n_desc && launch_add_descriptor(ids, n, c->desc, (int)c->n_desc, c->n, scales_dev, out, st)) return -1;
+    return 0;
+}
+
+}  // namespace mse
+
+namespace {
+
+int prep_table(mse_pq* pq, mse_searcher* s, const float* query_dev, float* t_dev, float* lut_dev) {
+    if (launch_pq_transform_vec(pq->transform_t, (int)pq->d, query_dev, t_dev, s->stream)) return -1;
+    return launch_pq_lut(pq->centroids, (int)pq->n_centroids, (int)pq->d, (int)pq->dpc, t_dev, lut_dev, s->stream);
+}
+
+// one lane of a batched scan: a searcher (its stream and scratch) and the lane's own transformed queries, tables and f16 queries
+struct ScanLane { mse_searcher* s; float* t; float* lut; uint16_t* qf16; };
+
+// what the steps of one scan call share
+struct ScanRun {
+    mse_pq* pq;
+    const mse_codes* c;
+    const PqFilterArg* fa;               // a filtered call's filter and mode, or null
+    size_t nq, r, k;
+    const float *queries_f32, *scales;   // host [nq][d]; host [n_desc] or null
+    // the destination: a packed block on the device (a sharded scan's hand-over: launch_block_finish, topk.hip; ids lifted by
+    // id_offset), or the caller's host arrays
+    void* block_dev; uint64_t id_offset; int64_t* scores; uint32_t* ids;
+    // filled by the steps
+    const mse_filter* f = nullptr;       // the allowed rows (null: all) ...
+    bool list = false;                   // ... and the resolved mode: LIST makes no pass over the codes (ADC over the filter's id list)
+    const uint32_t* mask = nullptr;      // f's bitmap words for the masked scans and the masked expansion (null: unfiltered kernels)
+    size_t mask_words = 0;
+    const float *queries_dev = nullptr, *scales_dev = nullptr;   // scales_dev: null unless scales AND descriptors are there
+    const uint8_t* desc = nullptr;       // the codes' descriptors when scales_dev, else null
+    // batches of 4 .. 2048 queries: all transformed queries (pq->b) and tables (pq->c) up front, in two launches (the same kernels the
+    // codec's batch entry points use; same arithmetic as the one-vector forms) instead of two small launches per query in front of every scan
+    bool prep_all = false;
+    ScanLane lanes[3] = {};
+    int n_lanes = 1;
+    bool four_ok = false, eight_ok = false;   // the nomination scans this call may use (scan_group_size)
+    size_t n_in_eight = 0;                    // the call's first n_in_eight queries went through eight-per-pass groups
+    int64_t* out_scores_dev = nullptr; uint32_t* out_ids_dev = nullptr;   // [nq][k] each
+    int* flags_dev = nullptr;                 // [nq], non-zero = certified / exact
+};
+
+// n consecutive queries from q0 on, sharing one pass over the codes, on lane `lane`
+struct ScanGroup { int lane; size_t q0; int n; };
+
+// a group's tables: inside the call's array when that was built up front, else built here in the lane's scratch; null: failed
+const float* group_tables(const ScanRun& run, const ScanGroup& g) {
+    const ScanLane& ln = run.lanes[g.lane];
+    const size_t d = run.pq->d, lut_floats = run.pq->n_chunks * run.pq->n_centroids;
+    if (run.prep_all) return run.pq->c.as<float>() + g.q0 * lut_floats;
+    for (int j = 0; j < g.n; j++)
+        if (prep_table(run.pq, ln.s, run.queries_dev + (g.q0 + j) * d, ln.t + j * d, ln.lut + j * lut_floats)) return nullptr;
+    return ln.lut;
+}
+
+// where level 0 of a tail's tournament comes from:
+//   GROUPS_EXACT      the exact scans' maxima (i64, one per 64 vectors): the n_sel = min(r, n_groups) best groups, all of them expanded
+//   GROUPS_NOMINATED  the integer scan's maxima (u32, group-major): n_nom groups expanded, one more selected only for its key
+//   ID_LIST           no scan -- LIST mode, and every codec shape without a group-maximum scan under a filter: the ADC scores of the
+//                     filter's ascending id list, the tournament over list positions (which order as their ids do)
+//   ALL_ROWS          codec shapes without a group-maximum scan: every vector's ADC score
+struct TailSource {
+    enum Kind { GROUPS_EXACT, GROUPS_NOMINATED, ID_LIST, ALL_ROWS } kind;
+    LevelRef l0;            // GROUPS_*: the scan's maxima (the other two take their scores in the tail, into s->scores)
+    size_t n_sel, n_nom;    // GROUPS_*: groups the tournament selects / of those, expanded into candidates
+    const Pq4Params* params;   // GROUPS_NOMINATED: the certificate's parameters
+};
+
+// Everything after the scan for the Q = g.n queries of a group, as ONE chain of launches with a query dimension (the kernels are
+// latency-bound: four chains in a row cost more than the scan): the r best by ADC score -- from the candidates of the selected groups,
+// re-scored by the gather kernel in the reference's arithmetic, or straight from the tournament over a list's scores -- then, for
+// GROUPS_NOMINATED, the certificate flag (1 = provably the exact top-r of all vectors; 0 asks the caller to repeat the query through
+// the exact scan), then with base vectors the exact fast_dot re-score of those r (+ descriptor bias) and the top k.  Under a filter the
+// disallowed vectors of the selected groups are dropped at the expansion (a dropped vector is ID_NONE: the gather kernel scores it
+// INT64_MIN and the select skips it).
+// The buffers of the lane's searcher, every one at its final size for the whole group before the first launch that uses any of them
+// (an ensure that grows frees the old allocation):
+//   gkeys        the selected groups' keys [Q][n_sel] until the certificate has read them; then the final top-k's keys [Q][k]
+//   cand_ids     the candidates [Q][n_nom * 64]
+//   cand_scores  their ADC scores; once the top-r select has read them, the exact scores [Q][r]
+//   out_ids      GROUPS_*: the top-r ids [Q][r] (a list's top-r ids stay where the tournament leaves them)
+//   sel_keys     the top-r ADC scores [Q][r]
+//   misc         the final top-k's ids [Q][k]
+//   scores       ID_LIST / ALL_ROWS: the list's ADC scores
+// Neither s->gmax nor, for GROUPS_*, s->scores is written: in a pair they hold query 1's and query 0's maxima until each one's own
+// tournament has read them, and in the nomination route s->gmax holds all Q queries' maxima until theirs has.
+// lut: the group's Q tables (a pair's second query makes a group of its own for its tail, with the pair's second table)
+int scan_tail(const ScanRun& run, const ScanGroup& g, const float* lut, const TailSource& src) {
+    const mse_pq* pq = run.pq;
+    const mse_codes* c = run.c;
+    const mse_filter* f = run.f;
+    mse_searcher* s = run.lanes[g.lane].s;
+    hipStream_t st = s->stream;
+    const size_t d = pq->d, r = run.r, k = run.k, Q = (size_t)g.n;
+    const bool groups = src.kind == TailSource::GROUPS_EXACT || src.kind == TailSource::GROUPS_NOMINATED;
+    const size_t n_cand = src.n_nom * 64, n_sel = src.n_sel;   // (both 0 without groups)
+    const uint32_t* list = src.kind == TailSource::ID_LIST ? f->ids : nullptr;
+    const size_t n_list = list ? f->count : c->n;   // (a filter's count is > 0 here: an empty filter is answered without a launch)
+    if (s->gkeys.ensure(Q * std::max(k, n_sel) * 8) || s->cand_ids.ensure(Q * n_cand * 4) || s->cand_scores.ensure(Q * std::max(r, n_cand) * 8) ||
+        s->out_ids.ensure(Q * r * 4) || s->sel_keys.ensure(Q * r * 8) || s->misc.ensure(Q * k * 4) || (!groups && s->scores.ensure(n_list * 8)))
+        return -1;
+    const uint32_t* top_ids = nullptr;                      // the r best by ADC score [Q][r] ...
+    const int64_t* top_scores = s->sel_keys.as<int64_t>();  // ... and their scores
+    size_t top_stride = r;
+    if (groups) {
+#ifdef MSE_DEV_KERNELS
+        // developer library, MSE_PQ_TAIL_SKIP=mask: the nomination scan WITHOUT stages of its tail (answers are garbage, every query is
+        // reported certified): what the tail costs the scans that run beside it.  1 tournament, 2 expand + re-score, 4 exact top-r,
+        // 8 certificate (and with any bit: nothing after the certificate either)
+        static const int tail_skip = getenv("MSE_PQ_TAIL_SKIP") ? atoi(getenv("MSE_PQ_TAIL_SKIP")) : 0;
+        const int skip = src.kind == TailSource::GROUPS_NOMINATED ? tail_skip : 0;
+#else
+        const int skip = 0;
+#endif
+        uint32_t* gsel = nullptr;                           // [Q][n_sel]
+        if (!(skip & 1) && descend(s, src.l0, (int)Q, (int)n_sel, &gsel, s->gkeys.p)) return -1;
+        if (!(skip & 2) && gsel) {
+            if (f ? launch_expand_groups_masked(gsel, n_sel, src.n_nom, 64, c->n, run.mask, run.mask_words, s->cand_ids.as<uint32_t>(), n_cand, (int)Q, st)
+                  : launch_expand_groups(gsel, n_sel, src.n_nom, 64, c->n, s->cand_ids.as<uint32_t>(), n_cand, (int)Q, st)) return -1;
+            if (launch_pq_adc(lut, (int)pq->n_chunks, (int)pq->n_centroids, c->codes, c->n, s->cand_ids.as<uint32_t>(), n_cand, run.desc,
+                              (int)c->n_desc, run.scales_dev, s->cand_scores.as<int64_t>(), s->n_cu, st, (int)Q, Q > 1 ? n_cand : 0)) return -1;
+        }
+        if (!(skip & 4)) {
+            SelectArgs a{};
+            a.kind = KEY_I64; a.list_ids = s->cand_ids.as<uint32_t>(); a.list_keys = s->cand_scores.p; a.list_stride = n_cand;
+            a.n_list = n_cand; a.k = (int)r; a.out_ids = s->out_ids.as<uint32_t>(); a.out_keys = s->sel_keys.p; a.out_stride = r; a.nq = (int)Q;
+            // GROUPS_EXACT: r group maxima reach the r-th best group's key, so r vectors do: the key is a floor for the select.  This
+            // leans on the scan kernels and pq_adc_kernel producing the SAME i64 for a vector (same adds in the same order, bias added
+            // after the conversion); tests/test_gpu_pq_index_graph.py::test_group_maxima_equal_the_gathered_scores pins exactly that.
+            // Under a filter the maxima are over ALLOWED vectors, so the argument holds as long as the r-th key belongs to a group with
+            // an allowed vector.  When fewer than r groups have one, the r-th key is INT64_MIN, whose sortable form is 0: a floor of 0
+            // cuts nothing, and padding (ID_NONE) is skipped by the select before the floor is looked at (topk.hip), so it is never
+            // admitted.  (The integer maxima of GROUPS_NOMINATED are no floor for exact scores.)
+            if (src.kind == TailSource::GROUPS_EXACT && n_sel == r) a.floor_hi = s->last_kth;
+            if (launch_select(a, st)) return -1;
+        }
+        if (skip) {
+            MSE_HIP_TRY(hipMemsetAsync(run.flags_dev + g.q0, 1, Q * sizeof(int), st));
+            return 0;
+        }
+        top_ids = s->out_ids.as<uint32_t>();
+        // the vectors that must exist among the nominated: min(r, rows) -- under a filter min(r, allowed rows).  The bound from the best
+        // excluded group stays sound there: its masked maximum bounds every ALLOWED vector outside the nominated groups, and a masked
+        // vector's key (the all-zero sum) is the smallest possible
+        if (src.kind == TailSource::GROUPS_NOMINATED &&
+            launch_pq4_certify(src.params, s->gkeys.as<uint32_t>(), (int)src.n_nom, (int)n_sel, top_ids, top_scores, r,
+                               (int)std::min(r, f ? f->count : c->n), (int)Q, run.flags_dev + g.q0, st)) return -1;
+    } else {
+        if (launch_pq_adc(lut, (int)pq->n_chunks, (int)pq->n_centroids, c->codes, c->n, list, n_list, run.desc, (int)c->n_desc, run.scales_dev,
+                          s->scores.as<int64_t>(), s->n_cu, st)) return -1;
+        LevelRef l0{KEY_I64, s->scores.p, n_list, 1, n_list, false, 0};
+        uint32_t* sel = nullptr;
+        if (descend(s, l0, 1, (int)r, &sel, s->sel_keys.p)) return -1;
+        if (list && launch_map_positions(sel, r, list, st)) return -1;
+        top_ids = sel;
+    }
+    if (s->base) {
+        // exact re-score: f16(query) . base[id] (+ descriptor bias), query_disk_index.rs:168-170,477 -- the group's queries per launch
+        uint16_t* qf16 = run.lanes[g.lane].qf16;
+        if (launch_f32_to_f16(run.queries_dev + g.q0 * d, Q * d, qf16, st)) return -1;
+        if (exact_rescore(s->base, c, run.scales_dev, qf16, top_ids, Q * r, r, s->cand_scores.as<int64_t>(), st)) return -1;
+        SelectArgs a{};
+        a.kind = KEY_I64; a.list_ids = top_ids; a.list_keys = s->cand_scores.p; a.list_stride = r; a.n_list = r;
+        a.k = (int)k; a.out_ids = s->misc.as<uint32_t>(); a.out_keys = s->gkeys.p; a.out_stride = k; a.nq = (int)Q;
+        if (launch_select(a, st)) return -1;
+        top_ids = s->misc.as<uint32_t>();
+        top_scores = s->gkeys.as<int64_t>();
+        top_stride = k;
+    }
+    uint32_t* const out_ids = run.out_ids_dev + g.q0 * k;
+    int64_t* const out_scores = run.out_scores_dev + g.q0 * k;
+    if (Q == 1) {   // (one row: the plain copies the one-query tail always made, not the strided copy's kernel)
+        MSE_HIP_TRY(hipMemcpyAsync(out_ids, top_ids, k * 4, hipMemcpyDeviceToDevice, st));
+        MSE_HIP_TRY(hipMemcpyAsync(out_scores, top_scores, k * 8, hipMemcpyDeviceToDevice, st));
+    } else {
+        MSE_HIP_TRY(hipMemcpy2DAsync(out_ids, k * 4, top_ids, top_stride * 4, k * 4, Q, hipMemcpyDeviceToDevice, st));
+        MSE_HIP_TRY(hipMemcpy2DAsync(out_scores, k * 8, top_scores, top_stride * 8, k * 8, Q, hipMemcpyDeviceToDevice, st));
+    }
+    return 0;
+}
+
+// One query or a PAIR of the flat ADC scan, exact, entirely on the lane's stream (no host synchronisation):
+//   table(query) -> scan of all codes keeping one maximum per 64 vectors (a pair shares ONE pass over the codes: pq_scan64x2_kernel)
+//   -> per query its own tail (two Q = 1 chains for a pair)
+// LIST mode and codec shapes without a group-maximum scan make no pass: their tails score the filter's id list, or every vector.
+int scan_exact_group(const ScanRun& run, const ScanGroup& g) {
+    const mse_pq* pq = run.pq;
+    const mse_codes* c = run.c;
+    mse_searcher* s = run.lanes[g.lane].s;
+    const size_t lut_floats = pq->n_chunks * pq->n_centroids, n_groups = (c->n + 63) / 64;
+    const bool gm = !run.list && pq_scan_gmax_supported((int)pq->n_chunks, (int)pq->n_centroids, run.desc, (int)c->n_desc, run.scales_dev);
+    const float* lut = group_tables(run, g);
+    if (!lut) return -1;
+    // a pair: query 0's maxima in s->scores, query 1's in s->gmax
+    int64_t* gmax[2] = {nullptr, nullptr};
+    if (gm) {
+        if (s->scores.ensure(n_groups * 8) || (g.n == 2 && s->gmax.ensure(n_groups * 8))) return -1;
+        gmax[0] = s->scores.as<int64_t>();
+        gmax[1] = s->gmax.as<int64_t>();
+        if (g.n == 2 ? launch_pq_scan_gmax2(lut, lut + lut_floats, c->codes, c->n, run.desc, run.scales_dev, gmax[0], gmax[1], s->n_cu, s->stream,
+                                            run.mask, run.mask_words)
+                     : launch_pq_scan_gmax(lut, c->codes, c->n, run.desc, run.scales_dev, gmax[0], s->n_cu, s->stream, run.mask, run.mask_words))
+            return -1;
+    }
+    const size_t rg = gm ? std::min(run.r, n_groups) : 0;
+    for (int j = 0; j < g.n; j++) {
+        TailSource src{gm ? TailSource::GROUPS_EXACT : run.f ? TailSource::ID_LIST : TailSource::ALL_ROWS,
+                       LevelRef{KEY_I64, gmax[j], n_groups, 1, n_groups, false, 0}, rg, rg, nullptr};
+        if (scan_tail(run, ScanGroup{g.lane, g.q0 + j, 1}, lut + j * lut_floats, src)) return -1;
+    }
+    return 0;
+}
+
+// the next event pair of the lane's pool (mse_pq_scan_timing: around the nomination scan's launch; read and returned by scan_drain_timing)
+int scan_event_pair(mse_searcher* s, hipEvent_t te[2]) {
+    while (s->ev_pool.size() < s->ev_used + 2) {
+        hipEvent_t e = nullptr;
+        MSE_HIP_TRY(hipEventCreate(&e));
+        s->ev_pool.push_back(e);
+    }
+    te[0] = s->ev_pool[s->ev_used++];
+    te[1] = s->ev_pool[s->ev_used++];
+    return 0;
+}
+
+// How many groups to nominate: the certificate needs every group whose integer maximum lies within ~2 eps of the r-th exact
+// score.  With 12-bit tables that is a few tens of vectors at 1e8 codes (r + max(64, r / 2) groups); the 8-bit step is 16 times
+// coarser and the band holds ~0.7 r vectors on random codes (simulated at 1e7 codes, r = 200: 339 groups reach it): 2 r + 112.
+size_t pq_nominated(size_t r, int NQ) { return NQ == 4 ? r + std::max<size_t>(64, r / 2) : 2 * r + 112; }
+
+// FOUR (12-bit tables) or EIGHT (8-bit tables) queries in one pass over the codes (pq_scan64x4_kernel: integer nomination under a
+// certificate, pq.hip), then ONE tail for all of them: per query the n_nom best groups by their integer maximum (+ one more, whose key
+// bounds everything excluded) are re-scored, and flags_dev[q] = 0 asks the caller to repeat query q through the exact scan.
+int scan_nominated_group(const ScanRun& run, const ScanGroup& g) {
+    const mse_codes* c = run.c;
+    mse_searcher* s = run.lanes[g.lane].s;
+    hipStream_t st = s->stream;
+    const int NQ = g.n;
+    const float* lut = group_tables(run, g);
+    if (!lut) return -1;
+    const size_t n_groups = (c->n + 63) / 64;
+    // one more group than nominated is selected, only for its key
+    const size_t n_nom = std::min(n_groups, pq_nominated(run.r, NQ));
+    const size_t n_sel = std::min(n_groups, n_nom + 1);
+    if (n_sel > (size_t)TOPK_KMAX) return fail("pq scan: r too large for the four-query scan");
+    if (s->pq4.ensure(pq4_table_bytes() + 8 * sizeof(Pq4Params)) || s->gmax.ensure((size_t)NQ * n_groups * 4)) return -1;
+    void* table = s->pq4.p;
+    Pq4Params* params = reinterpret_cast<Pq4Params*>(s->pq4.as<char>() + pq4_table_bytes());
+    if (launch_pq4_table(lut, run.scales_dev, NQ, table, params, st, NQ)) return -1;
+    hipEvent_t te[2] = {nullptr, nullptr};
+    if (run.pq->timing) {
+        if (scan_event_pair(s, te)) return -1;
+        MSE_HIP_TRY(hipEventRecord(te[0], st));
+    }
+    if (launch_pq_scan_gmax4(table, c->codes, c->n, run.desc, s->gmax.as<uint32_t>(), s->n_cu, st, NQ, run.mask, run.mask_words)) return -1;
+    if (te[1]) MSE_HIP_TRY(hipEventRecord(te[1], st));
+    // group-major: element (q, g) at gmax[g * NQ + q]
+    return scan_tail(run, g, lut, TailSource{TailSource::GROUPS_NOMINATED, LevelRef{KEY_U32, s->gmax.p, 1, (size_t)NQ, n_groups, false, 0}, n_sel, n_nom, params});
+}
+
+// queries go through in groups that share one pass over the codes: EIGHTS (8-bit tables) and FOURS (12-bit tables) -- integer
+// nomination under a certificate, pq_scan64x4_kernel --, then a PAIR (pq_scan64x2_kernel, exact), then a single one.  (A filtered LIST
+// call shares no pass over the codes: its queries go one by one.)  The size of the next group with `remaining` queries to go:
+int scan_group_size(size_t remaining, bool eight_ok, bool four_ok, bool list) {
+    return (eight_ok && remaining >= 8) ? 8 : (four_ok && remaining >= 4) ? 4 : (remaining >= 2 && !list) ? 2 : 1;
+}
+
+// the empty answer -- no codes, or a filter that allows no row: everything is padding and no scan is launched.  1: answered, 0: go on
+int scan_answer_empty(const ScanRun& run) {
+    const size_t n_out = run.nq * run.k;
+    if (!run.block_dev)
+        for (size_t i = 0; i < n_out; i++) { run.scores[i] = INT64_MIN; run.ids[i] = MSE_ID_NONE; }
+    if (run.c->n != 0 && !(run.f && run.f->count == 0)) return 0;
+    if (run.block_dev) {   // an empty shard still hands over a block: all slots empty
+        if (launch_block_finish(nullptr, nullptr, n_out, 0, reinterpret_cast<int64_t*>(run.block_dev),
+                                reinterpret_cast<uint32_t*>(static_cast<char*>(run.block_dev) + n_out * 8), nullptr)) return -1;
+        MSE_HIP_TRY(hipStreamSynchronize(nullptr));
+    }
+    return 1;
+}
+
+// all queries (+ scales) go up in ONE copy from pinned memory; every query then runs on the streams; ONE download at the end
+int scan_upload(ScanRun& run, mse_searcher* s) {
+    mse_pq* pq = run.pq;
+    const size_t nq = run.nq, k = run.k, d = pq->d, lut_floats = pq->n_chunks * pq->n_centroids;
+    const size_t sc_off = (nq * d * 4 + 255) & ~(size_t)255;
+    const size_t sc_bytes = (run.scales && run.c->n_desc) ? run.c->n_desc * 4 : 0;
+    const size_t in_bytes = sc_off + sc_bytes, out_bytes = nq * k * 12 + nq * 4;   // scores, ids, certificate flags
+    run.prep_all = nq >= 4 && nq <= 2048;
+    const size_t n_tab = run.prep_all ? nq : 8;
+    if (pq->a.ensure(in_bytes + 256) || pq->b.ensure(n_tab * d * 4) || pq->c.ensure(n_tab * lut_floats * 4)) return -1;
+    if (s->q_stage.ensure(8 * d * 2) || s->out_scores.ensure(out_bytes)) return -1;
+    if (pq->pin.ensure(std::max(in_bytes, out_bytes), (size_t)1 << 16)) return -1;
+    memcpy(pq->pin.p, run.queries_f32, nq * d * 4);
+    if (sc_bytes) memcpy(pq->pin.as<char>() + sc_off, run.scales, sc_bytes);
+    if (hipMemcpyAsync(pq->a.p, pq->pin.p, in_bytes, hipMemcpyHostToDevice, s->stream) != hipSuccess) return fail("H2D failed");
+    run.queries_dev = pq->a.as<float>();
+    run.scales_dev = sc_bytes ? reinterpret_cast<float*>(pq->a.as<char>() + sc_off) : nullptr;
+    run.desc = run.scales_dev ? run.c->desc : nullptr;
+    run.out_scores_dev = s->out_scores.as<int64_t>();
+    run.out_ids_dev = reinterpret_cast<uint32_t*>(s->out_scores.as<char>() + nq * k * 8);
+    run.flags_dev = reinterpret_cast<int*>(s->out_scores.as<char>() + nq * k * 12);
+    run.lanes[0] = ScanLane{s, pq->b.as<float>(), pq->c.as<float>(), s->q_stage.as<uint16_t>()};
+    return 0;
+}
+
+// Groups of queries alternate between TWO streams (each with its own scratch): the chain of small kernels that follows a scan
+// (tournament, re-score of the nominated groups, selects, certificate) runs beside the next group's scan, on the CUs that scan leaves
+// free.  (A third stream -- so that group u + 2 would not queue behind group u's tail -- and 16 / 24 / 32 spare CUs were measured in
+// round 4: 0.194-0.203 ms per query at 32 per call in every combination, two streams and 8 spare CUs being the best; there is room
+// for a third lane.)  Calls of fewer than four queries stay on the one lane.  A lane bound to another base than the call's is replaced.
+int scan_lanes(ScanRun& run) {
+    mse_pq* pq = run.pq;
+    mse_searcher* s = run.lanes[0].s;
+    const size_t d = pq->d;
+    if (run.nq < 4) return 0;
+    mse_searcher** extra[2] = {&pq->lane2, &pq->lane3};
+    DevBuf* qfs[2] = {&pq->qf2, &pq->qf3};
+#ifdef MSE_DEV_KERNELS
+    static const int n_extra = getenv("MSE_PQ_LANES") ? std::min(std::max(atoi(getenv("MSE_PQ_LANES")) - 1, 0), 2) : 1;   // developer library: 1-3 streams
+#else
+    const int n_extra = 1;
+#endif
+    if (pq->t2.ensure(8 * d * 4) || pq->lut2.ensure(8 * pq->n_chunks * pq->n_centroids * 4)) return -1;
+    for (int e = 0; e < n_extra; e++) {
+        mse_searcher*& ln = *extra[e];
+        if (ln && ln->base != s->base) { mse_searcher_free(ln); ln = nullptr; }
+        if (!ln) ln = s->base ? mse_searcher_new(s->base) : scratch_searcher_new();
+        if (!ln || qfs[e]->ensure(8 * d * 2)) return -1;
+        run.lanes[e + 1] = ScanLane{ln, pq->t2.as<float>(), pq->lut2.as<float>(), qfs[e]->as<uint16_t>()};   // (several lanes imply prep_all)
+        run.n_lanes = e + 2;
+    }
+    if (hipStreamSynchronize(s->stream) != hipSuccess) return fail("H2D failed");   // uploads visible to every stream
+    return 0;
+}
+
+// On the first lane's stream the flags' initial value and, for a prep_all call, every table; then the groups, alternating between the
+// lanes; then every other lane has finished
+int scan_dispatch(ScanRun& run) {
+    mse_pq* pq = run.pq;
+    hipStream_t st = run.lanes[0].s->stream;
+    const size_t r = run.r;
+    if (hipMemsetAsync(run.flags_dev, 0xff, run.nq * 4, st) != hipSuccess) return fail("memset failed");   // non-zero = certified / exact
+    if (run.prep_all && (launch_pq_transform(pq->transform, (int)pq->d, run.queries_dev, run.nq, pq->b.as<float>(), st) ||
+                         launch_pq_lut_batch(pq->centroids, (int)pq->n_centroids, (int)pq->d, (int)pq->dpc, pq->b.as<float>(), run.nq, pq->c.as<float>(), st)))
+        return -1;
+    if (run.n_lanes > 1 && hipStreamSynchronize(st) != hipSuccess) return fail("memset failed");
+    run.four_ok = !run.list && pq_scan_gmax_supported((int)pq->n_chunks, (int)pq->n_centroids, run.desc, (int)run.c->n_desc, run.scales_dev) &&
+                  r + std::max<size_t>(64, r / 2) + 1 <= (size_t)TOPK_KMAX;
+    // eight per pass while the 8-bit certificate holds for this quantiser's data: a batch in which more than an eighth of the
+    // eight-per-pass queries had to be repeated through the exact scan switches the handle back to four per pass for good
+    run.eight_ok = run.four_ok && !pq->avoid8 && pq_nominated(r, 8) + 1 <= (size_t)TOPK_KMAX;
+    bool ok = true;
+    size_t q = 0;
+    for (size_t unit = 0; q < run.nq && ok; unit++) {
+        const ScanGroup g{(int)(unit % (size_t)run.n_lanes), q, scan_group_size(run.nq - q, run.eight_ok, run.four_ok, run.list)};
+        ok = (g.n >= 4 ? scan_nominated_group(run, g) : scan_exact_group(run, g)) == 0;
+        if (g.n == 8) run.n_in_eight += 8;   // (the eights come first: scan_group_size)
+        q += g.n;
+    }
+    for (int w = 1; w < run.n_lanes; w++)
+        if (hipStreamSynchronize(run.lanes[w].s->stream) != hipSuccess) ok = false;
+    if (!ok) return std::string(mse_last_error()).empty() ? fail("scan failed") : -1;
+    return 0;
+}
+
+// a query whose certificate did not hold (rare: the band of +-eps around its r-th score reached past the nominated groups) is
+// repeated through the exact one-query scan, into the same output rows
+int scan_repeat_uncertified(ScanRun& run) {
+    mse_pq* pq = run.pq;
+    hipStream_t st = run.lanes[0].s->stream;
+    const size_t nq = run.nq;
+    if (!run.four_ok || nq < 4) return 0;
+    std::vector<int> flags(nq);
+    if (hipMemcpyAsync(flags.data(), run.flags_dev, nq * 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        return fail("D2H failed");
+    const size_t n8 = run.n_in_eight;
+    size_t bad8 = 0;
+    for (size_t j = 0; j < n8; j++) bad8 += !flags[j];
+    // filtered batches are left out of this decision: a sparse filter legitimately fails more certificates (fewer than r allowed
+    // vectors among the nominated groups), which says nothing about the quantiser's data
+    if (!run.f && n8 && bad8 * 8 > n8) pq->avoid8 = true;
+    for (size_t j = 0; j < nq; j++)
+        if (!flags[j]) {
+            pq->last_uncertified++;
+            if (scan_exact_group(run, ScanGroup{0, j, 1})) return std::string(mse_last_error()).empty() ? fail("scan failed") : -1;
+        }
+    return 0;
+}
+
+// the results leave the first lane's stream: as a packed block on the device, or through the pinned staging into the caller's arrays
+int scan_hand_over(const ScanRun& run) {
+    mse_searcher* s = run.lanes[0].s;
+    const size_t n_out = run.nq * run.k;
+    if (run.block_dev) {
+        if (launch_block_finish(run.out_scores_dev, run.out_ids_dev, n_out, run.id_offset, reinterpret_cast<int64_t*>(run.block_dev),
+                                reinterpret_cast<uint32_t*>(static_cast<char*>(run.block_dev) + n_out * 8), s->stream) ||
+            hipStreamSynchronize(s->stream) != hipSuccess) return fail("block hand-over failed");
+        return 0;
+    }
+    if (hipMemcpyAsync(run.pq->pin.p, s->out_scores.p, n_out * 12, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
+        hipStreamSynchronize(s->stream) != hipSuccess) return fail("D2H failed");
+    memcpy(run.scores, run.pq->pin.p, n_out * 8);
+    memcpy(run.ids, run.pq->pin.as<char>() + n_out * 8, n_out * 4);
+    for (size_t i = 0; i < n_out; i++)
+        if (run.ids[i] == MSE_ID_NONE) run.scores[i] = INT64_MIN;
+    return 0;
+}
+
+// every lane is idle: the scan launches' event pairs can be read, and go back to the pools.  Two figures: each pair's own time
+// (mse_pq_scan_timing), and the SUSTAINED rate -- from the first scan's start to the last scan's end of this call, over its scans (they
+// run back to back, alternating between the streams: what a launch costs when the next one is already waiting behind it)
+void scan_drain_timing(const ScanRun& run) {
+    mse_pq* pq = run.pq;
+    const mse_searcher* first = run.lanes[0].s;
+    size_t scans = 0;
+    float span = 0.0f;
+    for (int w = 0; w < run.n_lanes; w++) {
+        mse_searcher* ln = run.lanes[w].s;
+        float ms = 0.0f;
+        if (ln->ev_used >= 2 && first->ev_used >= 2) {
+            if (hipEventElapsedTime(&ms, first->ev_pool[0], ln->ev_pool[ln->ev_used - 1]) == hipSuccess) span = std::max(span, ms);
+            scans += ln->ev_used / 2;
+        }
+        for (size_t e = 0; e + 1 < ln->ev_used; e += 2)
+            if (hipEventElapsedTime(&ms, ln->ev_pool[e], ln->ev_pool[e + 1]) == hipSuccess) { pq->scan_ms_total += ms; pq->scan_launches++; }
+    }
+    if (scans >= 4 && span > 0.0f) { pq->span_ms_total += span; pq->span_scans += scans; }
+    for (int w = 0; w < run.n_lanes; w++) run.lanes[w].s->ev_used = 0;
+}
+
+// One call of the scan, for every entry point: all checks before anything is written; a call with nothing to do; the resolved mode of a
+// filtered call (AUTO: the plan's answer for this call); then the steps.  s: the caller's searcher, or null for the quantiser's own.
+// The unfiltered entry points make exactly the launches they always made.
+int scan_call(ScanRun& run, mse_searcher* s) {
+    if (check_pq_scan(run.pq, run.c, s, run.nq, run.r, run.k, run.fa)) return -1;
+    if (run.nq == 0 || run.k == 0) return 0;
+    if (!run.queries_f32 || !(run.block_dev || (run.scores && run.ids))) return fail("null argument");
+    if (run.fa) {
+        int mode = run.fa->mode;
+        if (mode == MSE_PQ_FILTER_AUTO && mse_pq_filtered_plan(run.c->n, run.fa->f->count, run.nq, &mode)) return -1;
+        run.f = run.fa->f;
+        run.list = mode == MSE_PQ_FILTER_LIST;
+        run.mask = run.f->words;
+        run.mask_words = run.f->n_words;
+    }
+    mse_pq* pq = run.pq;
+    run.r = std::max(run.r, run.k);
+    if (const int rc = scan_answer_empty(run)) return rc < 0 ? -1 : 0;
+    std::lock_guard<std::mutex> g(pq->mu);
+    pq->last_uncertified = 0;
+    if (!s) {
+        if (!pq->scratch && !(pq->scratch = scratch_searcher_new())) return -1;
+        s = pq->scratch;
+    }
+    if (scan_upload(run, s) || scan_lanes(run) || scan_dispatch(run) || scan_repeat_uncertified(run) || scan_hand_over(run))
+        return -1;
+    scan_drain_timing(run);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mse_pq_scan_topk_batch(mse_pq* pq, const mse_codes* c, mse_searcher* s_or_null, const float* queries_f32, size_t nq,
+                           const float* scales, size_t r, size_t k, int64_t* scores, uint32_t* ids) {
+    if (!scores || !ids) return fail("null output");
+    ScanRun run{pq, c, nullptr, nq, r, k, queries_f32, scales, nullptr, 0, scores, ids};
+    return scan_call(run, s_or_null);
+}
+
+int mse_pq_scan_topk_block(mse_pq* pq, const mse_codes* c, mse_searcher* s_or_null, const float* queries_f32, size_t nq, const float* scales,
+                           size_t r, size_t k, uint64_t id_offset, void* block_dev) {
+    if (!block_dev) return fail("null output block");
+    ScanRun run{pq, c, nullptr, nq, r, k, queries_f32, scales, block_dev, id_offset, nullptr, nullptr};
+    return scan_call(run, s_or_null);
+}
+
+// test hook: the group maxima the flat scan nominates with -- lut1 == null: pq_scan64_kernel<true> for one table; otherwise
+// pq_scan64x2_kernel for the pair.  out0 / out1: [ceil(n / 64)] i64 on the host.
 static int debug_pq_group_max(mse_pq* pq, const mse_codes* c, const mse_filter* f, const float* lut0, const float* lut1, const float* scales,
                               int64_t* out0, int64_t* out1);
 int mse_debug_pq_group_max(mse_pq* pq, const mse_codes* c, const float* lut0, const float* lut1, const float* scales, int64_t* out0,
@@ -1201,14 +1295,10 @@ void pq_run_batch(mse_pq* pq, std::vector<DispatchReq*>& batch) {
 
 int mse_pq_scan_topk(mse_pq* pq, const mse_codes* c, mse_searcher* s_or_null, const float* query_f32,
                      const float* scales, size_t r, size_t k, int64_t* scores, uint32_t* ids) {
-    if (!pq || !c) return fail("null quantiser or codes");
-    if (!query_f32 || !scores || !ids) return fail("null argument");
     // argument errors belong to this caller alone: they never enter the queue
-    if (c->code_size != pq->n_chunks) return fail("code size does not match the quantiser");
+    if (check_pq_scan(pq, c, s_or_null, 1, r, k, nullptr)) return -1;
+    if (!query_f32 || !scores || !ids) return fail("null argument");
     if (k == 0) return 0;
-    if (std::max(r, k) > (size_t)TOPK_KMAX - 64) return fail("r too large (max 1984)");
-    if (s_or_null && s_or_null->base && s_or_null->base->n != c->n) return fail("base and codes differ in length");
-    if (s_or_null && s_or_null->base && s_or_null->base->d != pq->d) return fail("base width differs from the quantiser");
     {
         std::lock_guard<std::mutex> g(pq->co_mu);
         if (!pq->co) {
@@ -1229,7 +1319,7 @@ int mse_pq_scan_topk(mse_pq* pq, const mse_codes* c, mse_searcher* s_or_null, co
 // ---- the flat scan over an allowed-row set (include/mse.h) ----
 // Where LIST overtakes SCAN.  The rule is a count of bytes:
 //   SCAN streams 64 code bytes + 4 descriptor bytes for every one of the n rows, once per PASS; a batch of nq queries makes
-//        nq / 8 passes of eight, then one of four, one pair and one single for what is left (pq_scan_topk_batch_impl);
+//        nq / 8 passes of eight, then one of four, one pair and one single for what is left (scan_group_size);
 //   LIST gathers one 64-byte code row + 4 descriptor bytes per allowed row PER QUERY.  A gathered 64-byte row occupies half of a
 //        128-byte line, so unless its neighbour is allowed too it moves twice its size: PQ_LIST_BYTE_COST = 2.
 // That alone -- LIST when nq * allowed * 2 <= passes * n -- was the first, unmeasured form.  Measured once (scripts/filtered_pq_probe.py,
@@ -1246,8 +1336,8 @@ int mse_pq_filtered_plan(size_t n_codes, size_t allowed, size_t nq, int* mode_ou
     if (!mode_out) return fail("pq_filtered_plan: null argument");
     if (allowed > n_codes) return fail("pq_filtered_plan: more allowed rows than codes");
     if (nq == 0) return fail("pq_filtered_plan: nq must be positive");
-    const size_t rem = nq % 8;
-    const size_t passes = nq / 8 + (rem >= 4 ? 1 : 0) + ((rem % 4) >= 2 ? 1 : 0) + (rem % 2);
+    size_t passes = nq / 8;   // the eights, then the groups the dispatch makes of what is left
+    for (size_t rem = nq % 8; rem; rem -= (size_t)scan_group_size(rem, true, true, false)) passes++;
     // (in double: the products pass 2^64 only far beyond any real call, but the comparison must not wrap)
     const double list_cost = (double)nq * ((double)allowed * PQ_ROW_BYTES * PQ_LIST_BYTE_COST + PQ_LIST_FIXED_BYTES);
     const double scan_cost = (double)passes * (double)n_codes * PQ_ROW_BYTES;
@@ -1255,27 +1345,11 @@ int mse_pq_filtered_plan(size_t n_codes, size_t allowed, size_t nq, int* mode_ou
     return 0;
 }
 
-// argument checks of the three filtered entry points: all before anything is written; *list = the resolved mode is LIST
-static int pq_filtered_args(mse_pq* pq, const mse_codes* c, const mse_filter* f, const mse_searcher* s, size_t nq, size_t r, size_t k, int mode,
-                            bool* list) {
-    if (!pq || !c) return fail("null quantiser or codes");
-    if (check_pq_filter(pq, c, f)) return -1;
-    if (mode != MSE_PQ_FILTER_AUTO && mode != MSE_PQ_FILTER_SCAN && mode != MSE_PQ_FILTER_LIST) return fail("unknown mode");
-    if (c->code_size != pq->n_chunks) return fail("code size does not match the quantiser");
-    if (std::max(r, k) > (size_t)TOPK_KMAX - 64) return fail("r too large (max 1984)");
-    if (s && s->base && s->base->n != c->n) return fail("base and codes differ in length");
-    if (s && s->base && s->base->d != pq->d) return fail("base width differs from the quantiser");
-    if (mode == MSE_PQ_FILTER_AUTO && nq && mse_pq_filtered_plan(c->n, f->count, nq, &mode)) return -1;
-    *list = mode == MSE_PQ_FILTER_LIST;
-    return 0;
-}
 int mse_pq_scan_topk_batch_filtered(mse_pq* pq, const mse_codes* c, const mse_filter* f, mse_searcher* s_or_null, const float* queries_f32,
                                     size_t nq, const float* scales, size_t r, size_t k, int mode, int64_t* scores, uint32_t* ids) {
-    bool list = false;
-    if (pq_filtered_args(pq, c, f, s_or_null, nq, r, k, mode, &list)) return -1;
-    if (nq == 0 || k == 0) return 0;
-    if (!queries_f32 || !scores || !ids) return fail("null argument");
-    return pq_scan_topk_batch_impl(pq, c, s_or_null, queries_f32, nq, scales, r, k, scores, ids, 0, nullptr, f, list);
+    const PqFilterArg fa{f, mode};
+    ScanRun run{pq, c, &fa, nq, r, k, queries_f32, scales, nullptr, 0, scores, ids};
+    return scan_call(run, s_or_null);
 }
 // (one query per call: straight to the batch path -- filtered calls do not meet in the quantiser's coalescer)
 int mse_pq_scan_topk_filtered(mse_pq* pq, const mse_codes* c, const mse_filter* f, mse_searcher* s_or_null, const float* query_f32,
@@ -1284,11 +1358,9 @@ int mse_pq_scan_topk_filtered(mse_pq* pq, const mse_codes* c, const mse_filter* 
 }
 int mse_pq_scan_topk_block_filtered(mse_pq* pq, const mse_codes* c, const mse_filter* f, mse_searcher* s_or_null, const float* queries_f32,
                                     size_t nq, const float* scales, size_t r, size_t k, int mode, uint64_t id_offset, void* block_dev) {
-    bool list = false;
-    if (pq_filtered_args(pq, c, f, s_or_null, nq, r, k, mode, &list)) return -1;
-    if (nq == 0 || k == 0) return 0;
-    if (!queries_f32 || !block_dev) return fail("null argument");
-    return pq_scan_topk_batch_impl(pq, c, s_or_null, queries_f32, nq, scales, r, k, nullptr, nullptr, id_offset, block_dev, f, list);
+    const PqFilterArg fa{f, mode};
+    ScanRun run{pq, c, &fa, nq, r, k, queries_f32, scales, block_dev, id_offset, nullptr, nullptr};
+    return scan_call(run, s_or_null);
 }
 
 int64_t mse_descriptor_product(const float* scales, size_t n_descriptors, const uint8_t* descriptors, uint32_t id) {

@@ -288,6 +288,20 @@ int exact_pass_list(mse_searcher* s, int nq_pass, int k, uint64_t id_offset, int
                     const uint32_t* ids, size_t n, const ListBias* bias, const mse_groups* g = nullptr, const uint32_t* dst_rows = nullptr);
 // a grouping may be used on base b: same device, no longer than the rows (group_api.hip); 0, or -1 with the error set
 int check_groups(const mse_base* b, const mse_groups* g);
+// The arguments of a PQ flat scan (api_pq.hip), in the order every entry point reports them: the handles; of a filtered call (fa) the
+// filter -- given, no longer than the codes, on the quantiser's device -- and its mode; code size against the quantiser; max(r, k)
+// within the tournament's limit; of a searcher with a base, its length against the codes and its width against the quantiser.
+// An unfiltered call with nothing to do (nq or k zero) is asked for no more than handles and code size.  0, or -1 with the error set.
+struct PqFilterArg { const mse_filter* f; int mode; };
+int check_pq_scan(const mse_pq* pq, const mse_codes* c, const mse_searcher* s, size_t nq, size_t r, size_t k, const PqFilterArg* fa);
+// ... and the two of its checks that stand alone: a sharded call has no single quantiser to hand and checks its numbers before its
+// shards check the rest
+int check_pq_mode(int mode);
+int check_pq_r(size_t r, size_t k);
+// The exact re-score of a PQ scan's top-r (query_disk_index.rs:168-170,477): out[i] = f16 query . base row ids[i], per_query ids to a
+// query of q16, + the descriptor bias only when scales AND descriptors are there (api_pq.hip)
+int exact_rescore(const mse_base* b, const mse_codes* c, const float* scales_dev, const void* q16, const uint32_t* ids, size_t n, size_t per_query,
+                  int64_t* out, hipStream_t st);
 // the dense path's scratch is bounded: queries one dense pass may take (1 .. 8) with a group table of g_len entries of `bytes` bytes each
 int dense_pass_queries(size_t g_len, size_t bytes);
 // the collapse half of a round of the grouped search's prefix path (bruteforce.hip), shared with the flat index

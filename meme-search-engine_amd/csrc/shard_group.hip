@@ -728,8 +728,7 @@ static int pq_rescore_members(const mse_base* b, const mse_codes* codes, uint64_
     int64_t* ex = bb.as<int64_t>();
     hipLaunchKernelGGL(members_local_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, gids, n, first_row, (uint64_t)b->n, local);
     MSE_HIP_TRY(hipGetLastError());
-    if (launch_score_rows(b->dev, b->n, (int)b->d, q16, false, local, n, r, ex, nullptr, st)) return -1;
-    if (scales_dev && codes->n_desc && launch_add_descriptor(local, n, codes->desc, (int)codes->n_desc, codes->n, scales_dev, ex, st)) return -1;
+    if (exact_rescore(b, codes, scales_dev, q16, local, n, r, ex, st)) return -1;
     return launch_block_finish(ex, local, n, first_row, reinterpret_cast<int64_t*>(blk), reinterpret_cast<uint32_t*>(blk + n * 8), st);
 }
 
@@ -748,7 +747,7 @@ static int pq_scan_topk_impl(mse_shard_group* G, const mse_shard_filter* sf, int
     if (!G || !queries_f32 || !scores || !ids) return fail("shard group pq scan: null argument");
     if (nq == 0 || k == 0) return 0;
     if (r < k) r = k;
-    if (r > (size_t)TOPK_KMAX - 64) return fail("r too large (max 1984)");
+    if (check_pq_r(r, k)) return -1;
     for (const Shard& sh : G->shards) if (!sh.pq || !sh.codes) return fail("shard group: a shard has no codec / codes attached (mse_shard_group_attach_pq)");
     const size_t d = G->d, n_desc = G->shards[0].codes->n_desc;
     const bool bias = scales && n_desc;
@@ -806,7 +805,7 @@ int mse_shard_group_pq_scan_topk_filtered(mse_shard_group* G, const mse_shard_fi
                                           size_t r, size_t k, int mode, int64_t* scores, uint32_t* ids) {
     if (!G) return fail("shard group pq scan: null argument");
     if (!sf) return fail("shard group: null shard filter");
-    if (mode != MSE_PQ_FILTER_AUTO && mode != MSE_PQ_FILTER_SCAN && mode != MSE_PQ_FILTER_LIST) return fail("unknown mode");
+    if (check_pq_mode(mode)) return -1;
     {
         std::lock_guard<std::mutex> call(G->call_mu);   // (a stale filter is refused even by a call that has nothing to do)
         if (check_shard_filter(G, sf)) return -1;
@@ -818,7 +817,7 @@ int mse_shard_group_pq_scan_topk_filtered(mse_shard_group* G, const mse_shard_fi
 int mse_shard_group_pq_scan_topk_grouped(mse_shard_group* G, const mse_shard_groups* sg, const mse_shard_filter* sf, const float* queries_f32,
                                          const float* scales, size_t nq, size_t r, size_t k, int mode, int64_t* scores, uint32_t* ids) {
     if (!G) return fail("shard group pq scan: null argument");
-    if (sf && mode != MSE_PQ_FILTER_AUTO && mode != MSE_PQ_FILTER_SCAN && mode != MSE_PQ_FILTER_LIST) return fail("unknown mode");
+    if (sf && check_pq_mode(mode)) return -1;
     {
         std::lock_guard<std::mutex> call(G->call_mu);
         if (sf && check_shard_filter(G, sf)) return -1;
@@ -1191,7 +1190,7 @@ static int comm_pq_scan_impl(mse_comm* c, mse_pq* pq, const mse_codes* codes, ms
     if (!c || !pq || !codes || !s || !s->base || !queries_f32) return fail("comm pq scan: null argument");
     if (nq == 0 || k == 0) return 0;
     if (r < k) r = k;
-    if (r > (size_t)TOPK_KMAX - 64) return fail("r too large (max 1984)");
+    if (check_pq_r(r, k)) return -1;
     const size_t d = s->base->d, n_desc = codes->n_desc, n = nq * r;
     const bool bias = scales && n_desc;
     hipStream_t st = s->stream;
@@ -1224,7 +1223,7 @@ int mse_comm_pq_scan_topk_filtered(mse_comm* c, mse_pq* pq, const mse_codes* cod
                                    const float* scales, size_t nq, size_t r, size_t k, int mode, uint64_t first_row, void* scores_dev,
                                    void* ids_dev) {
     if (!f) return fail("comm pq scan: null filter");
-    if (mode != MSE_PQ_FILTER_AUTO && mode != MSE_PQ_FILTER_SCAN && mode != MSE_PQ_FILTER_LIST) return fail("unknown mode");
+    if (check_pq_mode(mode)) return -1;
     return comm_pq_scan_impl(c, pq, codes, s, f, mode, queries_f32, scales, nq, r, k, first_row, scores_dev, ids_dev);
 }
 

@@ -108,6 +108,60 @@ def test_subset_identity_ragged_and_tied(gpu, mse, orc, n, r, k):
         f.close()
 
 
+@pytest.mark.parametrize("n", [70, 4097])
+@pytest.mark.parametrize("codec", ["64 x 256, three descriptors", "8 x 8"])
+def test_full_score_route(gpu, mse, orc, codec, n):
+    """The codec shapes without a group-maximum scan -- 64 x 256 with three descriptor bytes per row, and 8 chunks x 8 centroids --
+    score every row (unfiltered) or the filter's id list (either mode).  Five queries per batch (two pairs and a single): the batch
+    and the one-by-one calls equal the oracle pipeline bit for bit, and the all-rows filter equals the unfiltered call."""
+    r, k = 64, 10
+    rng = np.random.default_rng(n)
+    if codec == "8 x 8":
+        d, dpc, nc = 128, 16, 8
+        desc = scales = None
+    else:
+        d, dpc, nc = D, 18, 256
+        desc = rng.integers(0, 3, size=(n, 3), dtype=np.uint8)
+        scales = np.array([0.25, -0.125, 0.5], np.float32) / np.float32(512)
+    cents, T, _, _ = make_pq(orc, d, dpc, nc)
+    opq, gpq = orc.PQ(cents, T, dpc, d), mse.ProductQuantizer(cents, T, dpc, d)
+    codes = rng.integers(0, nc, size=(n, d // dpc), dtype=np.uint8)
+    gcodes = mse.Codes(codes, desc)
+    qs = (rng.standard_normal((5, d)) / np.sqrt(d)).astype(np.float32)
+    luts = [opq.preprocess_query(q) for q in qs]
+    bias = None if desc is None else opq.adc_desc(np.zeros((d // dpc, nc), np.float32), codes, desc, scales)
+    searchers = [None]
+    base = qhs = None
+    if d == D:   # (the re-score at the width it is tested at)
+        base = orc.f16_bits((rng.standard_normal((n, D)) / np.sqrt(D)).astype(np.float32))
+        qhs = [orc.f16_bits(q) for q in qs]
+        searchers.append(mse.Searcher(mse.VectorList.from_f16s(base, D)))
+    masks = filters_for(n, r, k, rng)
+    for s in searchers:
+        def want_for(allowed):
+            return [oracle_topk(orc, opq, luts[j], codes, bias, allowed, r, k, base if s else None, qhs[j] if s else None) for j in range(5)]
+        want = want_for(np.arange(n))
+        us, ui = gpq.scan_topk_batch(gcodes, qs, r, k, s, scales)
+        for j in range(5):
+            tag = (s is not None, j)
+            assert np.array_equal(ui[j], want[j][1]) and np.array_equal(us[j], want[j][0]), tag
+            s1, i1 = gpq.scan_topk(gcodes, qs[j], r, k, s, scales)
+            assert np.array_equal(s1, us[j]) and np.array_equal(i1, ui[j]), tag
+        for name in ("random 50 %", "a count below r", "none", "all rows"):
+            f = mse.RowFilter(masks[name])
+            want = want_for(np.flatnonzero(masks[name]))
+            for mode in MODES:
+                got_s, got_i = gpq.scan_topk_batch_filtered(gcodes, f, qs, r, k, s, scales, mode)
+                for j in range(5):
+                    tag = (name, s is not None, mode, j)
+                    assert np.array_equal(got_i[j], want[j][1]) and np.array_equal(got_s[j], want[j][0]), tag
+                    s1, i1 = gpq.scan_topk_filtered(gcodes, f, qs[j], r, k, s, scales, mode)
+                    assert np.array_equal(s1, got_s[j]) and np.array_equal(i1, got_i[j]), tag
+                if name == "all rows":
+                    assert np.array_equal(got_s, us) and np.array_equal(got_i, ui), (s is not None, mode)
+            f.close()
+
+
 def group_filters(n, rng):
     """random 50 %, random 1/64 and a filter shorter than the codes, each with some groups fully excluded"""
     g = np.arange(n) // 64
