@@ -345,6 +345,29 @@ __global__ __launch_bounds__(W * 64) void scan_mfma_kernel(const uint16_t* __res
 // Code object: register and scratch figures at launch_scan_mfma's 320-query branch.  The masked form (filtered search) spills two
 // registers with this order and keeps the every-other-group one.
 //
+// MID != 0 (the search kernel, GR = 64: plain, masked and tile-subset form): a row stage is recycled in the MIDDLE of the K block that
+// consumes it, and rows are fetched two blocks ahead -- no more LDS, no more registers.
+//   - Row block kb lives in stage kb & 1 (the K-block count is even).  The first tile's prologue fetches blocks 0 and 1, one into each
+//     stage, and query tile 0; vmcnt(0); barrier.
+//   - First half of iteration kb (MFMA groups t < NCTW, k step 0): the QI query pieces of tile kb + 1, in front of groups 0, 2, .. 8.
+//     No row pieces.  The A fragments of k step 1 are read at ct == NCTW - 2 as before, so by group NCTW every read of the stage is issued.
+//   - In front of group NCTW: s_waitcnt lgkmcnt(0) (those reads have returned), then a barrier, fenced for the scheduler on both
+//     sides.  Behind it no wave of the workgroup reads stage kb & 1 again in this iteration.  Every wave reaches it: it hangs on a
+//     constant of the unrolled loop, not on a lane or a wave, and the only early exit of the kernel is in front of the first barrier.
+//   - Second half: the four row pieces of block kb + 2 into stage kb & 1, in front of groups NCTW + 1, + 3, + 5, + 7.  Past the end of
+//     the tile, blocks nkb and nkb + 1 are blocks 0 and 1 of the workgroup's next tile (rn[]): a tile starts with its first two blocks
+//     in LDS or in flight.  Behind its last tile rn[] repeats rp[]: two blocks land in stages nobody reads again, and the vmcnt(0) at
+//     the end of the kernel waits for them.  (Fetching nothing there needs a uniform branch per piece and one at the closing wait;
+//     with those in the K loop hipcc spills 60 to 80 registers.)
+//   - Closing wait vmcnt(4), barrier.  A wave's loads and stores retire in order and the four youngest are the row pieces just
+//     issued, so everything older has landed: this iteration's query pieces and this wave's half of block kb + 1 (issued in the second
+//     half of iteration kb - 1); the partner's half is covered by the partner's own wait in front of the same barrier.  The epilogue's
+//     stores and atomics lie between two tiles in that queue and only make a wait stricter.
+// Rows get about 1.5 K blocks of flight instead of 0.85, query pieces 0.5 to 1 instead of at most 0.7.  The MFMAs, their order and their
+// operands are the same, so every group maximum is bit-identical.  MEASURED (profiles/scan_midblock_prof.txt, scan_midblock_ab.txt): the
+// closing vmcnt wait falls from 430-470 cycles per K block to 50, but most of that comes back at the two barriers and in the issue
+// stretch (stamped cycles per K block: 3 205 -> 3 150 dense, 3 245 -> 3 225 thresholded); whole steps at 1e8 rows gain about 2 %.
+//
 // The turn-over between two row tiles of the search kernel (BN = 320, GR = 64: TURN; plain, masked and tile-subset form).  Between
 // the last barrier of a tile and the first K block of the next all eight waves are in the same phase and no MFMA issues; the cycle
 // stamps (PROF = 1, MSE_SCAN_ABL=33, profiles/scan_turnover_prof.txt) put that stretch at 8.3 % (dense) and 9.1 % (thresholded) of a
@@ -367,10 +390,11 @@ typedef float float16v __attribute__((ext_vector_type(16)));
 #ifdef MSE_DEV_KERNELS
 // developer profile of the 2-D kernel (PROF = 1): shader cycles a wave spends [0] issuing a K block (barrier release -> closing wait),
 // [1] in the closing vmcnt wait, [2] at the barrier; [3] = K blocks counted; [4] in the turn-over between the K loops of two row tiles
-// (a tile's prologue, up to its first K block, and its epilogue, from its last closing barrier on), [5] = tiles counted.  s_memtime
+// (a tile's prologue, up to its first K block, and its epilogue, from its last closing barrier on), [5] = tiles counted, [6] at the
+// mid-block barrier of the MID schedule (its lgkmcnt wait and the barrier; taken out of [0]).  s_memtime
 // stamps sit where lgkmcnt is drained anyway.  MSE_SCAN_2D=161: the 256-query kernel; MSE_SCAN_ABL=33: the 320-query search kernel
 // (64 rows per maximum), plain and tile-subset form.
-__device__ unsigned long long g_scan_prof[6];
+__device__ unsigned long long g_scan_prof[7];
 __device__ __forceinline__ uint32_t memtime() { return (uint32_t)__builtin_amdgcn_s_memtime(); }   // deltas fit 32 bits
 #endif
 
@@ -381,7 +405,7 @@ template <> struct is_tile_subset<ScanSparse> : std::true_type {};
 template <typename... M> __device__ __forceinline__ ScanSparse tile_subset_of(const M&...) { return ScanSparse{}; }
 __device__ __forceinline__ ScanSparse tile_subset_of(const ScanSparse& sp) { return sp; }
 
-template <int S, int MF, int PROF = 0, int BN = 256, int GR = 32, typename... Mask>
+template <int S, int MF, int PROF = 0, int BN = 256, int GR = 32, int MID = 0, typename... Mask>
 __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __restrict__ base, size_t n_rows, int d,
                                                              const uint4* __restrict__ packed_ro,
                                                              float* __restrict__ gmax, int nq_pad, size_t n_tiles, uint32_t y_packed, uint32_t y_cols,
@@ -393,12 +417,13 @@ __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __r
     static_assert(!SPF || (BN == 320 && GR == 64), "a tile subset: the 320-query search pass only");
     static_assert(BN == 256 || (BN == 320 && MF == 16 && S == 2), "320 queries: 16x16x32 tiles on the two-stage ring only");
     static_assert(GR == 32 || (GR == 64 && MF == 16), "rows per written maximum: 32, or the wave's 64");
+    static_assert(MID == 0 || (S == 2 && BN == 320 && (PROF == 0 || PROF == 1)), "the mid-block barrier: the two-stage ring of the 320-query kernel");
     constexpr int HALF = BN / 2;             // queries of one query half
     constexpr int QT_BYTES = BN * 128;
     constexpr int QI = BN / 64;              // DMA pieces per wave per query tile: 8 waves x QI x 64 lanes = the tile's BN x 8 slots
     constexpr bool XF = S == 2 && PROF != 4; // two-stage ring: row pieces FIRST (see the closing wait); PROF = 4: query pieces first;
                                              // PROF = 5: rows first, one piece in front of every other MFMA group as in the S = 3 form
-    constexpr int CLOSE = S == 2 ? 0 : 4;    // DMAs that may still fly at the closing barrier
+    constexpr int CLOSE = S == 2 && !MID ? 0 : 4;   // DMAs that may still fly at the closing barrier (MID: the row pieces of block kb + 2)
     constexpr int RG_BYTES = 64 * 128;       // one K block of a row group
     constexpr bool TURN = BN == 320 && GR == 64;   // the search kernel's short turn-over between two row tiles (header comment)
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -439,7 +464,7 @@ __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __r
 #pragma unroll
         for (int u = 0; u < QI; u++) dma16(packed + u * 1024, qdst + u * 1024);
 #pragma unroll
-        for (int j = 0; j < S - 1; j++)
+        for (int j = 0; j < (MID ? S : S - 1); j++)   // MID: blocks 0 and 1, one into each stage
 #pragma unroll
             for (int u = 0; u < 4; u++) dma16(rp[u] + (size_t)(j % nkb) * 128, xbase + j * RG_BYTES + (qh * 4 + u) * 1024);
     }
@@ -465,7 +490,7 @@ __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __r
 
     int buf = 0;
 #ifdef MSE_DEV_KERNELS
-    uint32_t pt_issue = 0, pt_wait = 0, pt_bar = 0, pt_n = 0, pt_last = 0, pt_turn = 0, pt_tiles = 0;
+    uint32_t pt_issue = 0, pt_wait = 0, pt_bar = 0, pt_n = 0, pt_last = 0, pt_turn = 0, pt_tiles = 0, pt_mid = 0;
     if constexpr (PROF == 1) pt_last = memtime();
 #endif
     while (true) {
@@ -511,10 +536,13 @@ __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __r
             for (int j = 0; j < S; j++) {
                 const int kb = kb0 + j;
                 const int kq = kb + 1 == nkb ? 0 : kb + 1;
-                const int kf = kb + S - 1;
+                const int kf = MID ? kb + 2 : kb + S - 1;   // the row block fetched in this iteration
                 const bool x_next = kf >= nkb;
                 const size_t xoff = (size_t)(kf >= nkb ? kf - nkb : kf) * 128;
-                char* const xdst = xbase + ((j + S - 1) % S) * RG_BYTES + qh * 4096;
+                // MID: into the stage being consumed, behind the mid-block barrier.  (Behind its last tile a workgroup has nothing to
+                // fetch; rn[] then repeats rp[] and the two blocks land in stages nobody reads again.  Skipping them takes a uniform
+                // branch per piece and another at the closing wait, and with those hipcc spills 60 to 80 registers.)
+                char* const xdst = xbase + (MID ? j : (j + S - 1) % S) * RG_BYTES + qh * 4096;
                 const char* const qsrc = packed + (size_t)kq * QT_BYTES;
                 char* const qdst = qbase + (buf ^ 1) * QT_BYTES + wave * (QI * 1024);
                 auto issue_piece = [&](int p) {
@@ -542,9 +570,42 @@ __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __r
                         for (int rt = 0; rt < NRT; rt++) a[(ks + 1) & 1][rt] = as_half8(xs[rt * (MF * 8) + slot(ks + 1)]);
                     }
                     __builtin_amdgcn_sched_barrier(0);
+                    // MID: the mid-block barrier.  The A fragments of both k steps have been read (ct == NCTW - 2 above) and the lgkmcnt
+                    // wait retires them; behind the barrier no wave reads this row stage again before the closing barrier, so the row
+                    // pieces of block kb + 2 may land in it.  Every wave reaches it: t is a constant of the unrolled loop
+                    constexpr int MBAR = NCTW + (MID == 4 ? 1 : 0);
+                    if constexpr (MID != 0) {
+                        if (t == MBAR) {
+#ifdef MSE_DEV_KERNELS
+                            uint32_t m0 = 0;
+                            if constexpr (PROF == 1) m0 = memtime();
+#endif
+                            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                            __builtin_amdgcn_sched_barrier(0);
+                            __builtin_amdgcn_s_barrier();
+                            __builtin_amdgcn_sched_barrier(0);
+#ifdef MSE_DEV_KERNELS
+                            if constexpr (PROF == 1) {
+                                pt_mid += memtime() - m0;
+                                __builtin_amdgcn_sched_barrier(0);
+                            }
+#endif
+                        }
+                    }
                     {
                         constexpr int STEP = NT / (QI + 4);
                         int pc = -1;   // the DMA piece issued in front of MFMA group t (t is a constant of the unrolled loop)
+                        // MID: query pieces in the first half (in front of groups 0, 2, .. 8), row pieces behind the mid-block barrier:
+                        // MID = 2 (the product's) in front of groups NCTW + 1, + 3, + 5, + 7; MID = 1 in front of NCTW .. NCTW + 3.
+                        // Two more developer placements: MID = 3 as 1 with the queries in front of groups 1 .. 5; MID = 4 as 1 with the
+                        // barrier and the rows one group later
+                        if constexpr (MID != 0) {
+                            if (t < NCTW) {
+                                if (MID == 3 ? (t >= 1 && t <= QI) : (t % 2 == 0 && t / 2 < QI)) pc = 4 + (MID == 3 ? t - 1 : t / 2);
+                            } else if (MID == 2) {
+                                if ((t - MBAR) % 2 == 1 && (t - MBAR) / 2 < 4) pc = (t - MBAR) / 2;
+                            } else if (t >= MBAR && t - MBAR < 4) pc = t - MBAR;
+                        } else
                         // row pieces before groups 1-4, query pieces before 6, 8, ...; the masked form keeps the every-other-group
                         // order of PROF = 5: with the early order it spills two registers (12 B of scratch)
                         if constexpr (S == 2 && PROF != 4 && PROF != 5 && !MASKED) {
@@ -576,6 +637,8 @@ __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __r
                 } else
 #endif
                 {
+                    // MID: the CLOSE youngest loads are the row pieces of block kb + 2, issued behind the mid-block barrier of every
+                    // iteration; everything older -- this iteration's query pieces, the rows of block kb + 1 -- has landed
                     vm_wait<CLOSE>();
 #ifdef MSE_DEV_KERNELS
                     if constexpr (PROF != 2)   // PROF = 2: timing ablation WITHOUT the barrier (racy, results meaningless)
@@ -723,9 +786,10 @@ __global__ __launch_bounds__(W * 64) void scan_mfma2d_kernel(const uint16_t* __r
 #ifdef MSE_DEV_KERNELS
     if constexpr (PROF == 1) {
         if (lane == 0) {
-            atomicAdd(&g_scan_prof[0], (unsigned long long)pt_issue); atomicAdd(&g_scan_prof[1], (unsigned long long)pt_wait);
+            atomicAdd(&g_scan_prof[0], (unsigned long long)(pt_issue - pt_mid)); atomicAdd(&g_scan_prof[1], (unsigned long long)pt_wait);
             atomicAdd(&g_scan_prof[2], (unsigned long long)pt_bar); atomicAdd(&g_scan_prof[3], (unsigned long long)pt_n);
             atomicAdd(&g_scan_prof[4], (unsigned long long)pt_turn); atomicAdd(&g_scan_prof[5], (unsigned long long)pt_tiles);
+            if constexpr (MID != 0) atomicAdd(&g_scan_prof[6], (unsigned long long)pt_mid);
         }
     }
 #endif
@@ -922,12 +986,25 @@ int launch_2s(size_t grid, hipStream_t stream, const uint16_t* base, size_t n_ro
 }
 #endif
 
-template <int S, int MF, int PROF = 0, int BN = 256, int GR = 32, typename... Mask>
+template <int S, int MF, int PROF = 0, int BN = 256, int GR = 32, int MID = 0, typename... Mask>
 int launch_2d(size_t grid, hipStream_t stream, const uint16_t* base, size_t n_rows, int d, const uint4* packed,
               float* group_max, int nq_pad, Mask... mask) {
     const size_t lds = 2 * (size_t)(BN * 128) + (size_t)4 * S * 8192;   // 160 KiB at 256 queries (S = 3), 144 KiB at 320 (S = 2)
-    return launch_kernel(scan_mfma2d_kernel<S, MF, PROF, BN, GR, Mask...>, lds, grid, stream, base, n_rows, d, packed, group_max, nq_pad, mask...);
+    return launch_kernel(scan_mfma2d_kernel<S, MF, PROF, BN, GR, MID, Mask...>, lds, grid, stream, base, n_rows, d, packed, group_max, nq_pad, mask...);
 }
+
+// The schedule of the 320-query search kernels (scan_mfma2d_kernel, MID; 64 rows per maximum: plain, masked and tile-subset form alike):
+// the mid-block barrier and row blocks two ahead, the row pieces in front of every other MFMA group of the second half (MID = 2, the
+// best of the four placements measured: profiles/scan_midblock_prof.txt, scan_midblock_ab.txt).  0 = the schedule before it, in which
+// everything an iteration issues lands inside it; the 32-row forms keep that one (their masked form spills four registers with MID).
+constexpr int MID_320 = 2;
+#ifdef MSE_DEV_KERNELS
+// developer library: MSE_SCAN_MID=0 .. 4 selects the schedule of the unmasked 64-row forms (0 the one before, 1, 3, 4 the other placements)
+int dev_scan_mid() {
+    const int m = getenv("MSE_SCAN_MID") ? atoi(getenv("MSE_SCAN_MID")) : MID_320;
+    return m >= 0 && m <= 4 ? m : MID_320;
+}
+#endif
 
 }  // namespace
 
@@ -1024,8 +1101,25 @@ int launch_scan_mfma(const uint16_t* base, size_t n_rows, int d, const uint16_t*
     if (!mask && group_rows == 64 && nq_pad == 320 && getenv("MSE_SCAN_ABL") && atoi(getenv("MSE_SCAN_ABL")) == 32)
         rc = launch_2d<2, 16, 6, 320, 64>(grid, stream, base, n_rows, d, packed, group_max, gs);
     // MSE_SCAN_ABL=33: the same kernel with the cycle stamps of PROF = 1 (mse_dev_scan_prof); its results are the product kernel's
-    if (!mask && group_rows == 64 && nq_pad == 320 && getenv("MSE_SCAN_ABL") && atoi(getenv("MSE_SCAN_ABL")) == 33)
-        rc = launch_2d<2, 16, 1, 320, 64>(grid, stream, base, n_rows, d, packed, group_max, gs);
+    if (!mask && group_rows == 64 && nq_pad == 320 && getenv("MSE_SCAN_ABL") && atoi(getenv("MSE_SCAN_ABL")) == 33) {
+        switch (dev_scan_mid()) {
+            case 0: rc = launch_2d<2, 16, 1, 320, 64, 0>(grid, stream, base, n_rows, d, packed, group_max, gs); break;
+            case 1: rc = launch_2d<2, 16, 1, 320, 64, 1>(grid, stream, base, n_rows, d, packed, group_max, gs); break;
+            case 2: rc = launch_2d<2, 16, 1, 320, 64, 2>(grid, stream, base, n_rows, d, packed, group_max, gs); break;
+            case 3: rc = launch_2d<2, 16, 1, 320, 64, 3>(grid, stream, base, n_rows, d, packed, group_max, gs); break;
+            default: rc = launch_2d<2, 16, 1, 320, 64, 4>(grid, stream, base, n_rows, d, packed, group_max, gs); break;
+        }
+    }
+    // MSE_SCAN_MID alone: the unstamped search kernel on another schedule than the product's (an A/B within one library)
+    else if (!mask && group_rows == 64 && nq_pad == 320 && rc == -2 && dev_scan_mid() != MID_320) {
+        switch (dev_scan_mid()) {
+            case 0: rc = launch_2d<2, 16, 0, 320, 64, 0>(grid, stream, base, n_rows, d, packed, group_max, gs); break;
+            case 1: rc = launch_2d<2, 16, 0, 320, 64, 1>(grid, stream, base, n_rows, d, packed, group_max, gs); break;
+            case 2: rc = launch_2d<2, 16, 0, 320, 64, 2>(grid, stream, base, n_rows, d, packed, group_max, gs); break;
+            case 3: rc = launch_2d<2, 16, 0, 320, 64, 3>(grid, stream, base, n_rows, d, packed, group_max, gs); break;
+            default: rc = launch_2d<2, 16, 0, 320, 64, 4>(grid, stream, base, n_rows, d, packed, group_max, gs); break;
+        }
+    }
     if (rc != -2) {
         if (rc) return rc;
         if (ev_end) MSE_HIP_TRY(hipEventRecord(ev_end, stream));
@@ -1042,10 +1136,11 @@ int launch_scan_mfma(const uint16_t* base, size_t n_rows, int d, const uint16_t*
         // group_rows = 64 (the search passes): one maximum per wave's 64 rows instead of two per 32 -- half the array of group maxima,
         // half the 64-byte partial stores, half of what the tournament's first level reads back.  Code object of that form (with the
         // short turn-over of the kernel's header comment): 248 VGPRs unmasked, 250 masked (the mask is applied by selection in the
-        // epilogue), 0 spilled, 0 scratch, 2 waves per SIMD.
+        // epilogue), 0 spilled, 0 scratch, 2 waves per SIMD -- the same figures with the mid-block schedule (MID_320), which these
+        // 64-row forms carry.  The 32-row forms stay on the schedule before it (255 / 256 VGPRs; with MID the masked one spills four).
         // The tile-subset form of that kernel (launch_scan_mfma_tiles, the sparse maxima of api.hip mfma_pass): scan_mfma2d_kernel<2, 16,
         // 0, 320, 64, ScanSparse>: VGPRs: 250, ScratchSize [bytes/lane]: 0, Occupancy [waves/SIMD]: 2, SGPRs Spill: 0, VGPRs Spill: 0.
-        if (group_rows == 64) rc = run([&](auto... m) { return launch_2d<2, 16, 0, 320, 64>(grid, stream, base, n_rows, d, packed, group_max, gs, m...); });
+        if (group_rows == 64) rc = run([&](auto... m) { return launch_2d<2, 16, 0, 320, 64, MID_320>(grid, stream, base, n_rows, d, packed, group_max, gs, m...); });
         else rc = run([&](auto... m) { return launch_2d<2, 16, 0, 320>(grid, stream, base, n_rows, d, packed, group_max, gs, m...); });
     } else if (nq_pad == 192) {
         // 12 column tiles on the one-dimensional wave split (32 rows x 192 queries per wave, 96 accumulators): the point between
@@ -1078,9 +1173,18 @@ int launch_scan_mfma_tiles(const uint16_t* base, size_t n_rows, int d, const uin
         // Code object of this form (hipcc --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage): 250 VGPRs, 0 spilled,
         // 0 scratch, 2 waves per SIMD (with the wave index in a vector register and the list offsets hoisted out of the tile loop it
         // spilled 2 to 46 registers: see the kernel's epilogue)
-        auto kernel = scan_mfma2d_kernel<2, 16, 0, BN, 64, ScanSparse>;
+        auto kernel = scan_mfma2d_kernel<2, 16, 0, BN, 64, MID_320, ScanSparse>;
 #ifdef MSE_DEV_KERNELS
-        if (getenv("MSE_SCAN_ABL") && atoi(getenv("MSE_SCAN_ABL")) == 33) kernel = scan_mfma2d_kernel<2, 16, 1, BN, 64, ScanSparse>;   // cycle stamps
+        {   // MSE_SCAN_ABL=33: cycle stamps; MSE_SCAN_MID: another schedule
+            const bool prof = getenv("MSE_SCAN_ABL") && atoi(getenv("MSE_SCAN_ABL")) == 33;
+            switch (dev_scan_mid()) {
+                case 0: kernel = prof ? scan_mfma2d_kernel<2, 16, 1, BN, 64, 0, ScanSparse> : scan_mfma2d_kernel<2, 16, 0, BN, 64, 0, ScanSparse>; break;
+                case 1: kernel = prof ? scan_mfma2d_kernel<2, 16, 1, BN, 64, 1, ScanSparse> : scan_mfma2d_kernel<2, 16, 0, BN, 64, 1, ScanSparse>; break;
+                case 2: kernel = prof ? scan_mfma2d_kernel<2, 16, 1, BN, 64, 2, ScanSparse> : scan_mfma2d_kernel<2, 16, 0, BN, 64, 2, ScanSparse>; break;
+                case 3: kernel = prof ? scan_mfma2d_kernel<2, 16, 1, BN, 64, 3, ScanSparse> : scan_mfma2d_kernel<2, 16, 0, BN, 64, 3, ScanSparse>; break;
+                default: kernel = prof ? scan_mfma2d_kernel<2, 16, 1, BN, 64, 4, ScanSparse> : scan_mfma2d_kernel<2, 16, 0, BN, 64, 4, ScanSparse>; break;
+            }
+        }
 #endif
         const size_t lds = 2 * (size_t)(BN * 128) + (size_t)4 * 2 * 8192 + TAU_SLOTS * sizeof(float);   // 144 KiB + the thresholds' 1.5 KiB
         const size_t n_tiles = (n_rows + TILE_ROWS - 1) / TILE_ROWS;
@@ -1098,8 +1202,8 @@ int launch_scan_mfma_tiles(const uint16_t* base, size_t n_rows, int d, const uin
 
 #ifdef MSE_DEV_KERNELS
 // developer library only (not in include/mse.h): read and clear the counters of the profiled 2-D scan (MSE_SCAN_2D=161, MSE_SCAN_ABL=33)
-extern "C" __attribute__((visibility("default"))) int mse_dev_scan_prof(unsigned long long out[6]) {
-    unsigned long long z[6] = {0, 0, 0, 0, 0, 0};
+extern "C" __attribute__((visibility("default"))) int mse_dev_scan_prof(unsigned long long out[7]) {
+    unsigned long long z[7] = {0, 0, 0, 0, 0, 0, 0};
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(mse::g_scan_prof), sizeof(z)) != hipSuccess) return -1;
     if (hipMemcpyToSymbol(HIP_SYMBOL(mse::g_scan_prof), z, sizeof(z)) != hipSuccess) return -1;
     return 0;

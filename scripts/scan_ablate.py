@@ -1,5 +1,7 @@
 """Developer timing of the MFMA scan kernel alone (HIP events around the kernel): python scripts/scan_ablate.py [rows] [queries]
-MSE_SCAN_ABL=<bits> selects an ablated variant of the 256-query kernel (scan_mfma.hip); results are then meaningless."""
+MSE_SCAN_ABL=<bits> selects an ablated variant of the 256-query kernel (scan_mfma.hip); results are then meaningless.
+MSE_SCAN_MID=0..4 selects the schedule of the 320-query search kernel (0: without the mid-block barrier; scan_mfma.hip MID), with
+MSE_SCAN_ABL=33 its stamped form: the K block split into issue, mid-block barrier, closing wait and closing barrier, and the clock held."""
 import os
 import sys
 
@@ -47,15 +49,24 @@ if os.environ.get("CHECK") and os.environ.get("MSE_SCAN_2D") != "162":   # the v
 if os.environ.get("MSE_SCAN_2D") == "161" or os.environ.get("MSE_SCAN_ABL") == "33":   # developer library: where a wave's cycles go (scan_mfma.hip, PROF)
     import ctypes
     from mse import ffi
-    out = (ctypes.c_ulonglong * 6)()
+    out = (ctypes.c_ulonglong * 7)()
     ffi.lib().mse_dev_scan_prof(out)          # clear what the warm-up and the timed loop left
-    s.bruteforce_topk_dev(qs.device_ptr, nq, 10, out_s.data_ptr(), out_i.data_ptr(), mse.MODE_MFMA)
+    s.scan_timing(2)
+    REPS = 5                                  # back to back, so that the clock figure below is not that of a chip waking up
+    for _ in range(REPS):
+        s.bruteforce_topk_dev(qs.device_ptr, nq, 10, out_s.data_ptr(), out_i.data_ptr(), mse.MODE_MFMA)
     torch.cuda.synchronize()
     ffi.lib().mse_dev_scan_prof(out)
-    issue, wait, bar, nkb, turn, tiles = [int(x) for x in out]
-    tot = issue + wait + bar
-    print(f"profiled 2-D scan: per K block and wave {tot / nkb:.0f} cycles = issue {issue / nkb:.0f} + vmcnt wait {wait / nkb:.0f} + barrier {bar / nkb:.0f}"
-          f" ({nkb} wave-K-blocks)")
+    issue, wait, bar, nkb, turn, tiles, mid = [int(x) // REPS for x in out]
+    tot = issue + wait + bar + mid
+    print(f"profiled 2-D scan (MSE_SCAN_MID={os.environ.get('MSE_SCAN_MID', 'product')}): per K block and wave {tot / nkb:.0f} cycles = issue {issue / nkb:.0f}"
+          f" + mid-block barrier {mid / nkb:.0f} + vmcnt wait {wait / nkb:.0f} + barrier {bar / nkb:.0f} ({nkb} wave-K-blocks)")
+    # the clock the stamped kernel held: stamped cycles per wave slot (8 waves on each CU, every launch fills the chip at these sizes)
+    # over the HIP-event time of the step's scan launches
+    ms1, k1 = s.scan_timing(0)
+    slots = 8 * torch.cuda.get_device_properties(0).multi_processor_count
+    ms1 /= REPS
+    print(f"stamped step: scan {ms1:.3f} ms; {(tot + turn) / slots:.0f} stamped cycles per wave slot = {(tot + turn) / slots / ms1 / 1e6:.3f} GHz held")
     if tiles:   # per row tile and wave: its K loop against the turn-over (epilogue + prologue) around it
         print(f"per tile and wave: K loop {tot / tiles:.0f} cycles ({nkb / tiles:.1f} K blocks) + turn-over {turn / tiles:.0f} cycles = "
               f"{turn / (tot + turn) * 100:.2f} % of the tile ({tiles} wave-tiles, sparse maxima {os.environ.get('SPARSE', 'auto')})")
