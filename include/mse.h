@@ -1541,6 +1541,48 @@ typedef struct mse_debug_siglip_gemm_fused_args {
     int M, n_pad, n_seq, dh_pad, kdh_pad, dv_pad;   /* filled in by the hook */
 } mse_debug_siglip_gemm_fused_args;
 int mse_debug_siglip_gemm_fused(mse_debug_siglip_gemm_fused_args* args);
+/* test hooks for the towers' row kernels alone: each call makes ONE call of the launcher the towers use (launch_layernorm_d,
+ * launch_patchify, launch_rgb8_to_nchw_f16, launch_bmp24_to_nchw_f16, launch_embed_tokens, launch_f32_to_bf16_pad,
+ * launch_small_linear, launch_l2norm, launch_vt_ones_row), with the contract of the GEMM hooks.  Operands are host fp32 (u8 for the
+ * decoders, i64 for tokens), compact -- [rows][width] -- and are rounded in the hook (nearest even) to the type the towers hold them
+ * in and laid out with the leading dimension given (operand columns past the width hold 1e4).  Every destination -- the x that
+ * LayerNorm updates in place included -- lies between guard bands, is filled with bytes 0xA5 before the launch and comes back WHOLE,
+ * [rows][leading dimension], widened to fp32; a changed guard byte fails the call.  A geometry the launcher refuses is refused
+ * before anything is allocated.  What each launch writes is stated above the hooks in csrc/siglip_api.hip. */
+typedef struct mse_debug_siglip_layernorm_args {
+    int rows, width;
+    int ldx, x_is_f16;       /* x: rows of ldx elements, fp16 (the residual stream) or fp32 */
+    int ldd;                 /* delta */
+    int n_parts, part_rows, ldp;   /* parts: n_parts slabs of part_rows rows of ldp */
+    int ldo;                 /* out and out_f32 */
+    int wg;                  /* launch_layernorm_d's wg: 1 = layernorm_wg_kernel (a workgroup per row), 0 = layernorm_kernel (a wave per row) */
+    float eps;
+    const float* x;          /* [rows][width] */
+    const float* delta;      /* optional: bf16 [rows][width] */
+    const float* parts;      /* optional: fp32 [n_parts][rows][width], with bias fp32 [width] */
+    const float* bias;
+    const float *gamma, *beta;   /* fp32 [width] */
+    float* x_out;            /* x after the call, [rows][ldx] */
+    float* out;              /* optional: bf16 [rows][ldo] */
+    float* out_f32;          /* optional: fp32 [rows][ldo] */
+} mse_debug_siglip_layernorm_args;
+int mse_debug_siglip_layernorm(mse_debug_siglip_layernorm_args* args);
+/* img fp32 [B][C][H][W] (rounded to fp16 when is_f16); out bf16 [B * tstride][k_pad] */
+int mse_debug_siglip_patchify(const float* img, int is_f16, int B, int C, int H, int W, int P, int k_pad, int tstride, float* out);
+/* in u8 [B][H][W][C]; out fp16 [B][C][H][W] */
+int mse_debug_siglip_rgb8(const uint8_t* in, int B, int C, int H, int W, float* out);
+/* in: B BMP pixel arrays img_stride bytes apart, rows of row_stride bytes (BGR); flags[b] bit 0 = bottom row first; out fp16 [B][3][H][W] */
+int mse_debug_siglip_bmp24(const uint8_t* in, size_t img_stride, int row_stride, const uint8_t* flags, int B, int H, int W, float* out);
+/* tokens i64 [rows], tok_emb fp32 [vocab][D], pos fp32 [ctx][D]; out fp16 [rows][D] */
+int mse_debug_siglip_embed_tokens(const int64_t* tokens, const float* tok_emb, const float* pos, int vocab, int ctx, int D, int rows, float* out);
+/* in fp32 [rows][cols] (laid out with rows of ld_in); out bf16 [rows_pad][cols_pad] */
+int mse_debug_siglip_f32_to_bf16_pad(const float* in, int rows, int cols, int ld_in, int rows_pad, int cols_pad, float* out);
+/* x fp32 [B][K], w [N][K] (rounded to bf16), bias fp32 [N]; y fp32 [B][ldy] */
+int mse_debug_siglip_small_linear(const float* x, int ldx, const float* w, int ldw, const float* bias, int K, int N, int B, int ldy, float* y);
+/* x fp32 [B][width]; out_f32 / out_f16 (either may be NULL) [B][width] */
+int mse_debug_siglip_l2norm(const float* x, int ldx, int width, int B, int normalize, float* out_f32, float* out_f16);
+/* out: n_mats sentinel-filled bf16 [dv_pad][n_pad] matrices after launch_vt_ones_row */
+int mse_debug_siglip_vt_ones_row(int n_mats, int dh, int dv_pad, int n_pad, float* out);
 
 /* ---- SigLIP text tower: `model.encode_text(tokens)` + normalisation + fp16 serialisation
  * (clip_server.py:98-99,128-131,166).  open_clip's TextTransformer is a third-party dependency not vendored in

@@ -91,8 +91,8 @@ int launch_rgb8_to_nchw_f16(const uint8_t* in, void* out, int B, int C, int H, i
 int launch_vt_ones_row(uint16_t* vt, size_t n_mats, int dh, int dv_pad, int n_pad, hipStream_t st);
 int launch_pool_attention(const uint16_t* kv, int ldkv, const float* qlat, int B, int heads, int dh, int tokens, int tstride,
                           float* out, int ldo, hipStream_t st);
-int launch_small_linear(const float* x, int ldx, const uint16_t* w, int ldw, const float* bias, int K, int N, int B, int act,
-                        const float* res, int ldres, float* y, int ldy, hipStream_t st);
+int launch_small_linear(const float* x, int ldx, const uint16_t* w, int ldw, const float* bias, int K, int N, int B, float* y, int ldy,
+                        hipStream_t st);
 int launch_l2norm(const float* x, int ldx, int width, int B, int normalize, float* out_f32, uint16_t* out_f16, hipStream_t st);
 int launch_embed_tokens(const int64_t* tokens, const float* tok_emb, const float* pos, int vocab, int ctx, int D, size_t rows,
                         uint16_t* x_f16, hipStream_t st);

@@ -163,7 +163,7 @@ int mse_siglip_finalize(mse_siglip* m) {
     if (!m) return fail("null engine");
     if (m->check_loaded()) return -1;
     // the pooling query does not depend on the input: q = Linear(latent)   (model.py:94-95)
-    if (launch_small_linear(m->latent, m->D, m->wq, m->D, m->bq, m->D, m->D, 1, 0, nullptr, 0, m->qlat, m->D, m->stream)) return -1;
+    if (launch_small_linear(m->latent, m->D, m->wq, m->D, m->bq, m->D, m->D, 1, m->qlat, m->D, m->stream)) return -1;
     if (m->fold_layernorms()) return -1;
     MSE_HIP_TRY(hipStreamSynchronize(m->stream));
     m->finalized = true;
@@ -560,7 +560,7 @@ constexpr size_t DBG_GUARD = 4096;          // bytes of sentinel on either side 
 constexpr int DBG_SENTINEL = 0xA5;          // bf16 0xA5A5 = -7.17e-16, fp16 0xA5A5 = -0.02204, fp32 0xA5A5A5A5 = -2.87e-16: all finite
 constexpr size_t DBG_GEMM_MAX = (size_t)1 << 26;   // elements of any one operand or destination
 
-// A destination of the GEMM hooks: `bytes` of payload between two guard bands, all of it filled with the sentinel byte.
+// A destination of the GEMM and row hooks: `bytes` of payload between two guard bands, all of it filled with the sentinel byte.
 struct GuardedBuf {
     DevBuf buf;
     size_t bytes = 0;
@@ -577,7 +577,7 @@ struct GuardedBuf {
         MSE_HIP_TRY(hipMemcpy(g.data() + DBG_GUARD, reinterpret_cast<char*>(buf.p) + DBG_GUARD + bytes, DBG_GUARD, hipMemcpyDeviceToHost));
         for (size_t i = 0; i < g.size(); i++)
             if (g[i] != DBG_SENTINEL)
-                return fail(std::string("debug siglip gemm: a launch wrote ") + (i < DBG_GUARD ? "before" : "past") + " its destination (" + what + ")");
+                return fail(std::string("debug siglip: a launch wrote ") + (i < DBG_GUARD ? "before" : "past") + " its destination (" + what + ")");
         return 0;
     }
     template <typename T, typename F> int read(size_t n, float* out, F widen) const {
@@ -842,6 +842,264 @@ int mse_debug_siglip_gemm_fused(mse_debug_siglip_gemm_fused_args* p) {
     if (qkv) return o3.read(p->q, p->k, p->vt);
     if (out.check("out")) return -1;
     return out.read<uint16_t>(M * N, p->out, host_bf16_to_f32);
+}
+
+}  // extern "C"
+
+namespace {
+constexpr float DBG_ROWS_PAD = 1.0e4f;   // what the padding of the row hooks' OPERANDS holds: finite, exact in bf16 / fp16 / fp32, far from any input
+
+// [rows][ld] operand from host fp32 [rows][width]: T(conv(v)); columns width .. ld hold DBG_ROWS_PAD
+template <typename T, typename Conv>
+int upload_ld(DevBuf& d, const float* src, size_t rows, size_t width, size_t ld, Conv conv) {
+    std::vector<T> h(rows * ld, conv(DBG_ROWS_PAD));
+    for (size_t r = 0; r < rows; r++)
+        for (size_t c = 0; c < width; c++) h[r * ld + c] = conv(src[r * width + c]);
+    if (d.ensure(h.size() * sizeof(T))) return -1;
+    MSE_HIP_TRY(hipMemcpy(d.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+    return 0;
+}
+float same_f32(float v) { return v; }
+bool dbg_rows_fit(size_t a, size_t b = 1, size_t c = 1) {   // a * b * c elements of one operand or destination
+    return a && b && c && a <= DBG_GEMM_MAX && b <= DBG_GEMM_MAX && a * b <= DBG_GEMM_MAX && a * b * c <= DBG_GEMM_MAX;
+}
+}  // namespace
+
+extern "C" {
+
+// Test hooks for the towers' row kernels alone (mse.h: "row kernels"): each call makes ONE call of the launcher the towers use --
+//   mse_debug_siglip_layernorm        launch_layernorm_d      layernorm_kernel / layernorm_wg_kernel (wg), x fp32 or fp16
+//   mse_debug_siglip_patchify         launch_patchify         patchify8_kernel (P 14, k_pad % 8 == 0, k_pad <= 1024) or patchify_kernel
+//   mse_debug_siglip_rgb8             launch_rgb8_to_nchw_f16
+//   mse_debug_siglip_bmp24            launch_bmp24_to_nchw_f16
+//   mse_debug_siglip_embed_tokens     launch_embed_tokens
+//   mse_debug_siglip_f32_to_bf16_pad  launch_f32_to_bf16_pad
+//   mse_debug_siglip_small_linear     launch_small_linear
+//   mse_debug_siglip_l2norm           launch_l2norm
+//   mse_debug_siglip_vt_ones_row      launch_vt_ones_row
+// on a stream of the engines' kind, with the contract of the GEMM hooks.  Operands are host fp32 (u8 for the decoders, i64 for the
+// tokens), compact ([rows][width]); the hook rounds them (nearest even) to the type the towers hold them in and lays them out with
+// the leading dimension given, and the columns between the width and the leading dimension of an OPERAND hold 1e4, so a launch that
+// read them shows.  Every DESTINATION -- LayerNorm's x included, which the kernel updates in place -- lies between two guard bands
+// and is filled, guard bands included, with bytes 0xA5 before the launch (and, for x, before its rows are copied in); it comes back
+// WHOLE, [rows][leading dimension], widened to fp32, so a test sees what the launch left of the sentinel; a changed guard byte fails
+// the call.  A geometry the launcher refuses -- and a leading dimension smaller than its width or off the kernels' 4-element vector
+// alignment, a null operand, more than 2^26 elements -- is refused before anything is allocated.
+//
+// What a launch writes, read from siglip_kernels.hip:
+//   layernorm     x: with a delta (bf16 [rows][ldd], or n_parts fp32 slabs [part_rows][ldp] plus bias) columns 0 .. width of every
+//                 row are rewritten with x + delta rounded to x's type; with NO delta x is not written at all.  out (bf16) / out_f32
+//                 (either may be absent, both have rows of ldo): columns 0 .. width.  Columns width .. ld keep the sentinel.
+//   patchify      every one of the B * tstride * k_pad elements: columns >= C P P and rows t >= tokens of an image are ZEROED
+//                 (tokens = (H / P) * (W / P): pixels past the last whole patch are ignored, as by the stride-P convolution).
+//   rgb8 / bmp24  every element of [B][C][H][W] fp16.       embed_tokens: every element of [rows][D] fp16.
+//   f32_to_bf16_pad  every element of [rows_pad][cols_pad]; rows >= rows and columns >= cols are ZEROED.
+//   small_linear  y[b][0 .. N]; columns N .. ldy keep the sentinel.     l2norm: every element of [B][width] of the outputs asked for.
+//   vt_ones_row   row dh = 72 of each of the n_mats [80][n_pad] matrices = bf16 1.0; EVERYTHING else keeps the sentinel.
+int mse_debug_siglip_layernorm(mse_debug_siglip_layernorm_args* p) {
+    if (!p) return fail("debug siglip layernorm: null argument");
+    const int rows = p->rows, width = p->width, ldx = p->ldx, ldo = p->ldo;
+    if (rows <= 0 || width <= 0 || ldx < width || ldo < width || ldx % 4 || ldo % 4 || (p->x_is_f16 & ~1) || (p->wg & ~1) || !(p->eps > 0.0f))
+        return fail("debug siglip layernorm: rows, width > 0, ldx, ldo >= width and multiples of 4, x_is_f16 0 / 1, wg 0 / 1, eps > 0");
+    if (width % 4 || width > 2048) return fail("debug siglip layernorm: width must be a multiple of 4, at most 2048 (launch_layernorm_d)");
+    if (p->parts && (p->delta || p->n_parts < 1 || !p->bias || p->ldp % 4))
+        return fail("debug siglip layernorm: parts exclude a bf16 delta and need n_parts >= 1, a bias and ldp % 4 == 0 (launch_layernorm_d)");
+    if (p->delta && (p->ldd < width || p->ldd % 4)) return fail("debug siglip layernorm: ldd >= width, a multiple of 4");
+    if (p->parts && (p->ldp < width || p->part_rows < rows)) return fail("debug siglip layernorm: ldp >= width, part_rows >= rows");
+    if (!dbg_rows_fit(rows, ldx) || !dbg_rows_fit(rows, ldo) || (p->delta && !dbg_rows_fit(rows, p->ldd)) ||
+        (p->parts && !dbg_rows_fit(p->n_parts, p->part_rows, p->ldp)))
+        return fail("debug siglip layernorm: an operand exceeds 2^26 elements");
+    if (!p->x || !p->gamma || !p->beta || !p->x_out || (!p->out && !p->out_f32)) return fail("debug siglip layernorm: null argument");
+
+    const size_t R = rows, W = width, xb = p->x_is_f16 ? 2 : 4;
+    DevBuf ddelta, dparts, dbias, dgamma, dbeta;
+    GuardedBuf x, out, out_f32;
+    DbgStreams s;   // declared after every buffer: the stream is synchronised and destroyed before a buffer is freed
+    if (s.make(false)) return -1;
+    if (x.make(R * ldx * xb) || upload_f32(dgamma, p->gamma, W) || upload_f32(dbeta, p->beta, W)) return -1;
+    if (p->x_is_f16) {
+        std::vector<uint16_t> h(R * W);
+        for (size_t e = 0; e < h.size(); e++) h[e] = host_f16(p->x[e]);
+        MSE_HIP_TRY(hipMemcpy2D(x.as<char>(), (size_t)ldx * 2, h.data(), W * 2, W * 2, R, hipMemcpyHostToDevice));
+    } else {
+        MSE_HIP_TRY(hipMemcpy2D(x.as<char>(), (size_t)ldx * 4, p->x, W * 4, W * 4, R, hipMemcpyHostToDevice));
+    }
+    LnDelta d;
+    if (p->delta) {
+        if (upload_ld<uint16_t>(ddelta, p->delta, R, W, p->ldd, host_bf16)) return -1;
+        d.bf16 = ddelta.as<uint16_t>(); d.ldd = p->ldd;
+    } else if (p->parts) {
+        std::vector<float> h((size_t)p->n_parts * p->part_rows * p->ldp, DBG_ROWS_PAD);
+        for (size_t q = 0; q < (size_t)p->n_parts; q++)
+            for (size_t r = 0; r < R; r++)
+                for (size_t c = 0; c < W; c++) h[(q * p->part_rows + r) * p->ldp + c] = p->parts[(q * R + r) * W + c];
+        if (upload_f32(dparts, h.data(), h.size()) || upload_f32(dbias, p->bias, W)) return -1;
+        d.parts = dparts.as<float>(); d.n_parts = p->n_parts; d.part_stride = (size_t)p->part_rows * p->ldp; d.ldp = p->ldp;
+        d.bias = dbias.as<float>();
+    }
+    if ((p->out && out.make(R * ldo * 2)) || (p->out_f32 && out_f32.make(R * ldo * 4))) return -1;
+    MSE_HIP_TRY(hipDeviceSynchronize());   // uploads and fills ran on the null stream, which the hook's stream does not wait for
+    if (launch_layernorm_d(x.as<void>(), p->x_is_f16, ldx, d, dgamma.as<float>(), dbeta.as<float>(), p->eps, width, R,
+                           p->out ? out.as<uint16_t>() : nullptr, ldo, p->out_f32 ? out_f32.as<float>() : nullptr, p->wg, s.main))
+        return -1;
+    MSE_HIP_TRY(hipStreamSynchronize(s.main));
+    if (x.check("layernorm x") || (p->out && out.check("layernorm out")) || (p->out_f32 && out_f32.check("layernorm out_f32"))) return -1;
+    if (p->x_is_f16 ? x.read<uint16_t>(R * ldx, p->x_out, host_f16_to_f32) : x.read<float>(R * ldx, p->x_out, same_f32)) return -1;
+    if (p->out && out.read<uint16_t>(R * ldo, p->out, host_bf16_to_f32)) return -1;
+    if (p->out_f32 && out_f32.read<float>(R * ldo, p->out_f32, same_f32)) return -1;
+    return 0;
+}
+
+// img: host fp32 [B][C][H][W], rounded to fp16 when is_f16 (the towers' decoded images), else used as it is.  out: [B * tstride][k_pad].
+int mse_debug_siglip_patchify(const float* img, int is_f16, int B, int C, int H, int W, int P, int k_pad, int tstride, float* out) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || P <= 0 || k_pad <= 0 || tstride <= 0 || (is_f16 & ~1))
+        return fail("debug siglip patchify: B, C, H, W, P, k_pad, tstride > 0, is_f16 0 / 1");
+    if (H < P || W < P || k_pad < C * P * P) return fail("debug siglip patchify: H >= P, W >= P, k_pad >= C * P * P (launch_patchify)");
+    if (!dbg_rows_fit(B, (size_t)C * H, W) || !dbg_rows_fit(B, tstride, k_pad)) return fail("debug siglip patchify: an operand exceeds 2^26 elements");
+    if (!img || !out) return fail("debug siglip patchify: null argument");
+    const size_t n_in = (size_t)B * C * H * W, n_out = (size_t)B * tstride * k_pad;
+    DevBuf dimg;
+    GuardedBuf dout;
+    DbgStreams s;
+    if (s.make(false)) return -1;
+    if (is_f16 ? upload_ld<uint16_t>(dimg, img, 1, n_in, n_in, host_f16) : upload_f32(dimg, img, n_in)) return -1;
+    if (dout.make(n_out * 2)) return -1;
+    MSE_HIP_TRY(hipDeviceSynchronize());
+    if (launch_patchify(dimg.p, is_f16, B, C, H, W, P, k_pad, tstride, dout.as<uint16_t>(), s.main)) return -1;
+    MSE_HIP_TRY(hipStreamSynchronize(s.main));
+    if (dout.check("patches")) return -1;
+    return dout.read<uint16_t>(n_out, out, host_bf16_to_f32);
+}
+
+namespace {
+int dbg_decode(const uint8_t* in, size_t n_in, const uint8_t* flags, size_t img_stride, int row_stride, int B, int C, int H, int W, float* out) {
+    const size_t n_out = (size_t)B * C * H * W;
+    DevBuf din, dflags;
+    GuardedBuf dout;
+    DbgStreams s;
+    if (s.make(false)) return -1;
+    if (din.ensure(n_in) || dout.make(n_out * 2) || (flags && dflags.ensure(B))) return -1;
+    MSE_HIP_TRY(hipMemcpy(din.p, in, n_in, hipMemcpyHostToDevice));
+    if (flags) MSE_HIP_TRY(hipMemcpy(dflags.p, flags, B, hipMemcpyHostToDevice));
+    MSE_HIP_TRY(hipDeviceSynchronize());
+    if (flags ? launch_bmp24_to_nchw_f16(din.as<uint8_t>(), img_stride, row_stride, dflags.as<uint8_t>(), dout.as<void>(), B, H, W, s.main)
+              : launch_rgb8_to_nchw_f16(din.as<uint8_t>(), dout.as<void>(), B, C, H, W, s.main))
+        return -1;
+    MSE_HIP_TRY(hipStreamSynchronize(s.main));
+    if (dout.check("decoded image")) return -1;
+    return dout.read<uint16_t>(n_out, out, host_f16_to_f32);
+}
+}  // namespace
+
+// in: u8 [B][H][W][C] (RGB when C = 3).  out: fp16 [B][C][H][W].
+int mse_debug_siglip_rgb8(const uint8_t* in, int B, int C, int H, int W, float* out) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || !dbg_rows_fit(B, (size_t)C * H, W)) return fail("debug siglip rgb8: B, C, H, W > 0, at most 2^26 elements");
+    if (!in || !out) return fail("debug siglip rgb8: null argument");
+    return dbg_decode(in, (size_t)B * C * H * W, nullptr, 0, 0, B, C, H, W, out);
+}
+
+// in: B pixel arrays of 24-bit BMPs, img_stride bytes apart, rows of row_stride bytes, blue-green-red; flags[b] bit 0 = bottom row first.
+int mse_debug_siglip_bmp24(const uint8_t* in, size_t img_stride, int row_stride, const uint8_t* flags, int B, int H, int W, float* out) {
+    if (B <= 0 || H <= 0 || W <= 0 || !dbg_rows_fit(B, (size_t)3 * H, W) || row_stride < 3 * W || img_stride < (size_t)H * row_stride ||
+        !dbg_rows_fit(B, img_stride))
+        return fail("debug siglip bmp24: B, H, W > 0, row_stride >= 3 W, img_stride >= H * row_stride, at most 2^26 elements");
+    if (!in || !flags || !out) return fail("debug siglip bmp24: null argument");
+    return dbg_decode(in, (size_t)B * img_stride, flags, img_stride, row_stride, B, 3, H, W, out);
+}
+
+// tokens: i64 [rows]; tok_emb fp32 [vocab][D]; pos fp32 [ctx][D] (both stay fp32).  out: the fp16 residual rows [rows][D].
+int mse_debug_siglip_embed_tokens(const int64_t* tokens, const float* tok_emb, const float* pos, int vocab, int ctx, int D, int rows, float* out) {
+    if (vocab <= 0 || ctx <= 0 || D <= 0 || rows <= 0 || !dbg_rows_fit(vocab, D) || !dbg_rows_fit(ctx, D) || !dbg_rows_fit(rows, D))
+        return fail("debug siglip embed tokens: vocab, ctx, D, rows > 0, at most 2^26 elements");
+    if (D % 4) return fail("debug siglip embed tokens: D must be a multiple of 4 (launch_embed_tokens)");
+    if (!tokens || !tok_emb || !pos || !out) return fail("debug siglip embed tokens: null argument");
+    DevBuf dtok, demb, dpos;
+    GuardedBuf dout;
+    DbgStreams s;
+    if (s.make(false)) return -1;
+    if (dtok.ensure((size_t)rows * 8) || upload_f32(demb, tok_emb, (size_t)vocab * D) || upload_f32(dpos, pos, (size_t)ctx * D) ||
+        dout.make((size_t)rows * D * 2))
+        return -1;
+    MSE_HIP_TRY(hipMemcpy(dtok.p, tokens, (size_t)rows * 8, hipMemcpyHostToDevice));
+    MSE_HIP_TRY(hipDeviceSynchronize());
+    if (launch_embed_tokens(dtok.as<int64_t>(), demb.as<float>(), dpos.as<float>(), vocab, ctx, D, rows, dout.as<uint16_t>(), s.main)) return -1;
+    MSE_HIP_TRY(hipStreamSynchronize(s.main));
+    if (dout.check("embedded tokens")) return -1;
+    return dout.read<uint16_t>((size_t)rows * D, out, host_f16_to_f32);
+}
+
+// in: host fp32 [rows][cols], laid out with rows of ld_in.  out: bf16 [rows_pad][cols_pad].
+int mse_debug_siglip_f32_to_bf16_pad(const float* in, int rows, int cols, int ld_in, int rows_pad, int cols_pad, float* out) {
+    if (rows <= 0 || cols <= 0 || ld_in < cols || rows_pad < rows || cols_pad < cols || !dbg_rows_fit(rows, ld_in) || !dbg_rows_fit(rows_pad, cols_pad))
+        return fail("debug siglip f32 to bf16: rows, cols > 0, ld_in >= cols, rows_pad >= rows, cols_pad >= cols, at most 2^26 elements");
+    if (!in || !out) return fail("debug siglip f32 to bf16: null argument");
+    DevBuf din;
+    GuardedBuf dout;
+    DbgStreams s;
+    if (s.make(false)) return -1;
+    if (upload_ld<float>(din, in, rows, cols, ld_in, same_f32) || dout.make((size_t)rows_pad * cols_pad * 2)) return -1;
+    MSE_HIP_TRY(hipDeviceSynchronize());
+    if (launch_f32_to_bf16_pad(din.as<float>(), rows, cols, ld_in, dout.as<uint16_t>(), rows_pad, cols_pad, s.main)) return -1;
+    MSE_HIP_TRY(hipStreamSynchronize(s.main));
+    if (dout.check("padded bf16 rows")) return -1;
+    return dout.read<uint16_t>((size_t)rows_pad * cols_pad, out, host_bf16_to_f32);
+}
+
+// x: host fp32 [B][K] (stays fp32, rows of ldx); w: host fp32 [N][K], rounded to bf16, rows of ldw; bias fp32 [N].  y: fp32 [B][ldy].
+int mse_debug_siglip_small_linear(const float* x, int ldx, const float* w, int ldw, const float* bias, int K, int N, int B, int ldy, float* y) {
+    if (K <= 0 || N <= 0 || B <= 0 || ldx < K || ldw < K || ldy < N || !dbg_rows_fit(B, ldx) || !dbg_rows_fit(N, ldw) || !dbg_rows_fit(B, ldy))
+        return fail("debug siglip small linear: K, N, B > 0, ldx, ldw >= K, ldy >= N, at most 2^26 elements");
+    if (!x || !w || !bias || !y) return fail("debug siglip small linear: null argument");
+    DevBuf dx, dw, dbias;
+    GuardedBuf dy;
+    DbgStreams s;
+    if (s.make(false)) return -1;
+    if (upload_ld<float>(dx, x, B, K, ldx, same_f32) || upload_ld<uint16_t>(dw, w, N, K, ldw, host_bf16) || upload_f32(dbias, bias, N) ||
+        dy.make((size_t)B * ldy * 4))
+        return -1;
+    MSE_HIP_TRY(hipDeviceSynchronize());
+    if (launch_small_linear(dx.as<float>(), ldx, dw.as<uint16_t>(), ldw, dbias.as<float>(), K, N, B, dy.as<float>(), ldy, s.main)) return -1;
+    MSE_HIP_TRY(hipStreamSynchronize(s.main));
+    if (dy.check("small linear y")) return -1;
+    return dy.read<float>((size_t)B * ldy, y, same_f32);
+}
+
+// x: host fp32 [B][width], rows of ldx.  out_f32 / out_f16 (either may be NULL): [B][width].
+int mse_debug_siglip_l2norm(const float* x, int ldx, int width, int B, int normalize, float* out_f32, float* out_f16) {
+    if (width <= 0 || B <= 0 || ldx < width || (normalize & ~1) || !dbg_rows_fit(B, ldx))
+        return fail("debug siglip l2norm: width, B > 0, ldx >= width, normalize 0 / 1, at most 2^26 elements");
+    if (!x || (!out_f32 && !out_f16)) return fail("debug siglip l2norm: null argument");
+    const size_t n = (size_t)B * width;
+    DevBuf dx;
+    GuardedBuf d32, d16;
+    DbgStreams s;
+    if (s.make(false)) return -1;
+    if (upload_ld<float>(dx, x, B, width, ldx, same_f32) || (out_f32 && d32.make(n * 4)) || (out_f16 && d16.make(n * 2))) return -1;
+    MSE_HIP_TRY(hipDeviceSynchronize());
+    if (launch_l2norm(dx.as<float>(), ldx, width, B, normalize, out_f32 ? d32.as<float>() : nullptr, out_f16 ? d16.as<uint16_t>() : nullptr, s.main))
+        return -1;
+    MSE_HIP_TRY(hipStreamSynchronize(s.main));
+    if ((out_f32 && (d32.check("l2norm fp32") || d32.read<float>(n, out_f32, same_f32))) ||
+        (out_f16 && (d16.check("l2norm fp16") || d16.read<uint16_t>(n, out_f16, host_f16_to_f32))))
+        return -1;
+    return 0;
+}
+
+// out: the n_mats sentinel-filled bf16 [dv_pad][n_pad] matrices after the launch.
+int mse_debug_siglip_vt_ones_row(int n_mats, int dh, int dv_pad, int n_pad, float* out) {
+    if (n_mats <= 0 || n_pad <= 0 || dv_pad <= 0 || !dbg_rows_fit(n_mats, dv_pad, n_pad)) return fail("debug siglip vt ones row: n_mats, dv_pad, n_pad > 0, at most 2^26 elements");
+    if (dh != DBG_DH || dv_pad != DBG_DV_PAD) return fail("debug siglip vt ones row: the row-sum row assumes dh 72, dv_pad 80 (launch_vt_ones_row)");
+    if (!out) return fail("debug siglip vt ones row: null argument");
+    const size_t n = (size_t)n_mats * dv_pad * n_pad;
+    GuardedBuf vt;
+    DbgStreams s;
+    if (s.make(false)) return -1;
+    if (vt.make(n * 2)) return -1;
+    MSE_HIP_TRY(hipDeviceSynchronize());
+    if (launch_vt_ones_row(vt.as<uint16_t>(), n_mats, dh, dv_pad, n_pad, s.main)) return -1;
+    MSE_HIP_TRY(hipStreamSynchronize(s.main));
+    if (vt.check("vt")) return -1;
+    return vt.read<uint16_t>(n, out, host_bf16_to_f32);
 }
 
 // test hook: the residual stream ([batch*tokens][emb] fp32) as left by the last forward (after the last block)

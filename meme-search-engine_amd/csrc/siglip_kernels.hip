@@ -62,25 +62,6 @@ __device__ __forceinline__ void dma16_s(const void* sbase, uint32_t voff, uint32
 }
 #pragma clang diagnostic pop
 
-// erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7, below bf16 resolution by four orders of magnitude): one
-// reciprocal, one exp2, eight fused multiply-adds instead of libm's ~30-instruction erff in the GEMM epilogue
-__device__ __forceinline__ float gelu_erf(float x) {
-    const float z = fabsf(x) * 0.70710678118654752f;
-    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, z, 1.0f));
-    float p = fmaf(1.061405429f, t, -1.453152027f);
-    p = fmaf(p, t, 1.421413741f);
-    p = fmaf(p, t, -0.284496736f);
-    p = fmaf(p, t, 0.254829592f);
-    const float e = exp2f(-z * z * 1.4426950408889634f);
-    const float erf_abs = 1.0f - p * t * e;
-    const float erf_v = x < 0.0f ? -erf_abs : erf_abs;
-    return 0.5f * x * (1.0f + erf_v);
-}
-__device__ __forceinline__ float gelu_tanh(float x) {
-    const float u = 0.7978845608028654f * (x + 0.044715f * x * x * x);
-    return 0.5f * x * (1.0f + tanhf(u));
-}
-
 // GELU in the GEMM epilogues: x * sigmoid(u(x)), u an odd polynomial -- 5 packed-f32 operations, one exp2 and one
 // reciprocal per element (the A&S erf above costs three times the vector-ALU work, and the fc1 epilogue is ALU bound).
 //   tanh flavour: u = 2 * 0.79788456 (x + 0.044715 x^3)                      (the identity 0.5 (1 + tanh v) = sigmoid(2 v))
@@ -2114,11 +2095,10 @@ __global__ __launch_bounds__(256) void pool_attention_kernel(const uint16_t* __r
     }
 }
 
-// small dense layer on the vector ALU for the B-row tail of the MAP head: y[b][n] = act(x[b] . w[n] + bias[n]) (+ res)
+// small dense layer on the vector ALU (the latent-query projection of the MAP head, the text projection): y[b][n] = x[b] . w[n] + bias[n]
 __global__ __launch_bounds__(256) void small_linear_kernel(const float* __restrict__ x, int ldx, const uint16_t* __restrict__ w,
                                                            int ldw, const float* __restrict__ bias, int K, int N, int B,
-                                                           int act /*0 none, 1 gelu erf, 2 gelu tanh*/,
-                                                           const float* __restrict__ res, int ldres, float* __restrict__ y, int ldy) {
+                                                           float* __restrict__ y, int ldy) {
     const int lane = threadIdx.x & 63;
     const size_t wid = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     if (wid >= (size_t)B * N) return;
@@ -2131,8 +2111,6 @@ __global__ __launch_bounds__(256) void small_linear_kernel(const float* __restri
     for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
     if (lane == 0) {
         s += bias[n];
-        if (act == 1) s = gelu_erf(s); else if (act == 2) s = gelu_tanh(s);
-        if (res) s += res[(size_t)b * ldres + n];
         y[(size_t)b * ldy + n] = s;
     }
 }
@@ -2758,6 +2736,10 @@ int launch_layernorm(void* x, int x_is_f16, int ldx, const uint16_t* delta, int 
 
 int launch_patchify(const void* img, int is_f16, int B, int C, int H, int W, int P, int k_pad, int tstride, uint16_t* out,
                     hipStream_t st) {
+    // (H % P, W % P are allowed: like the stride-P convolution it replaces, the grid is H / P x W / P and the remainder is ignored -- the
+    // shipped 384-pixel images with 14-pixel patches leave 6)
+    if (P <= 0 || H < P || W < P) return fail("patchify: the image must hold at least one patch");
+    if (k_pad < C * P * P) return fail("patchify: k_pad is smaller than a patch (C * P * P)");
     const size_t total = (size_t)B * tstride * k_pad;
     if (P == 14 && k_pad % 8 == 0 && k_pad <= 1024 && (size_t)B * tstride < (1u << 31)) {   // the shipped geometry
         const unsigned rows = (unsigned)((size_t)B * tstride);
@@ -2892,11 +2874,10 @@ int launch_pool_attention(const uint16_t* kv, int ldkv, const float* qlat, int B
     return 0;
 }
 
-int launch_small_linear(const float* x, int ldx, const uint16_t* w, int ldw, const float* bias, int K, int N, int B, int act,
-                        const float* res, int ldres, float* y, int ldy, hipStream_t st) {
+int launch_small_linear(const float* x, int ldx, const uint16_t* w, int ldw, const float* bias, int K, int N, int B, float* y, int ldy,
+                        hipStream_t st) {
     const size_t waves = (size_t)B * N;
-    hipLaunchKernelGGL(small_linear_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, x, ldx, w, ldw, bias, K, N, B, act,
-                       res, ldres, y, ldy);
+    hipLaunchKernelGGL(small_linear_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, x, ldx, w, ldw, bias, K, N, B, y, ldy);
     MSE_HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -2911,6 +2892,7 @@ int launch_l2norm(const float* x, int ldx, int width, int B, int normalize, floa
 int launch_embed_tokens(const int64_t* tokens, const float* tok_emb, const float* pos, int vocab, int ctx, int D, size_t rows,
                         uint16_t* x_f16, hipStream_t st) {
     if (rows == 0) return 0;
+    if (D % 4) return fail("embed tokens: width must be a multiple of 4");
     hipLaunchKernelGGL(embed_tokens_kernel, dim3((unsigned)rows), dim3(128), 0, st, tokens, tok_emb, pos, vocab, ctx, D, rows,
                        reinterpret_cast<_Float16*>(x_f16));
     MSE_HIP_TRY(hipGetLastError());

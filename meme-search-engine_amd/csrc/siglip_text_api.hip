@@ -196,7 +196,7 @@ static int text_forward(mse_siglip_text* m, const int64_t* tokens, int batch, in
         else if (last.bf16) { df.bf16 = last.bf16 + (size_t)(T - 1) * D; df.ldd = T * D; }
         if (launch_layernorm_d(m->x + (size_t)(T - 1) * D, 1, T * D, df, m->lnf_g, m->lnf_b, c.eps, D, batch, nullptr, D, m->pooled, 1, st)) return -1;
     }
-    if (launch_small_linear(m->pooled, D, m->wproj, D, m->bproj, D, D, batch, 0, nullptr, 0, m->feat, D, st)) return -1;
+    if (launch_small_linear(m->pooled, D, m->wproj, D, m->bproj, D, D, batch, m->feat, D, st)) return -1;
     if (launch_l2norm(m->feat, D, D, batch, normalize, m->out_f32, m->out_f16, st)) return -1;
     return 0;
 }

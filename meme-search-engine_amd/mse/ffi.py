@@ -379,6 +379,15 @@ SIGNATURES = {
     "mse_debug_siglip_pool_attention": (C.c_int, [f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, f32p]),
     "mse_debug_siglip_gemm": (C.c_int, [vp]),
     "mse_debug_siglip_gemm_fused": (C.c_int, [vp]),
+    "mse_debug_siglip_layernorm": (C.c_int, [vp]),
+    "mse_debug_siglip_patchify": (C.c_int, [f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p]),
+    "mse_debug_siglip_rgb8": (C.c_int, [u8p, C.c_int, C.c_int, C.c_int, C.c_int, f32p]),
+    "mse_debug_siglip_bmp24": (C.c_int, [u8p, sz, C.c_int, u8p, C.c_int, C.c_int, C.c_int, f32p]),
+    "mse_debug_siglip_embed_tokens": (C.c_int, [i64p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, f32p]),
+    "mse_debug_siglip_f32_to_bf16_pad": (C.c_int, [f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p]),
+    "mse_debug_siglip_small_linear": (C.c_int, [f32p, C.c_int, f32p, C.c_int, f32p, C.c_int, C.c_int, C.c_int, C.c_int, f32p]),
+    "mse_debug_siglip_l2norm": (C.c_int, [f32p, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p]),
+    "mse_debug_siglip_vt_ones_row": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, f32p]),
     "mse_siglip_text_create": (vp, [vp]),
     "mse_siglip_text_destroy": (None, [vp]),
     "mse_siglip_text_n_weights": (C.c_int, [vp]),
@@ -431,6 +440,13 @@ class DebugSiglipGemmFusedArgs(C.Structure):
                 [("eps", C.c_float)] +
                 [(n, f32p) for n in ("x", "w", "bias", "gamma", "beta", "xres", "out", "q", "k", "vt", "stats")] +
                 [(n, C.c_int) for n in ("M", "n_pad", "n_seq", "dh_pad", "kdh_pad", "dv_pad")])
+
+
+class DebugSiglipLayernormArgs(C.Structure):
+    """mse_debug_siglip_layernorm_args (include/mse.h)"""
+    _fields_ = ([(n, C.c_int) for n in ("rows", "width", "ldx", "x_is_f16", "ldd", "n_parts", "part_rows", "ldp", "ldo", "wg")] +
+                [("eps", C.c_float)] +
+                [(n, f32p) for n in ("x", "delta", "parts", "bias", "gamma", "beta", "x_out", "out", "out_f32")])
 
 
 def lib():
