@@ -1173,9 +1173,9 @@ mse_filter* mse_filter_concat(const mse_filter* const* parts, const uint64_t* fi
  * scan over a graph's base (the lock notes of mse_graph_delete_rows / mse_graph_insert_rows).
  *   mse_pairs_rows / _count   rows of the base the list was made over | pairs
  *   mse_pairs_read            pairs first .. first + n of the canonical order (any output may be null); past the count is an error
- *   mse_join_stats            of the last mse_join_self on s: [0] tiles that did work, [1] pairs nominated, [2] pairs re-scored,
+ *   mse_join_stats            of the last join on s (mse_join_self, or mse_join_cross below): [0] tiles that did work, [1] pairs nominated, [2] pairs re-scored,
  *                             [3] pairs kept (or the count that did not fit), [4] strip launches repeated for a full buffer,
- *                             [5] rounds of the last keep-first resolution of a list made by s
+ *                             [5] rounds of the last keep-first resolution (or mse_pairs_admit) of a list made by s
  *   mse_join_timing           measurement hook (scripts/near_duplicate_probe.py): out (or null) receives the HIP-event milliseconds of the
  *                             last mse_join_self on s -- [0] tile launches, [1] re-score launches, [2] building the list in canonical
  *                             order -- then the switch is set; while it is on the call waits once more per launch
@@ -1189,7 +1189,7 @@ mse_filter* mse_filter_concat(const mse_filter* const* parts, const uint64_t* fi
  *   mse_pairs_groups            a fresh grouping: label rep[i] for every row of a group of two or more (the representative included),
  *                               MSE_GROUP_NONE for every other row; every member scores >= threshold against its representative
  *   mse_pairs_representatives   rep, mse_pairs_rows(p) entries, to the host
- * Not covered: connected-component grouping, a join between two bases or of a query batch against the rows, the shard group. */
+ * Not covered: connected-component grouping, the shard group. */
 typedef struct mse_pairs mse_pairs;
 mse_pairs* mse_join_self(mse_searcher* s, int64_t threshold, uint64_t window, const mse_filter* within_or_null, int mode, uint64_t max_pairs);
 void mse_pairs_free(mse_pairs* p);
@@ -1202,6 +1202,60 @@ int mse_debug_join_candidate_capacity(mse_searcher* s, uint64_t n);
 mse_filter* mse_pairs_duplicates(const mse_pairs* p);
 mse_groups* mse_pairs_groups(const mse_pairs* p);
 int mse_pairs_representatives(const mse_pairs* p, uint32_t* rep);
+/* ---- cross join: near-duplicates of incoming rows against a resident base, admission, select ----------------------------------------
+ * The self-join cleans an index that is dirty; this keeps a live one clean.  It is the exact form of the reference's ingest step -D
+ * (src/dump_processor.rs:375-392, a 64-bit binarisation hashed into a ring of the last 2^21 records).
+ *
+ * mse_join_cross: s searches the resident base B (n rows); `incoming` is a second base Q (m rows; mse_base_from_host, or
+ * mse_base_wrap_device over an encoder's f16 output) of the same width on the same device.  The result is EVERY pair (b, j) with b a row
+ * of B that within_or_null allows (when given), j a row of Q, and fast_dot(B[b], Q[j]) >= threshold -- the reference-order i64 score,
+ * the number mse_bruteforce_scores_f16 returns with Q[j] as the query; >=, saturation and NaN as for mse_join_self.
+ * The list is an mse_pairs of kind 1: a CSR over the incoming row j, which takes the hi role because it comes later in ingest order;
+ * within each j the base ids ascend, each with its exact score.  mse_pairs_read returns lo = base row, hi = incoming row in canonical
+ * order (hi ascending, then lo ascending); mse_pairs_rows is m.  There is no window: the two id spaces are unrelated.
+ *   mse_pairs_kind        0 for a self list, 1 for a cross list
+ *   mse_pairs_base_rows   n for a cross list, mse_pairs_rows for a self list
+ * mse_pairs_duplicates, _groups and _representatives on a cross list are errors that name mse_pairs_admit.
+ * The list's bytes do not depend on the run, the mode, the candidate buffer's size (mse_debug_join_candidate_capacity applies), earlier
+ * calls on s, whether Q was copied from the host or wrapped, or how the batch is cut: the list of rows [a, c) of Q given alone is the
+ * slice of the whole list with hi shifted by a.
+ * Modes as for mse_join_self.  EXACT scores every pair of the rectangle on the vector ALU in reference order.  MFMA and AUTO run 128 x 128
+ * tiles of the m x n rectangle on the f16 matrix cores and nominate by accumulator * 2^32 >= threshold - bound; every nomination is
+ * re-scored in reference order.  The bound is stated for a pair with one row from each base: the one-base formula of mse_join_self over
+ * the element-wise maximum of the two bases' three norm figures (largest row norm, largest subnormal mass of a row, largest component);
+ * |a||b| <= max^2, and the subnormal term is monotone in both of its figures.  MSE_GRAM_EPS_SCALE applies.  Where no bound can be stated
+ * -- a non-finite component in either base -- the exact tiles run whatever mode was asked for.
+ * Schedule: a strip is a run of base tiles by all incoming tiles (incoming fastest), so workgroups that are resident together share a
+ * base tile and the base streams from HBM once per strip; strips are cut along the incoming side too when m / 128 exceeds a strip.  The
+ * strip rule (one reservation per tile, windows of the scanned tile numbering when the buffer overflows), the data-only rank inside a
+ * tile and "a tile whose base rows `within` excludes altogether loads nothing" are the self-join's.
+ * mse_join_stats and mse_join_timing of s describe the last join on s, self or cross, with the same meaning per field.
+ * Errors, in this order: a null searcher or a null incoming base; a width or device mismatch between the two bases; the `within` errors
+ * of the filtered searches; an unknown mode.  m = 0 or n = 0 gives an empty list over m rows.  More than max_pairs pairs: an error that
+ * makes nothing and leaves the true count in stats [3].  A graph's base: pass mse_graph_live_filter(g, 0) as `within`, and keep deletes,
+ * inserts and restores on that graph out while the call runs, as for mse_join_self.
+ *
+ * mse_pairs_admit: keep-first continued from the index into the batch.  `among_or_null` is an ordinary self list over the same m incoming
+ * rows (mse_join_self on a searcher over Q).  The rule is the handler's retain loop (src/query_disk_index.rs:513-527) run over "allowed
+ * base rows first, all retained, then the batch in row order": incoming row j is KEPT iff it has no cross pair and no kept incoming row
+ * j' < j pairs with it in `among`.  A row dropped by the base is dropped and therefore drops nobody: with b ~ j1 ~ j2 and b !~ j2, j1 goes
+ * and j2 stays.  rep_base[j] (m entries, or null) is j's lowest base partner, 0xFFFFFFFF when it has none; rep_incoming[j] (m entries, or
+ * null) is j itself when j is kept, its lowest kept earlier `among` neighbour when that is what dropped it, 0xFFFFFFFF when the base
+ * dropped it.  *kept_out is a fresh filter over m rows, on the device.  Resolved on the device in the integer rounds of the self list,
+ * started from a state in which rows with a cross pair are already dropped; bit-reproducible; no label crosses to the host before the
+ * outputs.  among = null: only the base decides.  The rounds it took are left in mse_join_stats [5] of the searcher that made `cross`.
+ * Errors: `cross` is not a cross list; `among` is not a self list; the row counts or devices differ; kept_out is null.
+ *
+ * mse_base_select: a fresh owned base holding the rows of b that `keep` allows, in ascending order -- a 16-byte-vector row gather on the
+ * device.  With it an encoder's device output flows wrap -> cross join -> admit -> select -> mse_graph_insert_rows_dev without its rows
+ * crossing PCIe.  A filter longer than the base or on another device is an error; a count of 0 gives a base of 0 rows.
+ * Not covered: the shard group, connected-component grouping, an approximate join through the graph, PQ-code pre-filters. */
+mse_pairs* mse_join_cross(mse_searcher* s, const mse_base* incoming, int64_t threshold, const mse_filter* within_or_null, int mode,
+                          uint64_t max_pairs);
+int mse_pairs_kind(const mse_pairs* p);
+size_t mse_pairs_base_rows(const mse_pairs* p);
+int mse_pairs_admit(const mse_pairs* cross, const mse_pairs* among_or_null, mse_filter** kept_out, uint32_t* rep_base, uint32_t* rep_incoming);
+mse_base* mse_base_select(const mse_base* b, const mse_filter* keep);
 /* mse_shard_filter: one LOCAL filter per shard of a group, each on its shard's device -- what the filtered searches of the group take.
  *   mse_shard_group_filter             mse_filter_slice of `global` at each shard's first row and length.  A filter shorter than the group
  *                                      excludes the rows past it; one longer than max(first row + rows) over the shards is an error.

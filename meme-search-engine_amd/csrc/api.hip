@@ -233,6 +233,24 @@ mse_base* mse_base_generate(uint32_t seed, uint64_t first_row, size_t n_rows, si
     }
     return b;
 }
+mse_base* mse_base_select(const mse_base* b, const mse_filter* keep) {
+    if (!b) { fail("base_select: null base"); return nullptr; }
+    if (check_filter(b, keep)) return nullptr;
+    if (hipSetDevice(b->device) != hipSuccess) { fail("base_select: hipSetDevice failed"); return nullptr; }
+    mse_base* out = base_alloc(keep->count, b->d, true);
+    if (!out) return nullptr;
+    void* p = nullptr;
+    if (hipMalloc(&p, std::max<size_t>(keep->count * b->d * 2, 256)) != hipSuccess) { delete out; fail("hipMalloc failed for base vectors"); return nullptr; }
+    out->dev = reinterpret_cast<const uint16_t*>(p);
+    // 16-byte pieces when the source allows them (a wrapped base may start anywhere), 2-byte elements otherwise
+    const bool vec16 = reinterpret_cast<uintptr_t>(b->dev) % 16 == 0;
+    const int rc = vec16 ? launch_join_select_rows(b->dev, b->d * 2, keep->ids, keep->count, p, b->n_cu, nullptr)
+                         : launch_gather_rows_f16(b->dev, keep->ids, keep->count, (int)b->d, reinterpret_cast<uint16_t*>(p), nullptr);
+    if (rc || hipStreamSynchronize(nullptr) != hipSuccess) {
+        mse_base_free(out); if (!rc) fail("base_select: the row gather failed"); return nullptr;
+    }
+    return out;
+}
 void mse_base_free(mse_base* b) {
     if (!b) return;
     if (b->disp) mse_dispatcher_free(b->disp);   // joins its worker; no search may be in flight (as for the rows themselves)

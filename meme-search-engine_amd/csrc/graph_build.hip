@@ -1228,12 +1228,32 @@ namespace mse {
 
 // Bound, in the fixed-point scale, on |MFMA f16 sum - fast_dot| for two base rows: 2.8e-4 * (largest row norm)^2, the
 // allowance the scan's certificate uses.  *eps_fix = 0 when no bound can be stated (the exact kernels run).
+static int pair_bound_of(const uint32_t (&bits)[3], long long* eps_fix);
+
 int mfma_pair_bound(const mse_base* b, hipStream_t st, long long* eps_fix) {
     *eps_fix = 0;
     if (b->d % 64) return 0;
     if (ensure_base_norm(b, st)) return -1;
     uint32_t bits[3] = {0, 0, 0};
     MSE_HIP_TRY(hipMemcpy(bits, b->norm_bits_dev, 12, hipMemcpyDeviceToHost));
+    return pair_bound_of(bits, eps_fix);
+}
+
+// |a||b| <= max(|a|, |b|)^2, and the subnormal term grows with both of its figures: the larger of each figure bounds a mixed pair.  The
+// figures are non-negative floats (or NaN, which lies above every number as bits), so the maximum is taken on the bits
+int mfma_cross_bound(const mse_base* a, const mse_base* b, hipStream_t st, long long* eps_fix) {
+    *eps_fix = 0;
+    if (a->d % 64 || a->d != b->d) return 0;
+    if (ensure_base_norm(a, st) || ensure_base_norm(b, st)) return -1;
+    uint32_t bits[3] = {0, 0, 0}, other[3] = {0, 0, 0};
+    MSE_HIP_TRY(hipMemcpy(bits, a->norm_bits_dev, 12, hipMemcpyDeviceToHost));
+    MSE_HIP_TRY(hipMemcpy(other, b->norm_bits_dev, 12, hipMemcpyDeviceToHost));
+    for (int i = 0; i < 3; i++) bits[i] = std::max(bits[i], other[i]);
+    return pair_bound_of(bits, eps_fix);
+}
+
+static int pair_bound_of(const uint32_t (&bits)[3], long long* eps_fix) {
+    *eps_fix = 0;
     float mx, sub, ab;
     memcpy(&mx, &bits[0], 4); memcpy(&sub, &bits[1], 4); memcpy(&ab, &bits[2], 4);
     const char* sc = getenv("MSE_GRAM_EPS_SCALE");   // test hook: widen (or zero) the band in which the exact dot decides

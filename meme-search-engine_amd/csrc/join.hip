@@ -13,6 +13,11 @@
 // MFMA tiles nominate by `accumulator >= threshold - bound` (mfma_pair_bound: the certificate of DESIGN.md 3.2); exact tiles nominate by the
 // exact score itself.  Either way a lane quad re-scores each nominated pair in reference order (exact_dot.h) and only pairs at or above the
 // threshold are kept, so the kept set is the same in every mode.
+//
+// The cross join (mse_join_cross) runs the same tiles over a rectangle: the hi role is a row of a second, incoming base, the lo
+// role a row of the resident one (kernels.h JoinStrip).  the CROSS = true instances of the tile kernels take both bases, as does the re-score;
+// there is no triangle and no window, and `within` speaks for the resident rows only.  Workgroups that are resident together (blockIdx.x
+// fastest: the incoming tiles) share a base tile.
 #include "common.h"
 #include "kernels.h"
 #include "exact_dot.h"
@@ -35,8 +40,16 @@ struct TileGeom {
     bool live;
 };
 
+template <bool CROSS>
 __device__ __forceinline__ TileGeom tile_of_block(const JoinStrip& sp) {
     TileGeom g;
+    if (CROSS) {   // hi: the incoming tile, lo: the base tile; the grid is the strip's rectangle
+        g.th = sp.x0 + blockIdx.x;
+        g.tl = sp.h0 + blockIdx.y;
+        g.t = blockIdx.y * sp.span + blockIdx.x;
+        g.live = true;
+        return g;
+    }
     g.th = sp.h0 + blockIdx.y;
     g.t = blockIdx.y * sp.span + blockIdx.x;
     g.live = blockIdx.x <= g.th;
@@ -116,18 +129,23 @@ __device__ __forceinline__ bool tile_placement(const JoinStrip& sp, uint32_t t, 
 // registers).  Both operand panels (128 rows x 64 f16 of K) go through LDS in two stages: the global loads of stage s + 1 are issued before
 // the products of stage s and written to the other buffer after them, one barrier per stage.  Rows at or past n are read as row n - 1 and
 // excluded in the epilogue.
-__global__ __launch_bounds__(256, 2) void join_tile_mfma_kernel(const uint16_t* __restrict__ base, uint32_t n, int d, JoinStrip sp, double thr_lo) {
+// CROSS: hi rows come from `incoming` (n_inc rows), lo rows from `base`; every row below n_inc counts on the hi side, `within` on the lo side.
+template <bool CROSS>
+__global__ __launch_bounds__(256, 2) void join_tile_mfma_kernel(const uint16_t* __restrict__ base, uint32_t n, const uint16_t* __restrict__ incoming,
+                                                                uint32_t n_inc, int d, JoinStrip sp, double thr_lo) {
     extern __shared__ __align__(16) unsigned char lds[];
     __shared__ uint32_t wave_sums[4];
     __shared__ uint32_t lds_base[2];
-    const TileGeom g = tile_of_block(sp);
+    const uint16_t* __restrict__ rows_hi = CROSS ? incoming : base;
+    const uint32_t n_hi = CROSS ? n_inc : n;
+    const TileGeom g = tile_of_block<CROSS>(sp);
     if (!g.live) return;
     if (sp.tile_base) {   // a window launch: tiles without a slot in the window leave before any work
         const unsigned long long b = sp.tile_base[g.t], c = sp.tile_count[g.t];
         if (c == 0 || b + c <= sp.win_lo || b >= sp.win_lo + sp.cap) return;
     }
     uint32_t hb[4], lb[4];
-    tile_bits(sp.within, sp.within_words, g.th, n, hb);
+    tile_bits(CROSS ? nullptr : sp.within, sp.within_words, g.th, n_hi, hb);
     tile_bits(sp.within, sp.within_words, g.tl, n, lb);
     if (!(hb[0] | hb[1] | hb[2] | hb[3]) || !(lb[0] | lb[1] | lb[2] | lb[3])) {   // a tile whose rows are all excluded
         if (!sp.tile_base && threadIdx.x == 0) sp.tile_count[g.t] = 0;
@@ -144,7 +162,7 @@ __global__ __launch_bounds__(256, 2) void join_tile_mfma_kernel(const uint16_t* 
     for (int i = 0; i < 4; i++) {
         const int p = tid + 256 * i, row = p >> 3, piece = p & 7;
         const uint64_t rh = (uint64_t)g.th * JT + row, rl = (uint64_t)g.tl * JT + row;
-        src[0][i] = base + (size_t)(rh < n ? rh : n - 1) * d + piece * 8;
+        src[0][i] = rows_hi + (size_t)(rh < n_hi ? rh : n_hi - 1) * d + piece * 8;
         src[1][i] = base + (size_t)(rl < n ? rl : n - 1) * d + piece * 8;
         dst[i] = row * LROW + piece * 16;
     }
@@ -213,7 +231,7 @@ __global__ __launch_bounds__(256, 2) void join_tile_mfma_kernel(const uint16_t* 
             for (int v = 0; v < 16; v++) {
                 const int rl = wr * 64 + a * 32 + (v & 3) + 8 * (v >> 2) + 4 * (lane >> 5);
                 const uint64_t hi = hi0 + rl;
-                bool ok = col_ok && lo < hi && bit_of(hb, rl) && (sp.window == 0 || hi - lo <= sp.window);
+                bool ok = col_ok && (CROSS || lo < hi) && bit_of(hb, rl) && (CROSS || sp.window == 0 || hi - lo <= sp.window);
                 ok = ok && (double)acc[a][b][v] * 4294967296.0 >= thr_lo;
                 hit |= (uint64_t)ok << (a * 32 + b * 16 + v);
             }
@@ -240,8 +258,8 @@ __global__ __launch_bounds__(256, 2) void join_tile_mfma_kernel(const uint16_t* 
 // ---- the exact tile: every pair of the tile on the vector ALU in reference order ----------------------------------------------------
 // 64 lane quads; quad q scores pairs p = q, q + 64, ...: hi row p / 128, lo row p % 128 of the tile.  STORE = false counts the quad's hits,
 // STORE = true scores the tile again and stores them -- only tiles with a hit are scored twice.
-template <bool STORE>
-__device__ __forceinline__ uint32_t exact_tile_pass(const uint16_t* __restrict__ base, uint32_t n, int d, const JoinStrip& sp, const TileGeom& g,
+template <bool STORE, bool CROSS>
+__device__ __forceinline__ uint32_t exact_tile_pass(const uint16_t* __restrict__ rows_hi, const uint16_t* __restrict__ base, int d, const JoinStrip& sp, const TileGeom& g,
                                                     const uint32_t (&hb)[4], const uint32_t (&lb)[4], int64_t threshold,
                                                     unsigned long long slot, unsigned long long lo_slot, unsigned long long hi_slot) {
     const int q = threadIdx.x >> 2;
@@ -250,8 +268,8 @@ __device__ __forceinline__ uint32_t exact_tile_pass(const uint16_t* __restrict__
     for (int p = q; p < JT * JT; p += 64) {
         const int rl = p / JT, cl = p % JT;
         const uint64_t hi = hi0 + rl, lo = lo0 + cl;
-        if (!(lo < hi && bit_of(hb, rl) && bit_of(lb, cl) && (sp.window == 0 || hi - lo <= sp.window))) continue;   // the same for the quad's four lanes
-        const float f = quad_fast_dot_f32(base + (size_t)hi * d, base + (size_t)lo * d, d);
+        if (!((CROSS || lo < hi) && bit_of(hb, rl) && bit_of(lb, cl) && (CROSS || sp.window == 0 || hi - lo <= sp.window))) continue;   // the same for the quad's four lanes
+        const float f = quad_fast_dot_f32(rows_hi + (size_t)hi * d, base + (size_t)lo * d, d);
         if (scale_dot_result(f) < threshold) continue;
         if (STORE && (threadIdx.x & 3) == 0 && slot + hits >= lo_slot && slot + hits < hi_slot)
             sp.cand[slot + hits - lo_slot] = make_uint2((uint32_t)lo, (uint32_t)hi);
@@ -260,31 +278,35 @@ __device__ __forceinline__ uint32_t exact_tile_pass(const uint16_t* __restrict__
     return hits;
 }
 
-__global__ __launch_bounds__(256) void join_tile_exact_kernel(const uint16_t* __restrict__ base, uint32_t n, int d, JoinStrip sp, int64_t threshold) {
+template <bool CROSS>
+__global__ __launch_bounds__(256) void join_tile_exact_kernel(const uint16_t* __restrict__ base, uint32_t n, const uint16_t* __restrict__ incoming, uint32_t n_inc,
+                                                              int d, JoinStrip sp, int64_t threshold) {
     __shared__ uint32_t wave_sums[4];
     __shared__ uint32_t lds_base[2];
-    const TileGeom g = tile_of_block(sp);
+    const uint16_t* __restrict__ rows_hi = CROSS ? incoming : base;
+    const uint32_t n_hi = CROSS ? n_inc : n;
+    const TileGeom g = tile_of_block<CROSS>(sp);
     if (!g.live) return;
     if (sp.tile_base) {
         const unsigned long long b = sp.tile_base[g.t], c = sp.tile_count[g.t];
         if (c == 0 || b + c <= sp.win_lo || b >= sp.win_lo + sp.cap) return;
     }
     uint32_t hb[4], lb[4];
-    tile_bits(sp.within, sp.within_words, g.th, n, hb);
+    tile_bits(CROSS ? nullptr : sp.within, sp.within_words, g.th, n_hi, hb);
     tile_bits(sp.within, sp.within_words, g.tl, n, lb);
     if (!(hb[0] | hb[1] | hb[2] | hb[3]) || !(lb[0] | lb[1] | lb[2] | lb[3])) {
         if (!sp.tile_base && threadIdx.x == 0) sp.tile_count[g.t] = 0;
         return;
     }
     if (!sp.tile_base && threadIdx.x == 0) atomicAdd(sp.tiles_run, 1ull);
-    const uint32_t hits = exact_tile_pass<false>(base, n, d, sp, g, hb, lb, threshold, 0, 0, 0);
+    const uint32_t hits = exact_tile_pass<false, CROSS>(rows_hi, base, d, sp, g, hb, lb, threshold, 0, 0, 0);
     uint32_t total;
     // one count per quad: its first lane speaks for it
     const uint32_t rank0 = block_rank((threadIdx.x & 3) == 0 ? hits : 0u, wave_sums, &total);
     unsigned long long tbase, lo_slot, hi_slot;
     if (!tile_placement(sp, g.t, total, lds_base, &tbase, &lo_slot, &hi_slot)) return;
     const unsigned long long quad_slot = tbase + __shfl(rank0, (threadIdx.x & 63) & ~3);
-    (void)exact_tile_pass<true>(base, n, d, sp, g, hb, lb, threshold, quad_slot, lo_slot, hi_slot);
+    (void)exact_tile_pass<true, CROSS>(rows_hi, base, d, sp, g, hb, lb, threshold, quad_slot, lo_slot, hi_slot);
 }
 
 // exclusive prefix of the strip's tile counts, in tile order (one workgroup; each thread walks a contiguous run)
@@ -308,7 +330,8 @@ __global__ __launch_bounds__(256) void join_scan_tiles_kernel(const uint32_t* __
 // ---- the re-score: a lane quad per nominated pair ----------------------------------------------------------------------------------------
 // counters[0] += pairs at or above the threshold; while the running count stays within store_cap the pair is appended to conf (in arrival
 // order: the list is put into canonical order at the end) and counted into row_count[hi]
-__global__ __launch_bounds__(256) void join_rescore_kernel(const uint16_t* __restrict__ base, int d, const uint2* __restrict__ cand, size_t m,
+// (rows_hi: the base again, or the cross join's incoming rows)
+__global__ __launch_bounds__(256) void join_rescore_kernel(const uint16_t* __restrict__ base, const uint16_t* __restrict__ rows_hi, int d, const uint2* __restrict__ cand, size_t m,
                                                            int64_t threshold, unsigned long long* __restrict__ kept, JoinPair* __restrict__ conf,
                                                            unsigned long long store_cap, uint32_t* __restrict__ row_count) {
     const size_t quads = ((size_t)gridDim.x * blockDim.x) >> 2;
@@ -317,7 +340,7 @@ __global__ __launch_bounds__(256) void join_rescore_kernel(const uint16_t* __res
     for (size_t s = 0; s < steps; s++, i += quads) {
         if (i >= m) continue;   // (the quad's four lanes share i)
         const uint2 p = cand[i];
-        const int64_t sc = scale_dot_result(quad_fast_dot_f32(base + (size_t)p.y * d, base + (size_t)p.x * d, d));
+        const int64_t sc = scale_dot_result(quad_fast_dot_f32(rows_hi + (size_t)p.y * d, base + (size_t)p.x * d, d));
         if (sc >= threshold && (threadIdx.x & 3) == 0) {
             const unsigned long long at = atomicAdd(kept, 1ull);
             if (at < store_cap) {
@@ -435,23 +458,80 @@ __global__ void join_labels_kernel(const uint32_t* __restrict__ rep, const uint8
     labels[r] = (v != (uint32_t)r || has_member[r]) ? v : ID_NONE;
 }
 
+// ---- admission: keep-first continued from the resident rows into the incoming ones --------------------------------------------------
+// The resident rows come first in the walk and are all kept, so an incoming row with a cross pair is dropped before any round runs; the
+// rounds of join_round_kernel over the list AMONG the incoming rows then start from that state.  decide: there is no such list, the rest
+// is kept at once.
+__global__ void join_admit_init_kernel(const unsigned long long* __restrict__ cross_offsets, size_t m, bool decide, uint8_t* __restrict__ state,
+                                       unsigned long long* __restrict__ undecided) {
+    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= m) return;
+    const uint8_t st = cross_offsets[j + 1] > cross_offsets[j] ? 2 : decide ? 1 : 0;
+    state[j] = st;
+    if (st == 0) atomicAdd(undecided, 1ull);
+}
+
+__global__ __launch_bounds__(256) void join_admit_finish_kernel(const unsigned long long* __restrict__ cross_offsets, const uint32_t* __restrict__ cross_lo,
+                                                                const unsigned long long* __restrict__ among_offsets,
+                                                                const uint32_t* __restrict__ among_lo, size_t m, const uint8_t* __restrict__ state,
+                                                                uint32_t* __restrict__ rep_base, uint32_t* __restrict__ rep_incoming,
+                                                                uint32_t* __restrict__ kept_words) {
+    const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
+    bool kept = false;
+    if (j < m) {
+        const unsigned long long c0 = cross_offsets[j];
+        const bool by_base = cross_offsets[j + 1] > c0;
+        rep_base[j] = by_base ? cross_lo[c0] : ID_NONE;   // ascending: the first one is the lowest
+        kept = state[j] == 1;
+        uint32_t v = kept ? (uint32_t)j : ID_NONE;
+        if (!kept && !by_base && among_offsets)
+            for (unsigned long long e = among_offsets[j]; e < among_offsets[j + 1]; e++)
+                if (state[among_lo[e]] == 1) { v = among_lo[e]; break; }
+        rep_incoming[j] = v;
+    }
+    const unsigned long long w = __ballot(kept);
+    if ((threadIdx.x & 63) == 0) *reinterpret_cast<uint2*>(kept_words + (j >> 6) * 2) = make_uint2((uint32_t)w, (uint32_t)(w >> 32));
+}
+
+// ---- the selected rows of a base, packed: 16-byte pieces, consecutive threads on consecutive pieces of a row -------------------------
+__global__ __launch_bounds__(256) void join_select_rows_kernel(const uint4* __restrict__ in, size_t row_u4, const uint32_t* __restrict__ ids, size_t count,
+                                                               uint4* __restrict__ out) {
+    const size_t total = count * row_u4, step = (size_t)gridDim.x * blockDim.x;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += step) {
+        const size_t j = t / row_u4, c = t - j * row_u4;
+        out[t] = in[(size_t)ids[j] * row_u4 + c];
+    }
+}
+
 inline unsigned blocks_for(size_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 }  // namespace
 
 size_t join_tile_lds_bytes() { return 4 * PANEL; }
 
-int launch_join_tiles(bool exact, const uint16_t* base, size_t n, int d, const JoinStrip& sp, int64_t threshold, double thr_lo, hipStream_t stream) {
-    if (sp.n_hi == 0 || sp.span == 0) return 0;
-    if (sp.n_hi > 65535) return fail("join: more than 65535 hi tiles in a strip");
+template <bool CROSS>
+static int launch_join_tiles_of(bool exact, const uint16_t* base, size_t n, const uint16_t* incoming, size_t m, int d, const JoinStrip& sp,
+                                int64_t threshold, double thr_lo, hipStream_t stream) {
     const dim3 grid(sp.span, sp.n_hi), block(256);
     if (exact) {
-        hipLaunchKernelGGL(join_tile_exact_kernel, grid, block, 0, stream, base, (uint32_t)n, d, sp, threshold);
+        hipLaunchKernelGGL(join_tile_exact_kernel<CROSS>, grid, block, 0, stream, base, (uint32_t)n, incoming, (uint32_t)m, d, sp, threshold);
     } else {
         if (d % KC) return fail("join: the matrix-core tile needs a width that is a multiple of 64");
-        MSE_DYN_LDS(join_tile_mfma_kernel, join_tile_lds_bytes());
-        hipLaunchKernelGGL(join_tile_mfma_kernel, grid, block, join_tile_lds_bytes(), stream, base, (uint32_t)n, d, sp, thr_lo);
+        MSE_DYN_LDS(join_tile_mfma_kernel<CROSS>, join_tile_lds_bytes());
+        hipLaunchKernelGGL(join_tile_mfma_kernel<CROSS>, grid, block, join_tile_lds_bytes(), stream, base, (uint32_t)n, incoming, (uint32_t)m, d, sp, thr_lo);
     }
+    return 0;
+}
+
+int launch_join_tiles(bool exact, const uint16_t* base, size_t n, const uint16_t* incoming, size_t m, int d, const JoinStrip& sp, int64_t threshold,
+                      double thr_lo, hipStream_t stream) {
+    if (sp.n_hi == 0 || sp.span == 0) return 0;
+    if (sp.n_hi > 65535) return fail("join: more than 65535 tile rows in a strip");
+    if (incoming) {   // every tile of the rectangle must lie inside both bases: the kernels clamp rows, not tiles
+        if (n == 0 || m == 0 || (size_t)sp.h0 + sp.n_hi > (n + JT - 1) / JT || (size_t)sp.x0 + sp.span > (m + JT - 1) / JT)
+            return fail("join: a strip of the cross join reaches past its bases");
+        if (launch_join_tiles_of<true>(exact, base, n, incoming, m, d, sp, threshold, thr_lo, stream)) return -1;
+    } else if (launch_join_tiles_of<false>(exact, base, n, nullptr, 0, d, sp, threshold, thr_lo, stream)) return -1;
     MSE_HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -463,12 +543,13 @@ int launch_join_scan_tiles(const uint32_t* counts, size_t n_tiles, unsigned long
     return 0;
 }
 
-int launch_join_rescore(const uint16_t* base, int d, const uint2* cand, size_t m, int64_t threshold, unsigned long long* kept, JoinPair* conf,
+int launch_join_rescore(const uint16_t* base, const uint16_t* incoming, int d, const uint2* cand, size_t m, int64_t threshold, unsigned long long* kept, JoinPair* conf,
                         unsigned long long store_cap, uint32_t* row_count, int n_cu, hipStream_t stream) {
     if (m == 0) return 0;
     const size_t want = (m + 63) / 64;   // 64 quads per block
     const unsigned blocks = (unsigned)std::min<size_t>(want, (size_t)std::max(n_cu, 1) * 16);
-    hipLaunchKernelGGL(join_rescore_kernel, dim3(blocks), dim3(256), 0, stream, base, d, cand, m, threshold, kept, conf, store_cap, row_count);
+    hipLaunchKernelGGL(join_rescore_kernel, dim3(blocks), dim3(256), 0, stream, base, incoming ? incoming : base, d, cand, m, threshold, kept, conf,
+                       store_cap, row_count);
     MSE_HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -497,6 +578,36 @@ int launch_join_finish(const unsigned long long* offsets, const uint32_t* lo, si
     if (n == 0) return 0;
     hipLaunchKernelGGL(join_rep_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, stream, offsets, lo, n, state, rep, has_member, dup_words);
     hipLaunchKernelGGL(join_labels_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, stream, rep, has_member, n, labels);
+    MSE_HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_join_admit_init(const unsigned long long* cross_offsets, size_t m, bool decide, uint8_t* state, unsigned long long* undecided,
+                           hipStream_t stream) {
+    if (m == 0) return 0;
+    hipLaunchKernelGGL(join_admit_init_kernel, dim3(blocks_for(m, 256)), dim3(256), 0, stream, cross_offsets, m, decide, state, undecided);
+    MSE_HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_join_admit_finish(const unsigned long long* cross_offsets, const uint32_t* cross_lo, const unsigned long long* among_offsets,
+                             const uint32_t* among_lo, size_t m, const uint8_t* state, uint32_t* rep_base, uint32_t* rep_incoming,
+                             uint32_t* kept_words, hipStream_t stream) {
+    if (m == 0) return 0;
+    hipLaunchKernelGGL(join_admit_finish_kernel, dim3(blocks_for(m, 256)), dim3(256), 0, stream, cross_offsets, cross_lo, among_offsets, among_lo, m,
+                       state, rep_base, rep_incoming, kept_words);
+    MSE_HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_join_select_rows(const void* in, size_t row_bytes, const uint32_t* ids, size_t count, void* out, int n_cu, hipStream_t stream) {
+    const size_t total = count * (row_bytes / 16);
+    if (total == 0) return 0;
+    if (row_bytes % 16 || (reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) % 16)
+        return fail("select rows: rows must be whole 16-byte pieces at 16-byte aligned addresses");
+    const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)std::max(n_cu, 1) * 32);
+    hipLaunchKernelGGL(join_select_rows_kernel, dim3(blocks), dim3(256), 0, stream, reinterpret_cast<const uint4*>(in), row_bytes / 16, ids, count,
+                       reinterpret_cast<uint4*>(out));
     MSE_HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -351,16 +351,20 @@ int launch_delete_finish(uint32_t* deg, uint8_t* has_url, uint32_t* deleted, con
 // restore: bit cleared in `deleted`, has_url = 1
 int launch_delete_restore(uint8_t* has_url, uint32_t* deleted, const uint32_t* ids, size_t n_ids, hipStream_t stream);
 
-// ---- join.hip: the near-duplicate self-join (include/mse.h mse_join_self) -------------------------------------------
+// ---- join.hip: the near-duplicate joins (include/mse.h mse_join_self / mse_join_cross) ------------------------
 constexpr int JOIN_TILE = 128;   // rows per side of a Gram tile
 struct JoinPair { uint32_t lo, hi; int64_t score; };
 // One launch over a strip of the tile schedule: hi tiles h0 .. h0 + n_hi, tile t = (hi tile - h0) * span + x with lo tile = hi tile - x
 // (x < span; tiles outside the triangle or the window band do not exist).  tile_base == null: the strip's FIRST launch -- every tile writes
 // its nomination count to tile_count[t], reserves room at *cursor (zeroed by the caller) and stores its pairs if they end within cap;
 // *tiles_run += tiles that did work.  tile_base != null (the exclusive prefix of tile_count): a WINDOW launch -- the nominations numbered
-// win_lo .. win_lo + cap in tile order are stored at cand[number - win_lo]; tiles without one leave at once
+// win_lo .. win_lo + cap in tile order are stored at cand[number - win_lo]; tiles without one leave at once.
+// The CROSS join (a second base of incoming rows in the hi role) has a rectangle instead: blockIdx.y walks the n_hi BASE tiles from h0,
+// blockIdx.x the span INCOMING tiles from x0, tile t = y * span + x as above; every tile of the grid exists, window is 0 and `within`
+// speaks for the base rows only
 struct JoinStrip {
     uint32_t h0 = 0, n_hi = 0, span = 0;
+    uint32_t x0 = 0;                                      // cross join: first incoming tile of the strip
     uint64_t window = 0;                                  // hi - lo <= window (0: no limit)
     const uint32_t* within = nullptr; size_t within_words = 0;   // bitmap words of an mse_filter (null: every row)
     uint32_t* tile_count = nullptr;
@@ -372,12 +376,14 @@ struct JoinStrip {
 };
 size_t join_tile_lds_bytes();
 // exact: every pair of the tile scored in reference order and nominated by score >= threshold; else the matrix-core tile, nominating by
-// accumulator * 2^32 >= thr_lo (the caller's threshold - bound, rounded down to a double); d % 64 == 0 there
-int launch_join_tiles(bool exact, const uint16_t* base, size_t n, int d, const JoinStrip& sp, int64_t threshold, double thr_lo, hipStream_t stream);
+// accumulator * 2^32 >= thr_lo (the caller's threshold - bound, rounded down to a double); d % 64 == 0 there.  incoming != null: the cross
+// join's rectangle of m incoming rows (hi) by n base rows (lo)
+int launch_join_tiles(bool exact, const uint16_t* base, size_t n, const uint16_t* incoming, size_t m, int d, const JoinStrip& sp, int64_t threshold,
+                      double thr_lo, hipStream_t stream);
 int launch_join_scan_tiles(const uint32_t* counts, size_t n_tiles, unsigned long long* out, hipStream_t stream);
 // a lane quad per nominated pair: *kept += pairs with fast_dot >= threshold; those numbered below store_cap are appended to conf and counted
-// into row_count[hi]
-int launch_join_rescore(const uint16_t* base, int d, const uint2* cand, size_t m, int64_t threshold, unsigned long long* kept, JoinPair* conf,
+// into row_count[hi].  incoming != null: hi is a row of it (the cross join)
+int launch_join_rescore(const uint16_t* base, const uint16_t* incoming, int d, const uint2* cand, size_t m, int64_t threshold, unsigned long long* kept, JoinPair* conf,
                         unsigned long long store_cap, uint32_t* row_count, int n_cu, hipStream_t stream);
 // conf (count pairs, any order; row_count as the re-score left it, consumed) -> offsets [n + 1] over hi, and lo / hi / scores in canonical
 // order: hi ascending, then lo ascending
@@ -389,6 +395,18 @@ int launch_join_round(const unsigned long long* offsets, const uint32_t* lo, siz
 // rep, the dropped rows' bitmap (dup_words: whole 256-row tiles) and the group labels from the final state; has_member: n zeroed bytes
 int launch_join_finish(const unsigned long long* offsets, const uint32_t* lo, size_t n, const uint8_t* state, uint32_t* rep, uint8_t* has_member,
                        uint32_t* dup_words, uint32_t* labels, hipStream_t stream);
+// admission (mse_pairs_admit): state[j] = 2 for an incoming row with a cross pair, else 0 (1 when no rounds follow: `decide`);
+// *undecided += rows left at 0
+int launch_join_admit_init(const unsigned long long* cross_offsets, size_t m, bool decide, uint8_t* state, unsigned long long* undecided,
+                           hipStream_t stream);
+// from the final state: rep_base[j] = lowest base partner or ID_NONE; rep_incoming[j] = j (kept), the lowest kept earlier `among` neighbour
+// (dropped by it), ID_NONE (dropped by the base); kept_words: the kept rows as bitmap words (whole 256-row tiles, zero past m).
+// among_offsets null: no list among the incoming rows
+int launch_join_admit_finish(const unsigned long long* cross_offsets, const uint32_t* cross_lo, const unsigned long long* among_offsets,
+                             const uint32_t* among_lo, size_t m, const uint8_t* state, uint32_t* rep_base, uint32_t* rep_incoming,
+                             uint32_t* kept_words, hipStream_t stream);
+// out row j = in row ids[j], j < count, rows of row_bytes (a multiple of 16; both pointers 16-byte aligned)
+int launch_join_select_rows(const void* in, size_t row_bytes, const uint32_t* ids, size_t count, void* out, int n_cu, hipStream_t stream);
 
 // ---- scan_mfma.hip ---------------------------------------------------------------------------
 // group_max[q_pad_index][g] layout: [n_groups][nq_pad] floats (group-major), nq_pad multiple of 32

@@ -137,9 +137,12 @@ struct JoinState {
 };
 }  // namespace mse
 
-// result of mse_join_self (join.hip, join_api.hip; the list is immutable, the keep-first resolution is made on first use and kept)
+// result of mse_join_self / mse_join_cross (join.hip, join_api.hip; the list is immutable, a self list's keep-first resolution is made on
+// first use and kept).  A cross list (kind 1) is a CSR over the INCOMING rows (n_rows of them); its lo ids are rows of the resident base
 struct mse_pairs {
     int device = 0;
+    int kind = 0;                            // 0: self list, 1: cross list
+    size_t base_rows = 0;                    // rows of the resident base (a self list: n_rows)
     size_t n_rows = 0, count = 0;
     unsigned long long* offsets = nullptr;   // device [n_rows + 1]: the CSR over hi
     uint32_t *lo = nullptr, *hi = nullptr;   // device [count], canonical order
@@ -319,6 +322,9 @@ int ensure_base_norm(const mse_base* b, hipStream_t st);
 // Bound, in the fixed-point scale, on |MFMA f16 sum - fast_dot| for two rows of b (graph_build.hip; the certificate of DESIGN.md 3.2):
 // *eps_fix = 0 when none can be stated (a width that is no multiple of 64, a non-finite row)
 int mfma_pair_bound(const mse_base* b, hipStream_t st, long long* eps_fix);
+// the same for a pair with one row from each of two bases of one width: the one-base formula over the element-wise maximum of their
+// three norm figures
+int mfma_cross_bound(const mse_base* a, const mse_base* b, hipStream_t st, long long* eps_fix);
 // error bound of the matrix-core products robust_prune may decide by (graph_build.hip): *eps_fix = 0 means exact dots only
 int prune_mfma_eps(const mse_base* b, const ::mse_build_config* cfg, hipStream_t st, long long* eps_fix);
 // the limits mse_build_graph sets on the searcher, the graph and the config (graph_build.hip); 0, or -1 with the error set

@@ -135,6 +135,27 @@ INSERT_STATS = ("inserted", "batches")                                          
 COMPACT_STATS = ("live", "capacity", "edges_rewritten", "bytes_moved")               # stats_out[0..4) of mse_graph_compact
 
 
+class _DeviceRows:
+    """The rows of a VectorList in the shape insert_rows takes device rows in (data_ptr() and what it checks beside it)."""
+
+    is_cuda = True
+
+    def __init__(self, vecs):
+        self._vecs = vecs
+
+    def data_ptr(self):
+        return int(self._vecs.device_ptr or 0)
+
+    def numel(self):
+        return len(self._vecs) * self._vecs.d_emb
+
+    def element_size(self):
+        return 2
+
+    def is_contiguous(self):
+        return True
+
+
 class _RowDeletes:
     """delete_rows / deleted / restore_rows / insert_rows of the two classes that wrap an mse_graph (include/mse.h "delete rows and
     repair the graph", "insert rows into freed slots")."""
@@ -183,6 +204,69 @@ class _RowDeletes:
             live.close()
             if both is not None:
                 both.close()
+
+    def near_duplicates_of(self, searcher: Searcher, incoming, threshold, **kw):
+        """Searcher.near_duplicates_of over the graph's rows within live_filter() (has_url is not consulted): deleted slots hold stale rows
+        and do not pair.  within=... narrows it further.  Like every brute-force scan over a graph's base it takes no part in the graph's
+        lock: the caller keeps delete_rows, insert_rows and restores on this graph out while it runs."""
+        if searcher is None or getattr(searcher, "_h", None) is None:
+            raise MseError("near_duplicates_of needs the searcher over the graph's rows")
+        live = self.live_filter(False)
+        within = kw.pop("within", None)
+        both = None
+        try:
+            if within is not None:
+                if not isinstance(within, RowFilter):
+                    raise TypeError("within must be a RowFilter")
+                both = live & within
+            return searcher.near_duplicates_of(incoming, threshold, within=both if both is not None else live, **kw)
+        finally:
+            live.close()
+            if both is not None:
+                both.close()
+
+    def insert_unique_rows(self, searcher: Searcher, slots, rows, threshold, config, start, quantizer=None, codes=None, descriptors=None,
+                           has_url=None, batch=0):
+        """insert_rows of the rows that are new: a row of `rows` is inserted unless it scores >= threshold against a live row of the index or
+        against an earlier row of `rows` that is itself inserted (the keep-first rule, continued from the index into the batch).
+        Steps: near_duplicates_of within the live rows; near_duplicates of the batch itself; RowPairs.admit; insert_rows of the kept rows,
+        with their descriptors and flags, into the first kept.count slots.  rows: a VectorList, or a numpy array of f16 values / uint16
+        bits (one row per slot); the kept rows are gathered on the device and do not return to the host.  The other arguments are
+        insert_rows'.
+        Returns {"kept": boolean mask over rows, "rep_base", "rep_incoming": the Admission's arrays, "unused_slots": the slots left over,
+        "inserted", "batches": what insert_rows returns}.
+        Like every brute-force scan over a graph's base the two joins take no part in the graph's lock, and nothing holds it between the
+        join and the insert: the caller keeps delete_rows, insert_rows and restores on this graph out while it runs."""
+        if searcher is None or getattr(searcher, "_h", None) is None:
+            raise MseError("insert_unique_rows needs the searcher over the graph's rows")
+        sl = np.asarray(slots).reshape(-1)
+        owned = not isinstance(rows, VectorList)
+        q = VectorList.from_f16s(rows, searcher.vecs.d_emb) if owned else rows
+        qs = cross = among = adm = picked = None
+        try:
+            m = len(q)
+            if sl.size != m:
+                raise ValueError(f"one slot per row: {sl.size} slots for {m} rows")
+            cross = self.near_duplicates_of(searcher, q, threshold)
+            qs = Searcher(q)
+            among = qs.near_duplicates(threshold)
+            adm = cross.admit(among)
+            kept = adm.kept.to_mask()
+            k = int(adm.kept.count)
+            out = {"kept": kept, "rep_base": adm.rep_base, "rep_incoming": adm.rep_incoming, "unused_slots": sl[k:].copy(),
+                   "inserted": 0, "batches": 0}
+            if k:
+                picked = q.select(adm.kept)
+                de = None if descriptors is None else np.ascontiguousarray(descriptors, np.uint8).reshape(m, -1)[kept]
+                hu = None if has_url is None else np.ascontiguousarray(has_url, np.uint8).reshape(-1)[kept]
+                out.update(self.insert_rows(searcher, sl[:k], _DeviceRows(picked), config, start, quantizer, codes, de, hu, batch))
+            return out
+        finally:
+            for h in (picked, adm, among, cross, qs):
+                if h is not None:
+                    h.close()
+            if owned:
+                q.close()
 
     def delete_rows(self, searcher: Searcher, ids_or_filter, config, batch=0):
         """Remove rows from the live graph and repair the lists that pointed at them, on the device (mse_graph_delete_rows).

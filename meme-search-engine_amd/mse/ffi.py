@@ -215,6 +215,11 @@ SIGNATURES = {
     "mse_pairs_duplicates": (vp, [vp]),
     "mse_pairs_groups": (vp, [vp]),
     "mse_pairs_representatives": (C.c_int, [vp, u32p]),
+    "mse_join_cross": (vp, [vp, vp, C.c_int64, vp, C.c_int, C.c_uint64]),
+    "mse_pairs_kind": (C.c_int, [vp]),
+    "mse_pairs_base_rows": (sz, [vp]),
+    "mse_pairs_admit": (C.c_int, [vp, vp, C.POINTER(vp), u32p, u32p]),
+    "mse_base_select": (vp, [vp, vp]),
     "mse_shard_group_filter": (vp, [vp, vp]),
     "mse_shard_group_filter_from_local": (vp, [vp, C.POINTER(vp)]),
     "mse_shard_group_live_filter": (vp, [vp, C.c_int]),

@@ -100,6 +100,13 @@ class VectorList:
     def __getitem__(self, i):
         return self.rows(i, 1)[0]
 
+    def select(self, row_filter):
+        """A fresh VectorList holding the rows that `row_filter` (a RowFilter, not longer than this list, on its device) allows, in
+        ascending order (mse_base_select): a row gather on the device."""
+        if not isinstance(row_filter, RowFilter):
+            raise TypeError("row_filter must be a RowFilter")
+        return VectorList(check_ptr(ffi.lib().mse_base_select(self._h, row_filter._h), "mse_base_select"))
+
     def close(self):
         if self._h:
             ffi.lib().mse_base_free(self._h)
@@ -344,17 +351,56 @@ class RowGroups:
             pass
 
 
+class Admission:
+    """Result of RowPairs.admit: kept (a RowFilter over the incoming rows: the rows to insert), rep_base (uint32 per incoming row: its
+    lowest base partner, ID_NONE without one) and rep_incoming (uint32: the row itself when kept, its lowest kept earlier neighbour in the
+    batch when that dropped it, ID_NONE when the base dropped it)."""
+
+    def __init__(self, kept, rep_base, rep_incoming):
+        self.kept, self.rep_base, self.rep_incoming = kept, rep_base, rep_incoming
+
+    def close(self):
+        if self.kept is not None:
+            self.kept.close()
+            self.kept = None
+
+
 class RowPairs:
     """Result of Searcher.near_duplicates (mse_pairs): every pair (lo, hi), lo < hi, of rows of a base whose reference-order i64 score
     reaches the threshold, in canonical order (hi ascending, then lo ascending), each with its exact score.  The list lives on the device
     and is immutable.  len() is the number of rows of the base; .count the pairs.  duplicates(), groups() and representatives() apply the
-    keep-first rule (a row is kept iff no kept earlier row forms a pair with it), resolved on the device once per list."""
+    keep-first rule (a row is kept iff no kept earlier row forms a pair with it), resolved on the device once per list.
+    Searcher.near_duplicates_of gives a CROSS list (kind 1): lo is a row of the resident base, hi a row of the incoming one, len() the
+    incoming rows and base_rows the resident ones; its keep-first rule is admit()."""
 
     def __init__(self, handle):
         self._h = handle
 
     def __len__(self):
         return int(ffi.lib().mse_pairs_rows(self._h))
+
+    @property
+    def kind(self):
+        """0: a self list (near_duplicates), 1: a cross list (near_duplicates_of)"""
+        return int(ffi.lib().mse_pairs_kind(self._h))
+
+    @property
+    def base_rows(self):
+        """Rows of the resident base: what lo counts in a cross list; len() for a self list."""
+        return int(ffi.lib().mse_pairs_base_rows(self._h))
+
+    def admit(self, among=None):
+        """Keep-first continued from the index into the batch (mse_pairs_admit), on a cross list: an incoming row is kept iff it has no
+        pair in this list and no kept earlier incoming row pairs with it in `among`, the self list of the incoming rows (None: only the
+        base decides).  -> Admission."""
+        if among is not None and not isinstance(among, RowPairs):
+            raise TypeError("among must be a RowPairs")
+        m = len(self)
+        rb, ri = np.empty(m, np.uint32), np.empty(m, np.uint32)
+        kept = C.c_void_p()
+        check(ffi.lib().mse_pairs_admit(self._h, None if among is None else among._h, C.byref(kept), _p(rb, C.c_uint32), _p(ri, C.c_uint32)),
+              "mse_pairs_admit")
+        return Admission(RowFilter.from_handle(kept.value), rb, ri)
 
     @property
     def count(self):
@@ -497,15 +543,36 @@ class Searcher:
         return RowPairs(check_ptr(ffi.lib().mse_join_self(self._h, int(threshold), int(window), None if within is None else within._h, int(mode),
                                                           int(max_pairs)), "mse_join_self"))
 
+    def near_duplicates_of(self, incoming, threshold, within=None, mode=MODE_AUTO, max_pairs=1 << 32):
+        """The cross join (mse_join_cross) -> RowPairs of kind 1: all pairs (lo, hi) of a row lo of this searcher's base that `within` (a
+        RowFilter) allows when given, and a row hi of `incoming`, whose reference-order score is >= threshold.  incoming: a VectorList of
+        the base's width on its device, or a numpy array of f16 values / uint16 bits, which is uploaded.  threshold: an int is the i64
+        score, a float goes through scale_dot_result.  More than max_pairs pairs is an error; join_stats()["kept"] then holds the
+        count."""
+        if within is not None and not isinstance(within, RowFilter):
+            raise TypeError("within must be a RowFilter")
+        if isinstance(threshold, (float, np.floating)):
+            threshold = scale_dot_result(threshold)
+        if max_pairs < 0:
+            raise ValueError("max_pairs must not be negative")
+        owned = not isinstance(incoming, VectorList)
+        q = VectorList.from_f16s(incoming, self.vecs.d_emb) if owned else incoming
+        try:
+            return RowPairs(check_ptr(ffi.lib().mse_join_cross(self._h, q._h, int(threshold), None if within is None else within._h, int(mode),
+                                                               int(max_pairs)), "mse_join_cross"))
+        finally:
+            if owned:
+                q.close()
+
     def join_stats(self):
-        """Of the last near_duplicates call on this searcher (mse_join_stats); "rounds" is of the last keep-first resolution of one of
-        its lists."""
+        """Of the last near_duplicates or near_duplicates_of call on this searcher (mse_join_stats); "rounds" is of the last keep-first
+        resolution, or admit(), of one of its lists."""
         out = (C.c_uint64 * 6)()
         check(ffi.lib().mse_join_stats(self._h, out), "join_stats")
         return dict(zip(("tiles", "nominated", "rescored", "kept", "strips_repeated", "rounds"), (int(v) for v in out)))
 
     def join_timing(self, enable):
-        """Measurement hook (mse_join_timing): HIP-event milliseconds of the last near_duplicates call made while the switch was on --
+        """Measurement hook (mse_join_timing): HIP-event milliseconds of the last near_duplicates / near_duplicates_of call made while the switch was on --
         tile launches, re-score launches, building the list -- then sets the switch."""
         out = (C.c_double * 3)()
         check(ffi.lib().mse_join_timing(self._h, int(enable), out), "join_timing")
