@@ -1533,6 +1533,46 @@ int mse_siglip_encode_rgb8(mse_siglip* m, const uint8_t* rgb_hwc, int batch, int
 int mse_bmp24_info(const uint8_t* data, size_t size, uint32_t* width, uint32_t* height, uint32_t* pixel_offset, int* bottom_up);
 int mse_siglip_encode_bmp(mse_siglip* m, const uint8_t* const* bmps, const size_t* sizes, int batch, int normalize, float* out_f32,
                           uint16_t* out_f16);
+/* ---- Resize on the device: `resize_for_embed_sync` (src/common.rs:31-54), the step every image takes before it is embedded.  The
+ * image is squashed to exactly the target size with a two-pass convolution resize -- Hamming window when BOTH sides shrink, Lanczos3
+ * otherwise (common.rs:44), one filter for both passes, horizontal pass first into a u8 intermediate, a pass whose input and output
+ * lengths agree skipped, an image already of the target size copied.  The arithmetic is Pillow's 8-bit resample (weights in double on
+ * the host, integer coefficients of 22 fractional bits, int32 sums: tests/resize_ref.py restates it), bit for bit; the reference links
+ * the fast_image_resize crate, whose coefficient precision may differ in the last bit of a pixel.
+ * Limits, checked before anything is launched: widths and heights 1 .. 16384, no NULL pointer, a known filter, batch >= 1 (and
+ * <= max_batch for the engine calls).  Device staging is bounded: a call is processed in sub-batches of at most 1024 images whose
+ * uploads, intermediates, coefficient tables (and u8 results, for mse_resize_rgb8) stay below 256 MiB together, except that one image
+ * always goes through alone whatever it takes (16384 x 16384 -> 384 x 384: 786 MiB).  The tables of a sub-batch exist once more in
+ * host memory while they go up. */
+#define MSE_RESIZE_AUTO 0      /* the reference's rule (common.rs:44) */
+#define MSE_RESIZE_HAMMING 1
+#define MSE_RESIZE_LANCZOS3 2
+/* Host only (no device): the coefficient table of one axis, `in` -> `out` samples, filter MSE_RESIZE_HAMMING or _LANCZOS3 (src/common.rs:31-54).
+ * *ksize = row length of the table; bounds_out [out][2] = (first input sample, taps) of every output; coefs_out [out][ksize] = the
+ * integer weights, zero past the taps.  bounds_out / coefs_out may be NULL: size query. */
+int mse_resize_coeffs(int in, int out, int filter, int* ksize, int32_t* bounds_out, int32_t* coefs_out);
+/* Host only: the filter a w x h image resized to out_w x out_h gets (src/common.rs:31-54, the rule at :44): `filter` itself unless it is
+ * MSE_RESIZE_AUTO, then MSE_RESIZE_HAMMING when w > out_w and h > out_h, else MSE_RESIZE_LANCZOS3.  -1 for a refused argument. */
+int mse_resize_pick_filter(int w, int h, int out_w, int out_h, int filter);
+/* Resize alone (src/common.rs:31-54 without the BMP encoder): images[b] = host RGB bytes [heights[b]][widths[b]][3]; out_hwc_u8 = host
+ * [batch][out_h][out_w][3].  One launch per pass for each sub-batch, mixed sizes included. */
+int mse_resize_rgb8(const uint8_t* const* images, const uint32_t* widths, const uint32_t* heights, int batch, int out_w, int out_h, int filter,
+                    uint8_t* out_hwc_u8);
+/* Decoded images of any size in, features out (src/common.rs:31-54 + clip_server.py:131-146): upload, both passes, x / 127.5 - 1 and
+ * the fp16 rounding fused into the vertical pass, which writes the tower's input buffer, then the forward pass.  Equal to
+ * mse_resize_rgb8 to (img_size, img_size) followed by mse_siglip_encode_rgb8, bit for bit. */
+int mse_siglip_encode_rgb8_any(mse_siglip* m, const uint8_t* const* images, const uint32_t* widths, const uint32_t* heights, int batch, int filter,
+                               int normalize, float* out_f32, uint16_t* out_f16);
+/* The same from 24-bit uncompressed BMP files of any size (src/common.rs:31-54; header check: mse_bmp24_info): the pixel arrays go up
+ * as they are -- blue-green-red order, bottom-up rows and the 4-byte row padding are a matter of the kernels' source descriptor, there
+ * is no host decode.  Equal to decoding with PIL followed by mse_siglip_encode_rgb8_any, bit for bit. */
+int mse_siglip_encode_bmp_any(mse_siglip* m, const uint8_t* const* bmps, const size_t* sizes, int batch, int filter, int normalize,
+                              float* out_f32, uint16_t* out_f16);
+/* test hook (src/common.rs:31-54): the fp16 NCHW tower input [batch][3][img_size][img_size] the last _any call of this engine wrote */
+int mse_debug_siglip_resize_nchw(mse_siglip* m, int batch, uint16_t* out);
+/* measurement hook (scripts/resize_probe.py; src/common.rs:31-54): HIP-event milliseconds of the last resize of any kind in this
+ * process, summed over its sub-batches: ms[0] upload, ms[1] horizontal pass, ms[2] vertical pass, ms[3] their sum */
+int mse_resize_timing(double* ms);
 const void* mse_siglip_output_device(const mse_siglip* m, int which);  /* device result of the last call: 0 f32, 1 f16 */
 void* mse_siglip_stream(const mse_siglip* m);
 int mse_siglip_debug_residual(mse_siglip* m, float* out);             /* test hook: residual stream after the last block */

@@ -6,6 +6,7 @@
 #include "../../include/mse.h"
 #include "runtime.h"
 #include "siglip_encoder.h"
+#include "resize.h"
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -43,7 +44,13 @@ struct mse_siglip : Encoder {
     float* out_f32 = nullptr; uint16_t* out_f16 = nullptr;
     int last_batch = 0;
     bool no_small = false;       // MSE_SIGLIP_NOSMALL=1: calls of 1..4 images run the batch kernels too (bit-equal to rows of larger batches)
+    std::shared_ptr<mse::resize::Context> resize_ctx;   // staging and tables of the device resize in front of the tower (resize_api.hip)
 };
+
+// what resize_api.hip needs of an engine: it fills img_dev on the engine's stream, under the engine's lock, then calls the forward pass
+mse::resize::TowerInput mse::resize::tower_input(mse_siglip* m) {
+    return TowerInput{&m->call_mu, m->stream, m->img_dev, m->cfg.img_size, m->cfg.in_chans, m->max_batch, m->finalized, &m->resize_ctx};
+}
 
 extern "C" {
 

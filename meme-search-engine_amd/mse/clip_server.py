@@ -15,7 +15,10 @@ Contract (reference clip_server.py) -- kept byte compatible:
 Stages as in the reference: aiohttp handler -> preprocessing thread -> model thread, two bounded queues of 10
 (:125,130); a request travels as a `Job` whose asyncio future the handler awaits.  Images that are what the reference's
 clients send -- 24-bit BMP of the model's size (src/common.rs:31-54) -- skip the host decoder: the request bytes go to the
-device as they are (SiglipImageEngine.encode_bmp); anything else is decoded with PIL on the preprocessing thread.  Configuration = JSON file given as argv[1] with the reference's keys
+device as they are (SiglipImageEngine.encode_bmp); anything else is decoded with PIL on the preprocessing thread and, when it has
+another size, resized there (bicubic).  With the config key `device_resize` (default false) images of any size are resized on the
+device instead, with the reference's resize_for_embed filters: plain BMPs of any size go up as they are ("bmp_any"), other files are
+decoded on the host without resizing ("rgb8_any").  Configuration = JSON file given as argv[1] with the reference's keys
 (`device`, `model`, `model_path`, `model_name`, `max_batch_size`, `port`).
 
 The model call is the seam the reference fills with `fast_image_fns` / `model.encode_image`
@@ -52,6 +55,13 @@ def decode_image(data: bytes, size):
     return np.asarray(im, dtype=np.uint8)
 
 
+def decode_image_any(data: bytes):
+    """Host decoder of the `device_resize` path: decode, RGB, NO resize -> uint8 [h, w, 3] of whatever size the file has.  The resize
+    of the reference's resize_for_embed (src/common.rs:31-54) then runs on the device (SiglipImageEngine.encode_images)."""
+    from PIL import Image
+    return np.asarray(Image.open(io.BytesIO(data)).convert("RGB"), dtype=np.uint8)
+
+
 class Job:
     """One POST on its way through the two worker threads.  The handler awaits `done`; whichever stage ends the job --
     a failed check, a failed decode, the model -- resolves it from its own thread."""
@@ -62,7 +72,7 @@ class Job:
         self.text, self.images = text, images
         self._loop = loop
         self.done = loop.create_future() if loop is not None else None
-        self.stage = None          # what the preprocessing step hands to the model: ("tokens" | "bmp" | "rgb8" | "nchw", payload)
+        self.stage = None          # what the preprocessing step hands to the model: ("tokens" | "bmp" | "rgb8" | "nchw" | "bmp_any" | "rgb8_any", payload)
 
     def finish(self, ok, payload):
         if self.done is not None:
@@ -90,6 +100,10 @@ class ClipServer:
         self.tokenizer = tokenizer
         self.image_size = tuple(getattr(image_engine, "image_size", (384, 384)))
         self.embedding_size = int(image_engine.embedding_size)
+        # `device_resize` (default false: off-size images are resized on the host with PIL bicubic, as before): images of any size are
+        # resized on the device with the reference's own filters (src/common.rs:31-54) -- plain BMPs without any host decode
+        self.device_resize = (bool(config.get("device_resize", False)) and hasattr(image_engine, "encode_images")
+                              and hasattr(image_engine, "encode_bmp_any"))
         self.registry = registry or CollectorRegistry()
         self.items_ctr = Counter("modelserver_total_items", "Items run through model server", ["model", "modality"],
                                  registry=self.registry)
@@ -116,6 +130,13 @@ class ClipServer:
         if job.images:
             assert len(job.images) <= self.bs, f"max batch size is {self.bs}"
             eng = self.image_engine
+            if self.device_resize:
+                from .siglip import plain_bmp_size
+                # (a BMP with a side above 16 384 is not "plain" here: it is decoded below and the engine's own limit refuses it,
+                # which answers the request with that limit's message)
+                if all(plain_bmp_size(im) is not None for im in job.images):
+                    return "bmp_any", list(job.images)
+                return "rgb8_any", [decode_image_any(im) for im in job.images]
             if hasattr(eng, "encode_bmp"):
                 from .siglip import is_plain_bmp
                 if all(is_plain_bmp(im, self.image_size) for im in job.images):
@@ -140,7 +161,8 @@ class ClipServer:
             self.items_ctr.labels(self.model_name, "image").inc(n)
             with self.inference_time_hist.labels(self.model_name + "-image", n).time():
                 # the engine normalises on the device; result rows are unit norm like `features /= norm`
-                call = {"bmp": "encode_bmp", "rgb8": "encode_rgb8", "nchw": "encode_image"}[kind]
+                call = {"bmp": "encode_bmp", "rgb8": "encode_rgb8", "nchw": "encode_image", "bmp_any": "encode_bmp_any",
+                        "rgb8_any": "encode_images"}[kind]
                 f = np.asarray(getattr(engine, call)(payload), np.float32)
         self.batch_count_ctr.labels(self.model_name).inc()
         return f

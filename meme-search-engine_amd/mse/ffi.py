@@ -27,6 +27,7 @@ class BuildConfig(C.Structure):
 
 u8p, u16p, u32p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint16), C.POINTER(C.c_uint32)
 f32p, i64p = C.POINTER(C.c_float), C.POINTER(C.c_int64)
+i32p = C.POINTER(C.c_int32)
 sz, vp = C.c_size_t, C.c_void_p
 
 # name -> (restype, argtypes); kept in one table so tests can check it against include/mse.h
@@ -375,6 +376,13 @@ SIGNATURES = {
     "mse_siglip_encode_rgb8": (C.c_int, [vp, u8p, C.c_int, C.c_int, f32p, u16p]),
     "mse_bmp24_info": (C.c_int, [C.c_char_p, sz, u32p, u32p, u32p, C.POINTER(C.c_int)]),
     "mse_siglip_encode_bmp": (C.c_int, [vp, C.POINTER(C.c_char_p), C.POINTER(sz), C.c_int, C.c_int, f32p, u16p]),
+    "mse_resize_coeffs": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), i32p, i32p]),
+    "mse_resize_pick_filter": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mse_resize_rgb8": (C.c_int, [C.POINTER(vp), u32p, u32p, C.c_int, C.c_int, C.c_int, C.c_int, u8p]),
+    "mse_siglip_encode_rgb8_any": (C.c_int, [vp, C.POINTER(vp), u32p, u32p, C.c_int, C.c_int, C.c_int, f32p, u16p]),
+    "mse_siglip_encode_bmp_any": (C.c_int, [vp, C.POINTER(C.c_char_p), C.POINTER(sz), C.c_int, C.c_int, C.c_int, f32p, u16p]),
+    "mse_debug_siglip_resize_nchw": (C.c_int, [vp, C.c_int, u16p]),
+    "mse_resize_timing": (C.c_int, [C.POINTER(C.c_double)]),
     "mse_siglip_output_device": (vp, [vp, C.c_int]),
     "mse_siglip_stream": (vp, [vp]),
     "mse_siglip_debug_residual": (C.c_int, [vp, f32p]),

@@ -68,6 +68,79 @@ def is_plain_bmp(data, size):
     return (w.value, h.value) == tuple(size)
 
 
+RESIZE_FILTERS = {"auto": 0, "hamming": 1, "lanczos3": 2}   # MSE_RESIZE_* (include/mse.h)
+RESIZE_MAX_SIDE = 16384
+
+
+def _resize_filter(filter):
+    if filter not in RESIZE_FILTERS:
+        raise MseError(f"unknown resize filter {filter!r}: one of {sorted(RESIZE_FILTERS)}")
+    return RESIZE_FILTERS[filter]
+
+
+def _image_list(images):
+    """[h, w, 3] uint8 arrays -> (contiguous arrays kept alive, pointer array, widths, heights) for the C ABI."""
+    arrs = [np.ascontiguousarray(im, np.uint8) for im in images]
+    for a in arrs:
+        if a.ndim != 3 or a.shape[2] != 3:
+            raise MseError("every image must be [height, width, 3] uint8")
+    n = len(arrs)
+    ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in arrs])
+    widths = (C.c_uint32 * n)(*[a.shape[1] for a in arrs])
+    heights = (C.c_uint32 * n)(*[a.shape[0] for a in arrs])
+    return arrs, ptrs, widths, heights
+
+
+def resize_coeffs(n_in, n_out, filter):
+    """Host only: the coefficient table of one axis (mse_resize_coeffs) -> (ksize, bounds int32 [n_out, 2], coefs int32 [n_out, ksize])."""
+    f = _resize_filter(filter)
+    k = C.c_int()
+    check(ffi.lib().mse_resize_coeffs(n_in, n_out, f, C.byref(k), None, None), "resize_coeffs")
+    bounds = np.empty((n_out, 2), np.int32)
+    coefs = np.empty((n_out, k.value), np.int32)
+    check(ffi.lib().mse_resize_coeffs(n_in, n_out, f, C.byref(k), bounds.ctypes.data_as(ffi.i32p), coefs.ctypes.data_as(ffi.i32p)),
+          "resize_coeffs")
+    return k.value, bounds, coefs
+
+
+def resize_pick_filter(w, h, out_w, out_h, filter="auto"):
+    """Host only: the filter ("hamming" / "lanczos3") the library uses for a w x h image resized to out_w x out_h (mse_resize_pick_filter)."""
+    f = ffi.lib().mse_resize_pick_filter(w, h, out_w, out_h, _resize_filter(filter))
+    if f < 0:
+        raise MseError(f"resize_pick_filter failed: {ffi.last_error()}")
+    return {v: k for k, v in RESIZE_FILTERS.items()}[f]
+
+
+def resize_rgb8(images, size, filter="auto"):
+    """`resize_for_embed_sync` (src/common.rs:31-54) on the device: images = [h, w, 3] uint8 arrays of any sizes up to 16384, size =
+    (width, height) or one number for both.  Hamming when both sides shrink, Lanczos3 otherwise ("auto"), horizontal pass first;
+    Pillow's 8-bit arithmetic bit for bit.  Returns uint8 [n, height, width, 3]."""
+    out_w, out_h = (size, size) if np.isscalar(size) else size
+    arrs, ptrs, widths, heights = _image_list(images)
+    out = np.empty((len(arrs), int(out_h), int(out_w), 3), np.uint8)
+    check(ffi.lib().mse_resize_rgb8(ptrs, widths, heights, len(arrs), int(out_w), int(out_h), _resize_filter(filter),
+                                    out.ctypes.data_as(ffi.u8p)), "resize_rgb8")
+    return out
+
+
+def resize_timing():
+    """HIP-event milliseconds of the last resize in this process: dict(upload, horizontal, vertical, total)."""
+    ms = (C.c_double * 4)()
+    check(ffi.lib().mse_resize_timing(ms), "resize_timing")
+    return dict(zip(("upload", "horizontal", "vertical", "total"), ms))
+
+
+def plain_bmp_size(data):
+    """(width, height) of a 24-bit uncompressed BMP whose sides the device resize takes (1 .. 16384), else None."""
+    w, h = C.c_uint32(), C.c_uint32()
+    data = data if isinstance(data, bytes) else bytes(data)      # request bodies are bytes already: no copy of a multi-MB file
+    if ffi.lib().mse_bmp24_info(data, len(data), C.byref(w), C.byref(h), None, None) != 0:
+        return None
+    if not (1 <= w.value <= RESIZE_MAX_SIDE and 1 <= h.value <= RESIZE_MAX_SIDE):
+        return None
+    return w.value, h.value
+
+
 class _SiglipEngine:
     """Weight loading and release shared by the towers: the C functions `<_C>_n_weights`, `_weight_name`, `_set_weight`,
     `_finalize` and `_destroy` of the engine handle `_h`."""
@@ -186,6 +259,45 @@ class SiglipImageEngine(_SiglipEngine):
                                               of32.ctypes.data_as(ffi.f32p) if of32 is not None else None,
                                               of16.ctypes.data_as(ffi.u16p) if of16 is not None else None), "siglip_encode_bmp")
         return of32 if out == "f32" else of16
+
+    def _outputs(self, b, out):
+        of32 = np.empty((b, self.embedding_size), np.float32) if out == "f32" else None
+        of16 = np.empty((b, self.embedding_size), np.uint16) if out == "f16" else None
+        return of32, of16, (of32.ctypes.data_as(ffi.f32p) if of32 is not None else None), (of16.ctypes.data_as(ffi.u16p) if of16 is not None else None)
+
+    def encode_images(self, images, normalize=True, out="f32", filter="auto"):
+        """images: decoded RGB arrays [h, w, 3] uint8 of ANY sizes (up to 16384 a side).  The reference's resize_for_embed
+        (src/common.rs:31-54), the normalisation and the fp16 rounding run on the device and write the tower's input directly;
+        equal to encode_rgb8(resize_rgb8(images, img_size)) bit for bit."""
+        arrs, ptrs, widths, heights = _image_list(images)
+        b = len(arrs)
+        if b > self.max_batch:
+            raise MseError(f"max batch size is {self.max_batch}")
+        of32, of16, p32, p16 = self._outputs(b, out)
+        check(ffi.lib().mse_siglip_encode_rgb8_any(self._h, ptrs, widths, heights, b, _resize_filter(filter), int(normalize), p32, p16),
+              "siglip_encode_rgb8_any")
+        return of32 if out == "f32" else of16
+
+    def encode_bmp_any(self, files, normalize=True, out="f32", filter="auto"):
+        """files: 24-bit uncompressed BMP files of ANY size (bottom-up or top-down).  Header check on the host; the pixel arrays go to
+        the device as they are and are resized there (src/common.rs:31-54); equal to decoding with PIL and encode_images bit for bit."""
+        files = [bytes(f) for f in files]
+        b = len(files)
+        if b > self.max_batch:
+            raise MseError(f"max batch size is {self.max_batch}")
+        ptrs = (C.c_char_p * b)(*files)
+        sizes = (ffi.sz * b)(*[len(f) for f in files])
+        of32, of16, p32, p16 = self._outputs(b, out)
+        check(ffi.lib().mse_siglip_encode_bmp_any(self._h, ptrs, sizes, b, _resize_filter(filter), int(normalize), p32, p16),
+              "siglip_encode_bmp_any")
+        return of32 if out == "f32" else of16
+
+    def debug_resize_input(self, batch):
+        """Test hook: the fp16 NCHW tower input the last encode_images / encode_bmp_any call wrote, [batch, 3, s, s] float16."""
+        s = self.cfg["img_size"]
+        out = np.empty((batch, 3, s, s), np.uint16)
+        check(ffi.lib().mse_debug_siglip_resize_nchw(self._h, batch, out.ctypes.data_as(ffi.u16p)), "debug_siglip_resize_nchw")
+        return out.view(np.float16)
 
     def encode_image_device(self, dev_ptr, batch, dtype_f16=True, normalize=True):
         """Images already resident in HBM (the `fast_image_fns` call shape); result stays on the device:
