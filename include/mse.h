@@ -1487,6 +1487,57 @@ int mse_codes_describe(mse_codes* c, mse_graph* graph_or_null, const mse_scores*
  * three counting passes of the last select made while the switch was on; then the switch is set (0 off, 1 on, 2 on and reset). */
 int mse_describe_timing(int enable, double* mlp_ms_or_null, double* select_pass_ms_or_null /* [3] */);
 
+/* ---- Sparse-autoencoder features of a resident index (the reference's sae/): the encode on the device, without the rows leaving it ----
+ * SAE.forward up to the mask (sae/model.py:31-41): a = relu(up_proj(x)), t = kthvalue(a, d_hidden - top_k) -- the (top_k + 1)-th largest --
+ * and the kept set { j : a_j > t }, strictly: at most top_k features, fewer where values tie at t (model.py:37-40).  The checkpoint's
+ * tensors as torch stores them: up [d_hidden][d_emb] (up_proj.weight), up_bias [d_hidden] or NULL (up_proj_bias = False at
+ * sae/train.py:25-33, where d_hidden = 262144 and top_k = 128), down [d_emb][d_hidden] (down_proj.weight), down_bias [d_emb] or NULL;
+ * all f32, host pointers, copied (down is kept transposed).  1 <= top_k <= 256, top_k < d_hidden, d_emb >= 1.
+ * The arithmetic is fixed (csrc/sae.hip states it, tests/sae_ref.py restates it): the pre-activation is one k-ascending f32 fma chain
+ * from +0 (the f32 matrix cores), the bias one f32 add; a row's features come in canonical order -- activation descending, feature
+ * ascending -- and do not depend on the row's place in the call, the call's size, ids versus range or how d_hidden is split.  (The
+ * reference runs these products in TF32, sae/shared.py:4, and so pins no bits.)  A row with a NaN pre-activation is invalid: its count
+ * reads 0xFFFFFFFF, it holds no features and counts nowhere; +inf is an ordinary value. */
+typedef struct mse_sae mse_sae;
+typedef struct mse_features mse_features;
+mse_sae* mse_sae_load(const float* up, const float* up_bias_or_null, const float* down, const float* down_bias_or_null, size_t d_emb,
+                      size_t d_hidden, size_t top_k);
+void mse_sae_free(mse_sae* m);
+size_t mse_sae_d_emb(const mse_sae* m);
+size_t mse_sae_d_hidden(const mse_sae* m);
+size_t mse_sae_top_k(const mse_sae* m);
+/* The feature table of rows ids[i], i < n (any order, repeats allowed; each < mse_base_len), or first .. first + n when ids is NULL.
+ * count_features != 0: every kept feature of every valid row adds one to the model's counters (feature_activation_counter,
+ * model.py:23,42).  The table borrows the base's rows (mse_features_reconstruct reads them): the caller keeps the base alive.
+ * mse_sae_encode_f16: the same over f16 rows on the host, [n_rows][d] of any width d >= 1, of which the table keeps a device copy.
+ * Errors (a width that is not the model's, an id past the base, a wrapped base over host memory) leave the model and the base usable. */
+mse_features* mse_sae_encode_base(mse_sae* m, const mse_base* b, const uint32_t* ids_or_null, size_t first, size_t n, int count_features);
+mse_features* mse_sae_encode_f16(mse_sae* m, const uint16_t* rows_f16, size_t n_rows, size_t d, int count_features);
+void mse_features_free(mse_features* f);
+size_t mse_features_len(const mse_features* f);
+size_t mse_features_top_k(const mse_features* f);
+uint64_t mse_features_invalid_rows(const mse_features* f);
+/* counts [n] (0xFFFFFFFF: invalid row), features [n][top_k] (unused slots 0xFFFFFFFF), activations [n][top_k] (unused slots +0); any
+ * of the three may be NULL */
+int mse_features_read(const mse_features* f, uint32_t* counts_or_null, uint32_t* features_or_null, float* activations_or_null);
+/* down_proj over the kept features (model.py:43) and the row's share of mse_loss (sae/train.py:55-56): recon [n][d_emb] with
+ * r_d = fma(a, down[d][f], r_d) over the row's features in canonical order from down_bias[d] (or +0); sqerr [n] = sum over d of
+ * (f32(r_d - x_d))^2 in f64, in the fixed order csrc/sae.hip states.  An invalid row gives NaN in both.  m must be the model that made
+ * the table. */
+int mse_features_reconstruct(const mse_features* f, mse_sae* m, float* recon_or_null, double* sqerr_or_null);
+/* The rows that keep `feature` with an activation >= min_activation, as a filter over n_rows base rows (row ids[i], or first + i; a
+ * table made from host rows: i), built on the device (mse_filter_from_bits_dev) and usable wherever a filter is.  n_rows must cover
+ * every row the table speaks of. */
+mse_filter* mse_features_filter(const mse_features* f, uint32_t feature, float min_activation, size_t n_rows);
+/* out [d_hidden] = the counters; reset != 0 zeroes them after the read (reset_counters, model.py:26-29, returns the old values) */
+int mse_sae_counters(mse_sae* m, uint64_t* out_or_null, int reset);
+/* test and probe hook: split d_hidden over `parts` workgroups per row tile (1 .. 1024; fewer when there are fewer hidden tiles);
+ * 0 = automatic, enough parts for two workgroups per CU.  The answer does not depend on it. */
+int mse_sae_set_hidden_parts(mse_sae* m, int parts);
+/* measurement hook (scripts/sae_probe.py): HIP-event milliseconds of the encode and of the merge launches of the last encode made
+ * while the switch was on; then the switch is set (0 off, 1 on, 2 on and reset). */
+int mse_sae_timing(int enable, double* encode_ms_or_null, double* merge_ms_or_null);
+
 /* ---- SigLIP ViT image tower: the in-process seam of clip_server.py, `fast_image_fns[batch](images NCHW
  * fp16 on device) -> [batch, 1152]` (clip_server.py:31,66-82,105-112), plus the normalisation and fp16
  * serialisation of do_inference / run_inference (clip_server.py:115,166).  Graph: aitemplate/model.py:13-123;

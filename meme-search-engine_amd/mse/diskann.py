@@ -478,6 +478,11 @@ class DeviceGraph(_RowDeletes):
         descriptor bytes wholly before or wholly after.  ids: the rows scores' entries belong to, e.g. the slots just inserted."""
         codes.describe(scores, cdfs, ids, first, _graph=self._graph_handle())
 
+    def encode_features(self, sae, vecs_or_searcher, **kw):
+        """SparseAutoencoder.encode_rows over the index's rows, e.g. ids=the slots just inserted; RowFeatures.filter(...) of the result
+        goes wherever a filter over the graph's rows does (delete_rows, the filtered searches)."""
+        return sae.encode_rows(vecs_or_searcher, **kw)
+
     def close(self):
         if getattr(self, "_h", None):
             ffi.lib().mse_graph_free(self._h)

@@ -366,6 +366,24 @@ SIGNATURES = {
     "mse_scores_fit_cdfs": (C.c_int, [vp, sz, f32p]),
     "mse_codes_describe": (C.c_int, [vp, vp, vp, u32p, sz, f32p, sz]),
     "mse_describe_timing": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    # sparse-autoencoder features (csrc/sae.hip, csrc/sae_api.hip)
+    "mse_sae_load": (vp, [f32p, f32p, f32p, f32p, sz, sz, sz]),
+    "mse_sae_free": (None, [vp]),
+    "mse_sae_d_emb": (sz, [vp]),
+    "mse_sae_d_hidden": (sz, [vp]),
+    "mse_sae_top_k": (sz, [vp]),
+    "mse_sae_encode_base": (vp, [vp, vp, u32p, sz, sz, C.c_int]),
+    "mse_sae_encode_f16": (vp, [vp, u16p, sz, sz, C.c_int]),
+    "mse_features_free": (None, [vp]),
+    "mse_features_len": (sz, [vp]),
+    "mse_features_top_k": (sz, [vp]),
+    "mse_features_invalid_rows": (C.c_uint64, [vp]),
+    "mse_features_read": (C.c_int, [vp, u32p, u32p, f32p]),
+    "mse_features_reconstruct": (C.c_int, [vp, vp, f32p, C.POINTER(C.c_double)]),
+    "mse_features_filter": (vp, [vp, C.c_uint32, C.c_float, sz]),
+    "mse_sae_counters": (C.c_int, [vp, C.POINTER(C.c_uint64), C.c_int]),
+    "mse_sae_set_hidden_parts": (C.c_int, [vp, C.c_int]),
+    "mse_sae_timing": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "mse_siglip_create": (vp, [vp]),
     "mse_siglip_destroy": (None, [vp]),
     "mse_siglip_n_weights": (C.c_int, [vp]),
