@@ -1537,6 +1537,46 @@ int mse_sae_set_hidden_parts(mse_sae* m, int parts);
 /* measurement hook (scripts/sae_probe.py): HIP-event milliseconds of the encode and of the merge launches of the last encode made
  * while the switch was on; then the switch is set (0 off, 1 on, 2 on and reset). */
 int mse_sae_timing(int enable, double* encode_ms_or_null, double* merge_ms_or_null);
+/* The model's current weights (a trainer changes them): up [d_hidden][d_emb], up_bias [d_hidden], down [d_emb][d_hidden] as the
+ * checkpoint stores it, down_bias [d_emb]; any may be NULL, and a bias the model was loaded without is left unwritten. */
+int mse_sae_read_weights(mse_sae* m, float* up_or_null, float* up_bias_or_null, float* down_or_null, float* down_bias_or_null);
+
+/* ---- Sparse-autoencoder training over a resident index (the reference's sae/train.py:51-59): mse_loss, backward and
+ * torch.optim.AdamW on the device, over an mse_sae whose device weights are updated in place.  The forward pass is the encode above;
+ * the arithmetic of the backward pass and of the update is fixed (csrc/sae_train.hip states it, tests/sae_train_ref.py restates it),
+ * so a run is the same bytes however it is cut into calls, from ids or from host rows, and run to run.  The model needs a down_bias
+ * (the reference's decoder always has one).  The trainer must be freed before its model; a trainer whose model was freed refuses every
+ * call.  beta1, beta2 and eps act in f32; lr, weight_decay and the bias corrections are combined in double. */
+typedef struct mse_sae_trainer mse_sae_trainer;
+mse_sae_trainer* mse_sae_trainer_create(mse_sae* m, double lr, double beta1, double beta2, double eps, double weight_decay);
+void mse_sae_trainer_free(mse_sae_trainer* tr);
+/* completed steps (torch's `step`) */
+uint64_t mse_sae_trainer_step_count(const mse_sae_trainer* tr);
+/* n_steps steps of `batch` rows each: step s trains on rows ids[s * batch + i], i < batch, of the base (any order, repeats allowed).
+ * batch * top_k <= 65536.  A step with an invalid (NaN) row or a non-finite loss is refused: weights, moments, step count and feature
+ * counters stay as they were and the later steps of the call are not run; *steps_done_out tells how many steps completed (the call
+ * still returns 0) and losses_out [n_steps] holds that many losses (F.mse_loss of each step, before its update).  The call holds the
+ * model's lock and gives the model a new serial: an mse_features made before it is refused by mse_features_reconstruct.  Errors (a
+ * width that is not the model's, batch * top_k over the limit, an id past the base) leave every handle usable.
+ * mse_sae_trainer_steps_f16: the same over n_steps * batch f16 rows on the host, [.][d]. */
+int mse_sae_trainer_steps(mse_sae_trainer* tr, const mse_base* b, const uint32_t* ids, size_t batch, size_t n_steps, double* losses_out,
+                          size_t* steps_done_out);
+int mse_sae_trainer_steps_f16(mse_sae_trainer* tr, const uint16_t* rows_f16, size_t d, size_t batch, size_t n_steps, double* losses_out,
+                              size_t* steps_done_out);
+/* The optimizer's state: the step count and exp_avg / exp_avg_sq of every parameter in the checkpoint's layout (up's [d_hidden][d_emb],
+ * down's [d_emb][d_hidden]); the encoder bias's only where the model has one.  Read: any pointer may be NULL.  Write: all are needed. */
+int mse_sae_trainer_state_read(mse_sae_trainer* tr, uint64_t* t_out, float* m_up, float* v_up, float* m_up_bias_or_null, float* v_up_bias_or_null,
+                               float* m_down, float* v_down, float* m_down_bias, float* v_down_bias);
+int mse_sae_trainer_state_write(mse_sae_trainer* tr, uint64_t t, const float* m_up, const float* v_up, const float* m_up_bias_or_null,
+                                const float* v_up_bias_or_null, const float* m_down, const float* v_down, const float* m_down_bias,
+                                const float* v_down_bias);
+/* test and probe hook: with weight_decay = 0 the dense update leaves out feature rows that have never had a member (they do not move);
+ * 0 turns that off.  The bytes do not depend on it. */
+int mse_sae_trainer_set_skip(mse_sae_trainer* tr, int enable);
+/* measurement hook (scripts/sae_train_probe.py): out [4] = HIP-event milliseconds of the forward passes (with the gate), of the small
+ * backward kernels and of the dense update of the last training call made while the switch was on, and the steps they cover; then the
+ * switch is set (0 off, 1 on, 2 on and reset). */
+int mse_sae_trainer_timing(int enable, double* out_or_null /* [4] */);
 
 /* ---- SigLIP ViT image tower: the in-process seam of clip_server.py, `fast_image_fns[batch](images NCHW
  * fp16 on device) -> [batch, 1152]` (clip_server.py:31,66-82,105-112), plus the normalisation and fp16

@@ -2,23 +2,12 @@
 // reference: up_proj, down_proj and the feature counters), the device-resident feature table `mse_features` (model.py:31-41 per row), its
 // reconstruction and squared error (sae/train.py:55-56) and the row filter of one feature.  Everything runs on the null stream and returns
 // with it drained.
-#include "../../include/mse.h"
-#include "sae.h"
+#include "sae_model.h"
 #include <atomic>
 #include <new>
+#include <unordered_map>
 
 using namespace mse;
-
-struct mse_sae {
-    uint64_t serial = 0;         // which model a table was made by (an address can be reused)
-    int device = 0, n_cu = 256;
-    size_t d_emb = 0, d_hidden = 0, top_k = 0;
-    float *up = nullptr, *up_bias = nullptr, *downT = nullptr, *down_bias = nullptr;   // device; downT [d_hidden][d_emb]
-    unsigned long long* counters = nullptr;                                           // device [d_hidden]
-    int parts = 0;               // mse_sae_set_hidden_parts: 0 = automatic
-    std::mutex mu;               // guards the scratch below and the counters
-    DevBuf lists, pcount, pflag, misc;   // the parts' candidate lists, lengths and NaN flags; the invalid-row count
-};
 
 struct mse_features {
     uint64_t model_serial = 0;
@@ -42,7 +31,8 @@ std::mutex g_tm_mu;
 bool g_tm_on = false;
 double g_tm_encode = 0.0, g_tm_merge = 0.0;
 
-constexpr size_t LIST_BUDGET = (size_t)512 << 20;   // bytes of candidate lists one launch may use
+std::mutex g_live_mu;
+std::unordered_map<const mse_sae*, uint64_t> g_live;   // the live models and their uids (a trainer asks before it touches its model)
 
 struct EventPair {
     hipEvent_t a = nullptr, b = nullptr;
@@ -68,17 +58,6 @@ float* upload_f32(const float* host, size_t count) {
     if (hipMalloc((void**)&p, std::max<size_t>(count * 4, 256)) != hipSuccess) return nullptr;
     if (count && hipMemcpy(p, host, count * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(p); return nullptr; }
     return p;
-}
-
-// hidden parts of a call of n rows: as many workgroups as run at once, two per CU, and no more (workgroups take equally long, so one
-// past that number would be a second round); no part without a tile
-void choose_parts(const mse_sae* m, size_t n, int* parts, int* tiles_per_part) {
-    const size_t n_tiles = (m->d_hidden + SAE_HID_TILE - 1) / SAE_HID_TILE, row_tiles = (n + SAE_ROW_TILE - 1) / SAE_ROW_TILE;
-    size_t p = m->parts > 0 ? (size_t)m->parts : 2 * (size_t)m->n_cu / row_tiles;
-    p = std::max<size_t>(1, std::min<size_t>(p, std::min<size_t>(n_tiles, m->parts > 0 ? SAE_MAX_PARTS : 256)));
-    const size_t tpp = (n_tiles + p - 1) / p;
-    *tiles_per_part = (int)tpp;
-    *parts = (int)((n_tiles + tpp - 1) / tpp);
 }
 
 // the body of mse_sae_encode_base / mse_sae_encode_f16 over rows [n_rows][d] on `device` (the current one); returns drained.
@@ -114,9 +93,9 @@ mse_features* encode_rows(mse_sae* m, const uint16_t* rows_dev, uint16_t* rows_o
             MSE_HIP_TRY(hipMemcpy(f->ids, ids_or_null, n * 4, hipMemcpyHostToDevice));
         }
         int parts = 1, tpp = 1;
-        choose_parts(m, n, &parts, &tpp);
+        sae_choose_parts(m, n, &parts, &tpp);
         const size_t tile_bytes = (size_t)SAE_ROW_TILE * parts * cap * 8;
-        const size_t chunk_tiles = std::max<size_t>(1, LIST_BUDGET / tile_bytes);
+        const size_t chunk_tiles = std::max<size_t>(1, SAE_LIST_BUDGET / tile_bytes);
         const size_t chunk_rows = chunk_tiles * SAE_ROW_TILE;
         const size_t pad_rows = std::min(chunk_rows, (n + SAE_ROW_TILE - 1) / SAE_ROW_TILE * SAE_ROW_TILE);
         if (m->lists.ensure(pad_rows * parts * cap * 8) || m->pcount.ensure(pad_rows * parts * 4) || m->pflag.ensure(pad_rows * parts * 4) ||
@@ -165,6 +144,15 @@ mse_features* encode_rows(mse_sae* m, const uint16_t* rows_dev, uint16_t* rows_o
 
 }  // namespace
 
+namespace mse {
+uint64_t sae_next_serial() { return g_serial.fetch_add(1); }
+bool sae_model_alive(const mse_sae* m, uint64_t uid) {
+    std::lock_guard<std::mutex> g(g_live_mu);
+    auto it = g_live.find(m);
+    return it != g_live.end() && it->second == uid;
+}
+}  // namespace mse
+
 extern "C" {
 
 mse_sae* mse_sae_load(const float* up, const float* up_bias_or_null, const float* down, const float* down_bias_or_null, size_t d_emb,
@@ -178,6 +166,7 @@ mse_sae* mse_sae_load(const float* up, const float* up_bias_or_null, const float
     mse_sae* m = new (std::nothrow) mse_sae();
     if (!m) { fail("out of host memory"); return nullptr; }
     m->serial = g_serial.fetch_add(1);
+    m->uid = g_serial.fetch_add(1);
     m->d_emb = d_emb; m->d_hidden = d_hidden; m->top_k = top_k; m->n_cu = device_cu_count();
     bool ok = hipGetDevice(&m->device) == hipSuccess;
     float* down_dev = nullptr;
@@ -196,11 +185,13 @@ mse_sae* mse_sae_load(const float* up, const float* up_bias_or_null, const float
     }
     if (down_dev) (void)hipFree(down_dev);
     if (!ok) { mse_sae_free(m); fail("sae_load: device allocation/copy failed"); return nullptr; }
+    { std::lock_guard<std::mutex> g(g_live_mu); g_live[m] = m->uid; }
     return m;
 }
 
 void mse_sae_free(mse_sae* m) {
     if (!m) return;
+    { std::lock_guard<std::mutex> g(g_live_mu); g_live.erase(m); }
     for (void* p : {(void*)m->up, (void*)m->up_bias, (void*)m->downT, (void*)m->down_bias, (void*)m->counters})
         if (p) (void)hipFree(p);
     delete m;

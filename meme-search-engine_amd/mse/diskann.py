@@ -483,6 +483,10 @@ class DeviceGraph(_RowDeletes):
         goes wherever a filter over the graph's rows does (delete_rows, the filtered searches)."""
         return sae.encode_rows(vecs_or_searcher, **kw)
 
+    def train_features(self, trainer, vecs_or_searcher, ids, batch_size):
+        """SaeTrainer.train over the index's rows `ids` (live slots, in the order given)."""
+        return trainer.train(vecs_or_searcher, ids, batch_size)
+
     def close(self):
         if getattr(self, "_h", None):
             ffi.lib().mse_graph_free(self._h)

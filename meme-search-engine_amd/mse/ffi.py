@@ -384,6 +384,17 @@ SIGNATURES = {
     "mse_sae_counters": (C.c_int, [vp, C.POINTER(C.c_uint64), C.c_int]),
     "mse_sae_set_hidden_parts": (C.c_int, [vp, C.c_int]),
     "mse_sae_timing": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "mse_sae_read_weights": (C.c_int, [vp, f32p, f32p, f32p, f32p]),
+    # sparse-autoencoder training (csrc/sae_train.hip, csrc/sae_train_api.hip)
+    "mse_sae_trainer_create": (vp, [vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]),
+    "mse_sae_trainer_free": (None, [vp]),
+    "mse_sae_trainer_step_count": (C.c_uint64, [vp]),
+    "mse_sae_trainer_steps": (C.c_int, [vp, vp, u32p, sz, sz, C.POINTER(C.c_double), C.POINTER(sz)]),
+    "mse_sae_trainer_steps_f16": (C.c_int, [vp, u16p, sz, sz, sz, C.POINTER(C.c_double), C.POINTER(sz)]),
+    "mse_sae_trainer_state_read": (C.c_int, [vp, C.POINTER(C.c_uint64), f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p]),
+    "mse_sae_trainer_state_write": (C.c_int, [vp, C.c_uint64, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p]),
+    "mse_sae_trainer_set_skip": (C.c_int, [vp, C.c_int]),
+    "mse_sae_trainer_timing": (C.c_int, [C.c_int, C.POINTER(C.c_double)]),
     "mse_siglip_create": (vp, [vp]),
     "mse_siglip_destroy": (None, [vp]),
     "mse_siglip_n_weights": (C.c_int, [vp]),

@@ -1,7 +1,9 @@
-"""Sparse-autoencoder features of a resident index: the reference's sae/ (model.py, export_features.py) with the encode on the device.
-SparseAutoencoder holds a checkpoint trained by sae/train.py; encode_rows turns resident f16 rows into RowFeatures -- per row at most
+"""Sparse-autoencoder features of a resident index: the reference's sae/ (model.py, export_features.py, train.py) on the device.
+SparseAutoencoder holds a checkpoint trained by sae/train.py or by SaeTrainer below; encode_rows turns resident f16 rows into RowFeatures -- per row at most
 top_k (feature, activation) pairs, on the device -- from which come the feature counters (model.py:23-29,42), the reconstruction and its
-squared error (train.py:55-56), and a RowFilter per feature.  The arithmetic is fixed (csrc/sae.hip); tests/sae_ref.py restates it."""
+squared error (train.py:55-56), and a RowFilter per feature.  The arithmetic is fixed (csrc/sae.hip); tests/sae_ref.py restates it.
+SaeTrainer is train.py:51-59 -- mse_loss, backward, AdamW -- over the same resident rows, updating the model's device weights in place
+(csrc/sae_train.hip; tests/sae_train_ref.py restates it)."""
 import ctypes as C
 
 import numpy as np
@@ -31,9 +33,39 @@ class SparseAutoencoder:
         if down.shape != up.shape[::-1] or (ub is not None and ub.size != up.shape[0]) or (db is not None and db.size != up.shape[1]):
             raise MseError("sparse autoencoder: inconsistent tensor shapes")
         self.d_hidden, self.d_emb, self.top_k = up.shape[0], up.shape[1], int(top_k)
-        self.down = down                 # kept on the host for feature_queries
+        self._down, self._down_stale = down, False   # kept on the host for feature_queries; stale after a training call
+        self.has_up_bias, self.has_down_bias = ub is not None, db is not None
         self._h = check_ptr(ffi.lib().mse_sae_load(_p(up, C.c_float), None if ub is None else _p(ub, C.c_float), _p(down, C.c_float),
                                                    None if db is None else _p(db, C.c_float), self.d_emb, self.d_hidden, self.top_k), "mse_sae_load")
+
+    @classmethod
+    def random(cls, d_emb, d_hidden, top_k, seed, up_proj_bias=False):
+        """The initialisation of sae/model.py:20-22 from numpy's default_rng(seed): up ~ U(+-1/sqrt(d_emb)) (nn.Linear's default),
+        down = up transposed, down_bias ~ U(+-1/sqrt(d_hidden)), up_bias ~ U(+-1/sqrt(d_emb)) with up_proj_bias.  torch's
+        distribution, not torch's bits."""
+        rng = np.random.default_rng(seed)
+        bu, bd = 1.0 / np.sqrt(d_emb), 1.0 / np.sqrt(d_hidden)
+        up = rng.uniform(-bu, bu, (d_hidden, d_emb)).astype(np.float32)
+        ub = rng.uniform(-bu, bu, d_hidden).astype(np.float32) if up_proj_bias else None
+        db = rng.uniform(-bd, bd, d_emb).astype(np.float32)
+        return cls(up, np.ascontiguousarray(up.T), ub, db, top_k=top_k)
+
+    @property
+    def down(self):
+        """down_proj.weight [d_emb, d_hidden] on the host (re-read after a training call)"""
+        if self._down_stale:
+            self._down, self._down_stale = self.weights()[1], False
+        return self._down
+
+    def weights(self):
+        """(up [d_hidden, d_emb], down [d_emb, d_hidden], up_bias or None, down_bias or None): the current device weights, float32 --
+        the arguments of SparseAutoencoder(...)."""
+        up, down = np.empty((self.d_hidden, self.d_emb), np.float32), np.empty((self.d_emb, self.d_hidden), np.float32)
+        ub = np.empty(self.d_hidden, np.float32) if self.has_up_bias else None
+        db = np.empty(self.d_emb, np.float32) if self.has_down_bias else None
+        check(ffi.lib().mse_sae_read_weights(self._h, _p(up, C.c_float), None if ub is None else _p(ub, C.c_float), _p(down, C.c_float),
+                                             None if db is None else _p(db, C.c_float)), "sae_read_weights")
+        return up, down, ub, db
 
     @classmethod
     def from_state_dict(cls, sd, top_k):
@@ -195,6 +227,119 @@ class RowFeatures:
     def close(self):
         if getattr(self, "_h", None):
             ffi.lib().mse_features_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class StepRefused(MseError):
+    """A training step met an invalid (NaN) row or a non-finite loss and changed nothing; .steps_done steps of the call completed
+    before it and .losses holds their losses."""
+
+    def __init__(self, steps_done, losses):
+        super().__init__(f"sparse-autoencoder training: step {steps_done} of the call was refused (a NaN row or a non-finite loss); "
+                         f"{steps_done} step(s) completed")
+        self.steps_done, self.losses = steps_done, losses
+
+
+class SaeTrainer:
+    """sae/train.py:51-59 over a SparseAutoencoder: F.mse_loss, backward and torch.optim.AdamW (decoupled decay), on the device, in
+    place on the model's weights.  The model needs a down_bias.  The arithmetic is fixed, so a run is the same bytes however it is cut
+    into calls."""
+
+    def __init__(self, model, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        self.model = model
+        self._h = check_ptr(ffi.lib().mse_sae_trainer_create(model._h, float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay)),
+                            "mse_sae_trainer_create")
+
+    @property
+    def steps(self):
+        """completed steps (torch's `step`)"""
+        return int(ffi.lib().mse_sae_trainer_step_count(self._h))
+
+    def train(self, source, ids, batch_size):
+        """One step per batch_size consecutive entries of ids (rows of `source`: whatever encode_rows takes -- a VectorList, a Searcher
+        over one, or a 2-D array of f16 rows); a ragged last batch is dropped (train.py:88).  The ids are uploaded once and the steps
+        queued without a host round trip.  Returns the losses, float64 [steps]; raises StepRefused where a step was refused."""
+        i = np.asarray(ids)
+        if i.size and not np.issubdtype(i.dtype, np.integer):
+            raise TypeError("ids must be an integer array")
+        i = i.reshape(-1)
+        if i.size and (i.min() < 0 or i.max() > 0xFFFFFFFF):
+            raise ValueError("ids must be in 0 .. 2**32 - 1")
+        batch_size = int(batch_size)
+        if batch_size < 1:
+            raise ValueError("batch_size must be at least 1")
+        n_steps = i.size // batch_size
+        sel = np.ascontiguousarray(i[:n_steps * batch_size], np.uint32)
+        losses, done = np.zeros(n_steps, np.float64), C.c_size_t(0)
+        lp = _p(losses, C.c_double)
+        self.model._down_stale = True
+        if isinstance(source, np.ndarray):
+            host = _bits(source)
+            if host.ndim != 2:
+                raise MseError("train: host rows must be [n_rows, d]")
+            if sel.size and sel.max() >= host.shape[0]:
+                raise MseError(f"train: id {int(sel.max())} is not below the {host.shape[0]} rows")
+            rows = np.ascontiguousarray(host[sel.astype(np.int64)])
+            check(ffi.lib().mse_sae_trainer_steps_f16(self._h, _p(rows, C.c_uint16), host.shape[1], batch_size, n_steps, lp, C.byref(done)),
+                  "sae_trainer_steps_f16")
+        else:
+            vecs = getattr(source, "vecs", source)
+            if getattr(vecs, "_h", None) is None:
+                raise MseError("train needs a VectorList, a Searcher over one, or a 2-D array of f16 rows")
+            check(ffi.lib().mse_sae_trainer_steps(self._h, vecs._h, _p(sel, C.c_uint32), batch_size, n_steps, lp, C.byref(done)), "sae_trainer_steps")
+        if done.value < n_steps:
+            raise StepRefused(int(done.value), losses[:done.value].copy())
+        return losses
+
+    def step(self, source, ids):
+        """One step over the rows `ids` of source; returns its loss (before the update)."""
+        n = int(np.asarray(ids).size)
+        if n < 1:
+            raise ValueError("an empty batch")
+        return float(self.train(source, ids, n)[0])
+
+    def set_skip(self, on):
+        """Test and probe hook: whether the dense update may leave out never-touched feature rows (weight_decay = 0).  Same bytes."""
+        check(ffi.lib().mse_sae_trainer_set_skip(self._h, int(bool(on))), "sae_trainer_set_skip")
+
+    _STATE = ("m_up", "v_up", "m_up_bias", "v_up_bias", "m_down", "v_down", "m_down_bias", "v_down_bias")
+
+    def state(self):
+        """{"t": steps, "m_*" / "v_*": exp_avg / exp_avg_sq of up [d_hidden, d_emb], up_bias (with one), down [d_emb, d_hidden],
+        down_bias}: numpy arrays, the checkpoint's layout."""
+        m = self.model
+        shapes = {"up": (m.d_hidden, m.d_emb), "up_bias": (m.d_hidden,), "down": (m.d_emb, m.d_hidden), "down_bias": (m.d_emb,)}
+        out = {k: np.zeros(shapes[k[2:]], np.float32) for k in self._STATE if m.has_up_bias or "up_bias" not in k}
+        t = C.c_uint64(0)
+        check(ffi.lib().mse_sae_trainer_state_read(self._h, C.byref(t), *[None if k not in out else _p(out[k], C.c_float) for k in self._STATE]),
+              "sae_trainer_state_read")
+        out["t"] = int(t.value)
+        return out
+
+    def load_state(self, state):
+        m = self.model
+        shapes = {"up": (m.d_hidden, m.d_emb), "up_bias": (m.d_hidden,), "down": (m.d_emb, m.d_hidden), "down_bias": (m.d_emb,)}
+        args = []
+        for k in self._STATE:
+            if "up_bias" in k and not m.has_up_bias:
+                args.append(None)
+                continue
+            a = np.ascontiguousarray(state[k], np.float32)
+            if a.shape != shapes[k[2:]]:
+                raise MseError(f"load_state: {k} has shape {a.shape}, not {shapes[k[2:]]}")
+            args.append(a)
+        check(ffi.lib().mse_sae_trainer_state_write(self._h, int(state["t"]), *[None if a is None else _p(a, C.c_float) for a in args]),
+              "sae_trainer_state_write")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            ffi.lib().mse_sae_trainer_free(self._h)
             self._h = None
 
     def __del__(self):
