@@ -1578,6 +1578,72 @@ int mse_sae_trainer_set_skip(mse_sae_trainer* tr, int enable);
  * switch is set (0 off, 1 on, 2 on and reset). */
 int mse_sae_trainer_timing(int enable, double* out_or_null /* [4] */);
 
+/* ---- The ensemble rater of the reference's meme-rater/ on the device: the quality model whose scores become descriptor bytes, trained
+ * from rated pairs of resident rows, scored member by member, asked where its members disagree, exported as the wide score model.
+ * meme-rater/model.py:18-52: n_members one-hidden-layer MLPs (Linear d_emb -> d_emb, silu, Linear d_emb -> out_channels) under a
+ * Bradley-Terry head, p = sigmoid(score(first) - score(second)).  The weights live in the wide layout of
+ * ensemble_to_wide_model.py:44-55, all f32: up [n_members * d_emb][d_emb], bias [n_members * d_emb], down [out_channels][n_members *
+ * d_emb]; member m owns hidden units m * d_emb .. (m + 1) * d_emb.  The output layer's bias is not carried: the win probability is
+ * shift-invariant, its gradient is g - g = 0, and the export zeroes it (ensemble_to_wide_model.py:36-37).  One hidden layer only (the
+ * export's own TODO at :43), no dropout (train.py:40 trains with 0.0).  1 <= n_members <= 64, 1 <= out_channels <= 8.
+ * The arithmetic is fixed (csrc/rater.hip states it, tests/rater_ref.py restates it, bit for bit): the exponential is
+ * csrc/rater_math.h's, written in correctly rounded f32 operations only. */
+typedef struct mse_rater mse_rater;
+typedef struct mse_rater_trainer mse_rater_trainer;
+typedef struct mse_member_scores mse_member_scores;
+/* host pointers, copied */
+mse_rater* mse_rater_create(const float* up, const float* bias, const float* down, size_t d_emb, size_t n_members, size_t out_channels);
+void mse_rater_free(mse_rater* r);
+/* the current device weights (a trainer changes them), the arguments of mse_rater_create; any may be NULL */
+int mse_rater_read_weights(mse_rater* r, float* up_or_null, float* bias_or_null, float* down_or_null);
+/* meme-rater/train.py:61: torch.optim.AdamW over every parameter, in place on the rater's device weights.  beta1, beta2 and eps act
+ * in f32; lr, weight_decay and the bias corrections are combined in double.  The trainer must be freed before its
+ * rater; a trainer whose rater was freed refuses every call. */
+mse_rater_trainer* mse_rater_trainer_create(mse_rater* r, double lr, double beta1, double beta2, double eps, double weight_decay);
+void mse_rater_trainer_free(mse_rater_trainer* tr);
+/* completed steps (torch's `step`) */
+uint64_t mse_rater_trainer_step_count(const mse_rater_trainer* tr);
+/* n_steps steps of train_step (train.py:63-71: F.binary_cross_entropy on the win probabilities, backward, optimizer.step) with `batch`
+ * pairs per member, 1 <= batch <= 64: in step s member m sees the pairs pair_ids[s][m][b][0 .. 2] -- rows of the base, first and
+ * second; each member its own data order as train.py:116-118 gives it -- with targets[s][m][b][c] in [0, 1].  The ids are checked
+ * against the base and uploaded once; the steps are queued without a host round trip.  A step with a non-finite row or a non-finite
+ * loss is refused: weights, moments and step count stay as they were and the later steps of the call are not run; *steps_done_out tells
+ * how many steps completed (the call still returns 0) and losses_out [n_steps] holds that many losses (each step's, before its update).
+ * Errors (a width that is not the rater's, a batch over the limit, an id past the base) leave every handle usable.
+ * mse_rater_trainer_steps_f16: the same over f16 rows on the host, [n_rows][d], uploaded once, and indices into them. */
+int mse_rater_trainer_steps(mse_rater_trainer* tr, const mse_base* b, const uint32_t* pair_ids /* [n_steps][M][batch][2] */,
+                            const float* targets /* [n_steps][M][batch][C] */, size_t batch, size_t n_steps, double* losses_out,
+                            size_t* steps_done_out);
+int mse_rater_trainer_steps_f16(mse_rater_trainer* tr, const uint16_t* rows_f16, size_t n_rows, size_t d, const uint32_t* pair_idx,
+                                const float* targets, size_t batch, size_t n_steps, double* losses_out, size_t* steps_done_out);
+/* The optimizer's state, what save_ckpt keeps beside the weights (train.py:98-102): the step count and exp_avg / exp_avg_sq of up,
+ * bias and down in the wide layout.  Read: any pointer may be NULL.  Write: all are needed. */
+int mse_rater_trainer_state_read(mse_rater_trainer* tr, uint64_t* t_out, float* m_up, float* v_up, float* m_bias, float* v_bias, float* m_down,
+                                 float* v_down);
+int mse_rater_trainer_state_write(mse_rater_trainer* tr, uint64_t t, const float* m_up, const float* v_up, const float* m_bias, const float* v_bias,
+                                  const float* m_down, const float* v_down);
+/* test hook: the scores s [M][2 * batch][C] the forward pass of the last completed step of the last call made of its slots (slot 2 b is
+ * pair b's first row); *batch_out = that step's batch.  An error where the last call ended in a refusal or no call was made. */
+int mse_rater_trainer_last_scores(mse_rater_trainer* tr, float* out_or_null, size_t* batch_out_or_null);
+/* measurement hook (scripts/rater_probe.py): out [4] = HIP-event milliseconds of the forward passes, of the small backward kernels and
+ * of the dense update of the last training call made while the switch was on, and the steps they cover; then the switch is set (0 off,
+ * 1 on, 2 on and reset). */
+int mse_rater_trainer_timing(int enable, double* out_or_null /* [4] */);
+/* Every member's scores of rows ids[i], i < n (any order, repeats allowed; each < mse_base_len), or first .. first + n when ids is
+ * NULL: a device table [n][M][C] of the rule's s, unscaled (model.py:38, the ensemble's stacked outputs without the output bias).  A
+ * row's scores are the same bits however it is asked for, and the bits the trainer's forward pass makes of that row.
+ * mse_member_scores_from_f16: the same over f16 rows on the host, [n_rows][d]. */
+mse_member_scores* mse_member_scores_from_base(mse_rater* r, const mse_base* b, const uint32_t* ids_or_null, size_t first, size_t n);
+mse_member_scores* mse_member_scores_from_f16(mse_rater* r, const uint16_t* rows_f16, size_t n_rows, size_t d, const uint32_t* ids_or_null,
+                                              size_t first, size_t n);
+void mse_member_scores_free(mse_member_scores* s);
+size_t mse_member_scores_len(const mse_member_scores* s);
+int mse_member_scores_read(const mse_member_scores* s, float* out /* [n][M][C] */);
+/* active_learning.py:50-53: out[i] = max over channels of torch.var over members (correction 1) of the win probabilities
+ * sigmoid(s[a_idx[i]] - s[b_idx[i]]), indices into the table; in the fixed order csrc/rater.hip states.  A table of one member is
+ * refused. */
+int mse_member_scores_pair_variance(mse_member_scores* s, const uint32_t* a_idx, const uint32_t* b_idx, size_t n_pairs, float* out /* [n_pairs] */);
+
 /* ---- SigLIP ViT image tower: the in-process seam of clip_server.py, `fast_image_fns[batch](images NCHW
  * fp16 on device) -> [batch, 1152]` (clip_server.py:31,66-82,105-112), plus the normalisation and fp16
  * serialisation of do_inference / run_inference (clip_server.py:115,166).  Graph: aitemplate/model.py:13-123;

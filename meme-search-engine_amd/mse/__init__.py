@@ -14,5 +14,6 @@ from .index import ScalarQuantizerIndex  # noqa: F401
 from .common import decode_fp16_buffer, chunk_fp16_buffer, get_total_embedding  # noqa: F401
 from .index_pack import ScoreModel, RowScores, descriptor_buckets  # noqa: F401
 from .sae import SparseAutoencoder, RowFeatures, SaeTrainer, StepRefused  # noqa: F401
+from .rater import Rater, RaterTrainer, MemberScores, RaterStepRefused, map_rating  # noqa: F401
 from .partition import ShardPartitioner, medioid_ids  # noqa: F401
 from .shard import ShardGroup, ShardFilter, ShardGroups, Comm, shard_range  # noqa: F401

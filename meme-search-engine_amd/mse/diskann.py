@@ -487,6 +487,18 @@ class DeviceGraph(_RowDeletes):
         """SaeTrainer.train over the index's rows `ids` (live slots, in the order given)."""
         return trainer.train(vecs_or_searcher, ids, batch_size)
 
+    def train_rater(self, trainer, vecs_or_searcher, pairs, ratings, epochs, rng, batch_size=1):
+        """RaterTrainer.train over rated pairs of the index's rows (live slots)."""
+        return trainer.train(vecs_or_searcher, pairs, ratings, epochs, rng, batch_size)
+
+    def rate_pairs(self, rater, vecs_or_searcher, a, b, k):
+        """The k candidate pairs (a[i], b[i]) of the index's rows that the rater's members disagree on most, as MemberScores.top_pairs
+        gives them: the rows that occur are scored once, member by member, and the pairs ranked over that table."""
+        a, b = np.asarray(a).reshape(-1), np.asarray(b).reshape(-1)
+        rows, inv = np.unique(np.concatenate([a, b]), return_inverse=True)
+        table = rater.member_scores(vecs_or_searcher, ids=rows)
+        return table.top_pairs(inv[:a.size], inv[a.size:], k)
+
     def close(self):
         if getattr(self, "_h", None):
             ffi.lib().mse_graph_free(self._h)

@@ -395,6 +395,25 @@ SIGNATURES = {
     "mse_sae_trainer_state_write": (C.c_int, [vp, C.c_uint64, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p]),
     "mse_sae_trainer_set_skip": (C.c_int, [vp, C.c_int]),
     "mse_sae_trainer_timing": (C.c_int, [C.c_int, C.POINTER(C.c_double)]),
+    # the ensemble rater (csrc/rater.hip, csrc/rater_api.hip)
+    "mse_rater_create": (vp, [f32p, f32p, f32p, sz, sz, sz]),
+    "mse_rater_free": (None, [vp]),
+    "mse_rater_read_weights": (C.c_int, [vp, f32p, f32p, f32p]),
+    "mse_rater_trainer_create": (vp, [vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]),
+    "mse_rater_trainer_free": (None, [vp]),
+    "mse_rater_trainer_step_count": (C.c_uint64, [vp]),
+    "mse_rater_trainer_steps": (C.c_int, [vp, vp, u32p, f32p, sz, sz, C.POINTER(C.c_double), C.POINTER(sz)]),
+    "mse_rater_trainer_steps_f16": (C.c_int, [vp, u16p, sz, sz, u32p, f32p, sz, sz, C.POINTER(C.c_double), C.POINTER(sz)]),
+    "mse_rater_trainer_state_read": (C.c_int, [vp, C.POINTER(C.c_uint64), f32p, f32p, f32p, f32p, f32p, f32p]),
+    "mse_rater_trainer_state_write": (C.c_int, [vp, C.c_uint64, f32p, f32p, f32p, f32p, f32p, f32p]),
+    "mse_rater_trainer_last_scores": (C.c_int, [vp, f32p, C.POINTER(sz)]),
+    "mse_rater_trainer_timing": (C.c_int, [C.c_int, C.POINTER(C.c_double)]),
+    "mse_member_scores_from_base": (vp, [vp, vp, u32p, sz, sz]),
+    "mse_member_scores_from_f16": (vp, [vp, u16p, sz, sz, u32p, sz, sz]),
+    "mse_member_scores_free": (None, [vp]),
+    "mse_member_scores_len": (sz, [vp]),
+    "mse_member_scores_read": (C.c_int, [vp, f32p]),
+    "mse_member_scores_pair_variance": (C.c_int, [vp, u32p, u32p, sz, f32p]),
     "mse_siglip_create": (vp, [vp]),
     "mse_siglip_destroy": (None, [vp]),
     "mse_siglip_n_weights": (C.c_int, [vp]),
